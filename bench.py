@@ -12,7 +12,13 @@ ef = --ef; recall@10 against the exact result, distance evaluations / expansions
 algorithmic bytes => achieved HBM GB/s.  Rank 0 times the CPU restatement of the reference beside both legs
 (oracle mode R brute force; oracle HNSW search over the very same graph, all host cores).
 
-    python bench.py                       # 1 GPU
+A plain run does the headline only: set-up, settle / warm-up steps, the K timed steps, the result line.  Everything
+else below (the graph, bf16, SQ8, per-metric and sharded legs, roofline / kernel timing and traffic passes, CPU
+baselines, the oracle comparison, the full record in bench_legs*.json) runs with --full.  --dump-outputs DIR writes
+what the last timed step returned as .npy files (the inputs are seeded: equal arguments, equal inputs).
+
+    python bench.py                       # 1 GPU, headline only
+    python bench.py --full                # 1 GPU, every leg
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -92,7 +98,38 @@ def parse():
     p.add_argument("--no-m128-leg", action="store_true", help="skip the graph leg at the reference's own preset for this corpus (HnswParams::million_scale)")
     p.add_argument("--m128-rows", type=int, default=1_000_000, help="rows of the million_scale(768) leg (M 128 / ef_construction 1600)")
     p.add_argument("--cpu-hnsw-queries", type=int, default=20000)
-    return p.parse_args()
+    # what a run does: without --full only the headline (set-up, settle / warm-up steps, the K timed steps, the result line); every
+    # other leg, check and diagnostic above (roofline and kernel timing, traffic passes, tiles, k curve, host entry, graph / bf16 / SQ8 /
+    # metric / sharded legs, CPU baselines, the oracle comparison, the full record in bench_legs*.json) runs with --full only
+    p.add_argument("--full", action="store_true", help="run every leg, check and diagnostic besides the headline (default: the headline only)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the last timed step returned (ids, scores, counts of rank 0) to DIR/<name>.npy as float64 / float32")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be >= 1")
+    return a
+
+
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs at most; a larger output is written as a fixed, seeded sample of its query rows
+
+
+def dump_outputs(d, ids, scores, counts):
+    """--dump-outputs: the arrays a caller of the timed path receives for the last timed step (one row per query), as .npy files
+    (ids and counts as float64 — exact below 2**53 — scores as float32).  Outputs above DUMP_LIMIT keep a sorted sample of rows drawn
+    with a fixed seed, and `rows.npy` names the rows kept."""
+    import numpy as np
+    out = {"ids": ids.cpu().numpy().astype(np.float64), "scores": scores.cpu().numpy().astype(np.float32),
+           "counts": counts.cpu().numpy().astype(np.float64)}
+    nq = out["counts"].shape[0]
+    row_bytes = sum(v[:1].nbytes for v in out.values())
+    if nq * row_bytes > DUMP_LIMIT:
+        keep = (DUMP_LIMIT - 4096) // (row_bytes + 8)   # (+ the row's index in rows.npy; 4 KB for the .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(nq, keep, replace=False))
+        out = {n_: v[rows] for n_, v in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for n_, v in out.items():
+        np.save(os.path.join(d, n_ + ".npy"), v)
 
 # ---- the line the driver parses -------------------------------------------------------------------------------------------------
 COMPACT_LIMIT = 4096   # bytes; the driver's record keeps a bounded tail of stdout (round 4's 25 KB line was cut: BENCH_r04.parsed = null)
@@ -410,10 +447,11 @@ def main():
     # are what the caller asked for, and `repeat_ms_per_step` (the same K steps once more) still shows what is left of the effect.
     # (one-time set-up of the kernel timing the LAST timed step switches on — the library creates its HIP events at first use and
     # the runtime turns the queue's profiling on at the first timed record: 1.8 ms inside the 30-ms timed window on one box of the
-    # pool, twice, `profiles/r06sel3_*` / `r06ae_*` — is paid here, on an untimed step)
-    va.set_kernel_timing(True)
-    step(0)
-    va.set_kernel_timing(False)
+    # pool, twice, `profiles/r06sel3_*` / `r06ae_*` — is paid here, on an untimed step; not in a headline-only run, which times no kernel)
+    if a.full or a.pmc_child:
+        va.set_kernel_timing(True)
+        step(0)
+        va.set_kernel_timing(False)
     for i in range(max(0, a.settle_steps)):
         step(i)
     for i in range(a.warmup):
@@ -432,7 +470,8 @@ def main():
             pass
     t0 = time.perf_counter()
     for i in range(a.steps):
-        events_on_last(i, a.steps)
+        if a.full:
+            events_on_last(i, a.steps)
         step(a.warmup + i)
     torch.cuda.synchronize()
     dt_mine = time.perf_counter() - t0  # this rank's own steps (the timed region below ends behind the barrier: the slowest rank's)
@@ -442,19 +481,8 @@ def main():
     sel_ms, sel_launches = ix.last_selection_ms()      # HIP events around every launch of the selection kernel, last step
     va.set_kernel_timing(False)
     dt = max_over_ranks(dt)
-    # (diagnostic, not `value`: the same K steps once more, right behind the timed region — how much of ms_per_step is the chip still
-    # settling into the workload behind W warm-up steps)
-    t0r = time.perf_counter()
-    for i in range(a.steps):
-        step(a.warmup + a.steps + i)
-    torch.cuda.synchronize()
-    repeat_ms_per_step = (time.perf_counter() - t0r) / a.steps * 1e3
-    host_sample = corpus[:sample_rows].cpu().numpy() if rank == 0 else None
-    host_full = None
-    if rank == 0 and a.check_queries > 0:
-        host_full = host_sample if sample_rows == N else corpus.cpu().numpy()
-    del corpus
-    torch.cuda.empty_cache()
+    if a.dump_outputs and rank == 0:  # before anything else writes the output buffers
+        dump_outputs(a.dump_outputs, out_ids, out_sc, out_n)
     qps = world * Q * a.steps / dt
     replicas_per_rank = gather_rows([float(rank), Q * a.steps / dt_mine], ("rank", "qps"))
 
@@ -502,6 +530,46 @@ def main():
     split_active = (mfma and not a.no_split and a.select_level > 0 and a.tile >= 128 and Q >= 224 and Q * 8 >= ((Q + 255) // 256) * 256 * 7
                     and K <= 10 and N >= 65536 and D % 32 == 0 and D >= 64)
 
+    # the kernel the headline step is bound by (`roofline.kernel`): the level the last timed step took, read before any other search call
+    level = ix.last_select_level()
+    headline_kernel = (kernel_name(tile, mfma) if not split_active else
+                       f"sweep_topk_gemm_bf16_glds<{a.metric},SPLIT>" if level == 1 else
+                       (f"sweep_topk_gemm_bf16_pp<dot, WIDE> over normalised bf16 images of rows and queries ({a.metric}; ping-pong pipeline, candidates to global lists)"
+                        if level == 4 else f"sweep_topk_gemm_bf16_pp<{a.metric}> (plain bf16 selection, ping-pong pipeline)"))
+
+    headline = {
+        "metric": "qps_at_recall10_1Mx768_k10", "value": round(qps, 1), "unit": "queries/s", "n_gpus": world,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{N}x{D} f32 {a.metric}, k={K}, exact distance sweep + fused GPU top-k "
+                               f"(BASELINE configs[1]); {Q} queries/step, {tile} queries per corpus pass "
+                               f"({headline_kernel})",
+                   "rows": N, "dim": D, "k": K, "queries_per_step": Q,
+                   "parallelism": "replicas x%d (query stream split, no collective)" % world},
+        "replicas_per_rank": replicas_per_rank, "settle_steps": max(0, a.settle_steps),
+    }
+    if not a.full:  # the headline alone: its line, no record file
+        if use_dist:
+            dist.destroy_process_group()
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(compact_line(dict(headline, device=va.device_name(local)), None)) + "\n").encode())
+        return
+
+    # (diagnostic, not `value`: the same K steps once more, right behind the timed region — how much of ms_per_step is the chip still
+    # settling into the workload behind W warm-up steps)
+    t0r = time.perf_counter()
+    for i in range(a.steps):
+        step(a.warmup + a.steps + i)
+    torch.cuda.synchronize()
+    repeat_ms_per_step = (time.perf_counter() - t0r) / a.steps * 1e3
+    host_sample = corpus[:sample_rows].cpu().numpy() if rank == 0 else None
+    host_full = None
+    if rank == 0 and a.check_queries > 0:
+        host_full = host_sample if sample_rows == N else corpus.cpu().numpy()
+    del corpus
+    torch.cuda.empty_cache()
+
     def exact_roofline(kms, nl):
         tf = flops / (kms * 1e-3) / 1e12 if kms > 0 else 0.0
         return {"bound": "mfma", "achieved": round(tf, 1), "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -521,17 +589,13 @@ def main():
         # device-driven fallback launch.  achieved = ALGORITHMIC flop (2*rows*dim*queries) / that time against the bf16
         # dense peak; the selection issues 3 bf16 MFMAs per algorithmic product (hi.hi + hi.lo + lo.hi).
         nq_last, unproven = ix.last_split_stats()
-        level = ix.last_select_level()
         mfmas_per_product = 3.0 if level == 1 else 1.0
-        sel_kernel = (f"sweep_topk_gemm_bf16_glds<{a.metric},SPLIT>" if level == 1 else
-                      (f"sweep_topk_gemm_bf16_pp<dot, WIDE> over normalised bf16 images of rows and queries ({a.metric}; ping-pong pipeline, candidates to global lists)"
-                       if level == 4 else f"sweep_topk_gemm_bf16_pp<{a.metric}> (plain bf16 selection, ping-pong pipeline)"))
         # the dominant kernel = the selection kernel: its launches of one step sweep every row behind the seed prefix once
         # (algorithmic flop 2 * rows * dim * queries per step), their durations are summed from HIP events around each launch
         sel_tf = (2.0 * (N - 4096) * D * tile) / (sel_ms * 1e-3) / 1e12 if sel_ms > 0 else 0.0
         roofline = {"bound": "mfma", "achieved": round(sel_tf, 1), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                     "frac": round(sel_tf / BF16_MFMA_PEAK_TFLOPS, 4), "traffic": None,
-                    "kernel": sel_kernel,
+                    "kernel": headline_kernel,
                     "kernel_ms": round(sel_ms, 4), "launches_timed": sel_launches,
                     "kernel_ms_note": "sum over the step's launches of the selection kernel (growing row ranges, thresholds re-seeded in between); "
                                       "HIP events on the last of the timed steps only (a record idles the GPU ~6 us either side of the launch)",
@@ -1863,15 +1927,7 @@ def main():
             device_state = [f"rocm-smi unavailable: {ex}"]
     if rank == 0:
         line = {
-            "metric": "qps_at_recall10_1Mx768_k10", "value": round(qps, 1), "unit": "queries/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{N}x{D} f32 {a.metric}, k={K}, exact distance sweep + fused GPU top-k "
-                                   f"(BASELINE configs[1]); {Q} queries/step, {tile} queries per corpus pass "
-                                   f"({roofline['kernel']})",
-                       "rows": N, "dim": D, "k": K, "queries_per_step": Q,
-                       "parallelism": "replicas x%d (query stream split, no collective)" % world},
-            "replicas_per_rank": replicas_per_rank, "repeat_ms_per_step": round(repeat_ms_per_step, 4), "settle_steps": max(0, a.settle_steps),
+            **headline, "repeat_ms_per_step": round(repeat_ms_per_step, 4),
             "recall_at_10": recall, "parity_check": check,
             # the headline's algorithmic flop over the WHOLE step's time / peak — from ms_per_step (the timed region's wall clock over its
             # steps, what `value` is computed from), not from the last step's event pair (roofline.whole_batch keeps that one)

@@ -31,6 +31,47 @@ def test_defaults_are_the_baseline_configuration(monkeypatch):
     assert (a.gpus, a.steps, a.warmup) == (8, 5, 2)
 
 
+def test_a_plain_run_is_the_headline_alone_and_dumps_nothing(monkeypatch):
+    """every leg besides the headline waits for --full; --dump-outputs names a directory and is off by default; --steps is the number of
+    timed steps, so it cannot be 0"""
+    import pytest
+    b = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, "")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_past_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    b = load_bench()
+    rng = np.random.default_rng(1)
+    ids = torch.from_numpy(rng.integers(0, 1_000_000, (300, 10)))
+    sc = torch.from_numpy(rng.standard_normal((300, 10)).astype(np.float32))
+    n = torch.full((300,), 10, dtype=torch.int32)
+    b.dump_outputs(str(tmp_path / "all"), ids, sc, n)
+    got = {f: np.load(tmp_path / "all" / (f + ".npy")) for f in ("ids", "scores", "counts")}
+    assert sorted(os.listdir(tmp_path / "all")) == ["counts.npy", "ids.npy", "scores.npy"]
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"], ids.numpy())
+    assert got["scores"].dtype == np.float32 and np.array_equal(got["scores"].view(np.uint32), sc.numpy().view(np.uint32))
+    assert got["counts"].dtype == np.float64 and np.array_equal(got["counts"], n.numpy())
+    # past the limit: a sorted, seeded sample of whole rows (the same on every run), `rows` naming them
+    monkeypatch.setattr(b, "DUMP_LIMIT", 4096 + 100 * (10 * 8 + 10 * 4 + 8 + 8))
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), ids, sc, n)
+    rows = np.load(tmp_path / "s1" / "rows.npy")
+    assert rows.size == 100 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "ids.npy"), ids.numpy()[rows.astype(np.int64)])
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= b.DUMP_LIMIT
+
+
 def test_without_a_gpu_the_bench_fails_loudly_and_prints_no_line():
     env = dict(os.environ)
     env.pop("RANK", None)

@@ -5,7 +5,7 @@ O=$R/gpurun_out/pmc_icache
 mkdir -p $O
 rocprofv3 --list-avail 2>/dev/null | grep -o "SQC_[A-Z0-9_]*\|SQ_IFETCH[A-Z0-9_]*\|SQ_INST_LEVEL[A-Z0-9_]*" | sort -u > $O/avail.txt
 cat $O/avail.txt | tr '\n' ' '; echo
-HL="--steps 10 --warmup 2 --no-cpu-baseline --check-queries 0 --no-tiles --no-hnsw --no-sq8-leg --no-sharded-leg --no-traffic-pass --no-latency-legs --no-bf16-leg"
+HL="--full --steps 10 --warmup 2 --no-cpu-baseline --check-queries 0 --no-tiles --no-hnsw --no-sq8-leg --no-sharded-leg --no-traffic-pass --no-latency-legs --no-bf16-leg"
 run() { n=$1; shift
   timeout 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$n -- python $R/bench.py $HL > $O/$n.log 2>&1
   echo "$n rc=$?"; find $O/$n -name "*_kernel_trace.csv" -delete; }
