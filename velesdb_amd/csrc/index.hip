@@ -882,7 +882,8 @@ static int32_t brute_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride,
       hipError_t le = launch_sweep_f32_qlds(ix->metric, (int)B, a, blocks, st);
       if (le != hipSuccess) return fail(VDB_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString(le));
     } else {
-      launch_sweep_f32(ix->metric, (int)B, a, blocks, st);
+      hipError_t le = launch_sweep_f32(ix->metric, (int)B, a, blocks, st);
+      if (le != hipSuccess) return fail(VDB_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString(le));
     }
     if (ev) (void)hipEventRecord(ev->b, st);
     MergeArgs m{};

@@ -433,11 +433,16 @@ static int32_t ensure_cosn(vdb_hip_index* ix, hipStream_t st) {
 }
 static inline bool cosine_normalised(const vdb_hip_index* ix) { return g_cosn && ix->metric == VDB_COSINE && ix->dim % 64 == 0; }
 
+// the gathered exact pass of a Euclidean batch's unproven queries: the vector-ALU sweep, 8 queries per pass with the query tile in
+// LDS (32 B per element): it must fit 160 KiB — at k = 128 up to dim ~4 860, the reference allows 65 536
+static bool l2_gather_fits(uint32_t dim, uint32_t k) { return sweep_lds_bytes(8, k, dim, sweep_cpl_for_dim(dim)) <= 160 * 1024; }
+
 int select_level_l2(vdb_hip_index* ix, uint32_t nq_left, uint32_t k) {
   if (!opt_selector(ix) || opt_engine(ix) != 1 || opt_max_tile(ix) < 128) return 0;
   if (ix->metric != VDB_EUCLIDEAN) return 0;
   if (ix->dim % 64 != 0 || ix->dim < 128 || ix->row_stride != ix->dim) return 0;
   if (k == 0 || k > kGemmBf16MaxK || ix->n_rows < kGemmBf16MinRows || ix->n_rows >= 0xFFFFFF00ull) return 0;
+  if (!l2_gather_fits(ix->dim, k)) return 0;
   if (!select_chunk(nq_left)) return 0;
   if (ix->sel_stats && ix->sel_stats[2] != ix->sel_seq_seen) {
     ix->sel_seq_seen = ix->sel_stats[2];
@@ -773,7 +778,8 @@ int32_t brute_split_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, 
     af.k = k;
     af.qmap = qmap;
     af.qcount = qcount;
-    launch_sweep_f32(VDB_EUCLIDEAN, 8, af, f_blocks, st, (int)((nqg + 7) / 8));
+    e = launch_sweep_f32(VDB_EUCLIDEAN, 8, af, f_blocks, st, (int)((nqg + 7) / 8));
+    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("gathered fallback launch: ") + hipGetErrorString(e));
     MergeArgs mg{};
     mg.part_keys = af.part_keys;
     mg.ext_ids = ix->ext_ids.as<uint64_t>();
@@ -895,7 +901,9 @@ int select_level_wide(vdb_hip_index* ix, uint32_t nq_left, uint32_t k, bool sq8)
   // ~25 instead of 64 rows to re-score: DESIGN 4.1f) — and a handle the data defeats falls back to those levels, not to the exact kernels
   if (k == 0 || k > kWideMaxK || ix->n_rows < kGemmBf16MinRows || ix->n_rows >= 0xFFFFFF00ull) return 0;
   if (k <= kGemmBf16MaxK && (opt_selector(ix) < 3 || !g_wide_small_k)) return 0;
-  if (!sq8 && ix->metric != VDB_EUCLIDEAN && sweep_mfma_lds_bytes(1, k, ix->dim) > 160 * 1024) return 0;  // (the gathered exact pass of the unproven queries)
+  // (the gathered exact pass of the unproven queries)
+  if (!sq8 && ix->metric != VDB_EUCLIDEAN && sweep_mfma_lds_bytes(1, k, ix->dim) > 160 * 1024) return 0;
+  if (!sq8 && ix->metric == VDB_EUCLIDEAN && !l2_gather_fits(ix->dim, k)) return 0;
   if (!select_chunk(nq_left, sq8 ? kSelectMinQueriesSq8 : 0)) return 0;
   if (ix->sel_stats && ix->sel_stats[2] != ix->sel_seq_seen) {
     ix->sel_seq_seen = ix->sel_stats[2];
@@ -1137,12 +1145,9 @@ int32_t brute_wide_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
   am.qmap = qmap;
   am.qcount = qcount;
   am.qcount_max = nqg;
-  if (l2) {
-    launch_sweep_f32(VDB_EUCLIDEAN, 8, am, g_blocks, st, (int)((nqg + 7) / 8));
-  } else {
-    e = launch_sweep_mfma(ix->metric, g_nqt, am, g_blocks, st, (int)((nqg + g_B - 1) / g_B));
-    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("gathered fallback launch: ") + hipGetErrorString(e));
-  }
+  e = l2 ? launch_sweep_f32(VDB_EUCLIDEAN, 8, am, g_blocks, st, (int)((nqg + 7) / 8))
+         : launch_sweep_mfma(ix->metric, g_nqt, am, g_blocks, st, (int)((nqg + g_B - 1) / g_B));
+  if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("gathered fallback launch: ") + hipGetErrorString(e));
   MergeArgs mg{};
   mg.part_keys = am.part_keys;
   mg.ext_ids = ix->ext_ids.as<uint64_t>();

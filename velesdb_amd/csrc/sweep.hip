@@ -1971,26 +1971,27 @@ __global__ __launch_bounds__(256) void score_rows(ScoreArgs a) {
 
 // ---- host-callable launchers ------------------------------------------------------------
 template <int METRIC, int B, int CPL>
-static void launch_sweep_t(const SweepArgs& a, int blocks, size_t lds, hipStream_t st, int groups) {
+static hipError_t launch_sweep_t(const SweepArgs& a, int blocks, size_t lds, hipStream_t st, int groups) {
   hipLaunchKernelGGL((sweep_topk_f32<METRIC, B, CPL>), dim3(blocks, groups), dim3(256), lds, st, a);
+  return hipGetLastError();
 }
 template <int METRIC, int B>
-static void launch_sweep_cpl(const SweepArgs& a, int cpl, int blocks, size_t lds, hipStream_t st, int groups) {
+static hipError_t launch_sweep_cpl(const SweepArgs& a, int cpl, int blocks, size_t lds, hipStream_t st, int groups) {
   switch (cpl) {
-    case 1: launch_sweep_t<METRIC, B, 1>(a, blocks, lds, st, groups); break;
-    case 2: launch_sweep_t<METRIC, B, 2>(a, blocks, lds, st, groups); break;
-    case 3: launch_sweep_t<METRIC, B, 3>(a, blocks, lds, st, groups); break;
-    case 4: launch_sweep_t<METRIC, B, 4>(a, blocks, lds, st, groups); break;
-    default: launch_sweep_t<METRIC, B, 0>(a, blocks, lds, st, groups); break;
+    case 1: return launch_sweep_t<METRIC, B, 1>(a, blocks, lds, st, groups);
+    case 2: return launch_sweep_t<METRIC, B, 2>(a, blocks, lds, st, groups);
+    case 3: return launch_sweep_t<METRIC, B, 3>(a, blocks, lds, st, groups);
+    case 4: return launch_sweep_t<METRIC, B, 4>(a, blocks, lds, st, groups);
+    default: return launch_sweep_t<METRIC, B, 0>(a, blocks, lds, st, groups);
   }
 }
 template <int METRIC>
-static void launch_sweep_b(const SweepArgs& a, int B, int cpl, int blocks, size_t lds, hipStream_t st, int groups) {
+static hipError_t launch_sweep_b(const SweepArgs& a, int B, int cpl, int blocks, size_t lds, hipStream_t st, int groups) {
   switch (B) {
-    case 1: launch_sweep_cpl<METRIC, 1>(a, cpl, blocks, lds, st, groups); break;
-    case 2: launch_sweep_cpl<METRIC, 2>(a, cpl, blocks, lds, st, groups); break;
-    case 4: launch_sweep_cpl<METRIC, 4>(a, cpl, blocks, lds, st, groups); break;
-    default: launch_sweep_cpl<METRIC, 8>(a, cpl, blocks, lds, st, groups); break;
+    case 1: return launch_sweep_cpl<METRIC, 1>(a, cpl, blocks, lds, st, groups);
+    case 2: return launch_sweep_cpl<METRIC, 2>(a, cpl, blocks, lds, st, groups);
+    case 4: return launch_sweep_cpl<METRIC, 4>(a, cpl, blocks, lds, st, groups);
+    default: return launch_sweep_cpl<METRIC, 8>(a, cpl, blocks, lds, st, groups);
   }
 }
 
@@ -2006,13 +2007,13 @@ int sweep_cpl_for_dim(uint32_t dim) {
   return (c >= 1 && c <= 4) ? c : 0;
 }
 
-void launch_sweep_f32(int metric, int B, const SweepArgs& a, int blocks, hipStream_t st, int groups) {
+hipError_t launch_sweep_f32(int metric, int B, const SweepArgs& a, int blocks, hipStream_t st, int groups) {
   const int cpl = sweep_cpl_for_dim(a.dim);
   const size_t lds = sweep_lds_bytes(B, a.k, a.dim, cpl);
   switch (metric) {
-    case kCosine: launch_sweep_b<kCosine>(a, B, cpl, blocks, lds, st, groups); break;
-    case kEuclidean: launch_sweep_b<kEuclidean>(a, B, cpl, blocks, lds, st, groups); break;
-    default: launch_sweep_b<kDot>(a, B, cpl, blocks, lds, st, groups); break;
+    case kCosine: return launch_sweep_b<kCosine>(a, B, cpl, blocks, lds, st, groups);
+    case kEuclidean: return launch_sweep_b<kEuclidean>(a, B, cpl, blocks, lds, st, groups);
+    default: return launch_sweep_b<kDot>(a, B, cpl, blocks, lds, st, groups);
   }
 }
 

@@ -153,7 +153,8 @@ hipError_t launch_hnsw_search(const HnswSearchArgs& a, int slots, hipStream_t st
 
 size_t sweep_lds_bytes(int B, uint32_t k, uint32_t dim, int cpl);
 int sweep_cpl_for_dim(uint32_t dim);
-void launch_sweep_f32(int metric, int B, const SweepArgs& a, int blocks, hipStream_t st, int groups = 1);
+// returns hipSuccess or the launch error (a tile above 160 KiB of LDS does not launch: callers check, select_stage.hip l2_gather_fits)
+hipError_t launch_sweep_f32(int metric, int B, const SweepArgs& a, int blocks, hipStream_t st, int groups = 1);
 // large query tiles (B = 16 / 32) with the queries in LDS; dim % 256 == 0 and dim <= 1024 only
 constexpr int kQldsWaves16 = 4;   // waves per block for B = 16 (3 blocks per CU)
 constexpr int kQldsWaves32 = 16;  // waves per block for B = 32
