@@ -1,8 +1,10 @@
 """Stamped timeline of the selection kernel's k-tile: runs the headline batch (1 M x 768 cosine, 1 024
 queries, k = 10) on a -DVDB_PP_STAMP variant of the library (tools/probes/pp_variants.sh) and prints, for one wave of each wave row
 of block 8, the average shader cycles per k-tile spent in each segment of the four-phase schedule of sweep_topk_gemm_bf16_pp.
-    python tools/probes/pp_stamp_probe.py tools/probes/out/libvelesdb_hip_stamp1.so [rows] [cosine|hamming|jaccard]
-(hamming / jaccard: the four-bit instance, rows of uniform bits; a row tile is 3 k-tiles of 256 dimensions instead of 12 of 64)"""
+    python tools/probes/pp_stamp_probe.py tools/probes/out/libvelesdb_hip_stamp1.so [rows] [cosine|hamming|jaccard] [k]
+(hamming / jaccard: the four-bit instance, rows of uniform bits; a row tile is 3 k-tiles of 256 dimensions instead of 12 of 64).
+Cosine batches take the WIDE instance (selection level 4) at every k, whose stamps a -DVDB_PP_STAMP_METRIC=2 build reads (the
+normalised images run the DotProduct instance); the k <= 10 instance (level 2) is stamped with the default metric."""
 import ctypes as C
 import os
 import sys
@@ -25,7 +27,8 @@ N = int(sys.argv[2]) if len(sys.argv) > 2 else 1_000_000
 METRIC = sys.argv[3] if len(sys.argv) > 3 else "cosine"
 BITS = METRIC in ("hamming", "jaccard")
 KT_PER_ROW_TILE = 3 if BITS else 12
-D, Q, K = 768, 1024, 10
+D, Q = 768, 1024
+K = int(sys.argv[4]) if len(sys.argv) > 4 else 10
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev)
 g.manual_seed(42)
@@ -45,7 +48,9 @@ if BITS:
 qs = qs.cpu().numpy()
 for _ in range(4):
     ids, sc, cnt = ix.search_batch_brute_force(qs, K)
-assert BITS or ix.last_select_level() == 2, ix.last_select_level()
+LEVEL = ix.last_select_level()
+assert BITS or LEVEL in (2, 4), LEVEL
+print(f"selection level {LEVEL} ({'WIDE' if LEVEL == 4 else 'block-local lists'}), k = {K}")
 L = C.CDLL(lib_path)
 buf = (C.c_ulonglong * 64)()
 rc = L.vdb_hip_debug_pp_stamps(buf)

@@ -1,7 +1,8 @@
 // g16_protocol.inc — textually included right behind g16_quicktest.inc, once EVERY wave of the block has passed the same
 // number of barriers: the hot lanes are looked at, survivors queued, appended to the candidate buffers and compacted, in rounds
-// separated by block barriers.  Needs: what g16_quicktest.inc left (last, lane, halfp, hm, thrv, gmv, nvalid) + a, acc, rt, wr, wq, wib, nq_t, k,
-// qn, vns, tauk, cnts, cand, flags, wq_keys, wq_qs, qcnt, epoch, VDB_G16_ACC_ELEM(x, element), compact(), METRIC, HIB, BM, CAP, QCAP
+// separated by block barriers (WIDE: the finish puts the survivors straight into the block's stash; one barrier, no rounds).
+// Needs: what g16_quicktest.inc left (last, lane, halfp, hm, thrv, gmv, nvalid) + a, acc, rt, wr, wq, wib, nq_t, k,
+// q0, qn, vns, tauk, cnts, cand, flags, wq_keys, wq_qs, qcnt, epoch, VDB_G16_ACC_ELEM(x, element), compact(), METRIC, HIB, BM, CAP, QCAP
 // (QCAP <= 64).
 #ifndef VDB_PP_STAMP_AT
 #define VDB_PP_STAMP_AT(SLOT) do { } while (0)
@@ -105,6 +106,23 @@ _Pragma("unroll") \
           const uint64_t key = make_key<HIB>(score, row); \
           bool take = (HAVE) & (row < a.n_rows) & (key < tauk[b]); \
           if (take && a.alive) take = a.alive[row] != 0;  /* soft-deleted rows are filtered where it is rare */ \
+          if constexpr (WIDE) { \
+            /* WIDE: straight into the block's STASH — the query's CAP slots of the candidate buffers, which the instance keeps no list \
+               in; cnts[b] counts every survivor, an LDS atomic (no device-scope round trip, nothing drains the LDS-DMA queue).  A full \
+               slot row (rare) sends the entry to the query's global list on its own; the stash is flushed behind the last row tile \
+               (g16_writeout.inc).  Nothing is queued: FITS always holds, qcnt stays 0 */ \
+            if (take) { \
+              const uint32_t si = atomicAdd(&cnts[b], 1u); \
+              if (si < (uint32_t)CAP) { \
+                cand[(size_t)b * CAP + si] = key; \
+              } else { \
+                const uint32_t qg = q0 + b; \
+                const uint32_t gi = atomicAdd(&a.wide_cnt[qg], 1u); \
+                if (gi < a.wide_cap) a.wide_keys[(size_t)qg * a.wide_cap + gi] = key; \
+              } \
+            } \
+            FITS = true; \
+          } else { \
           const uint64_t mt = __ballot(take); \
           FITS = qcnt + (uint32_t)__popcll(mt) <= (uint32_t)QCAP; \
           if (FITS) { \
@@ -114,6 +132,7 @@ _Pragma("unroll") \
               wq_qs[slot] = (uint8_t)b; \
             } \
             qcnt += (uint32_t)__popcll(mt); \
+          } \
           } \
         } while (0)
 #ifndef VDB_G16_NO_DUMP  // (the lock-step kernel leaves it out: its k-loop pays for every scalar the epilogue keeps alive)
@@ -208,6 +227,13 @@ _Pragma("unroll") \
 #undef VDB_G16_FINISH
       }
       VDB_PP_STAMP_AT(12);  // look phase (scan + finish)
+      if constexpr (WIDE) {
+        // WIDE: every survivor is in the stash already and the bound does not move — no append, no round to repeat, no flags.  The one
+        // barrier left is the last k-tile's closing barrier (the next row tile's norms land in vns, which every quick test has read)
+        __syncthreads();
+        VDB_PP_STAMP_AT(13);
+        break;
+      }
       // (flags[0] = the LATEST round somebody asked to repeat.  Nothing holds a wave back behind its own read of the word below, so a
       // fast wave may already be in round e + 1 — and mark it — while a slower one, still appending in round e, has not read yet: the
       // reader therefore tests `>= epoch`, not `== epoch` (a wave can only be in round e + 1 because round e WAS marked; epochs only
@@ -227,18 +253,7 @@ _Pragma("unroll") \
       }
       // ---- (3) append the queue to the candidate buffers; an entry whose buffer is full stays queued ----
       bool want = false;
-      if constexpr (WIDE) {
-        // the query's GLOBAL list takes every finished entry (it passed `key < tauk[b]`, and the bound of a WIDE launch does not move):
-        // one device-scope counter per query, entries past the capacity are dropped — the count says so (sweep_wide.hip)
-        const uint32_t ln3 = lane_now();
-        if (ln3 < qcnt) {
-          const uint64_t key = wq_keys[ln3];
-          const uint32_t qg = q0 + (uint32_t)wq_qs[ln3];
-          const uint32_t idx = atomicAdd(&a.wide_cnt[qg], 1u);
-          if (idx < a.wide_cap) a.wide_keys[(size_t)qg * a.wide_cap + idx] = key;
-        }
-        qcnt = 0;
-      } else {
+      {
         const uint32_t ln3 = lane_now();  // (re-derived, not carried across the look phase: see lane_now)
         const uint64_t key = ln3 < qcnt ? wq_keys[ln3] : kKeyInvalid;
         const uint32_t b = ln3 < qcnt ? wq_qs[ln3] : 0u;

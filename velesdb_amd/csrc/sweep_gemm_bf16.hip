@@ -80,7 +80,7 @@ struct Bf16GemmArgs {
   unsigned long long* dbg;  // (-DVDB_PP_STAMP variant builds only; nullptr otherwise)
   // WIDE instance (k beyond the candidate buffers: sweep_wide.hip): no list is kept in the block — every row that passes the query's
   // launch-constant bound tau0 is appended to the query's global list [nq][wide_cap] (a counter per query; entries past the capacity
-  // are dropped and show as a count above it)
+  // are dropped and show as a count above it), through the block's stash in LDS (g16_protocol.inc, g16_writeout.inc)
   uint64_t* wide_keys;
   uint32_t* wide_cnt;
   uint32_t wide_cap;
@@ -468,7 +468,10 @@ __device__ __forceinline__ void pp_wait_dma6() { asm volatile("s_waitcnt vmcnt(6
 // `qnorms_half` carry the bit counts |v|, |q| as floats (Hamming: dim); the accumulators hold the exact integer dot products.
 // WIDE: the instance for k beyond the candidate buffers (11 .. kWideMaxK, sweep_wide.hip): the same k-loop and quick test under a bound
 // that stays what the launch was given (tau0: the k-th best approximate score seen so far, lowered by twice the error bound); the
-// epilogue appends every survivor to the query's global list instead of a block-local top-k, and nothing is written out at the end.
+// epilogue appends every survivor to the query's global list instead of a block-local top-k.  The survivors of a row tile go into a
+// block-local STASH (the query's slots of the candidate buffers, an LDS atomic each; a full slot row sends the entry to the global list
+// on its own), which the block flushes behind its last row tile — one device-scope counter update per query with entries, then the keys.
+// So the epilogue has no rounds and no flags: the quick test, the look phase and the one barrier the k-tile protocol needs.
 template <int METRIC, bool FP4 = false, bool WIDE = false>
 __global__ __launch_bounds__(512, 2) void sweep_topk_gemm_bf16_pp(Bf16GemmArgs a) {
   static_assert(FP4 == (METRIC == kHamming || METRIC == kJaccard), "the four-bit instance serves the bit metrics, the bf16 instance Cosine / DotProduct");
@@ -838,6 +841,16 @@ void launch_seed_tau(const uint64_t* ids, const float* scores, const uint32_t* n
 
 #if VDB_PP_STAMP
 static unsigned long long* g_pp_stamp_buf = nullptr;
+// the stamp buffer of the variant build (every launch of a batch writes it; the last — the largest — launch's numbers stay)
+static unsigned long long* pp_stamp_dbg() {
+  static unsigned long long* dbg = [] {
+    void* p = nullptr;
+    if (hipMalloc(&p, 512) == hipSuccess) (void)hipMemset(p, 0, 512);
+    return static_cast<unsigned long long*>(p);
+  }();
+  g_pp_stamp_buf = dbg;
+  return dbg;
+}
 }  // namespace vdb
 extern "C" int32_t vdb_hip_debug_pp_stamps(unsigned long long* out /* [2][20] */) {
   if (!vdb::g_pp_stamp_buf) return -1;
@@ -938,6 +951,9 @@ hipError_t launch_sweep_gemm_bf16_wide(int metric, const Bf16GemmPlan& p, const 
   a.wide_keys = wide_keys;
   a.wide_cnt = wide_cnt;
   a.wide_cap = wide_cap;
+#if VDB_PP_STAMP
+  a.dbg = pp_stamp_dbg();
+#endif
   return metric == kCosine ? launch_g16_wide<kCosine>(a, p.blocks, st) : launch_g16_wide<kDot>(a, p.blocks, st);
 }
 
@@ -970,15 +986,7 @@ hipError_t launch_sweep_gemm_bf16_glds(int metric, const Bf16GemmPlan& p, const 
   a.blk_tau = blk_tau;
   a.qnorms_half = qnorms_half;
 #if VDB_PP_STAMP
-  {
-    static unsigned long long* dbg = [] {
-      void* p = nullptr;
-      if (hipMalloc(&p, 512) == hipSuccess) (void)hipMemset(p, 0, 512);
-      return static_cast<unsigned long long*>(p);
-    }();
-    g_pp_stamp_buf = dbg;
-    a.dbg = dbg;  // (every launch of the batch writes it; the last — the largest — launch's numbers stay)
-  }
+  a.dbg = pp_stamp_dbg();
 #endif
   if (metric == kHamming) return launch_g16_fp4<kHamming>(a, p.blocks, st);
   if (metric == kJaccard) return launch_g16_fp4<kJaccard>(a, p.blocks, st);
