@@ -76,10 +76,24 @@ enum vdb_search_mode {
   VDB_SEARCH_BRUTE_BINARY = 6, /* exact scan by BinaryQuantizedVector::hamming_distance (quantization.rs:123-135) between
                            the sign bits of the query and of every row; scores = the distance as f32, smallest first.
                            Needs VDB_STORAGE_BINARY; any metric.                                              */
-  VDB_SEARCH_BRUTE_BF16 = 3 /* exact scan over the bf16 copy of the rows with bf16-rounded queries and f32
+  VDB_SEARCH_BRUTE_BF16 = 3, /* exact scan over the bf16 copy of the rows with bf16-rounded queries and f32
                            accumulation on the matrix cores: half_precision::dot_product / cosine_similarity on
-                           VectorData::BF16 (half_precision.rs:199-255).  Cosine / DotProduct only; needs
-                           vdb_hip_index_enable_bf16.  Raw scores, best first.                       */
+                           VectorData::BF16 (half_precision.rs:199-255); needs vdb_hip_index_enable_bf16 or
+                           vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16).  On a Euclidean handle (the second call
+                           only): half_precision::euclidean_distance (:257-287), sqrt of an f32 chain of (q - v)^2 over the
+                           rounded values, smallest first.  Raw scores, best first.                  */
+  VDB_SEARCH_BRUTE_F16 = 7  /* the same over the IEEE f16 copy of the rows (VectorData::F16: round to nearest even, overflow to
+                           +-inf beyond 65 504, f16 subnormals kept) with f16-rounded queries: Cosine / DotProduct on the matrix
+                           cores (v_mfma_f32_16x16x32_f16, f32 accumulation); Euclidean (half_precision.rs:257-279) as sqrt of an f32
+                           chain of (q - v)^2 over the rounded values, smallest first.  Needs
+                           vdb_hip_index_enable_half_precision(VDB_PRECISION_F16).                                   */
+};
+
+/* VectorPrecision (half_precision.rs:36-44), the reference's order */
+enum vdb_vector_precision {
+  VDB_PRECISION_F32 = 0,
+  VDB_PRECISION_F16 = 1,
+  VDB_PRECISION_BF16 = 2
 };
 
 /* StorageMode (core/quantization.rs:17-29): which quantised copy of the rows the index keeps next to the f32 rows */
@@ -182,6 +196,13 @@ int32_t vdb_hip_index_get_quantized(vdb_hip_index* idx, uint64_t id, uint8_t* ou
 /* keeps a bf16 copy (round to nearest even, VectorData::from_f32_slice(.., BF16), half_precision.rs:94-101) of every
  * row next to the f32 rows, for VDB_SEARCH_BRUTE_BF16; +2 bytes per element of HBM */
 int32_t vdb_hip_index_enable_bf16(vdb_hip_index* idx);
+/* VectorData::from_f32_slice(.., precision) for every row (half_precision.rs:94-101): keeps a half-precision copy (rows present now and
+ * rows that arrive later through insert / upload / upload_dev; soft deletes honoured) next to the f32 rows, +2 bytes per element of
+ * HBM, for VDB_SEARCH_BRUTE_F16 (VDB_PRECISION_F16) / VDB_SEARCH_BRUTE_BF16 (VDB_PRECISION_BF16).  Cosine, DotProduct and Euclidean
+ * handles; VDB_ERR_UNSUPPORTED for Hamming / Jaccard and for VDB_PRECISION_F32.  Both precisions may be enabled on one handle (two
+ * images).  On Cosine / DotProduct, VDB_PRECISION_BF16 is vdb_hip_index_enable_bf16 (which keeps refusing Euclidean handles).  A
+ * multi-device handle forwards the call to every shard. */
+int32_t vdb_hip_index_enable_half_precision(vdb_hip_index* idx, int32_t precision);
 /* links every row that is not in the graph yet (rows that arrived through upload/upload_dev), same
  * schedule as insert_batch_parallel; afterwards the HNSW search modes are available. */
 int32_t vdb_hip_index_build_graph(vdb_hip_index* idx, uint32_t max_batch);
@@ -411,7 +432,10 @@ enum vdb_kernel_bit {
   VDB_KERNEL_SQ8 = 512,            /* sweep_topk_sq8                                                                   */
   VDB_KERNEL_HNSW = 1024,          /* hnsw_search_kernel                                                               */
   VDB_KERNEL_HNSW_INT8 = 2048,     /* hnsw_search_int8_kernel                                                          */
-  VDB_KERNEL_BITS_GEMM = 4096      /* Hamming / Jaccard batches as a four-bit GEMM distance (sweep_topk_gemm_bf16_pp<.., FP4>) */
+  VDB_KERNEL_BITS_GEMM = 4096,     /* Hamming / Jaccard batches as a four-bit GEMM distance (sweep_topk_gemm_bf16_pp<.., FP4>) */
+  VDB_KERNEL_F16 = 8192,           /* an IEEE f16 instance of a matrix-core family ran (VDB_SEARCH_BRUTE_F16): set NEXT TO the family's
+                                      bit — SWEEP_MFMA_BF16 / GEMM_BF16 / GEMM_BF16_GLDS then name the f16 instance of that kernel      */
+  VDB_KERNEL_SWEEP_HALF_L2 = 16384 /* sweep_topk_half_l2 (Euclidean difference chain over the f16 / bf16 rows)                        */
 };
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same

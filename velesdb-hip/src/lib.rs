@@ -110,6 +110,18 @@ fn c_path<P: AsRef<Path>>(p: P) -> io::Result<CString> {
         .map_err(|_| io::Error::new(io::ErrorKind::InvalidInput, "path contains a NUL byte"))
 }
 
+/// `VectorPrecision` (`half_precision.rs:36-44`), same discriminants as `enum vdb_vector_precision`.
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+#[repr(i32)]
+pub enum VectorPrecision {
+    /// What the index always keeps (4 bytes per element).
+    F32 = sys::VDB_PRECISION_F32,
+    /// IEEE binary16: round to nearest even, overflow to infinity beyond 65 504, subnormals kept.
+    F16 = sys::VDB_PRECISION_F16,
+    /// bfloat16: the upper half of an f32, round to nearest even.
+    BF16 = sys::VDB_PRECISION_BF16,
+}
+
 /// How a multi-GPU handle spreads its rows (`enum vdb_shard_mode`).
 #[derive(Debug, Clone, Copy, PartialEq, Eq)]
 pub enum ShardMode {
@@ -736,6 +748,14 @@ impl HipHnswIndex {
         check(unsafe { sys::vdb_hip_index_enable_bf16(self.h) });
     }
 
+    /// Keeps a half-precision copy of the rows (`VectorData::from_f32_slice(.., precision)`, `half_precision.rs:94-101`) for
+    /// [`Self::search_batch_brute_force_half`]: Cosine, DotProduct and Euclidean indexes; `VectorPrecision::F32` is refused
+    /// (the f32 rows are what the index always keeps).
+    pub fn enable_half_precision(&self, precision: VectorPrecision) {
+        // SAFETY: live handle.
+        check(unsafe { sys::vdb_hip_index_enable_half_precision(self.h, precision as i32) });
+    }
+
     fn search_batch_mode(&self, queries: &[&[f32]], k: usize, ef: usize, mode: i32) -> Vec<Vec<(u64, f32)>> {
         if queries.is_empty() || k == 0 {
             return queries.iter().map(|_| Vec::new()).collect();
@@ -770,6 +790,19 @@ impl HipHnswIndex {
     #[must_use]
     pub fn search_batch_brute_force_bf16(&self, queries: &[&[f32]], k: usize) -> Vec<Vec<(u64, f32)>> {
         self.search_batch_mode(queries, k, 0, sys::VDB_SEARCH_BRUTE_BF16)
+    }
+
+    /// Exact scan over the half-precision copy of the rows with queries rounded the same way: `half_precision::dot_product` /
+    /// `cosine_similarity` / `euclidean_distance` on `VectorData::{F16, BF16}` (`half_precision.rs:199-287`); needs
+    /// [`Self::enable_half_precision`] with the same precision.
+    #[must_use]
+    pub fn search_batch_brute_force_half(&self, queries: &[&[f32]], k: usize, precision: VectorPrecision) -> Vec<Vec<(u64, f32)>> {
+        let mode = match precision {
+            VectorPrecision::F16 => sys::VDB_SEARCH_BRUTE_F16,
+            VectorPrecision::BF16 => sys::VDB_SEARCH_BRUTE_BF16,
+            VectorPrecision::F32 => sys::VDB_SEARCH_BRUTE,
+        };
+        self.search_batch_mode(queries, k, 0, mode)
     }
 
     /// `StorageMode::SQ8` collections: asymmetric distances against the stored codes (`quantization.rs:410-554`).

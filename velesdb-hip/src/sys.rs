@@ -39,6 +39,12 @@ pub const VDB_SEARCH_BRUTE_BF16: i32 = 3;
 pub const VDB_SEARCH_HNSW_INT8: i32 = 4;
 pub const VDB_SEARCH_BRUTE_SQ8: i32 = 5;
 pub const VDB_SEARCH_BRUTE_BINARY: i32 = 6;
+pub const VDB_SEARCH_BRUTE_F16: i32 = 7;
+
+// enum vdb_vector_precision
+pub const VDB_PRECISION_F32: i32 = 0;
+pub const VDB_PRECISION_F16: i32 = 1;
+pub const VDB_PRECISION_BF16: i32 = 2;
 
 // enum vdb_storage_mode
 pub const VDB_STORAGE_FULL: i32 = 0;
@@ -80,6 +86,8 @@ pub const VDB_KERNEL_SQ8: i32 = 512;
 pub const VDB_KERNEL_HNSW: i32 = 1024;
 pub const VDB_KERNEL_HNSW_INT8: i32 = 2048;
 pub const VDB_KERNEL_BITS_GEMM: i32 = 4096;
+pub const VDB_KERNEL_F16: i32 = 8192;
+pub const VDB_KERNEL_SWEEP_HALF_L2: i32 = 16384;
 
 pub const VDB_COMM_ID_BYTES: usize = 128;
 
@@ -101,6 +109,7 @@ extern "C" {
     pub fn vdb_hip_index_set_storage_mode(idx: *mut VdbHipIndex, mode: i32) -> i32;
     pub fn vdb_hip_index_get_quantized(idx: *mut VdbHipIndex, id: u64, out: *mut u8, cap: usize, len: *mut usize) -> i32;
     pub fn vdb_hip_index_enable_bf16(idx: *mut VdbHipIndex) -> i32;
+    pub fn vdb_hip_index_enable_half_precision(idx: *mut VdbHipIndex, precision: i32) -> i32;
     pub fn vdb_hip_index_build_graph(idx: *mut VdbHipIndex, max_batch: u32) -> i32;
     pub fn vdb_hip_index_upload(idx: *mut VdbHipIndex, ids: *const u64, vecs_rowmajor: *const f32, n: u64, inserted: *mut u64) -> i32;
     pub fn vdb_hip_index_upload_dev(idx: *mut VdbHipIndex, id_base: u64, d_vecs_rowmajor: *const f32, n: u64, stream: *mut c_void) -> i32;

@@ -159,6 +159,10 @@ void copy_image_fields(vdb_hip_index* c, const vdb_hip_index* p) {
   c->bf16_enabled = p->bf16_enabled;
   c->bf16_stride = p->bf16_stride;
   c->bf16_rows = p->bf16_rows;
+  c->rows_f16 = p->rows_f16;
+  c->norms_f16 = p->norms_f16;
+  c->f16_enabled = p->f16_enabled;
+  c->f16_rows = p->f16_rows;
   c->l2_img = p->l2_img;
   c->l2_rho = p->l2_rho;
   c->l2_seed = p->l2_seed;
@@ -340,6 +344,9 @@ int32_t ensure_capacity(vdb_hip_index* ix, uint64_t want) {
   if (ix->bf16_enabled && ((e = ix->rows_bf16.reserve((ncap + kRowSlack) * ix->bf16_stride * 2, true, st)) != hipSuccess ||
                            (e = ix->norms_bf16.reserve((ncap + kRowSlack) * 4, true, st)) != hipSuccess))
     return fail(VDB_ERR_OOM, std::string("grow bf16 rows: ") + hipGetErrorString(e));
+  if (ix->f16_enabled && ((e = ix->rows_f16.reserve((ncap + kRowSlack) * ix->bf16_stride * 2, true, st)) != hipSuccess ||
+                          (e = ix->norms_f16.reserve((ncap + kRowSlack) * 4, true, st)) != hipSuccess))
+    return fail(VDB_ERR_OOM, std::string("grow f16 rows: ") + hipGetErrorString(e));
   // the lazily built selection images grow HERE (exclusive lock), never inside a search (shared lock: other contexts hold views)
   if (ix->l2_img.cap && (e = ix->l2_img.reserve((ncap + kRowSlack) * (size_t)(ix->dim + 64) * 2, true, st)) != hipSuccess)
     return fail(VDB_ERR_OOM, std::string("grow Euclidean selection image: ") + hipGetErrorString(e));
@@ -390,6 +397,11 @@ static int32_t finish_append(vdb_hip_index* ix, uint64_t first, uint64_t n) {
     launch_prep_bf16(ix->rows.as<float>(), ix->row_stride, ix->rows_bf16.as<uint16_t>(), ix->bf16_stride,
                      ix->norms_bf16.as<float>(), (uint32_t)first, (uint32_t)n, ix->dim, ix->stream, ix->bf16_rho.as<uint32_t>());
     ix->bf16_rows = first + n;
+  }
+  if (ix->f16_enabled) {
+    launch_prep_f16(ix->rows.as<float>(), ix->row_stride, ix->rows_f16.as<uint16_t>(), ix->bf16_stride, ix->norms_f16.as<float>(),
+                    (uint32_t)first, (uint32_t)n, ix->dim, ix->stream);
+    ix->f16_rows = first + n;
   }
   if (ix->split_enabled) {
     launch_split_vectors(ix->rows.as<float>(), ix->row_stride, ix->rows_split.as<uint16_t>(), nullptr, (uint32_t)first,
@@ -921,6 +933,7 @@ int32_t search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint3
   }
   if (mode == VDB_SEARCH_BRUTE) return brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
   if (mode == VDB_SEARCH_BRUTE_BF16) return brute_bf16_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  if (mode == VDB_SEARCH_BRUTE_F16) return brute_bf16_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st, /*f16=*/true);
   if (mode == VDB_SEARCH_BRUTE_SQ8) {
     // large Cosine / DotProduct batches: bf16 selection over the dequantised rows + the reference chain for the candidates +
     // proof (level 3); everything else, and what a handle's data defeats, on the exact SQ8 sweep
@@ -1013,6 +1026,7 @@ std::vector<DevBuf*> index_buffers(vdb_hip_index* ix) {
   std::vector<DevBuf*> v = {
       &ix->rows, &ix->norms, &ix->bits, &ix->alive, &ix->ext_ids,           // rows
       &ix->rows_bf16, &ix->norms_bf16, &ix->bf16_rho, &ix->rows_split,      // bf16 copy, split-bf16 image
+      &ix->rows_f16, &ix->norms_f16,                                        // f16 copy
       &ix->l2_img, &ix->l2_seed, &ix->l2_rho,                               // Euclidean selection images
       &ix->cosn_img, &ix->cosn_rho,                                         // Cosine selection image (normalised rows)
       &ix->sq_min, &ix->sq_scale, &ix->codes, &ix->codes_sq,                // int8 traversal
@@ -1473,21 +1487,31 @@ int32_t vdb_hip_set_int8_oversampling(uint32_t ratio) {
   });
 }
 
-// keeps a bf16 copy of the rows (round to nearest even) for VDB_SEARCH_BRUTE_BF16; existing rows are converted now,
-// later inserts / uploads as they arrive
-int32_t vdb_hip_index_enable_bf16(vdb_hip_index* ix) {
-  return vdb::guarded([&]() -> int32_t {
-  if (!ix) return fail(VDB_ERR_INVALID_ARG, "null argument");
-  if (ix->group) return group_for_all(ix, 1, 0);
-  std::lock_guard<vdb::IndexMutex> g(ix->mu);
-  if (ix->bf16_enabled) return VDB_OK;
-  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT)
-    return fail(VDB_ERR_UNSUPPORTED, "bf16 sweep: Cosine and DotProduct only");
+// keeps a half-precision copy of the rows (VectorData::from_f32_slice, half_precision.rs:94-101: round to nearest even) for
+// VDB_SEARCH_BRUTE_BF16 / VDB_SEARCH_BRUTE_F16; existing rows are converted now, later inserts / uploads as they arrive.
+// (caller: exclusive lock held, metric checked)
+static int32_t enable_half_locked(vdb_hip_index* ix, int32_t precision) {
+  if (precision == VDB_PRECISION_BF16 ? ix->bf16_enabled : ix->f16_enabled) return VDB_OK;
   VDB_ENTER(ix);
-  ix->bf16_stride = ((uint64_t)ix->dim + 7) / 8 * 8;
+  ix->bf16_stride = ((uint64_t)ix->dim + 7) / 8 * 8;  // (both copies: dim rounded up to 16 bytes, zero-padded)
+  const size_t cap_rows = std::max<uint64_t>(ix->capacity, 1) + kRowSlack;
   hipError_t e;
-  if ((e = ix->rows_bf16.reserve((std::max<uint64_t>(ix->capacity, 1) + kRowSlack) * ix->bf16_stride * 2, false, ix->stream)) != hipSuccess ||
-      (e = ix->norms_bf16.reserve((std::max<uint64_t>(ix->capacity, 1) + kRowSlack) * 4, false, ix->stream)) != hipSuccess)
+  if (precision == VDB_PRECISION_F16) {
+    if ((e = ix->rows_f16.reserve(cap_rows * ix->bf16_stride * 2, false, ix->stream)) != hipSuccess ||
+        (e = ix->norms_f16.reserve(cap_rows * 4, false, ix->stream)) != hipSuccess)
+      return fail(VDB_ERR_OOM, std::string("f16 rows: ") + hipGetErrorString(e));
+    ix->f16_enabled = true;
+    if (ix->n_rows) {
+      launch_prep_f16(ix->rows.as<float>(), ix->row_stride, ix->rows_f16.as<uint16_t>(), ix->bf16_stride, ix->norms_f16.as<float>(), 0,
+                      (uint32_t)ix->n_rows, ix->dim, ix->stream);
+      VDB_HIP(hipGetLastError());
+      VDB_HIP(hipStreamSynchronize(ix->stream));
+    }
+    ix->f16_rows = ix->n_rows;
+    return VDB_OK;
+  }
+  if ((e = ix->rows_bf16.reserve(cap_rows * ix->bf16_stride * 2, false, ix->stream)) != hipSuccess ||
+      (e = ix->norms_bf16.reserve(cap_rows * 4, false, ix->stream)) != hipSuccess)
     return fail(VDB_ERR_OOM, std::string("bf16 rows: ") + hipGetErrorString(e));
   {
     const int32_t rr = reset_bf16_rho(ix, ix->stream);
@@ -1502,6 +1526,28 @@ int32_t vdb_hip_index_enable_bf16(vdb_hip_index* ix) {
   }
   ix->bf16_rows = ix->n_rows;
   return VDB_OK;
+}
+int32_t vdb_hip_index_enable_bf16(vdb_hip_index* ix) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix) return fail(VDB_ERR_INVALID_ARG, "null argument");
+  if (ix->group) return group_for_all(ix, 1, 0);
+  std::lock_guard<vdb::IndexMutex> g(ix->mu);
+  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT)
+    return fail(VDB_ERR_UNSUPPORTED, "bf16 sweep: Cosine and DotProduct only");
+  return enable_half_locked(ix, VDB_PRECISION_BF16);
+  });
+}
+// VectorPrecision::{F16, BF16} for Cosine, DotProduct and Euclidean handles
+int32_t vdb_hip_index_enable_half_precision(vdb_hip_index* ix, int32_t precision) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix) return fail(VDB_ERR_INVALID_ARG, "null argument");
+  if (precision == VDB_PRECISION_F32) return fail(VDB_ERR_UNSUPPORTED, "half precision: F32 is what the index always keeps");
+  if (precision != VDB_PRECISION_F16 && precision != VDB_PRECISION_BF16) return fail(VDB_ERR_INVALID_ARG, "bad vector precision");
+  if (ix->group) return group_for_all(ix, 4, precision);
+  std::lock_guard<vdb::IndexMutex> g(ix->mu);
+  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, "half precision: Cosine, DotProduct and Euclidean only");
+  return enable_half_locked(ix, precision);
   });
 }
 
@@ -1686,6 +1732,7 @@ int32_t vdb_hip_index_vacuum(vdb_hip_index* ix, uint64_t* count) {
   ix->any_dead = false;
   ix->n_rows = 0;
   ix->bf16_rows = 0;
+  ix->f16_rows = 0;
   ix->split_rows = 0;
   ix->l2_rows = 0;
   ix->cosn_rows = 0;

@@ -41,18 +41,65 @@ static bool gemm_bf16_glds_enabled() {
 }
 
 
-// exact sweep over the bf16 copy of the rows: half_precision::dot_product / cosine_similarity semantics
-// (half_precision.rs:199-255) for nq device-resident f32 queries (rounded to bf16 by the kernel)
+// Euclidean over a half copy (half_precision::euclidean_distance, half_precision.rs:257-287): the streaming difference-chain sweep of
+// sweep_half_l2.hip for every batch size — query tiles of 16 (4 / 1 where LDS or the batch is smaller), the corpus re-read per tile
+static int32_t brute_half_l2_dev(vdb_hip_index* ix, const uint16_t* rows16, bool f16, const float* d_q, uint64_t q_stride, uint32_t nq,
+                                 uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
+  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  ix->last_kernels |= VDB_KERNEL_SWEEP_HALF_L2;
+  for (uint32_t q0 = 0; q0 < nq;) {
+    const uint32_t rem = nq - q0;
+    int B = rem > 4 ? 16 : (rem > 1 ? 4 : 1);
+    while (B > 1 && sweep_half_l2_lds_bytes(B, k, ix->dim) > 160 * 1024) B /= 4;
+    const size_t lds = sweep_half_l2_lds_bytes(B, k, ix->dim);
+    if (lds > 160 * 1024) return fail(VDB_ERR_UNSUPPORTED, "half-precision Euclidean sweep: dim / k too large for the LDS query tile");
+    const uint32_t tile = std::min<uint32_t>((uint32_t)B, rem);
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 3));  // (three 4-wave blocks per CU: the kernel runs at 3 waves per SIMD)
+    const uint32_t ngroups = (uint32_t)((ix->n_rows + (64 / B) - 1) / (64 / B));
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)ngroups + 3) / 4, (int64_t)ix->n_cus * per_cu));
+    if (ix->s_part_keys.reserve((size_t)B * blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+    EventPair* ev = next_events(ix);
+    if (ev) (void)hipEventRecord(ev->a, st);
+    const hipError_t e = launch_sweep_half_l2(f16, B, rows16, ix->bf16_stride, alive, d_q + (size_t)q0 * q_stride, q_stride,
+                                              ix->s_part_keys.as<uint64_t>(), (uint32_t)ix->n_rows, ix->dim, tile, k, blocks, st);
+    if (ev) (void)hipEventRecord(ev->b, st);
+    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("half-precision Euclidean sweep launch: ") + hipGetErrorString(e));
+    MergeArgs m{};
+    m.part_keys = ix->s_part_keys.as<uint64_t>();
+    m.ext_ids = ix->ext_ids.as<uint64_t>();
+    m.out_ids = d_ids + (size_t)q0 * k;
+    m.out_scores = d_scores + (size_t)q0 * k;
+    m.out_n = d_n + q0;
+    m.n_lists = (uint32_t)blocks;
+    m.k = k;
+    launch_merge(false, m, tile, st);
+    q0 += tile;
+  }
+  VDB_HIP(hipGetLastError());
+  return VDB_OK;
+}
+
+// exact sweep over a half-precision copy of the rows: half_precision::dot_product / cosine_similarity / euclidean_distance semantics
+// (half_precision.rs:199-287) for nq device-resident f32 queries (rounded to the precision on the device); f16: the IEEE f16 copy and
+// the f16 instances of the same kernels (VDB_SEARCH_BRUTE_F16), else the bf16 copy
 int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k,
-                              uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
-  if (!ix->bf16_enabled) return fail(VDB_ERR_STATE, "bf16 sweep: call vdb_hip_index_enable_bf16 first");
-  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT)
-    return fail(VDB_ERR_UNSUPPORTED, "bf16 sweep: Cosine and DotProduct only");
+                              uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st, bool f16) {
+  if (f16) {
+    if (!ix->f16_enabled) return fail(VDB_ERR_STATE, "f16 sweep: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
+  } else if (!ix->bf16_enabled) {
+    return fail(VDB_ERR_STATE, "bf16 sweep: call vdb_hip_index_enable_bf16 first");
+  }
+  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, "half-precision sweep: Cosine, DotProduct and Euclidean only");
   if (nq == 0) return VDB_OK;
   if (k == 0 || ix->n_rows == 0) {
     VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
     return VDB_OK;
   }
+  const uint16_t* rows16 = f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>();
+  const float* norms16 = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
+  if (ix->metric == VDB_EUCLIDEAN) return brute_half_l2_dev(ix, rows16, f16, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  if (f16) ix->last_kernels |= VDB_KERNEL_F16;
   const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
   for (uint32_t q0 = 0; q0 < nq;) {
     const uint32_t rem = nq - q0;
@@ -95,17 +142,17 @@ int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
         uint64_t* tau0 = reinterpret_cast<uint64_t*>(sd + off_tau);
         const uint16_t* q16 = ix->s_misc.as<uint16_t>();
         launch_round_queries_bf16(d_q + (size_t)q0 * q_stride, q_stride, ix->s_misc.as<uint16_t>(), ix->bf16_stride, nqg,
-                                  ix->dim, st);
+                                  ix->dim, st, f16);
         float* qn_half = reinterpret_cast<float*>(sd + off_qn);  // norms of the rounded queries, once per batch
-        launch_query_norms_bf16(q16, ix->bf16_stride, qn_half, nqg, ix->dim, st);
+        launch_query_norms_bf16(q16, ix->bf16_stride, qn_half, nqg, ix->dim, st, f16);
         // the 256 x 256 kernel stages whole 256-query tiles: zero rows behind the batch
         VDB_HIP(hipMemsetAsync(ix->s_misc.as<uint16_t>() + (size_t)nqg * ix->bf16_stride, 0, (size_t)256 * ix->bf16_stride * 2, st));
         VDB_HIP(hipMemsetAsync(parts, 0xFF, (size_t)nqg * lists * k * 8, st));  // every slot: kKeyInvalid
         ix->last_kernels |= VDB_KERNEL_GEMM_BF16_GLDS | VDB_KERNEL_GEMM_BF16;  // (the seed prefix: the 128 x 128 kernel)
         EventPair* evg = next_events(ix);
         if (evg) (void)hipEventRecord(evg->a, st);
-        e3 = launch_sweep_gemm_bf16(ix->metric, sp, ix->rows_bf16.as<uint16_t>(), ix->bf16_stride, ix->norms_bf16.as<float>(),
-                                    alive, q16, ix->bf16_stride, reinterpret_cast<uint64_t*>(sd), R0, ix->dim, nqg, k, st);
+        e3 = launch_sweep_gemm_bf16(ix->metric, sp, rows16, ix->bf16_stride, norms16,
+                                    alive, q16, ix->bf16_stride, reinterpret_cast<uint64_t*>(sd), R0, ix->dim, nqg, k, st, f16);
         if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 seed sweep launch: ") + hipGetErrorString(e3));
         MergeArgs ms{};
         ms.part_keys = reinterpret_cast<const uint64_t*>(sd);
@@ -118,7 +165,7 @@ int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
         launch_merge(true, ms, nqg, st);
         launch_seed_tau(ms.out_ids, ms.out_scores, ms.out_n, tau0, parts, lists, nqg, k, st);  // list 0 = the seed's top-k
         e3 = run_gemm_schedule(
-            sch, ix->metric, ix->rows_bf16.as<uint16_t>(), ix->bf16_stride, ix->norms_bf16.as<float>(), alive, q16, ix->bf16_stride, tau0, parts, lists,
+            sch, ix->metric, rows16, ix->bf16_stride, norms16, alive, q16, ix->bf16_stride, tau0, parts, lists,
             /*list_first=*/1, ix->dim, nqg, k, st, /*split=*/false, nullptr, nullptr, qn_half, [](int) {},
             [&](int, uint32_t, bool last) {
               if (last) return;  // bound for the next launch: k-th best key over everything swept so far
@@ -126,7 +173,8 @@ int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
               ms.n_lists = lists;
               launch_merge(true, ms, nqg, st);
               launch_seed_tau(ms.out_ids, ms.out_scores, ms.out_n, tau0, nullptr, 0, nqg, k, st);
-            });
+            },
+            f16);
         if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 gemm sweep launch: ") + hipGetErrorString(e3));
         if (evg) (void)hipEventRecord(evg->b, st);
         MergeArgs mg{};
@@ -154,13 +202,13 @@ int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
             (e3 = ix->s_misc.reserve((size_t)nqg * ix->bf16_stride * 2, false, st)) != hipSuccess)
           return fail(VDB_ERR_OOM, "bf16 GEMM scratch");
         launch_round_queries_bf16(d_q + (size_t)q0 * q_stride, q_stride, ix->s_misc.as<uint16_t>(), ix->bf16_stride, nqg,
-                                  ix->dim, st);
+                                  ix->dim, st, f16);
         ix->last_kernels |= VDB_KERNEL_GEMM_BF16;
         EventPair* evg = next_events(ix);
         if (evg) (void)hipEventRecord(evg->a, st);
-        e3 = launch_sweep_gemm_bf16(ix->metric, gp, ix->rows_bf16.as<uint16_t>(), ix->bf16_stride, ix->norms_bf16.as<float>(),
+        e3 = launch_sweep_gemm_bf16(ix->metric, gp, rows16, ix->bf16_stride, norms16,
                                     alive, ix->s_misc.as<uint16_t>(), ix->bf16_stride, ix->s_part_keys.as<uint64_t>(),
-                                    (uint32_t)ix->n_rows, ix->dim, nqg, k, st);
+                                    (uint32_t)ix->n_rows, ix->dim, nqg, k, st, f16);
         if (evg) (void)hipEventRecord(evg->b, st);
         if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 gemm sweep launch: ") + hipGetErrorString(e3));
         MergeArgs mg{};
@@ -194,9 +242,9 @@ int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
     EventPair* ev = next_events(ix);
     if (ev) (void)hipEventRecord(ev->a, st);
     ix->last_kernels |= VDB_KERNEL_SWEEP_MFMA_BF16;
-    e = launch_sweep_bf16(ix->metric, nqt, ix->rows_bf16.as<uint16_t>(), ix->bf16_stride, ix->norms_bf16.as<float>(),
+    e = launch_sweep_bf16(ix->metric, nqt, rows16, ix->bf16_stride, norms16,
                           alive, d_q + (size_t)q0 * q_stride, q_stride, ix->s_part_keys.as<uint64_t>(),
-                          (uint32_t)ix->n_rows, ix->dim, tile, k, blocks, st);
+                          (uint32_t)ix->n_rows, ix->dim, tile, k, blocks, st, f16);
     if (ev) (void)hipEventRecord(ev->b, st);
     if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 sweep launch: ") + hipGetErrorString(e));
     MergeArgs m{};

@@ -422,6 +422,7 @@ int32_t group_for_all(vdb_hip_index* ix, int op, uint32_t arg) {
       case 0: return vdb_hip_index_build_graph(c, arg);
       case 1: return vdb_hip_index_enable_bf16(c);
       case 2: return vdb_hip_index_set_storage_mode(c, (int32_t)arg);
+      case 4: return vdb_hip_index_enable_half_precision(c, (int32_t)arg);
       default: return vdb_hip_index_train_quantizer(c, arg);
     }
   });

@@ -612,11 +612,20 @@ __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
   return (uint16_t)(u >> 16);
 }
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
+// IEEE binary16 (half::f16::from_f32): v_cvt_f16_f32 — round to nearest even, overflow to +-inf beyond 65 504, gradual underflow to
+// f16 subnormals (the code object keeps 16-bit denormals), NaN stays NaN; the way back is exact
+__device__ __forceinline__ uint16_t f32_to_f16_rne(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
+__device__ __forceinline__ float f16_to_f32(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+template <bool F16>
+__device__ __forceinline__ uint16_t f32_to_half(float f) { return F16 ? f32_to_f16_rne(f) : f32_to_bf16_rne(f); }
+template <bool F16>
+__device__ __forceinline__ float half_to_f32(uint16_t h) { return F16 ? f16_to_f32(h) : bf16_to_f32(h); }
 
 // rows f32 -> bf16 copy + norm of the ROUNDED row (canonical lane-chain order over the rounded values); rho_max_bits != nullptr:
 // the row's rounding residual ratio |x - bf16(x)| / |x| (f64 sums: no f32 row underflows them) raises a device scalar — the
 // measured error bound of the level-2 selection (sweep_split.hip select_eps_q).  Rows with non-finite elements contribute
 // nothing: their scores are non-finite too and never proven.
+template <bool F16>
 __global__ __launch_bounds__(256) void prep_bf16_rows(const float* rows, uint64_t row_stride, uint16_t* out,
                                                       uint64_t out_stride, float* norms, uint32_t row0, uint32_t n_rows,
                                                       uint32_t dim, uint32_t* rho_max_bits) {
@@ -635,10 +644,10 @@ __global__ __launch_bounds__(256) void prep_bf16_rows(const float* rows, uint64_
         const uint32_t i = c * 4 + e;
         if (i < out_stride) {
           const float v = i < dim ? p[i] : 0.0f;
-          const uint16_t h = i < dim ? f32_to_bf16_rne(v) : (uint16_t)0;
+          const uint16_t h = i < dim ? f32_to_half<F16>(v) : (uint16_t)0;
           o[i] = h;
           if (i < dim) {
-            const float x = bf16_to_f32(h);
+            const float x = half_to_f32<F16>(h);
             acc = __builtin_fmaf(x, x, acc);
             if (rho_max_bits) {
               const float d = v - x;  // exact in f32
@@ -675,7 +684,10 @@ struct Bf16SweepArgs {
   uint32_t n_rows, dim, nq, k, KU;
 };
 
-template <int METRIC, int NQT, int WAVES>
+// F16: the same kernel over the IEEE f16 copy of the rows (VDB_SEARCH_BRUTE_F16): the conversion and v_mfma_f32_16x16x32_f16 — same
+// fragments, same lane maps — are the only differences.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+template <int METRIC, int NQT, int WAVES, bool F16 = false>
 __global__ __launch_bounds__(WAVES * 64, (WAVES == 16 ? 4 : 2)) void sweep_topk_mfma_bf16(Bf16SweepArgs a) {
   constexpr int B = NQT * 16;
   constexpr bool HIB = true;
@@ -704,7 +716,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 16 ? 4 : 2)) void sweep_topk_
     const uint32_t b = idx / a.dim, kx = idx % a.dim;
     if (b < a.nq) {
       const uint32_t t = b >> 4, j = b & 15, U = kx >> 8, m = (kx >> 5) & 7, kk = (kx >> 3) & 3, e = kx & 7;
-      qs[((((size_t)U * NQT + t) * 8 + m) * 64 + kk * 16 + j) * 8 + e] = f32_to_bf16_rne(a.queries[(size_t)b * a.q_stride + kx]);
+      qs[((((size_t)U * NQT + t) * 8 + m) * 64 + kk * 16 + j) * 8 + e] = f32_to_half<F16>(a.queries[(size_t)b * a.q_stride + kx]);
     }
   }
   if (METRIC == kCosine) {  // norm of the ROUNDED query, canonical lane-chain order
@@ -716,7 +728,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 16 ? 4 : 2)) void sweep_topk_
         for (int e = 0; e < 4; e++) {
           const uint32_t i = c * 4 + e;
           if (i < a.dim) {
-            const float x = bf16_to_f32(f32_to_bf16_rne(qp[i]));
+            const float x = half_to_f32<F16>(f32_to_half<F16>(qp[i]));
             nacc = __builtin_fmaf(x, x, nacc);
           }
         }
@@ -765,11 +777,13 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 16 ? 4 : 2)) void sweep_topk_
       const uint16_t* qb = qs + ((size_t)U * NQT * 8 * 64 + lane) * 8;
 #pragma unroll
       for (int m = 0; m < 8; m++) {
-        const bf16x8 afrag = __builtin_bit_cast(bf16x8, av[m]);
 #pragma unroll
         for (int t = 0; t < NQT; t++) {
           const uint4 bu = *reinterpret_cast<const uint4*>(qb + (size_t)(t * 8 + m) * 512);
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afrag, __builtin_bit_cast(bf16x8, bu), acc[t], 0, 0, 0);
+          if (F16)
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av[m]), __builtin_bit_cast(f16x8, bu), acc[t], 0, 0, 0);
+          else
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av[m]), __builtin_bit_cast(bf16x8, bu), acc[t], 0, 0, 0);
         }
       }
     };
@@ -2110,40 +2124,45 @@ void launch_prep_bf16(const float* rows, uint64_t row_stride, uint16_t* out, uin
                       uint32_t row0, uint32_t n_rows, uint32_t dim, hipStream_t st, uint32_t* rho_max_bits) {
   if (n_rows == 0) return;
   const int blocks = (int)std::min<uint64_t>(((uint64_t)n_rows + 3) / 4, 4096);
-  hipLaunchKernelGGL(prep_bf16_rows, dim3(blocks), dim3(256), 0, st, rows, row_stride, out, out_stride, norms, row0,
+  hipLaunchKernelGGL(prep_bf16_rows<false>, dim3(blocks), dim3(256), 0, st, rows, row_stride, out, out_stride, norms, row0,
                      n_rows, dim, rho_max_bits);
 }
-template <int METRIC, int NQT, int WAVES>
+void launch_prep_f16(const float* rows, uint64_t row_stride, uint16_t* out, uint64_t out_stride, float* norms,
+                     uint32_t row0, uint32_t n_rows, uint32_t dim, hipStream_t st) {
+  if (n_rows == 0) return;
+  const int blocks = (int)std::min<uint64_t>(((uint64_t)n_rows + 3) / 4, 4096);
+  hipLaunchKernelGGL(prep_bf16_rows<true>, dim3(blocks), dim3(256), 0, st, rows, row_stride, out, out_stride, norms, row0,
+                     n_rows, dim, (uint32_t*)nullptr);
+}
+template <int METRIC, int NQT, int WAVES, bool F16>
 static hipError_t launch_bf16_t(const Bf16SweepArgs& a, int blocks, size_t lds, hipStream_t st) {
   static bool done = false;
   if (lds > 64 * 1024 && !done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_mfma_bf16<METRIC, NQT, WAVES>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_mfma_bf16<METRIC, NQT, WAVES, F16>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     done = true;
   }
-  hipLaunchKernelGGL((sweep_topk_mfma_bf16<METRIC, NQT, WAVES>), dim3(blocks), dim3(WAVES * 64), lds, st, a);
+  hipLaunchKernelGGL((sweep_topk_mfma_bf16<METRIC, NQT, WAVES, F16>), dim3(blocks), dim3(WAVES * 64), lds, st, a);
   return hipGetLastError();
+}
+template <int METRIC, bool F16>
+static hipError_t launch_bf16_m(int nqt, const Bf16SweepArgs& a, int blocks, size_t lds, hipStream_t st) {
+  switch (nqt) {
+    case 6: return launch_bf16_t<METRIC, 6, kBf16WavesBig, F16>(a, blocks, lds, st);
+    case 4: return launch_bf16_t<METRIC, 4, kBf16WavesBig, F16>(a, blocks, lds, st);
+    case 2: return launch_bf16_t<METRIC, 2, kBf16WavesSmall, F16>(a, blocks, lds, st);
+    default: return launch_bf16_t<METRIC, 1, kBf16WavesSmall, F16>(a, blocks, lds, st);
+  }
 }
 hipError_t launch_sweep_bf16(int metric, int nqt, const uint16_t* rows, uint64_t row_stride, const float* norms,
                              const uint8_t* alive, const float* queries, uint64_t q_stride, uint64_t* part_keys,
-                             uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks, hipStream_t st) {
+                             uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks, hipStream_t st, bool f16) {
   Bf16SweepArgs a{rows, norms, alive, queries, part_keys, row_stride, q_stride, n_rows, dim, nq, k, (dim + 255) / 256};
   const size_t lds = sweep_bf16_lds_bytes(nqt, k, dim);
-  if (metric == kCosine) {
-    switch (nqt) {
-      case 6: return launch_bf16_t<kCosine, 6, kBf16WavesBig>(a, blocks, lds, st);
-      case 4: return launch_bf16_t<kCosine, 4, kBf16WavesBig>(a, blocks, lds, st);
-      case 2: return launch_bf16_t<kCosine, 2, kBf16WavesSmall>(a, blocks, lds, st);
-      default: return launch_bf16_t<kCosine, 1, kBf16WavesSmall>(a, blocks, lds, st);
-    }
-  }
-  switch (nqt) {
-    case 6: return launch_bf16_t<kDot, 6, kBf16WavesBig>(a, blocks, lds, st);
-    case 4: return launch_bf16_t<kDot, 4, kBf16WavesBig>(a, blocks, lds, st);
-    case 2: return launch_bf16_t<kDot, 2, kBf16WavesSmall>(a, blocks, lds, st);
-    default: return launch_bf16_t<kDot, 1, kBf16WavesSmall>(a, blocks, lds, st);
-  }
+  if (f16)
+    return metric == kCosine ? launch_bf16_m<kCosine, true>(nqt, a, blocks, lds, st) : launch_bf16_m<kDot, true>(nqt, a, blocks, lds, st);
+  return metric == kCosine ? launch_bf16_m<kCosine, false>(nqt, a, blocks, lds, st) : launch_bf16_m<kDot, false>(nqt, a, blocks, lds, st);
 }
 
 void launch_euclid_rerank(const EuclidRerankArgs& a, const float* norms, uint32_t n_rows, uint32_t nq, hipStream_t st) {

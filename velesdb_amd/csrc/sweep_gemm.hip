@@ -99,8 +99,10 @@ __device__ __forceinline__ float select_acc(const f32x4 (&acc)[RF][NQF], uint32_
 // read / staging instruction / barrier, half the row re-reads — the bf16 multiply is 16x cheaper per element than the
 // exact-f32 one, so there the per-step instruction overhead is what bounds the kernel.  (The f32 instance of the big
 // tile was measured too: bit-identical, 120.6 vs 122.8 TFLOP/s at 1 024 queries — not kept.)
-template <int METRIC, int NQF, bool QVEC, bool FULL, bool BF16, int RF = 4, int WAVES = 4>
+// F16 (with BF16 = "two-byte elements"): the IEEE f16 copy and v_mfma_f32_16x16x32_f16 (VDB_SEARCH_BRUTE_F16), nothing else differs.
+template <int METRIC, int NQF, bool QVEC, bool FULL, bool BF16, int RF = 4, int WAVES = 4, bool F16 = false>
 __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 1 : 2) void sweep_topk_gemm_f32(GemmSweepArgs ga) {
+  static_assert(!F16 || BF16, "the f16 instance is a two-byte instance");
   static_assert(!BF16 || FULL, "the bf16 variant has no zero-fill path");
   static_assert((RF == 4 && WAVES == 4) || (RF == 8 && WAVES == 8 && NQF == 4 && BF16), "supported tile shapes");
   constexpr int ES = BF16 ? 2 : 4;        // bytes per element in HBM
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 1 : 2) void sweep_topk_gem
         for (int e = 0; e < 4; e++) {
           const uint32_t i = c * 4 + e;
           if (i < a.dim) {
-            const float x = __uint_as_float((uint32_t)qp[i] << 16);
+            const float x = F16 ? (float)__builtin_bit_cast(_Float16, qp[i]) : __uint_as_float((uint32_t)qp[i] << 16);
             nacc = __builtin_fmaf(x, x, nacc);
           }
         }
@@ -388,14 +390,17 @@ _Pragma("unroll") \
       __builtin_amdgcn_s_setprio(0);
       if (BF16) {
         typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+        typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 #pragma unroll
         for (int m = 0; m < MB; m++)
 #pragma unroll
           for (int rf = 0; rf < RF; rf++)
 #pragma unroll
             for (int t = 0; t < NQF; t++)
-              acc[rf][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av[m][rf]),
-                                                                  __builtin_bit_cast(bf16x8, bv[m][t]), acc[rf][t], 0, 0, 0);
+              acc[rf][t] = F16 ? __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av[m][rf]),
+                                                                        __builtin_bit_cast(f16x8, bv[m][t]), acc[rf][t], 0, 0, 0)
+                               : __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av[m][rf]),
+                                                                         __builtin_bit_cast(bf16x8, bv[m][t]), acc[rf][t], 0, 0, 0);
       } else {
 #pragma unroll
       for (int m = 0; m < MB; m++) {
@@ -631,16 +636,16 @@ void sweep_gemm_plan(uint32_t nq, uint32_t n_rows, int n_cus, uint32_t k, GemmPl
   p->blocks = (int)(G * p->nqt);
 }
 
-template <int METRIC, int NQF, bool QVEC, bool FULL, bool BF16, int RF = 4, int WAVES = 4>
+template <int METRIC, int NQF, bool QVEC, bool FULL, bool BF16, int RF = 4, int WAVES = 4, bool F16 = false>
 static hipError_t launch_gemm_v(const GemmSweepArgs& ga, int blocks, size_t lds, hipStream_t st) {
   static bool done = false;
   if (lds > 64 * 1024 && !done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_gemm_f32<METRIC, NQF, QVEC, FULL, BF16, RF, WAVES>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_gemm_f32<METRIC, NQF, QVEC, FULL, BF16, RF, WAVES, F16>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     done = true;
   }
-  hipLaunchKernelGGL((sweep_topk_gemm_f32<METRIC, NQF, QVEC, FULL, BF16, RF, WAVES>), dim3(blocks), dim3(WAVES * 64), lds, st, ga);
+  hipLaunchKernelGGL((sweep_topk_gemm_f32<METRIC, NQF, QVEC, FULL, BF16, RF, WAVES, F16>), dim3(blocks), dim3(WAVES * 64), lds, st, ga);
   return hipGetLastError();
 }
 template <int METRIC, int NQF>
@@ -684,6 +689,7 @@ hipError_t launch_sweep_gemm(int metric, const GemmPlan& p, const SweepArgs& a, 
 
 // ---- bf16 variant: rows16 / queries16 are bf16 (uint16), strides in elements, dim % 64 == 0 ----
 // round-to-nearest-even copy of the query batch (VectorData::from_f32_slice(.., BF16), half_precision.rs:94-101)
+template <bool F16>
 __global__ __launch_bounds__(256) void round_queries_bf16(const float* q, uint64_t q_stride, uint16_t* out, uint64_t out_stride,
                                                           uint32_t nq, uint32_t dim) {
   const uint64_t n = (uint64_t)nq * out_stride;
@@ -692,7 +698,9 @@ __global__ __launch_bounds__(256) void round_queries_bf16(const float* q, uint64
     uint16_t h = 0;
     if (d < dim) {
       uint32_t u = __float_as_uint(q[(size_t)b * q_stride + d]);
-      if ((u & 0x7FFFFFFFu) > 0x7F800000u) {
+      if (F16) {  // IEEE f16: v_cvt_f16_f32 (round to nearest even, overflow to inf, subnormals kept)
+        h = __builtin_bit_cast(uint16_t, (_Float16)__uint_as_float(u));
+      } else if ((u & 0x7FFFFFFFu) > 0x7F800000u) {
         h = (uint16_t)((u >> 16) | 0x0040u);  // NaN stays NaN (quiet)
       } else {
         u += 0x7FFFu + ((u >> 16) & 1u);
@@ -703,16 +711,19 @@ __global__ __launch_bounds__(256) void round_queries_bf16(const float* q, uint64
   }
 }
 void launch_round_queries_bf16(const float* q, uint64_t q_stride, uint16_t* out, uint64_t out_stride, uint32_t nq,
-                               uint32_t dim, hipStream_t st) {
+                               uint32_t dim, hipStream_t st, bool f16) {
   const uint64_t n = (uint64_t)nq * out_stride;
-  hipLaunchKernelGGL(round_queries_bf16, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, q,
-                     q_stride, out, out_stride, nq, dim);
+  const dim3 grid((unsigned)std::min<uint64_t>((n + 255) / 256, 4096));
+  if (f16)
+    hipLaunchKernelGGL(round_queries_bf16<true>, grid, dim3(256), 0, st, q, q_stride, out, out_stride, nq, dim);
+  else
+    hipLaunchKernelGGL(round_queries_bf16<false>, grid, dim3(256), 0, st, q, q_stride, out, out_stride, nq, dim);
 }
 
 hipError_t launch_sweep_gemm_bf16(int metric, const GemmPlan& p, const uint16_t* rows16, uint64_t row_stride,
                                   const float* norms, const uint8_t* alive, const uint16_t* queries16, uint64_t q_stride,
                                   uint64_t* part_keys, uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k,
-                                  hipStream_t st) {
+                                  hipStream_t st, bool f16) {
   GemmSweepArgs ga;
   ga.s = SweepArgs{};
   ga.s.rows = reinterpret_cast<const float*>(rows16);        // bytes; the kernel addresses them as ES = 2
@@ -732,6 +743,23 @@ hipError_t launch_sweep_gemm_bf16(int metric, const GemmPlan& p, const uint16_t*
   ga.qper = p.qper;
   ga.cap = sweep_gemm_cap(k);
   ga.tile_needed = nullptr;
+  if (f16) {  // the IEEE f16 instances (VDB_SEARCH_BRUTE_F16)
+    if (p.big)
+      return metric == kCosine ? launch_gemm_v<kCosine, 4, true, true, true, 8, 8, true>(ga, p.blocks, p.lds, st)
+                               : launch_gemm_v<kDot, 4, true, true, true, 8, 8, true>(ga, p.blocks, p.lds, st);
+    if (metric == kCosine) {
+      switch (p.nqf) {
+        case 2: return launch_gemm_v<kCosine, 2, true, true, true, 4, 4, true>(ga, p.blocks, p.lds, st);
+        case 3: return launch_gemm_v<kCosine, 3, true, true, true, 4, 4, true>(ga, p.blocks, p.lds, st);
+        default: return launch_gemm_v<kCosine, 4, true, true, true, 4, 4, true>(ga, p.blocks, p.lds, st);
+      }
+    }
+    switch (p.nqf) {
+      case 2: return launch_gemm_v<kDot, 2, true, true, true, 4, 4, true>(ga, p.blocks, p.lds, st);
+      case 3: return launch_gemm_v<kDot, 3, true, true, true, 4, 4, true>(ga, p.blocks, p.lds, st);
+      default: return launch_gemm_v<kDot, 4, true, true, true, 4, 4, true>(ga, p.blocks, p.lds, st);
+    }
+  }
   if (p.big)
     return metric == kCosine ? launch_gemm_v<kCosine, 4, true, true, true, 8, 8>(ga, p.blocks, p.lds, st)
                              : launch_gemm_v<kDot, 4, true, true, true, 8, 8>(ga, p.blocks, p.lds, st);

@@ -436,17 +436,21 @@ _Pragma("unroll") \
 // accumulation registers ("+a"): the epilogue's quick test then paid one v_accvgpr_read per accumulator, 128 per wave and row tile,
 // its floor.  Same k-loop, instruction for instruction; measured on one box, same run (profiles/r05b_accv_ab.log): selection
 // launches of a 1 024-query step 1.534-1.547 -> 1.463-1.474 ms, step 1.753 -> 1.671 ms, the 10 M bf16 batch 13.87-13.95 -> 13.26-13.30 ms.
-template <bool FP4>
+template <bool FP4, bool F16>
 __device__ __forceinline__ void mfma_accv(f32x4& c, const f32x4& a, const f32x4& b) {
   if (FP4)
     asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0] cbsz:4 blgp:4" : "+v"(c) : "v"(a), "v"(b), "v"(0x7F7F7F7Fu));
+  else if (F16)
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
   else
     asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
 }
-template <bool FP4>
+template <bool FP4, bool F16>
 __device__ __forceinline__ void mfma_accv_first(f32x4& c, const f32x4& a, const f32x4& b) {
   if (FP4)
     asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, 0, %3, %3 op_sel_hi:[0,0,0] cbsz:4 blgp:4" : "=&v"(c) : "v"(a), "v"(b), "v"(0x7F7F7F7Fu));
+  else if (F16)
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
   else
     asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
 }
@@ -472,8 +476,11 @@ __device__ __forceinline__ void pp_wait_dma6() { asm volatile("s_waitcnt vmcnt(6
 // block-local STASH (the query's slots of the candidate buffers, an LDS atomic each; a full slot row sends the entry to the global list
 // on its own), which the block flushes behind its last row tile — one device-scope counter update per query with entries, then the keys.
 // So the epilogue has no rounds and no flags: the quick test, the look phase and the one barrier the k-tile protocol needs.
-template <int METRIC, bool FP4 = false, bool WIDE = false>
-__global__ __launch_bounds__(512, 2) void sweep_topk_gemm_bf16_pp(Bf16GemmArgs a) {
+// F16: the IEEE f16 images of VDB_SEARCH_BRUTE_F16 — same bytes per element, same fragments, v_mfma_f32_16x16x32_f16.  The body is
+// shared; the f16 instances have a kernel name of their own (sweep_topk_gemm_f16_pp, below the body).
+template <int METRIC, bool FP4, bool WIDE, bool F16>
+__device__ __forceinline__ void gemm16_pp_body(Bf16GemmArgs a) {
+  static_assert(!F16 || (!FP4 && !WIDE), "the f16 instance is a result-mode instance");
   static_assert(FP4 == (METRIC == kHamming || METRIC == kJaccard), "the four-bit instance serves the bit metrics, the bf16 instance Cosine / DotProduct");
   constexpr bool HIB = METRIC != kHamming;  // Cosine / DotProduct / Jaccard: higher is better; Hamming: a distance
   constexpr int BM = kG16BM, BN = kG16BN, WAVES = kG16Waves, CAP = kG16Cap, QCAP = kG16Queue;
@@ -524,7 +531,7 @@ __global__ __launch_bounds__(512, 2) void sweep_topk_gemm_bf16_pp(Bf16GemmArgs a
         for (int e = 0; e < 4; e++) {
           const uint32_t i = c * 4 + e;
           if (i < a.dim) {
-            const float x = __uint_as_float((uint32_t)qp[i] << 16);
+            const float x = F16 ? (float)__builtin_bit_cast(_Float16, qp[i]) : __uint_as_float((uint32_t)qp[i] << 16);
             nacc = __builtin_fmaf(x, x, nacc);
           }
         }
@@ -599,8 +606,8 @@ _Pragma("unroll") \
       for (int rf_ = 0; rf_ < 4; rf_++) \
 _Pragma("unroll") \
         for (int t_ = 0; t_ < 2; t_++) { \
-          if ((FIRST) && m_ == 0) mfma_accv_first<FP4>(acc[(RF0) + rf_][(T0) + t_], AV[rf_][m_], bv[(T0) + t_][m_]); \
-          else mfma_accv<FP4>(acc[(RF0) + rf_][(T0) + t_], AV[rf_][m_], bv[(T0) + t_][m_]); \
+          if ((FIRST) && m_ == 0) mfma_accv_first<FP4, F16>(acc[(RF0) + rf_][(T0) + t_], AV[rf_][m_], bv[(T0) + t_][m_]); \
+          else mfma_accv<FP4, F16>(acc[(RF0) + rf_][(T0) + t_], AV[rf_][m_], bv[(T0) + t_][m_]); \
         } \
   } while (0)
 
@@ -793,9 +800,14 @@ _Pragma("unroll") \
 #endif
 #include "g16_writeout.inc"
 }
+template <int METRIC, bool FP4 = false, bool WIDE = false>
+__global__ __launch_bounds__(512, 2) void sweep_topk_gemm_bf16_pp(Bf16GemmArgs a) { gemm16_pp_body<METRIC, FP4, WIDE, false>(a); }
+template <int METRIC>
+__global__ __launch_bounds__(512, 2) void sweep_topk_gemm_f16_pp(Bf16GemmArgs a) { gemm16_pp_body<METRIC, false, false, true>(a); }
 
 // Norms of the rounded queries of a result-mode batch, once per batch instead of once per block: one wave per query, the
 // chain the kernels above run when qnorms_half is absent (canonical lane-chain order, as sweep_topk_mfma_bf16).
+template <bool F16>
 __global__ __launch_bounds__(256) void query_norms_bf16_kernel(const uint16_t* q16, uint64_t q_stride, float* out, uint32_t nq, uint32_t dim) {
   const uint32_t lane = threadIdx.x & 63u, b = blockIdx.x * 4u + (threadIdx.x >> 6);
   if (b >= nq) return;
@@ -806,15 +818,16 @@ __global__ __launch_bounds__(256) void query_norms_bf16_kernel(const uint16_t* q
     for (int e = 0; e < 4; e++) {
       const uint32_t i = c * 4 + e;
       if (i < dim) {
-        const float x = __uint_as_float((uint32_t)qp[i] << 16);
+        const float x = F16 ? (float)__builtin_bit_cast(_Float16, qp[i]) : __uint_as_float((uint32_t)qp[i] << 16);
         nacc = __builtin_fmaf(x, x, nacc);
       }
     }
   const float n = sqrtf(butterfly_all(nacc));
   if (lane == 0) out[b] = n;
 }
-void launch_query_norms_bf16(const uint16_t* q16, uint64_t q_stride, float* out, uint32_t nq, uint32_t dim, hipStream_t st) {
-  hipLaunchKernelGGL(query_norms_bf16_kernel, dim3((nq + 3) / 4), dim3(256), 0, st, q16, q_stride, out, nq, dim);
+void launch_query_norms_bf16(const uint16_t* q16, uint64_t q_stride, float* out, uint32_t nq, uint32_t dim, hipStream_t st, bool f16) {
+  if (f16) hipLaunchKernelGGL(query_norms_bf16_kernel<true>, dim3((nq + 3) / 4), dim3(256), 0, st, q16, q_stride, out, nq, dim);
+  else hipLaunchKernelGGL(query_norms_bf16_kernel<false>, dim3((nq + 3) / 4), dim3(256), 0, st, q16, q_stride, out, nq, dim);
 }
 
 // From a merged prefix top-k (internal rows + raw scores, merge_topk with ext_ids = nullptr): the query's bound for the
@@ -881,6 +894,19 @@ static hipError_t launch_g16_pp(const Bf16GemmArgs& a, int blocks, hipStream_t s
     done = true;
   }
   hipLaunchKernelGGL((sweep_topk_gemm_bf16_pp<METRIC>), dim3(blocks), dim3(512), kG16Lds, st, a);
+  return hipGetLastError();
+}
+
+template <int METRIC>
+static hipError_t launch_g16_pp_f16(const Bf16GemmArgs& a, int blocks, hipStream_t st) {
+  static bool done = false;
+  if (!done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_gemm_f16_pp<METRIC>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    done = true;
+  }
+  hipLaunchKernelGGL((sweep_topk_gemm_f16_pp<METRIC>), dim3(blocks), dim3(512), kG16Lds, st, a);
   return hipGetLastError();
 }
 
@@ -961,7 +987,7 @@ hipError_t launch_sweep_gemm_bf16_glds(int metric, const Bf16GemmPlan& p, const 
                                        const float* norms, const uint8_t* alive, const uint16_t* queries16, uint64_t q_stride,
                                        const uint64_t* tau0, uint64_t* part_keys, uint32_t list_stride, uint32_t list_off,
                                        uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st, bool split, const float* qnorms,
-                                       uint64_t* blk_tau, const float* qnorms_half) {
+                                       uint64_t* blk_tau, const float* qnorms_half, bool f16) {
   Bf16GemmArgs a{};
   a.rows = rows16;
   a.norms = norms;
@@ -988,6 +1014,10 @@ hipError_t launch_sweep_gemm_bf16_glds(int metric, const Bf16GemmPlan& p, const 
 #if VDB_PP_STAMP
   a.dbg = pp_stamp_dbg();
 #endif
+  if (f16) {  // result mode over the IEEE f16 images: the ping-pong kernel's f16 instance (no lock-step / split form)
+    if (split || (metric != kCosine && metric != kDot)) return hipErrorInvalidValue;
+    return metric == kCosine ? launch_g16_pp_f16<kCosine>(a, p.blocks, st) : launch_g16_pp_f16<kDot>(a, p.blocks, st);
+  }
   if (metric == kHamming) return launch_g16_fp4<kHamming>(a, p.blocks, st);
   if (metric == kJaccard) return launch_g16_fp4<kJaccard>(a, p.blocks, st);
   if (split)

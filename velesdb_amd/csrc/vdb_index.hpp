@@ -166,6 +166,11 @@ struct vdb_hip_index {
   bool bf16_enabled = false;
   uint64_t bf16_stride = 0;  // bf16 elements per row (multiple of 8)
   uint64_t bf16_rows = 0;    // rows converted so far
+  // optional IEEE f16 copy of the rows + the norms of the ROUNDED rows (vdb_hip_index_enable_half_precision(VDB_PRECISION_F16)): an image
+  // of its own — the bf16 copy above is also the selection stage's image and never changes.  Stride = bf16_stride's rule.
+  vdb::DevBuf rows_f16, norms_f16;
+  bool f16_enabled = false;
+  uint64_t f16_rows = 0;
   // split-bf16 image of the f32 rows (hi + lo per element, 4 bytes like the f32 row: sweep_split.hip), built at the first
   // large exact Cosine / DotProduct batch and kept up to date from then on
   vdb::DevBuf rows_split;
@@ -342,7 +347,7 @@ int32_t search_batch_host(vdb_hip_index* ix, const float* queries, uint32_t nq, 
                           uint64_t* out_ids, float* out_scores, uint32_t* out_n);
 int32_t group_for_all(vdb_hip_index* ix, int op, uint32_t arg);
 int32_t group_set_option(vdb_hip_index* ix, int32_t option, int64_t value);
-vdb_hip_index* group_first_shard(vdb_hip_index* ix);  // op: 0 build_graph, 1 enable_bf16, 2 storage mode, 3 quantizer
+vdb_hip_index* group_first_shard(vdb_hip_index* ix);  // op: 0 build_graph, 1 enable_bf16, 2 storage mode, 3 quantizer, 4 enable_half_precision
 int32_t group_search_host(vdb_hip_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t mode,
                           uint32_t rerank_k, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
 int32_t group_search_dev(vdb_hip_index* ix, const float* d_q, uint32_t nq, uint32_t k, uint32_t ef, int32_t mode,

@@ -188,12 +188,13 @@ void sweep_gemm_plan(uint32_t nq, uint32_t n_rows, int n_cus, uint32_t k, GemmPl
 hipError_t launch_sweep_gemm(int metric, const GemmPlan& p, const SweepArgs& a, hipStream_t st,
                              const uint32_t* tile_needed = nullptr);
 // bf16 variant of the same kernel (dim % 64 == 0): rows16 = the bf16 row copy, queries16 = launch_round_queries_bf16 output
+// (f16 = true everywhere below: the IEEE f16 images of VDB_SEARCH_BRUTE_F16 instead of bf16 — same layout, the f16 instances)
 void launch_round_queries_bf16(const float* q, uint64_t q_stride, uint16_t* out, uint64_t out_stride, uint32_t nq,
-                               uint32_t dim, hipStream_t st);
+                               uint32_t dim, hipStream_t st, bool f16 = false);
 hipError_t launch_sweep_gemm_bf16(int metric, const GemmPlan& p, const uint16_t* rows16, uint64_t row_stride,
                                   const float* norms, const uint8_t* alive, const uint16_t* queries16, uint64_t q_stride,
                                   uint64_t* part_keys, uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k,
-                                  hipStream_t st);
+                                  hipStream_t st, bool f16 = false);
 // bf16 GEMM-distance sweep for big batches (sweep_gemm_bf16.hip): 256 x 256 block tile, LDS-DMA staging, seeded thresholds
 // (struct Bf16GemmPlan, sweep_gemm_bf16_plan: vdb_gemm_schedule.hpp)
 constexpr uint32_t kGemmBf16MaxK = 10;          // candidate buffers of 12 keys per query
@@ -203,7 +204,8 @@ hipError_t launch_sweep_gemm_bf16_glds(int metric, const Bf16GemmPlan& p, const 
                                        const float* norms, const uint8_t* alive, const uint16_t* queries16, uint64_t q_stride,
                                        const uint64_t* tau0, uint64_t* part_keys, uint32_t list_stride, uint32_t list_off,
                                        uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st, bool split = false,
-                                       const float* qnorms = nullptr, uint64_t* blk_tau = nullptr, const float* qnorms_half = nullptr);
+                                       const float* qnorms = nullptr, uint64_t* blk_tau = nullptr, const float* qnorms_half = nullptr,
+                                       bool f16 = false);
 // ---- ONE launch schedule for every user of the 256 x 256 selection kernel (the bf16 result path and the exact / SQ8 selection
 // stage of index.hip, the bit metrics of bits_gemm.hip): a corpus is swept in a few launches of growing size, each starting from
 // bounds re-seeded out of everything swept before it — a block's epilogue costs ~0.2 us per candidate it has to finish, so the
@@ -215,21 +217,21 @@ template <class Pre, class Post>
 static inline hipError_t run_gemm_schedule(const GemmSchedule& s, int metric, const uint16_t* rows16, uint64_t row_stride, const float* norms,
                                            const uint8_t* alive, const uint16_t* queries16, uint64_t q_stride, const uint64_t* tau0, uint64_t* part_keys,
                                            uint32_t list_stride, uint32_t list_first, uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st, bool split,
-                                           const float* qnorms, uint64_t* blk_tau, const float* qnorms_half, Pre&& pre, Post&& post);
+                                           const float* qnorms, uint64_t* blk_tau, const float* qnorms_half, Pre&& pre, Post&& post, bool f16 = false);
 // norms of the rounded queries of a result-mode batch (qnorms_half above)
-void launch_query_norms_bf16(const uint16_t* q16, uint64_t q_stride, float* out, uint32_t nq, uint32_t dim, hipStream_t st);
+void launch_query_norms_bf16(const uint16_t* q16, uint64_t q_stride, float* out, uint32_t nq, uint32_t dim, hipStream_t st, bool f16 = false);
 void launch_seed_tau(const uint64_t* ids, const float* scores, const uint32_t* n, uint64_t* tau0, uint64_t* list,
                      uint32_t list_stride, uint32_t nq, uint32_t k, hipStream_t st, bool hib = true);
 template <class Pre, class Post>
 static inline hipError_t run_gemm_schedule(const GemmSchedule& s, int metric, const uint16_t* rows16, uint64_t row_stride, const float* norms,
                                            const uint8_t* alive, const uint16_t* queries16, uint64_t q_stride, const uint64_t* tau0, uint64_t* part_keys,
                                            uint32_t list_stride, uint32_t list_first, uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st, bool split,
-                                           const float* qnorms, uint64_t* blk_tau, const float* qnorms_half, Pre&& pre, Post&& post) {
+                                           const float* qnorms, uint64_t* blk_tau, const float* qnorms_half, Pre&& pre, Post&& post, bool f16) {
   uint32_t list_off = list_first;
   for (int j = 0; j < s.n_launch; j++) {
     pre(j);
     const hipError_t e = launch_sweep_gemm_bf16_glds(metric, s.bp[j], rows16, row_stride, norms, alive, queries16, q_stride, tau0, part_keys, list_stride,
-                                                     list_off, dim, nq, k, st, split, qnorms, blk_tau, qnorms_half);
+                                                     list_off, dim, nq, k, st, split, qnorms, blk_tau, qnorms_half, f16);
     if (e != hipSuccess) return e;
     list_off += s.bp[j].G;
     post(j, list_off, j + 1 == s.n_launch);
@@ -249,7 +251,15 @@ void launch_prep_bf16(const float* rows, uint64_t row_stride, uint16_t* out, uin
                       uint32_t row0, uint32_t n_rows, uint32_t dim, hipStream_t st, uint32_t* rho_max_bits = nullptr);
 hipError_t launch_sweep_bf16(int metric, int nqt, const uint16_t* rows, uint64_t row_stride, const float* norms,
                              const uint8_t* alive, const float* queries, uint64_t q_stride, uint64_t* part_keys,
-                             uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks, hipStream_t st);
+                             uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks, hipStream_t st, bool f16 = false);
+// IEEE f16 copy of the rows (round to nearest even, overflow to inf, subnormals kept) + the norm of the ROUNDED row
+void launch_prep_f16(const float* rows, uint64_t row_stride, uint16_t* out, uint64_t out_stride, float* norms,
+                     uint32_t row0, uint32_t n_rows, uint32_t dim, hipStream_t st);
+// half-row Euclidean sweep (sweep_half_l2.hip): half_precision::euclidean_distance over the f16 / bf16 copy of the rows
+size_t sweep_half_l2_lds_bytes(int B, uint32_t k, uint32_t dim);
+hipError_t launch_sweep_half_l2(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,
+                                uint64_t q_stride, uint64_t* part_keys, uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks,
+                                hipStream_t st);
 void launch_merge(bool higher_is_better, const MergeArgs& m, uint32_t nq, hipStream_t st);
 void launch_max_norm(const float* norms, uint32_t n_rows, uint32_t* out_bits, hipStream_t st);  // bits of max |v| (NaN propagates)
 // ---- exact f32 Cosine / Dot batches through split-bf16 selection + exact re-scoring + proof (sweep_split.hip) ----

@@ -11,6 +11,7 @@ All compute happens in libvelesdb_hip.so; this file only marshals numpy buffers.
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import os
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -20,7 +21,7 @@ from . import _ffi
 from ._ffi import check, lib
 from .params import DistanceMetric, DualPrecisionConfig, HnswParams, SearchQuality
 
-MODE_AUTO, MODE_BRUTE, MODE_HNSW, MODE_BRUTE_BF16, MODE_HNSW_INT8, MODE_BRUTE_SQ8, MODE_BRUTE_BINARY = 0, 1, 2, 3, 4, 5, 6
+MODE_AUTO, MODE_BRUTE, MODE_HNSW, MODE_BRUTE_BF16, MODE_HNSW_INT8, MODE_BRUTE_SQ8, MODE_BRUTE_BINARY, MODE_BRUTE_F16 = 0, 1, 2, 3, 4, 5, 6, 7
 OPT_MAX_QUERY_TILE, OPT_SWEEP_ENGINE, OPT_SELECTOR_LEVEL, OPT_INT8_OVERSAMPLING, OPT_KERNEL_TIMING = 0, 1, 2, 3, 4
 # the combining front of the host-pointer search entry points (include/velesdb_hip.h): queries per combined launch (0 = off),
 # waiting window of a leader in microseconds, combined batches in flight
@@ -29,8 +30,17 @@ KIND_ENGINE, KIND_RAW = 0, 1
 # enum vdb_kernel_bit (HnswIndex.last_kernels)
 (KERNEL_SWEEP_VALU, KERNEL_SWEEP_MFMA_F32, KERNEL_GEMM_F32, KERNEL_SWEEP_MFMA_BF16, KERNEL_GEMM_BF16, KERNEL_GEMM_BF16_GLDS,
  KERNEL_SELECT_BF16, KERNEL_SELECT_SPLIT, KERNEL_BITS, KERNEL_SQ8, KERNEL_HNSW, KERNEL_HNSW_INT8, KERNEL_BITS_GEMM) = (1 << i for i in range(13))
+# an f16 instance of a matrix-core family ran (set next to the family's bit); the half-row Euclidean sweep
+KERNEL_F16, KERNEL_SWEEP_HALF_L2 = 1 << 13, 1 << 14
 SHARD_REPLICA, SHARD_RANGE = 0, 1
 COMM_ID_BYTES = 128
+
+
+class VectorPrecision(enum.IntEnum):
+    """VectorPrecision (half_precision.rs:36-44), the discriminants of enum vdb_vector_precision."""
+    F32 = 0
+    F16 = 1
+    BF16 = 2
 
 
 def _f32(a) -> np.ndarray:
@@ -326,6 +336,24 @@ class HnswIndex:
             qs = qs.reshape(1, -1)
         self._validate(qs)
         return self._search_raw(qs, k, 0, MODE_BRUTE_BF16)
+
+    def enable_half_precision(self, precision) -> None:
+        """Keeps a half-precision copy of the rows (VectorData::from_f32_slice(.., precision), half_precision.rs:94-101) for
+        search_batch_brute_force_half: Cosine, DotProduct and Euclidean indexes; F16 and BF16 may both be enabled."""
+        check(lib().vdb_hip_index_enable_half_precision(self._h, int(precision)))
+
+    def search_batch_brute_force_half(self, queries, k: int, precision):
+        """Exact scan over the half-precision copy of the rows with queries rounded the same way: half_precision::dot_product /
+        cosine_similarity / euclidean_distance on VectorData::{F16, BF16} (half_precision.rs:199-287); numpy outputs like
+        search_batch_brute_force.  Needs enable_half_precision(precision)."""
+        precision = VectorPrecision(int(precision))
+        if precision == VectorPrecision.F32:
+            raise ValueError("half-precision search: F16 or BF16")
+        qs = _f32(queries)
+        if qs.ndim == 1:
+            qs = qs.reshape(1, -1)
+        self._validate(qs)
+        return self._search_raw(qs, k, 0, MODE_BRUTE_F16 if precision == VectorPrecision.F16 else MODE_BRUTE_BF16)
 
     # ---- storage modes (core/quantization.rs) -----------------------------------------------
     def set_storage_mode(self, mode) -> None:
