@@ -985,28 +985,57 @@ int32_t brute_wide_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
   ix->last_kernels |= VDB_KERNEL_SELECT_BF16;
   const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
   const uint32_t n = (uint32_t)ix->n_rows, dim = ix->dim;
-  // the seed sample: one key per 16 rows, its k-th best is the first bound — 4 096 rows (256 keys) bound a small k well enough that the
-  // first launch passes ~100 rows per query; a k of 100 needs the 1 024 keys of 16 384 rows (seed_scores_bf16: 32 us against 100)
-  // (VELESDB_WIDE_SEED_ROWS=n, probe builds: the sample's size for k <= kWideSmallSeedMaxK)
+  // The seed: a SAMPLE of the first rows, the k-th best of its keys is the first bound (any k rows with approximate scores >= A' prove
+  // tau = A' - 2 delta; the selection launches sweep the sample rows again, which is what lets the sample drop rows).
+  // Selections whose metric is DotProduct (normalised Cosine, DotProduct, Euclidean's augmented form): the selection kernel's own SAMPLE
+  // instance (sweep_gemm_bf16.hip, g16_sample.inc) over the first 16 384 rows (k <= kWideSmallSeedMaxK) or 32 768, one row tile per
+  // block, one key per 64 rows — the quick test's lane maxima, at the selection kernel's rate.  The bound it yields is the one the old
+  // first head launch existed to reach (the k-th best over the first 16 384 rows), so that launch and its re-seed are gone: the head is
+  // {5, 16} tiles per row group where {1, 4, 16} followed the small seed.  vdb_wide_sample.hpp, DESIGN 4.1f.
+  // Selections whose metric is Cosine (SQ8 Cosine; VELESDB_COSINE_NORMALISED=0) keep seed_scores_bf16: one key per 16 rows of 4 096 rows
+  // (256 keys) for a small k, the 1 024 keys of 16 384 rows for a k of 100 (32 us against 100), and the {1, 4, 16} head.
+  // (probe builds: VELESDB_WIDE_SAMPLE=0 restores seed_scores_bf16 + {1, 4, 16} everywhere; VELESDB_WIDE_SAMPLE_TILES=t row tiles per
+  // block of the sample launch, t times the rows; VELESDB_WIDE_SAMPLE_GROUP=32|64 rows per key; VELESDB_WIDE_SEED_ROWS=n: the size of
+  // seed_scores_bf16's sample for k <= kWideSmallSeedMaxK)
+  static const bool g_wide_sample = [] {
+    const char* e = probe_env("VELESDB_WIDE_SAMPLE");
+    return !(e && e[0] == '0');
+  }();
+  static const uint32_t g_sample_tiles = [] {
+    const char* e = probe_env("VELESDB_WIDE_SAMPLE_TILES");
+    const long v = e ? atol(e) : 0;
+    return v >= 1 && v <= 4 ? (uint32_t)v : 1u;
+  }();
+  static const uint32_t g_sample_group = [] {
+    const char* e = probe_env("VELESDB_WIDE_SAMPLE_GROUP");
+    const long v = e ? atol(e) : 0;
+    return v == 32 || v == 64 ? (uint32_t)v : kWideSampleGroupRows;
+  }();
+  WideSamplePlan smp{};
+  if (g_wide_sample && sel_metric == VDB_DOT) wide_sample_plan(nqg, n, k, g_sample_tiles, g_sample_group, &smp);
+  const bool sample = smp.rows != 0;
   static const uint32_t g_small_seed_rows = [] {
     const char* e = probe_env("VELESDB_WIDE_SEED_ROWS");
     const long v = e ? atol(e) : 0;
     return v >= 1024 && v <= (long)kWideSeedRows ? (uint32_t)v / 256u * 256u : kSplitSeedRows;
   }();
-  const uint32_t R0 = std::min<uint32_t>(k <= kWideSmallSeedMaxK ? g_small_seed_rows : kWideSeedRows, n), ngrp = (R0 + 15) / 16;
+  const uint32_t R0 = std::min<uint32_t>(k <= kWideSmallSeedMaxK ? g_small_seed_rows : kWideSeedRows, n);
+  const uint32_t ngrp = sample ? smp.ngrp : (R0 + 15) / 16;  // sample keys per query
   GemmSchedule sch;
   {
     // tiles per row group of the first launches (VELESDB_WIDE_STEPS="a,b,c": schedule probes)
-    static const std::array<uint32_t, 3> mult = [] {
-      std::array<uint32_t, 3> m{1, 4, 16};
+    static const std::array<uint32_t, 4> mult = [] {
+      std::array<uint32_t, 4> m{0, 0, 0, 0};  // [3]: the switch is set
       if (const char* e = probe_env("VELESDB_WIDE_STEPS")) {
         unsigned a = 0, b = 0, c = 0;
         const int got = sscanf(e, "%u,%u,%u", &a, &b, &c);
-        m = {got >= 1 ? a : 0u, got >= 2 ? b : 0u, got >= 3 ? c : 0u};
+        m = {got >= 1 ? a : 0u, got >= 2 ? b : 0u, got >= 3 ? c : 0u, 1u};
       }
       return m;
     }();
-    const uint32_t head[3] = {mult[0], mult[1], mult[2]};
+    const uint32_t head_seed[3] = {1, 4, 16};  // behind seed_scores_bf16's small sample
+    const uint32_t* dflt = sample ? kWideSampleHead : head_seed;
+    const uint32_t head[3] = {mult[3] ? mult[0] : dflt[0], mult[3] ? mult[1] : dflt[1], mult[3] ? mult[2] : dflt[2]};
     gemm_schedule(nqg, 0, n, ix->n_cus, head, 0, &sch);
   }
   // the gathered exact pass of the unproven queries: the streaming matrix-core kernel, as many 16-query tiles per pass as k leaves room
@@ -1078,9 +1107,19 @@ int32_t brute_wide_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
   wa.cap = kWideCap;
   wa.k = k;
   wa.dim = dim;
-  // seed: a sample of the first rows on the bf16 pipe (one key per 16 rows), its k-th best -> the first bound
-  launch_seed_scores_bf16(sel_metric, img_rows, img_stride, sel_norms, alive, q16, img_stride, qnorms, ix->s_part_keys.as<uint64_t>(), R0,
-                          nqg, sel_dim, st);
+  // seed: a sample of the first rows on the bf16 pipe, its k-th best -> the first bound.  The SAMPLE instance is a launch of the selection
+  // kernel and is timed as one (last_selection_ms: the selection kernel's launches of the step)
+  if (sample) {
+    EventPair* evs = next_sel_events(ix);
+    if (evs) (void)hipEventRecord(evs->a, st);
+    e = launch_sweep_gemm_bf16_sample(smp.bp, img_rows, img_stride, sel_norms, alive, q16, img_stride, ix->s_part_keys.as<uint64_t>(), ngrp, smp.grp_rows,
+                                      sel_dim, nqg, st, qnorms);
+    if (evs) (void)hipEventRecord(evs->b, st);
+    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("wide sample launch: ") + hipGetErrorString(e));
+  } else {
+    launch_seed_scores_bf16(sel_metric, img_rows, img_stride, sel_norms, alive, q16, img_stride, qnorms, ix->s_part_keys.as<uint64_t>(), R0, nqg,
+                            sel_dim, st);
+  }
   if (l2) launch_wide_seed_l2(wa, ix->s_part_keys.as<uint64_t>(), ngrp, dim_a, nqg, st);
   else launch_wide_seed(ix->metric, wa, ix->s_part_keys.as<uint64_t>(), ngrp, nqg, st);
   for (int j = 0; j < sch.n_launch; j++) {

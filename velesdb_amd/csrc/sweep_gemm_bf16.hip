@@ -84,6 +84,9 @@ struct Bf16GemmArgs {
   uint64_t* wide_keys;
   uint32_t* wide_cnt;
   uint32_t wide_cap;
+  // SAMPLE instance (the WIDE selection's seed: g16_sample.inc): no bound, no list — per row tile every lane writes the best of its 32
+  // rows per query column as ONE key to part_keys[q * list_stride + group]; sample_grp = rows per key, 32 (a lane) or 64 (two lanes)
+  uint32_t sample_grp;
 };
 
 // The lane id, re-derived where it is needed: a value computed from threadIdx before the main loop stays live across it,
@@ -478,9 +481,14 @@ __device__ __forceinline__ void pp_wait_dma6() { asm volatile("s_waitcnt vmcnt(6
 // So the epilogue has no rounds and no flags: the quick test, the look phase and the one barrier the k-tile protocol needs.
 // F16: the IEEE f16 images of VDB_SEARCH_BRUTE_F16 — same bytes per element, same fragments, v_mfma_f32_16x16x32_f16.  The body is
 // shared; the f16 instances have a kernel name of their own (sweep_topk_gemm_f16_pp, below the body).
-template <int METRIC, bool FP4, bool WIDE, bool F16>
+// SAMPLE: the seed of the WIDE selection (select_stage.hip brute_wide_dev) — the same prologue and k-loop over the first rows of the
+// corpus, one row tile per block; the epilogue is the quick test's reduction alone (a lane's 32 accumulators per query column -> their
+// maximum), stored as one sample key per (query, row group) for wide_seed / wide_seed_l2 (g16_sample.inc).  No bound, no look phase, no
+// stash, no lists.  A kernel name of its own as well (sweep_topk_sample_bf16_pp).
+template <int METRIC, bool FP4, bool WIDE, bool F16, bool SAMPLE = false>
 __device__ __forceinline__ void gemm16_pp_body(Bf16GemmArgs a) {
   static_assert(!F16 || (!FP4 && !WIDE), "the f16 instance is a result-mode instance");
+  static_assert(!SAMPLE || (METRIC == kDot && !FP4 && !WIDE && !F16), "the sample instance serves the selections whose metric is DotProduct");
   static_assert(FP4 == (METRIC == kHamming || METRIC == kJaccard), "the four-bit instance serves the bit metrics, the bf16 instance Cosine / DotProduct");
   constexpr bool HIB = METRIC != kHamming;  // Cosine / DotProduct / Jaccard: higher is better; Hamming: a distance
   constexpr int BM = kG16BM, BN = kG16BN, WAVES = kG16Waves, CAP = kG16Cap, QCAP = kG16Queue;
@@ -618,6 +626,15 @@ _Pragma("unroll") \
 
   uint32_t qcnt = 0;   // entries in this wave's queue (carried over while their candidate buffer is full)
   uint32_t epoch = 0;  // block-uniform: ++ per synchronisation point of the epilogue protocol
+  if constexpr (SAMPLE) {  // (the sample instance keeps no list)
+    (void)compact;
+    (void)qcnt;
+    (void)epoch;
+    (void)cand;
+    (void)flags;
+    (void)wq_qs;
+    (void)k;
+  }
 
   // positions in the flat stream: (rt1, kt1) = k-tile c + 1, (rt2, kt2) = k-tile c + 2, both clamped to the last k-tile (a
   // request past the end re-fetches the last k-tile into a slot nobody reads again: the request count per phase stays
@@ -763,6 +780,9 @@ _Pragma("unroll") \
     // stamped timeline.  profiles/r05q_*: step 1.665-1.675 -> 1.646 ms, Jaccard batches 0.722-0.724 -> 0.677-0.687 ms.)
     if (wr == 0) pp_barrier();
     VDB_PP_STAMP_AT(11);
+    if constexpr (SAMPLE) {
+#include "g16_sample.inc"
+    } else {
 #define VDB_G16_ACC_F(V) (V)
 #include "g16_quicktest.inc"
     if constexpr (METRIC == kHamming || METRIC == kJaccard) {
@@ -775,6 +795,7 @@ _Pragma("unroll") \
 #include "g16_protocol.inc"
 #undef VDB_G16_ACC_ELEM
 #undef VDB_G16_ACC_F
+    }
     // A rows 0-63 of the next row tile's first k-tile (landed: waited for in phase 3 above).  Unconditional — behind the last
     // row tile it reads a stage nobody uses: a conditional read would keep the OLD fragments alive across the epilogue
     VDB_PP_LANE();
@@ -798,12 +819,15 @@ _Pragma("unroll") \
     for (int i = 0; i < 28; i++) d[i] = st_acc[i];
   }
 #endif
+  if constexpr (!SAMPLE) {  // (the sample's keys were stored tile by tile)
 #include "g16_writeout.inc"
+  }
 }
 template <int METRIC, bool FP4 = false, bool WIDE = false>
 __global__ __launch_bounds__(512, 2) void sweep_topk_gemm_bf16_pp(Bf16GemmArgs a) { gemm16_pp_body<METRIC, FP4, WIDE, false>(a); }
 template <int METRIC>
 __global__ __launch_bounds__(512, 2) void sweep_topk_gemm_f16_pp(Bf16GemmArgs a) { gemm16_pp_body<METRIC, false, false, true>(a); }
+__global__ __launch_bounds__(512, 2) void sweep_topk_sample_bf16_pp(Bf16GemmArgs a) { gemm16_pp_body<kDot, false, false, false, true>(a); }
 
 // Norms of the rounded queries of a result-mode batch, once per batch instead of once per block: one wave per query, the
 // chain the kernels above run when qnorms_half is absent (canonical lane-chain order, as sweep_topk_mfma_bf16).
@@ -923,6 +947,17 @@ static hipError_t launch_g16_wide(const Bf16GemmArgs& a, int blocks, hipStream_t
   return hipGetLastError();
 }
 
+static hipError_t launch_g16_sample(const Bf16GemmArgs& a, int blocks, hipStream_t st) {
+  static bool done = false;
+  if (!done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_sample_bf16_pp), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    done = true;
+  }
+  hipLaunchKernelGGL(sweep_topk_sample_bf16_pp, dim3(blocks), dim3(512), kG16Lds, st, a);
+  return hipGetLastError();
+}
+
 template <int METRIC>
 static hipError_t launch_g16_fp4(const Bf16GemmArgs& a, int blocks, hipStream_t st) {
   static bool done = false;
@@ -981,6 +1016,38 @@ hipError_t launch_sweep_gemm_bf16_wide(int metric, const Bf16GemmPlan& p, const 
   a.dbg = pp_stamp_dbg();
 #endif
   return metric == kCosine ? launch_g16_wide<kCosine>(a, p.blocks, st) : launch_g16_wide<kDot>(a, p.blocks, st);
+}
+
+// SAMPLE instance: the rows [p.row_lo, p.row_hi) of a DotProduct-form selection image, one key per (query, grp_rows rows) to
+// keys[q * ngrp + group] (groups counted from p.row_lo; ngrp >= (p.row_hi - p.row_lo) / grp_rows, grp_rows = 32 or 64)
+hipError_t launch_sweep_gemm_bf16_sample(const Bf16GemmPlan& p, const uint16_t* rows16, uint64_t row_stride, const float* norms, const uint8_t* alive,
+                                         const uint16_t* queries16, uint64_t q_stride, uint64_t* keys, uint32_t ngrp, uint32_t grp_rows, uint32_t dim,
+                                         uint32_t nq, hipStream_t st, const float* qnorms) {
+  // (every group of every row tile of the range has its slot; the kernel drops a group past ngrp all the same)
+  if ((grp_rows != 32 && grp_rows != 64) || p.row_lo % kG16BM || p.row_hi <= p.row_lo ||
+      (uint64_t)ngrp * grp_rows < ((uint64_t)(p.row_hi - p.row_lo) + kG16BM - 1) / kG16BM * kG16BM)
+    return hipErrorInvalidValue;
+  Bf16GemmArgs a{};
+  a.rows = rows16;
+  a.norms = norms;
+  a.alive = alive;
+  a.queries = queries16;
+  a.part_keys = keys;
+  a.list_stride = ngrp;
+  a.sample_grp = grp_rows;
+  a.row_stride = row_stride;
+  a.q_stride = q_stride;
+  a.n_rows = p.row_hi;
+  a.row_tile0 = p.row_lo / kG16BM;
+  a.dim = dim;
+  a.nq = nq;
+  a.k = kGemmBf16MaxK;  // (unused)
+  a.KT = dim / 64;
+  a.G = p.G;
+  a.nqt = p.nqt;
+  a.qper = p.qper;
+  a.qnorms = qnorms;
+  return launch_g16_sample(a, p.blocks, st);
 }
 
 hipError_t launch_sweep_gemm_bf16_glds(int metric, const Bf16GemmPlan& p, const uint16_t* rows16, uint64_t row_stride,

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "vdb_gemm_schedule.hpp"
+#include "vdb_wide_sample.hpp"
 
 namespace vdb {
 
@@ -14,6 +15,7 @@ constexpr uint32_t kWidePoolMax = 1024;    // candidates one block re-scores exa
 constexpr uint32_t kWideSeedRows = 16384;  // rows of the seed sample (one key per 16 rows: seed_scores_bf16)
 constexpr uint32_t kWideSeedGroups = kWideSeedRows / 16;
 constexpr uint32_t kWideSmallSeedMaxK = 32; // up to this k the k <= 10 stage's 4 096-row sample seeds the batch (256 keys: k-th best of them)
+static_assert(kWideSampleMaxKeys == kWideSeedGroups && kWideSampleSmallK == kWideSmallSeedMaxK, "vdb_wide_sample.hpp restates them");
 constexpr uint32_t kWideGivenUp = 1u;      // state bit: no bound exists or the list overflowed — the exact fallback answers the query
 
 struct WideArgs {
@@ -70,5 +72,10 @@ hipError_t launch_sweep_gemm_bf16_wide(int metric, const Bf16GemmPlan& p, const 
                                        const uint8_t* alive, const uint16_t* queries16, uint64_t q_stride, const uint64_t* tau0,
                                        uint64_t* wide_keys, uint32_t* wide_cnt, uint32_t wide_cap, uint32_t dim, uint32_t nq, hipStream_t st,
                                        const float* qnorms);
+// the SAMPLE instance of the same kernel over the first rows of a DotProduct-form selection image (the seed: vdb_wide_sample.hpp): one
+// key per (query, grp_rows rows) to keys[q * ngrp + group]
+hipError_t launch_sweep_gemm_bf16_sample(const Bf16GemmPlan& p, const uint16_t* rows16, uint64_t row_stride, const float* norms, const uint8_t* alive,
+                                         const uint16_t* queries16, uint64_t q_stride, uint64_t* keys, uint32_t ngrp, uint32_t grp_rows, uint32_t dim,
+                                         uint32_t nq, hipStream_t st, const float* qnorms);
 
 }  // namespace vdb
