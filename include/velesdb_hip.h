@@ -82,11 +82,22 @@ enum vdb_search_mode {
                            vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16).  On a Euclidean handle (the second call
                            only): half_precision::euclidean_distance (:257-287), sqrt of an f32 chain of (q - v)^2 over the
                            rounded values, smallest first.  Raw scores, best first.                  */
-  VDB_SEARCH_BRUTE_F16 = 7  /* the same over the IEEE f16 copy of the rows (VectorData::F16: round to nearest even, overflow to
+  VDB_SEARCH_BRUTE_F16 = 7, /* the same over the IEEE f16 copy of the rows (VectorData::F16: round to nearest even, overflow to
                            +-inf beyond 65 504, f16 subnormals kept) with f16-rounded queries: Cosine / DotProduct on the matrix
                            cores (v_mfma_f32_16x16x32_f16, f32 accumulation); Euclidean (half_precision.rs:257-279) as sqrt of an f32
                            chain of (q - v)^2 over the rounded values, smallest first.  Needs
                            vdb_hip_index_enable_half_precision(VDB_PRECISION_F16).                                   */
+  VDB_SEARCH_HNSW_F16 = 8,  /* VDB_SEARCH_HNSW over the IEEE f16 copy of the rows: NativeHnsw::search (graph.rs:251-270) on the handle's
+                           graph under the same result mapping (`ef` = 0 -> Balanced, max(ef, k), soft-deleted rows dropped after
+                           the cut, scores through transform_score), every distance of the walk taken between the query rounded
+                           to f16 (VectorData::from_f32_slice) and the row's f16 image: -dot, 1 - cosine_similarity (0.0
+                           similarity when a norm is < f32::EPSILON), euclidean_distance (half_precision.rs:199-287), summed in
+                           the canonical order of the f32 walk.  Half the bytes per visited node, no training step.  Needs
+                           vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) (VDB_ERR_STATE otherwise, as
+                           VDB_SEARCH_BRUTE_F16) and a graph (VDB_ERR_STATE).  Served by vdb_hip_index_search / _search_batch /
+                           _search_batch_dev and by REPLICA device groups; RANGE groups answer VDB_ERR_UNSUPPORTED.  The
+                           rerank / multi-entry / with_config entry points and VDB_SEARCH_AUTO never take this walk.      */
+  VDB_SEARCH_HNSW_BF16 = 9  /* the same over the bf16 copy (VDB_PRECISION_BF16)                                                 */
 };
 
 /* VectorPrecision (half_precision.rs:36-44), the reference's order */
@@ -435,7 +446,8 @@ enum vdb_kernel_bit {
   VDB_KERNEL_BITS_GEMM = 4096,     /* Hamming / Jaccard batches as a four-bit GEMM distance (sweep_topk_gemm_bf16_pp<.., FP4>) */
   VDB_KERNEL_F16 = 8192,           /* an IEEE f16 instance of a matrix-core family ran (VDB_SEARCH_BRUTE_F16): set NEXT TO the family's
                                       bit — SWEEP_MFMA_BF16 / GEMM_BF16 / GEMM_BF16_GLDS then name the f16 instance of that kernel      */
-  VDB_KERNEL_SWEEP_HALF_L2 = 16384 /* sweep_topk_half_l2 (Euclidean difference chain over the f16 / bf16 rows)                        */
+  VDB_KERNEL_SWEEP_HALF_L2 = 16384, /* sweep_topk_half_l2 (Euclidean difference chain over the f16 / bf16 rows)                       */
+  VDB_KERNEL_HNSW_HALF = 32768     /* hnsw_search_half_kernel (VDB_SEARCH_HNSW_F16 / _BF16; VDB_KERNEL_F16 next to it for the f16 instance) */
 };
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same

@@ -805,6 +805,20 @@ impl HipHnswIndex {
         self.search_batch_mode(queries, k, 0, mode)
     }
 
+    /// Graph search over the half-precision copy of the rows: `NativeHnsw::search` on the index's graph exactly as
+    /// [`Self::search_batch_parallel`] (`ef_search` 0 = Balanced, `max(ef_search, k)`, scores through `transform_score`), every
+    /// distance taken between the query rounded to `precision` and the row's half image (`half_precision.rs:199-287`); needs
+    /// [`Self::enable_half_precision`] with the same precision and a graph.  `F32` is the plain graph search.
+    #[must_use]
+    pub fn search_batch_half_graph(&self, queries: &[&[f32]], k: usize, ef_search: usize, precision: VectorPrecision) -> Vec<Vec<(u64, f32)>> {
+        let mode = match precision {
+            VectorPrecision::F16 => sys::VDB_SEARCH_HNSW_F16,
+            VectorPrecision::BF16 => sys::VDB_SEARCH_HNSW_BF16,
+            VectorPrecision::F32 => sys::VDB_SEARCH_HNSW,
+        };
+        self.search_batch_mode(queries, k, ef_search, mode)
+    }
+
     /// `StorageMode::SQ8` collections: asymmetric distances against the stored codes (`quantization.rs:410-554`).
     #[must_use]
     pub fn search_batch_sq8(&self, queries: &[&[f32]], k: usize) -> Vec<Vec<(u64, f32)>> {

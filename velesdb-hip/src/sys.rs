@@ -40,6 +40,8 @@ pub const VDB_SEARCH_HNSW_INT8: i32 = 4;
 pub const VDB_SEARCH_BRUTE_SQ8: i32 = 5;
 pub const VDB_SEARCH_BRUTE_BINARY: i32 = 6;
 pub const VDB_SEARCH_BRUTE_F16: i32 = 7;
+pub const VDB_SEARCH_HNSW_F16: i32 = 8;
+pub const VDB_SEARCH_HNSW_BF16: i32 = 9;
 
 // enum vdb_vector_precision
 pub const VDB_PRECISION_F32: i32 = 0;
@@ -88,6 +90,7 @@ pub const VDB_KERNEL_HNSW_INT8: i32 = 2048;
 pub const VDB_KERNEL_BITS_GEMM: i32 = 4096;
 pub const VDB_KERNEL_F16: i32 = 8192;
 pub const VDB_KERNEL_SWEEP_HALF_L2: i32 = 16384;
+pub const VDB_KERNEL_HNSW_HALF: i32 = 32768;
 
 pub const VDB_COMM_ID_BYTES: usize = 128;
 

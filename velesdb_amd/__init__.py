@@ -13,6 +13,7 @@ from .index import (KERNEL_BITS, KERNEL_BITS_GEMM, KERNEL_GEMM_BF16, KERNEL_GEMM
                     KERNEL_SELECT_BF16, KERNEL_SELECT_SPLIT, KERNEL_SQ8, KERNEL_SWEEP_MFMA_BF16, KERNEL_SWEEP_MFMA_F32,
                     KERNEL_SWEEP_VALU)
 from .index import KERNEL_F16, KERNEL_SWEEP_HALF_L2, MODE_BRUTE_F16, VectorPrecision  # noqa: F401
+from .index import KERNEL_HNSW_HALF, MODE_HNSW_BF16, MODE_HNSW_F16  # noqa: F401
 from .params import DistanceMetric, DualPrecisionConfig, HnswParams, SearchQuality, StorageMode  # noqa: F401
 
 __all__ = ["HnswIndex", "NativeHnswIndex", "HipDistance", "GpuAccelerator", "DistanceMetric", "HnswParams", "SearchQuality", "StorageMode", "DualPrecisionConfig", "VectorPrecision",

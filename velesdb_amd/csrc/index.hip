@@ -970,6 +970,17 @@ int32_t search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint3
     return hnsw_search_int8_dev(ix, d_q, q_stride, nq, k, ef == 0 ? balanced_ef(k) : ef, rerank_k ? rerank_k : opt_oversampling(ix), cap_mult,
                                 d_ids, d_scores, d_n, st);
   }
+  if (mode == VDB_SEARCH_HNSW_F16 || mode == VDB_SEARCH_HNSW_BF16) {
+    // VDB_SEARCH_HNSW's rules over the half image (hnsw_half.hip); the rerank and multi-entry forms exist for the f32 walk only
+    if (rerank_k || d_extra_eps || ix->raw_ef)
+      return fail(VDB_ERR_UNSUPPORTED, "half-precision graph search: no rerank / multi-entry form (use VDB_SEARCH_HNSW)");
+    const bool f16 = mode == VDB_SEARCH_HNSW_F16;
+    if (ef == 0) ef = balanced_ef(k);
+    ef = std::max(ef, k);  // SearchQuality::Custom(ef) = max(ef, k), params.rs:317
+    if (used_hnsw) *used_hnsw = true;
+    ix->last_kernels |= VDB_KERNEL_HNSW_HALF | (f16 ? VDB_KERNEL_F16 : 0);
+    return hnsw_search_half_dev(ix, f16, d_q, q_stride, nq, k, ef, cap_mult, d_ids, d_scores, d_n, st);
+  }
   if (mode != VDB_SEARCH_AUTO && mode != VDB_SEARCH_HNSW) return fail(VDB_ERR_INVALID_ARG, "bad search mode");
   if (rerank_k) {
     // search_with_rerank(_quality): the candidate search runs with k = rerank_k (search.rs:124,310)

@@ -133,7 +133,8 @@ static void run_batch(vdb_hip_index* handle, CombineReq* const* reqs, size_t n_r
 static int leader_limit(const vdb_hip_index* handle, const CombineReq& r) {
   const int64_t o = opt_value(handle, VDB_OPT_COMBINE_INFLIGHT);
   if (o > 0) return (int)o;
-  const bool walk = r.mode == VDB_SEARCH_HNSW || r.mode == VDB_SEARCH_HNSW_INT8 || r.mode == VDB_SEARCH_AUTO;
+  const bool walk = r.mode == VDB_SEARCH_HNSW || r.mode == VDB_SEARCH_HNSW_INT8 || r.mode == VDB_SEARCH_HNSW_F16 ||
+                    r.mode == VDB_SEARCH_HNSW_BF16 || r.mode == VDB_SEARCH_AUTO;
   return walk ? 2 : 1;
 }
 

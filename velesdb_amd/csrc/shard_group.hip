@@ -540,6 +540,7 @@ int32_t group_search_host(vdb_hip_index* ix, const float* queries, uint32_t nq, 
   }
   const int32_t m = resolve_mode(ix, mode);
   if (m == VDB_SEARCH_HNSW_INT8) return fail(VDB_ERR_UNSUPPORTED, "int8 traversal: replicas only");
+  if (m == VDB_SEARCH_HNSW_F16 || m == VDB_SEARCH_HNSW_BF16) return fail(VDB_ERR_UNSUPPORTED, "half-precision graph search: replicas only");
   int32_t rc = for_each_shard(g, [&](size_t s) -> int32_t {
     vdb_hip_index* c = g->shards[s];
     std::lock_guard<vdb::IndexMutex> cl(c->mu);
@@ -588,6 +589,8 @@ int32_t group_search_dev(vdb_hip_index* ix, const float* d_q, uint32_t nq, uint3
   const bool replica = g->mode == VDB_SHARD_REPLICA;
   const int32_t m = replica ? mode : resolve_mode(ix, mode);
   if (!replica && m == VDB_SEARCH_HNSW_INT8) return fail(VDB_ERR_UNSUPPORTED, "int8 traversal: replicas only");
+  if (!replica && (m == VDB_SEARCH_HNSW_F16 || m == VDB_SEARCH_HNSW_BF16))
+    return fail(VDB_ERR_UNSUPPORTED, "half-precision graph search: replicas only");
   const size_t kk = std::max<uint32_t>(k, 1);
   int32_t rc = for_each_shard(g, [&](size_t s) -> int32_t {
     vdb_hip_index* c = g->shards[s];

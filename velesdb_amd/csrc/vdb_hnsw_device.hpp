@@ -1,7 +1,8 @@
 // vdb_hnsw_device.hpp — device building blocks shared by the traversal (hnsw_kernels.hip) and
 // construction (hnsw_build.hip) kernels: the sorted candidate/result list in LDS, the block-wide
 // distance phase (DistanceEngine::distance, native/distance.rs:75-85, canonical arithmetic) and small
-// wave-uniform helpers.
+// wave-uniform helpers; and the walk itself (hnsw_walk_body), one text for the f32 / packed-bit rows
+// (hnsw_kernels.hip) and the f16 / bf16 images (hnsw_half.hip).
 #pragma once
 #include "vdb_device.hpp"
 #include "vdb_kernels.hpp"
@@ -478,6 +479,96 @@ __device__ __forceinline__ void dist_phase_f32(const DistCtx& a, const float4* q
   }
 }
 
+// ---- half-precision rows (VectorData::F16 / BF16, half_precision.rs:94-101): IEEE f16 or bf16 images of the rows, the query
+// rounded the same way (VectorData::from_f32_slice) and kept as f32.  Both conversions to f32 are exact.
+template <bool F16>
+__device__ __forceinline__ float round_to_half(float f) {  // f32 -> half (round to nearest even) -> f32
+  if (F16) return (float)(_Float16)f;  // v_cvt_f16_f32 / v_cvt_f32_f16: overflow to +-inf, gradual underflow, NaN stays NaN
+  uint32_t u = __float_as_uint(f);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return __uint_as_float((u | 0x00400000u) & 0xFFFF0000u);  // NaN stays NaN (quiet)
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return __uint_as_float(u & 0xFFFF0000u);
+}
+template <bool F16>
+__device__ __forceinline__ float4 round_to_half4(const float4& v) {
+  return float4{round_to_half<F16>(v.x), round_to_half<F16>(v.y), round_to_half<F16>(v.z), round_to_half<F16>(v.w)};
+}
+// four consecutive half elements (8 bytes, element 0 in the low half of w.x) as f32
+template <bool F16>
+__device__ __forceinline__ float4 half4_to_f32(const uint2& w) {
+  if (F16) {
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    const f16x2 lo = __builtin_bit_cast(f16x2, w.x), hi = __builtin_bit_cast(f16x2, w.y);
+    return float4{(float)lo.x, (float)lo.y, (float)hi.x, (float)hi.y};
+  }
+  return float4{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u), __uint_as_float(w.y << 16),
+                __uint_as_float(w.y & 0xFFFF0000u)};
+}
+__device__ __forceinline__ uint2 ld_half4(const uint16_t* p) { return *reinterpret_cast<const uint2*>(p); }
+
+// nb_id[0..m) -> nb_d[0..m) over the half image: half_precision::dot_product / cosine_similarity / euclidean_distance
+// (half_precision.rs:199-287) as DistanceEngine::distance reports them (-dot, 1 - cosine, the root).  The summation order is
+// dist_phase_f32's, unchanged — element i in 4-element chunk i / 4, chunk c in lane c % 64, one fmaf chain per lane, the xor
+// butterfly — so over image H the results are bit for bit dist_phase_f32's over the f32 rows dequant(H) with the same (rounded)
+// query: a lane loads 8 bytes per chunk (512 B per wave instruction) and converts in registers.  a.rows = the image
+// (uint16_t elements), a.row_stride = its stride in elements (a multiple of 8, the padding zero), a.norms = the norms of the
+// ROUNDED rows.  q / qgen hold the rounded query.
+template <int METRIC, int CPL, int WAVES, int R, bool F16>
+__device__ __forceinline__ void dist_phase_half(const DistCtx& a, const float4* q, float qnorm, const float* qgen, uint32_t m,
+                                                lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib) {
+  constexpr int OP = (METRIC == kEuclidean) ? kOpL2 : kOpDot;
+  const uint16_t* rows = reinterpret_cast<const uint16_t*>(a.rows);
+  const int d4 = (int)((a.dim + 3) / 4);
+  for (uint32_t j0 = (uint32_t)wib * R; j0 < m; j0 += WAVES * R) {
+    float acc[R];
+    const uint32_t jn = j0 + (uint32_t)(lane & (R - 1));
+    float vnorm = 1.0f;  // (requested with the rows: behind the reduction it is a second dependent round trip)
+    if (METRIC == kCosine && lane < R && jn < m) vnorm = a.norms[nb_id[jn]];
+    if (CPL > 0) {
+      uint2 v[R][CPL > 0 ? CPL : 1];
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        const uint32_t j = j0 + r < m ? j0 + r : m - 1;
+        const uint16_t* p = rows + (size_t)nb_id[j] * a.row_stride + (size_t)lane * 4;
+#pragma unroll
+        for (int c = 0; c < CPL; c++) v[r][c] = ld_half4(p + c * 256);
+      }
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        float s = 0.0f;
+#pragma unroll
+        for (int c = 0; c < CPL; c++) s = chain4<OP>(s, q[c], half4_to_f32<F16>(v[r][c]));
+        acc[r] = s;
+      }
+    } else {
+      const uint16_t* rp[R];
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        const uint32_t j = j0 + r < m ? j0 + r : m - 1;
+        rp[r] = rows + (size_t)nb_id[j] * a.row_stride;
+        acc[r] = 0.0f;
+      }
+      for (int c = lane; c < d4; c += 64) {  // (4 * d4 <= row_stride: the last chunk's load stays inside the row)
+        const float4 qq = ld4(qgen + c * 4);
+        const int nv = (int)a.dim - c * 4;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          const float4 x = half4_to_f32<F16>(ld_half4(rp[r] + c * 4));
+          acc[r] = nv >= 4 ? chain4<OP>(acc[r], qq, x) : chain4_tail<OP>(acc[r], qq, x, nv);
+        }
+      }
+    }
+    reduce_rows<R>(acc, lane);
+    if (lane < R && jn < m) {
+      float d;
+      if (METRIC == kCosine) d = 1.0f - finish_score_half<kCosine>(acc[0], qnorm, vnorm);  // half_precision.rs:237-253
+      else if (METRIC == kEuclidean) d = finish_score<kEuclidean>(acc[0], 0.0f, 0.0f);     // :257-287
+      else d = -acc[0];                                                                    // :199-225
+      nb_d[jn] = d;
+    }
+  }
+}
+
 template <int METRIC>
 __device__ __forceinline__ void dist_phase_bits(const DistCtx& a, const uint32_t* qbits, uint32_t m,
                                                 lds_vu32* nb_id, lds_vf32* nb_d, bool raw = false) {
@@ -508,5 +599,524 @@ __device__ __forceinline__ void dist_phase_bits(const DistCtx& a, const uint32_t
   }
 }
 
+
+// ---- the graph walk shared by the traversal kernels (hnsw_kernels.hip: f32 rows and packed bits; hnsw_half.hip: the f16 / bf16
+// images): NativeHnsw::search, statement for statement — see the head of hnsw_kernels.hip.  DIST is the distance phase: it owns the
+// query (registers, or the LDS scratch behind the lists for dimensions that are no multiple of 256) and evaluates nb_id[0..m) ->
+// nb_d[0..m) with all waves of the block; everything else — phases, lists, visited set, counters, result mapping — is the same text
+// for every row format, so the formats cannot drift apart.
+enum WalkPhase : int {
+  P_START = 0,   // evaluate dist(q, cur) on `layer`
+  P_G_ENTRY,     // consume it as best_dist (graph.rs:407)
+  P_G_LOAD,      // load neighbours of best (graph.rs:410)
+  P_G_SCAN,      // scan them with strict < (graph.rs:413-421)
+  P_G_DONE,      // no improvement: next layer down
+  P_Z_ENTRY,     // layer 0: push the entry point (graph.rs:464-469)
+  P_Z_POP,       // pop nearest candidate, termination test, gather unvisited neighbours (:471-499)
+  P_Z_ADMIT,     // admission of the evaluated neighbours in list order (:500-511)
+  P_FINISH,
+  P_R_DONE       // rerank: raw scores of the candidates are in nb_d
+};
+
+// the f32 rows (Cosine / Euclidean / DotProduct, canonical arithmetic) and the packed bits (Hamming / Jaccard)
+template <int METRIC, int CPL, int WAVES, int R>
+struct WalkDistF32 {
+  static constexpr bool BITS = (METRIC == kHamming || METRIC == kJaccard);
+  static constexpr int TPB = WAVES * 64;
+  DistCtx dc;
+  float* qgen;
+  uint32_t* qbits;
+  float4 q[CPL > 0 ? CPL : 1];
+  float qnorm;
+  __device__ __forceinline__ void init(const HnswSearchArgs& a, unsigned char* qscratch) {
+    dc = DistCtx{a.rows, a.norms, a.bits, a.row_stride, a.dim, a.words};
+    qgen = reinterpret_cast<float*>(qscratch);
+    qbits = reinterpret_cast<uint32_t*>(qscratch);
+  }
+  // every thread of the block; the caller's barrier follows
+  __device__ __forceinline__ void load_query(const float* qp, int lane) {
+    const int d4 = (int)((dc.dim + 3) / 4);
+    qnorm = 0.0f;
+    if (BITS) {
+      for (uint32_t w = threadIdx.x; w < dc.words; w += TPB) {
+        uint32_t bitsw = 0;
+        for (uint32_t e = 0; e < 32; e++) {
+          const uint32_t i = w * 32 + e;
+          if (i < dc.dim && qp[i] > 0.5f) bitsw |= 1u << e;
+        }
+        qbits[w] = bitsw;
+      }
+    } else if (CPL > 0) {
+      float nacc = 0.0f;
+#pragma unroll
+      for (int c = 0; c < CPL; c++) {
+        q[c] = ld4(qp + (size_t)(c * 64 + lane) * 4);
+        nacc = chain4<kOpDot>(nacc, q[c], q[c]);
+      }
+      if (METRIC == kCosine) qnorm = sqrtf(butterfly_all(nacc));
+    } else {
+      const int qlen = d4 * 4;
+      for (int i = threadIdx.x; i < qlen; i += TPB) qgen[i] = i < (int)dc.dim ? qp[i] : 0.0f;
+      __syncthreads();
+      if (METRIC == kCosine) {
+        float nacc = 0.0f;
+        for (int c = lane; c < d4; c += 64) {
+          const float4 x = ld4(qgen + c * 4);
+          const int nv = (int)dc.dim - c * 4;
+          nacc = nv >= 4 ? chain4<kOpDot>(nacc, x, x) : chain4_tail<kOpDot>(nacc, x, x, nv);
+        }
+        qnorm = sqrtf(butterfly_all(nacc));
+      }
+    }
+  }
+  __device__ __forceinline__ void eval(uint32_t m, lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib, bool raw) const {
+    if (BITS)
+      dist_phase_bits<METRIC>(dc, qbits, m, nb_id, nb_d, raw);
+    else
+      dist_phase_f32<METRIC, CPL, WAVES, R>(dc, q, qnorm, qgen, m, nb_id, nb_d, lane, wib, raw);
+  }
+};
+
+// the f16 / bf16 image of the rows (hnsw_half.hip): the query is rounded once here, the Cosine query norm is the canonical chain
+// over the ROUNDED query
+template <int METRIC, int CPL, int WAVES, int R, bool F16>
+struct WalkDistHalf {
+  static constexpr int TPB = WAVES * 64;
+  DistCtx dc;  // rows = the image, row_stride in half elements, norms of the rounded rows
+  float* qgen;
+  float4 q[CPL > 0 ? CPL : 1];
+  float qnorm;
+  __device__ __forceinline__ void init(const HnswSearchArgs& a, unsigned char* qscratch) {
+    dc = DistCtx{a.rows, a.norms, nullptr, a.row_stride, a.dim, 0};
+    qgen = reinterpret_cast<float*>(qscratch);
+  }
+  __device__ __forceinline__ void load_query(const float* qp, int lane) {
+    const int d4 = (int)((dc.dim + 3) / 4);
+    qnorm = 0.0f;
+    if (CPL > 0) {
+      float nacc = 0.0f;
+#pragma unroll
+      for (int c = 0; c < CPL; c++) {
+        q[c] = round_to_half4<F16>(ld4(qp + (size_t)(c * 64 + lane) * 4));
+        nacc = chain4<kOpDot>(nacc, q[c], q[c]);
+      }
+      if (METRIC == kCosine) qnorm = sqrtf(butterfly_all(nacc));
+    } else {
+      const int qlen = d4 * 4;
+      for (int i = threadIdx.x; i < qlen; i += TPB) qgen[i] = i < (int)dc.dim ? round_to_half<F16>(qp[i]) : 0.0f;
+      __syncthreads();
+      if (METRIC == kCosine) {
+        float nacc = 0.0f;
+        for (int c = lane; c < d4; c += 64) {
+          const float4 x = ld4(qgen + c * 4);
+          const int nv = (int)dc.dim - c * 4;
+          nacc = nv >= 4 ? chain4<kOpDot>(nacc, x, x) : chain4_tail<kOpDot>(nacc, x, x, nv);
+        }
+        qnorm = sqrtf(butterfly_all(nacc));
+      }
+    }
+  }
+  __device__ __forceinline__ void eval(uint32_t m, lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib, bool) const {
+    dist_phase_half<METRIC, CPL, WAVES, R, F16>(dc, q, qnorm, qgen, m, nb_id, nb_d, lane, wib);
+  }
+};
+
+template <int METRIC, int CPL, int NS, bool LAT, bool VIS, bool RAWEF, class DIST>
+__device__ __forceinline__ void hnsw_walk_body(const HnswSearchArgs& a) {
+  constexpr int WAVES = LAT ? 16 : 4, TPB = WAVES * 64;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = lane_id();
+  const int wib = (int)rfl(threadIdx.x >> 6);
+  const uint32_t cap = a.cap, nbmax = a.nbmax;
+  const uint32_t ef_launch = a.ef;
+  uint32_t ef_query = a.ef;  // RAWEF only (wave-uniform)
+#define ef (RAWEF ? ef_query : ef_launch)
+  lds_vu64* keys = (lds_vu64*)(lds_void_p)(smem);
+  lds_vu32* nb_id = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8);
+  lds_vf32* nb_d = (lds_vf32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 4);
+  lds_vu32* ctl = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8);
+  lds_vu8* flags = (lds_vu8*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8 + 16);
+  const size_t qoff = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+
+  uint32_t* vis = a.visited + (size_t)blockIdx.x * a.vis_words;
+  uint32_t* vlog = a.vlog + (size_t)blockIdx.x * a.vlog_cap;
+  // VIS: the exact visited set in LDS (zero between queries); a query stops with the overflow flag before it is 3/4 full
+  const VisSet vs{reinterpret_cast<uint32_t*>(smem + a.vis_off), (1u << a.vis_log2) - 1u, 32u - a.vis_log2};
+  const uint32_t vis_limit = VIS ? (3u << a.vis_log2) / 4u : 0xFFFFFFFFu;
+  if (VIS) {
+    vs.clear(threadIdx.x, TPB);
+    __syncthreads();
+  }
+  DIST dist;
+  dist.init(a, smem + qoff);
+
+  for (uint32_t qi = blockIdx.x; qi < a.nq; qi += gridDim.x) {
+    const float* qp = a.queries + (size_t)qi * a.q_stride;
+    dist.load_query(qp, lane);
+    __syncthreads();
+
+    // ---- leader state (meaningful in wave 0 only; every value is wave-uniform) ----
+    CandList<NS> list;
+    list.init(keys, flags, cap);
+    uint32_t n_dist = 0, n_expand = 0, logn = 0, overflow = 0, m_prev = 0, rr_m = 0;
+    bool spec = false;        // LAT: the distance phase in flight evaluates ALL neighbours of the expanded node ...
+    uint64_t spec_mask = 0;   // ... and these lanes' neighbours were unvisited (known behind that phase)
+    // the neighbour list of the PREDICTED next pop — the nearest unexpanded candidate left behind by this pop — requested with this
+    // pop's own list: when the admission puts nothing in front of it (most expansions once the beam has settled), the next pop finds
+    // its ids in registers and the walk is one dependent memory round trip shorter.  A wrong guess costs 260 bytes.  Not counted:
+    // n_dist / n_expand are what the reference's loop counts (graph.rs:471-511).
+    uint32_t pf_node = 0xFFFFFFFFu, pf_nb = 0, pf_cnt = 0, pf_hits = 0;
+    // (latency-mode instances only: the throughput instances sit at the 128-register line that lets four walks share a CU, and the
+    // three registers this needs across the distance phase put 20 of theirs into scratch)
+    const bool PF = LAT && a.pf_ids != 0;
+    int phase = P_START;
+    int layer = (int)a.max_layer;
+    uint32_t cur = a.entry_point;
+    float best_d = 0.0f;
+
+    for (;;) {
+      if (wib == 0) {
+        bool ready = false;
+        uint32_t m = 0, done = 0, raw = 0;
+        while (!ready) {
+          if (phase == P_START) {
+            if (lane == 0) nb_id[0] = cur;
+            m = 1;
+            if (layer == 0 && a.extra_eps) {  // search_multi_entry: the drawn ids that are not yet entry points (graph.rs:335-338)
+              uint32_t e0 = cur, e1 = 0xFFFFFFFFu, e2 = 0xFFFFFFFFu;
+              for (uint32_t j = 0; j < 3; j++) {
+                const uint32_t id = a.extra_eps[(size_t)qi * 3 + j];
+                if (id == 0xFFFFFFFFu || id == e0 || id == e1 || id == e2) continue;
+                if (lane == 0) nb_id[m] = id;
+                if (m == 1) e1 = id; else e2 = id;  // (a third new id has nothing behind it to be compared with)
+                m++;
+              }
+            }
+            // graph.rs:463-468 pushes EVERY entry point into `results` with no cut, and graph.rs:503-509 pops at most one entry per
+            // push: with more entry points than ef_search the result set simply stays at that size — which is what a search with
+            // ef = the number of entry points does from its first step (results full from the start: same admission test
+            // `dist < furthest`, same single pop, same stop rule `len >= ef`).  Only NativeHnsw-level calls get here with ef < m:
+            // search_multi_entry with ef_search < 4 and several probes, or ef_search = 0 (which therefore acts as 1).
+            if (RAWEF && layer == 0) ef_query = max(ef_launch, m);
+            ready = true;
+            phase = layer > 0 ? P_G_ENTRY : P_Z_ENTRY;
+          } else if (phase == P_G_ENTRY) {
+            best_d = rflf(nb_d[0]);
+            n_dist += 1;
+            phase = P_G_LOAD;
+          } else if (phase == P_G_LOAD) {
+            const HnswLayerRef L = a.layers[layer];
+            uint32_t nc = rfl(L.cnt[cur]);
+            nc = min(nc, min(L.stride, nbmax));
+            for (uint32_t base = 0; base < nc; base += 64) {
+              const uint32_t t = base + lane;
+              if (t < nc) nb_id[t] = L.nbr[(size_t)cur * L.stride + t];
+            }
+            if (nc == 0) {
+              phase = P_G_DONE;
+            } else {
+              m = nc;
+              ready = true;
+              phase = P_G_SCAN;
+            }
+          } else if (phase == P_G_SCAN) {
+            n_dist += m_prev;
+            // sequential scan with strict `<` == first index attaining the minimum, if below best
+            float mn = 0.0f;
+            uint32_t besti = 0xFFFFFFFFu;
+            for (uint32_t base = 0; base < m_prev; base += 64) {
+              const uint32_t t = base + lane;
+              const float d = t < m_prev ? nb_d[t] : 0.0f;
+              const bool ok = t < m_prev && d < best_d;  // raw compare: NaN never improves
+              const uint64_t okm = __ballot(ok);
+              if (okm) {
+                float v = ok ? d : __uint_as_float(0x7F800000u);
+#pragma unroll
+                for (int s = 32; s >= 1; s >>= 1) v = fminf(v, shx(v, s));
+                v = rflf(v);
+                if (besti == 0xFFFFFFFFu || v < mn) {
+                  const uint64_t eq = __ballot(ok && d == v);
+                  besti = base + (uint32_t)__ffsll((long long)eq) - 1;
+                  mn = v;
+                }
+              }
+            }
+            if (besti != 0xFFFFFFFFu) {
+              cur = rfl(nb_id[besti]);
+              best_d = rflf(nb_d[besti]);
+              phase = P_G_LOAD;
+            } else {
+              phase = P_G_DONE;
+            }
+          } else if (phase == P_G_DONE) {
+            layer -= 1;
+            phase = P_START;
+          } else if (phase == P_Z_ENTRY) {
+            // graph.rs:463-468: every entry point is evaluated, pushed to both heaps and marked visited (one unless search_multi_entry)
+            for (uint32_t t = 0; t < m_prev; t++) {
+              const float d = rflf(nb_d[t]);
+              const uint32_t ep = rfl(nb_id[t]);
+              n_dist += 1;
+              list.insert(make_key<false>(d, ep), lane, overflow);
+              if (lane == 0) {
+                if (VIS) {
+                  (void)vs.test_and_set(ep);
+                } else {
+                  atomicOr(&vis[ep >> 5], 1u << (ep & 31));
+                  if (a.vlog_cap) vlog[t] = ep;
+                }
+              }
+            }
+            logn = m_prev;
+            phase = P_Z_POP;
+          } else if (phase == P_Z_POP) {
+            const uint32_t idx = list.first_unexpanded(lane);
+            if (idx == kNoIndex) {
+              phase = P_FINISH;  // candidates empty (graph.rs:471)
+            } else {
+              const uint64_t ckey = list.key_at(idx, lane);
+              bool stop = false;
+              if (list.size() >= ef) stop = key_dist(ckey) > key_dist(list.key_at(ef - 1, lane));  // graph.rs:474
+              if (!stop && VIS && logn + nbmax > vis_limit) {  // the LDS set could pass 3/4: the caller re-runs on the bitmap
+                overflow = 1;
+                stop = true;
+              }
+              if (stop) {
+                phase = P_FINISH;
+              } else {
+                list.mark_expanded(idx, lane);
+                n_expand += 1;
+                const uint32_t cnode = (uint32_t)ckey;
+                const HnswLayerRef L = a.layers[0];
+                // the neighbour ids are requested together with the count (one memory round trip instead of two)
+                const uint32_t lim = min(L.stride, nbmax);
+                uint32_t nb0 = 0, ncv = 0;
+                if (PF && pf_node == cnode) {
+                  nb0 = pf_nb;
+                  ncv = pf_cnt;
+                  pf_hits += 1;
+                } else {
+                  if ((uint32_t)lane < lim) nb0 = L.nbr[(size_t)cnode * L.stride + lane];
+                  ncv = L.cnt[cnode];
+                }
+                uint32_t nc = rfl(ncv);
+                nc = min(nc, lim);
+                if (PF) {
+                  // (behind the wait for this pop's own list: where the two paths above join, the compiler waits for EVERY load in
+                  // flight — requested in front of that, the prediction's round trip was paid by every pop: 2 % slower than none)
+                  const uint32_t idx2 = list.first_unexpanded(lane);
+                  pf_node = 0xFFFFFFFFu;
+                  if (idx2 != kNoIndex) {
+                    pf_node = (uint32_t)list.key_at(idx2, lane);
+                    if ((uint32_t)lane < lim) pf_nb = L.nbr[(size_t)pf_node * L.stride + lane];
+                    pf_cnt = L.cnt[pf_node];
+                  }
+                }
+                if (LAT && a.lat_spec) {  // (nc <= 64, host) every neighbour is evaluated; the visited verdicts follow with the distances
+                  if ((uint32_t)lane < nc) nb_id[lane] = nb0;
+                  m = nc;
+                  spec = nc != 0;
+                } else {
+                for (uint32_t base = 0; base < nc; base += 64) {
+                    const uint32_t t = base + lane;
+                    const bool valid = t < nc;
+                    uint32_t nb = nb0;
+                    bool newly = false;
+                    if (valid) {
+                      if (base != 0) nb = L.nbr[(size_t)cnode * L.stride + t];
+                      const uint32_t bit = 1u << (nb & 31);
+                      newly = VIS ? vs.test_and_set(nb) : (atomicOr(&vis[nb >> 5], bit) & bit) == 0;  // visited.insert (graph.rs:499)
+                    }
+                    const uint64_t mask = __ballot(newly);
+                    const uint32_t before = (uint32_t)__popcll(mask & lt_mask(lane));
+                    if (newly) {
+                      nb_id[m + before] = nb;
+                      if (!VIS && logn + before < a.vlog_cap) vlog[logn + before] = nb;
+                    }
+                    m += (uint32_t)__popcll(mask);
+                    logn += (uint32_t)__popcll(mask);
+                  }
+                }
+                if (m != 0) {
+                  ready = true;
+                  phase = P_Z_ADMIT;
+                }
+              }
+            }
+          } else if (phase == P_Z_ADMIT) {
+            if (LAT && a.lat_spec) {  // the unvisited ones of the evaluated neighbours, in list order: counters and the undo log
+              n_dist += (uint32_t)__popcll(spec_mask);
+              if (!VIS && (spec_mask >> lane & 1ull)) {
+                const uint32_t pos = logn + (uint32_t)__popcll(spec_mask & lt_mask(lane));
+                if (pos < a.vlog_cap) vlog[pos] = nb_id[lane];
+              }
+              logn += (uint32_t)__popcll(spec_mask);
+            } else {
+              n_dist += m_prev;
+            }
+            for (uint32_t base = 0; base < m_prev; base += 64) {
+              const uint32_t t = base + lane;
+              const float d = t < m_prev ? nb_d[t] : 0.0f;
+              uint32_t size = list.size() < ef ? list.size() : ef;
+              float far = key_dist(list.key_at(size - 1, lane));
+              // pre-filter against the furthest distance at chunk start: it only decreases while the
+              // result set is full, so a neighbour rejected now would be rejected at its turn too
+              uint64_t mask = __ballot(t < m_prev && (d < far || size < ef));
+              if (LAT && a.lat_spec) mask &= spec_mask;
+              // two or more to admit: all at once (vdb_hnsw_device.hpp admit_batch) unless distances tie exactly
+              if (NS > 0 && (mask & (mask - 1)) != 0ull &&
+                  list.admit_batch(mask, d, t < m_prev ? nb_id[t] : 0u, lane, ef, keys, flags))
+                mask = 0ull;
+              while (mask) {
+                const int src = __ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const float dj = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(d), src));
+                size = list.size() < ef ? list.size() : ef;
+                far = key_dist(list.key_at(size - 1, lane));
+                if (dj < far || size < ef) {  // graph.rs:503
+                  const uint32_t nbj = nb_id[base + src];
+                  list.insert(make_key<false>(dj, nbj), lane, overflow);
+                  list.truncate(ef, lane);
+                }
+              }
+            }
+            phase = P_Z_POP;
+          } else if (phase == P_FINISH) {
+            if (a.rerank_k == 0) {
+              done = 1;
+              ready = true;
+            } else {
+              // search_with_rerank (search.rs:118-160): candidates = the search result for k = rerank_k (soft-deleted
+              // rows dropped, search.rs:86-91); their rows are re-scored with the raw compute_distance
+              const uint32_t size = list.size() < ef ? list.size() : ef;
+              const uint32_t kk = a.rerank_k < size ? a.rerank_k : size;
+              for (uint32_t base = 0; base < kk; base += 64) {
+                const uint32_t e = base + lane;
+                const bool v = e < kk;
+                const uint32_t node = v ? (uint32_t)list.chunk_key(base, lane) : 0;
+                bool al = v;
+                if (v && a.alive) al = a.alive[node] != 0;
+                const uint64_t mask = __ballot(al);
+                if (al) nb_id[m + (uint32_t)__popcll(mask & lt_mask(lane))] = node;
+                m += (uint32_t)__popcll(mask);
+              }
+              raw = 1;
+              rr_m = m;
+              phase = P_R_DONE;
+              if (m == 0) done = 1;
+              ready = true;
+            }
+          } else {  // P_R_DONE
+            done = 1;
+            ready = true;
+          }
+        }
+        if (lane == 0) {
+          ctl[0] = m;
+          ctl[1] = done;
+          ctl[2] = logn;
+          ctl[3] = raw;
+        }
+        m_prev = m;
+      }
+      __syncthreads();
+      const uint32_t m = ctl[0];
+      if (ctl[1]) break;
+      const bool raw = ctl[3] != 0;
+      uint32_t spec_old = 0, spec_bit = 0;
+      const bool spec_lane = LAT && wib == 0 && spec && (uint32_t)lane < m;
+      if (spec_lane) {  // visited.insert (graph.rs:499) for every neighbour, in flight beside the row fetches below
+        const uint32_t nb = nb_id[lane];
+        spec_bit = 1u << (nb & 31);
+        spec_old = VIS ? (vs.test_and_set(nb) ? 0u : spec_bit) : atomicOr(&vis[nb >> 5], spec_bit);
+      }
+      dist.eval(m, nb_id, nb_d, lane, wib, raw);
+      if (LAT && wib == 0) {
+        spec_mask = spec ? __ballot(spec_lane && (spec_old & spec_bit) == 0) : 0ull;
+        spec = false;
+      }
+      __syncthreads();
+    }
+
+    // ---- rerank results: stable sort of the re-scored candidates in the metric's order (distance.rs:95-103),
+    // cut to k.  sort key = (order-key(score) << 32 | candidate position): unique, rank = #smaller keys ----
+    if (a.rerank_k != 0) {
+      if (wib == 0) {
+        const uint32_t m = rr_m;  // candidates re-scored in the last distance phase (0 if none)
+        constexpr bool HIB = higher_is_better(METRIC);
+        const uint32_t outn = m < a.k ? m : a.k;
+        for (uint32_t i = lane; i < m; i += 64) keys[i] = make_key<HIB>(nb_d[i], i);
+        for (uint32_t i = lane; i < m; i += 64) {
+          const uint64_t mine = keys[i];
+          uint32_t rank = 0;
+          for (uint32_t j = 0; j < m; j++) rank += keys[j] < mine ? 1u : 0u;
+          if (rank < a.k) {
+            const uint32_t node = nb_id[i];
+            a.out_ids[(size_t)qi * a.k + rank] = a.ext_ids ? a.ext_ids[node] : (uint64_t)node;
+            a.out_scores[(size_t)qi * a.k + rank] = nb_d[i];
+          }
+        }
+        for (uint32_t e = outn + lane; e < a.k; e += 64) {
+          a.out_ids[(size_t)qi * a.k + e] = ~0ull;
+          a.out_scores[(size_t)qi * a.k + e] = __uint_as_float(0x7FC00000u);
+        }
+        if (lane == 0) {
+          a.out_n[qi] = overflow ? 0xFFFFFFFFu : outn;
+          if (a.stats) {
+            atomicAdd(&a.stats[0], (unsigned long long)n_dist);
+            atomicAdd(&a.stats[1], (unsigned long long)n_expand);
+            if (pf_hits) atomicAdd(&a.stats[2], (unsigned long long)pf_hits);
+          }
+        }
+      }
+    } else
+    // ---- results: first k of the sorted result set, soft-deleted rows dropped after the cut
+    // (search.rs:86-91), scores through transform_score ----
+    if (wib == 0) {
+      const uint32_t size = list.size() < ef ? list.size() : ef;
+      const uint32_t kk = a.k < size ? a.k : size;
+      uint32_t outn = 0;
+      for (uint32_t base = 0; base < kk; base += 64) {
+        const uint32_t e = base + lane;
+        const bool v = e < kk;
+        const uint64_t key = v ? list.chunk_key(base, lane) : 0;
+        const uint32_t node = (uint32_t)key;
+        bool al = v;
+        if (v && a.alive) al = a.alive[node] != 0;
+        const uint64_t mask = __ballot(al);
+        const uint32_t p = outn + (uint32_t)__popcll(mask & lt_mask(lane));
+        if (al) {
+          a.out_ids[(size_t)qi * a.k + p] = a.ext_ids ? a.ext_ids[node] : (uint64_t)node;
+          a.out_scores[(size_t)qi * a.k + p] = transform_score_dev(METRIC, key_dist(key));
+        }
+        outn += (uint32_t)__popcll(mask);
+      }
+      for (uint32_t e = outn + lane; e < a.k; e += 64) {
+        a.out_ids[(size_t)qi * a.k + e] = ~0ull;
+        a.out_scores[(size_t)qi * a.k + e] = __uint_as_float(0x7FC00000u);
+      }
+      if (lane == 0) {
+        a.out_n[qi] = overflow ? 0xFFFFFFFFu : outn;
+        if (a.stats) {
+          atomicAdd(&a.stats[0], (unsigned long long)n_dist);
+          atomicAdd(&a.stats[1], (unsigned long long)n_expand);
+          if (pf_hits) atomicAdd(&a.stats[2], (unsigned long long)pf_hits);
+        }
+      }
+    }
+    // ---- undo the visited bits of this query ----
+    const uint32_t nlog = ctl[2];
+    if (VIS) {
+      __syncthreads();  // (ctl[2] read by everybody before the next query's leader rewrites it)
+      vs.clear(threadIdx.x, TPB);
+    } else if (nlog <= a.vlog_cap) {
+      for (uint32_t i = threadIdx.x; i < nlog; i += TPB) vis[vlog[i] >> 5] = 0;
+    } else {
+      for (uint64_t i = threadIdx.x; i < a.vis_words; i += TPB) vis[i] = 0;
+    }
+    __syncthreads();
+  }
+#undef ef
+}
 
 }  // namespace vdb

@@ -366,6 +366,14 @@ EventPair* next_events(vdb_hip_index* ix);  // nullptr when kernel timing is off
 int32_t hnsw_search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint32_t ef,
                         uint32_t cap_mult, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st,
                         uint32_t rerank_k = 0, const uint32_t* d_extra_eps = nullptr);
+struct HnswSearchArgs;  // vdb_kernels.hpp
+// the launch-independent part of hnsw_search_dev (args, scratch, counters); *slots = 0: nothing to launch
+int32_t hnsw_search_prepare(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint32_t ef,
+                            uint32_t cap_mult, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st,
+                            uint32_t rerank_k, const uint32_t* d_extra_eps, vdb::HnswSearchArgs* out, int* slots);
+// hnsw_half.hip: the same search over the f16 / bf16 image of the rows (VDB_SEARCH_HNSW_F16 / _BF16)
+int32_t hnsw_search_half_dev(vdb_hip_index* ix, bool f16, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint32_t ef,
+                             uint32_t cap_mult, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st);
 // hnsw_build.hip; max_batch 1 = the reference's sequential insert, 0 = default batched schedule
 int32_t graph_insert_rows(vdb_hip_index* ix, uint64_t first, uint64_t n, uint32_t max_batch);
 int32_t ensure_traversal_scratch(vdb_hip_index* ix, hipStream_t st, int want_slots = 0);

@@ -32,6 +32,9 @@ KIND_ENGINE, KIND_RAW = 0, 1
  KERNEL_SELECT_BF16, KERNEL_SELECT_SPLIT, KERNEL_BITS, KERNEL_SQ8, KERNEL_HNSW, KERNEL_HNSW_INT8, KERNEL_BITS_GEMM) = (1 << i for i in range(13))
 # an f16 instance of a matrix-core family ran (set next to the family's bit); the half-row Euclidean sweep
 KERNEL_F16, KERNEL_SWEEP_HALF_L2 = 1 << 13, 1 << 14
+# graph search over the f16 / bf16 copy of the rows (VDB_SEARCH_HNSW_F16 / _BF16) and its kernel family
+MODE_HNSW_F16, MODE_HNSW_BF16 = 8, 9
+KERNEL_HNSW_HALF = 1 << 15
 SHARD_REPLICA, SHARD_RANGE = 0, 1
 COMM_ID_BYTES = 128
 
@@ -354,6 +357,21 @@ class HnswIndex:
             qs = qs.reshape(1, -1)
         self._validate(qs)
         return self._search_raw(qs, k, 0, MODE_BRUTE_F16 if precision == VectorPrecision.F16 else MODE_BRUTE_BF16)
+
+    def search_batch_half_graph(self, queries, k: int, ef_search: int, precision):
+        """Graph search over the half-precision copy of the rows: NativeHnsw::search on the index's graph exactly as
+        search_batch_parallel (ef_search = 0 -> Balanced, max(ef_search, k), scores through transform_score), every distance taken
+        between the query rounded to `precision` and the row's half image (half_precision.rs:199-287) — half the bytes of the f32
+        walk per visited node.  Needs enable_half_precision(precision) and a graph.  Returns what search_batch_int8 returns."""
+        precision = VectorPrecision(int(precision))
+        if precision == VectorPrecision.F32:
+            raise ValueError("half-precision graph search: F16 or BF16")
+        qs = _f32(queries)
+        if qs.ndim == 1:
+            qs = qs.reshape(1, -1)
+        self._validate(qs)
+        ids, sc, cnt = self._search_raw(qs, k, ef_search, MODE_HNSW_F16 if precision == VectorPrecision.F16 else MODE_HNSW_BF16)
+        return [self._tuples(ids[i], sc[i], cnt[i]) for i in range(qs.shape[0])]
 
     # ---- storage modes (core/quantization.rs) -----------------------------------------------
     def set_storage_mode(self, mode) -> None:
