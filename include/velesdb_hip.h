@@ -279,6 +279,40 @@ int32_t vdb_hip_index_search_batch_dev(vdb_hip_index* idx, const float* d_querie
                                        uint32_t k, uint32_t ef, int32_t mode, uint64_t* d_out_ids,
                                        float* d_out_scores, uint32_t* d_out_n, void* stream);
 
+/* ---- filtered exact search: an id allow-list applied inside the sweep ----
+ * The reference's `_with_filter` searches (collection/search/vector.rs:164-239, batch.rs:26-136) post-filter: they over-fetch
+ * max(4k, k + 10) candidates and drop what the predicate rejects, so a selective filter returns fewer than k results although many
+ * rows match.  Here the caller hands over the SET OF IDS that matched (payloads and predicates stay the caller's) and the device
+ * answers the exact top-k among exactly those rows.
+ *
+ * A filter is an immutable snapshot of internal rows.  `ids` are mapped through the handle's id map at creation (under the handle's
+ * lock); unknown ids and duplicates are ignored; negate != 0 = "every row present now except these".  *matched (nullable) = rows in
+ * the set (rows that are soft-deleted but still present count; they are dropped at search time).  n_ids == 0 with negate == 0 is a
+ * legal empty filter: every search with it answers out_n = 0.  Rows inserted after creation are not in the filter; rows removed
+ * after creation are excluded (the live flags are read at search time).  vdb_hip_index_vacuum and the load_* calls renumber the
+ * rows of a handle: a filter created before them answers VDB_ERR_STATE, a filter of another handle VDB_ERR_INVALID_ARG — never
+ * results.  A filter may be used by any number of concurrent searches.  It must be destroyed before its index; after the index is
+ * gone it is valid for vdb_hip_filter_destroy only.  Costs n_rows / 8 + 4 * matched bytes of HBM.
+ * VDB_ERR_UNSUPPORTED: a multi-device handle or a member of a process group. */
+/* opaque.  At this boundary the filter handle is an untyped pointer: callers declare `vdb_hip_filter* f` and pass `&f` / `f` as
+ * below; the index handle stays the one struct type of the ABI (what the binding checks of this project and sys.rs know). */
+typedef void vdb_hip_filter;
+int32_t vdb_hip_index_filter_create(vdb_hip_index* idx, const uint64_t* ids, uint64_t n_ids, int32_t negate, uint64_t* matched,
+                                    void** out);
+void vdb_hip_filter_destroy(void* f);
+/* vdb_hip_index_search_batch in VDB_SEARCH_BRUTE restricted to the filter's rows, all five metrics: ids, ranks and score bits are
+ * those VDB_SEARCH_BRUTE returns on an index that holds only the allowed live rows, inserted in the same order under the same ids
+ * (the arithmetic is the handle's: vdb_hip_index_sweep_arith_mode) — a filter never changes a score.  Outputs, tie order, padding,
+ * raw scores, k limits and errors as vdb_hip_index_search_batch.  f == NULL: VDB_ERR_INVALID_ARG.  Every other mode and every
+ * multi-device handle: VDB_ERR_UNSUPPORTED (HnswIndex::search_filtered's over-fetch rule stays the shim's for the graph modes).
+ * Two routes, same bits: the LISTED sweep (sweep_topk_listed: only the filter's rows are read, gathered by index; Cosine /
+ * DotProduct / Euclidean; VDB_KERNEL_SWEEP_LISTED) and MASK SUBSTITUTION (the filter AND the live flags become the call's row mask
+ * and every tier of the exact path serves it).  VDB_OPT_FILTER_ROUTE picks; auto = listed iff matched <= rows / 4 and
+ * matched * nq <= 8 * rows (a stated guess, not a measurement: DESIGN 4.1g).  A filtered call never shares a launch with another
+ * call (it does not go through the combining front) and leaves the handle's adaptive selection state as it found it. */
+int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* idx, const void* f, const float* queries_rowmajor, uint32_t nq,
+                                            uint32_t k, int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+
 /* ---- DistanceEngine::batch_distance / GpuAccelerator::batch_{cosine_similarity,
  * euclidean_distance,dot_product} (native/distance.rs:21-24; gpu_backend.rs:157,355,397) ----
  * n rows of dim floats against one query; out has n floats, same order as the rows. */
@@ -349,7 +383,10 @@ enum vdb_option {
   VDB_OPT_COMBINE_MAX_BATCH = 5,
   VDB_OPT_COMBINE_WINDOW_US = 6,
   VDB_OPT_COMBINE_INFLIGHT = 7,
-  VDB_OPT_COUNT_ = 8
+  /* route of vdb_hip_index_search_batch_filtered: <= 0 = auto (the rule stated there), 1 = the listed sweep wherever the metric has
+   * it, 2 = mask substitution.  Like every option it never changes a result. */
+  VDB_OPT_FILTER_ROUTE = 8,
+  VDB_OPT_COUNT_ = 9
 };
 int32_t vdb_hip_index_set_option(vdb_hip_index* idx, int32_t option, int64_t value);
 int32_t vdb_hip_index_get_option(vdb_hip_index* idx, int32_t option, int64_t* value); /* the effective value */
@@ -447,7 +484,8 @@ enum vdb_kernel_bit {
   VDB_KERNEL_F16 = 8192,           /* an IEEE f16 instance of a matrix-core family ran (VDB_SEARCH_BRUTE_F16): set NEXT TO the family's
                                       bit — SWEEP_MFMA_BF16 / GEMM_BF16 / GEMM_BF16_GLDS then name the f16 instance of that kernel      */
   VDB_KERNEL_SWEEP_HALF_L2 = 16384, /* sweep_topk_half_l2 (Euclidean difference chain over the f16 / bf16 rows)                       */
-  VDB_KERNEL_HNSW_HALF = 32768     /* hnsw_search_half_kernel (VDB_SEARCH_HNSW_F16 / _BF16; VDB_KERNEL_F16 next to it for the f16 instance) */
+  VDB_KERNEL_HNSW_HALF = 32768,    /* hnsw_search_half_kernel (VDB_SEARCH_HNSW_F16 / _BF16; VDB_KERNEL_F16 next to it for the f16 instance) */
+  VDB_KERNEL_SWEEP_LISTED = 65536  /* sweep_topk_listed / sweep_topk_listed_m (vdb_hip_index_search_batch_filtered, the listed route) */
 };
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""GPU probe of the filtered exact search (vdb_hip_index_search_batch_filtered), single MI355X, host-pointer calls (the filtered
+entry point has no device-resident variant yet, so every figure carries the query upload and the result download — the unfiltered
+yardstick is measured through the same kind of call).  Prints and writes what DESIGN.md 4.1g quotes, per metric:
+
+  for every selectivity (share of the rows the filter allows) and batch size, k = 10:
+    ms per call on the forced listed route, on the forced mask route, under the auto rule, and of the unfiltered VDB_SEARCH_BRUTE
+    call on the same handle in the same run (no unfiltered code differs from the parent: that is the yardstick);
+    which forced route is faster, and how far auto is from it;
+    one query on the listed route: count x dim x 4 B / time, as a fraction of the whole-row gather rate --gather-tbs;
+  --rider: HnswIndex.search_filtered (the over-fetch rule) for one query with the number of results it actually returned
+  (needs the graph: build_graph over every row first — minutes at 1 M rows, off by default).
+
+Every figure is the median of --repeats blocks, each block the mean over enough calls to last ~--block-ms; the spread is
+(max - min) / median over the blocks.  Not part of the product or the test-suite."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import velesdb_amd as va  # noqa: E402
+
+p = argparse.ArgumentParser()
+p.add_argument("--rows", type=int, default=1_000_000)
+p.add_argument("--dim", type=int, default=768)
+p.add_argument("--k", type=int, default=10)
+p.add_argument("--metrics", default="cosine,euclidean")
+p.add_argument("--selectivities", default="0.001,0.01,0.1,0.5")
+p.add_argument("--nq", default="1,16,64,256,1024")
+p.add_argument("--repeats", type=int, default=5)
+p.add_argument("--block-ms", type=float, default=40.0)
+p.add_argument("--gather-tbs", type=float, default=5.7, help="whole-row gather rate to compare one-query listed calls with, TB/s")
+p.add_argument("--rider", action="store_true")
+p.add_argument("--out", default="")
+a = p.parse_args()
+dev = torch.device("cuda", 0)
+st = torch.cuda.current_stream().cuda_stream
+METRICS = {"cosine": va.DistanceMetric.Cosine, "euclidean": va.DistanceMetric.Euclidean, "dot": va.DistanceMetric.DotProduct}
+
+
+def build(metric):
+    ix = va.HnswIndex(a.dim, metric, va.HnswParams(32, 400, a.rows))
+    g = torch.Generator(device=dev)
+    g.manual_seed(42)
+    for base in range(0, a.rows, 250_000):
+        n = min(250_000, a.rows - base)
+        c = torch.randn((n, a.dim), generator=g, device=dev)
+        torch.cuda.synchronize()
+        ix.upload_dev(base, c.data_ptr(), n, st)
+        torch.cuda.synchronize()
+        del c
+    return ix
+
+
+def measure(fn):
+    """median ms per call over blocks, relative spread of the blocks"""
+    for _ in range(3):
+        fn()
+    t0 = time.perf_counter()
+    fn()
+    one = max(time.perf_counter() - t0, 1e-6)
+    iters = int(min(200, max(3, a.block_ms * 1e-3 / one)))
+    blocks = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            fn()
+        blocks.append((time.perf_counter() - t0) / iters * 1e3)
+    med = statistics.median(blocks)
+    return med, (max(blocks) - min(blocks)) / med
+
+
+table = []
+for mname in a.metrics.split(","):
+    ix = build(METRICS[mname])
+    ix.set_option(va.OPT_COMBINE_MAX_BATCH, 0)  # the unfiltered yardstick launches alone too
+    rng = np.random.default_rng(7)
+    if a.rider:
+        t0 = time.perf_counter()
+        ix.build_graph()
+        print(f"# {mname}: graph over {a.rows} rows in {time.perf_counter() - t0:.1f} s", flush=True)
+    for nq in [int(x) for x in a.nq.split(",")]:
+        Q = rng.standard_normal((nq, a.dim)).astype(np.float32)
+        plain, plain_sp = measure(lambda: ix.search_batch_brute_force(Q, a.k))
+        for sel in [float(x) for x in a.selectivities.split(",")]:
+            count = max(1, int(a.rows * sel))
+            allowed = np.sort(rng.choice(a.rows, size=count, replace=False)).astype(np.uint64)
+            with ix.create_filter(allowed) as flt:
+                row = dict(metric=mname, rows=a.rows, dim=a.dim, k=a.k, nq=nq, selectivity=sel, count=count, unfiltered_ms=plain, unfiltered_spread=plain_sp)
+                ref = None
+                for name, route in (("listed", va.FILTER_ROUTE_LISTED), ("mask", va.FILTER_ROUTE_MASK), ("auto", va.FILTER_ROUTE_AUTO)):
+                    ix.set_option(va.OPT_FILTER_ROUTE, route)
+                    got = ix.search_batch_brute_force_filtered(Q, a.k, flt)
+                    if name == "auto":
+                        row["auto_took"] = "listed" if ix.last_kernels() & va.KERNEL_SWEEP_LISTED else "mask"
+                    if ref is None:
+                        ref = got
+                    else:  # the routes agree bit for bit (a probe that times wrong answers measures nothing)
+                        assert np.array_equal(ref[0], got[0]) and np.array_equal(ref[1].view(np.uint32), got[1].view(np.uint32)), (mname, nq, sel, name)
+                    row[name + "_ms"], row[name + "_spread"] = measure(lambda: ix.search_batch_brute_force_filtered(Q, a.k, flt))
+                best = min(("listed", "mask"), key=lambda r: row[r + "_ms"])
+                row["better"] = best
+                row["auto_over_better"] = row["auto_ms"] / row[best + "_ms"]
+                if nq == 1:
+                    row["listed_gather_tbs"] = count * a.dim * 4 / (row["listed_ms"] * 1e-3) / 1e12
+                    row["listed_gather_fraction"] = row["listed_gather_tbs"] / a.gather_tbs
+                if a.rider and nq == 1:
+                    keep = set(int(x) for x in allowed)
+                    t0 = time.perf_counter()
+                    res = ix.search_filtered(Q[0], a.k, lambda i: i in keep)
+                    row["rider_ms"], row["rider_results"] = (time.perf_counter() - t0) * 1e3, len(res)
+                table.append(row)
+                print(json.dumps(row), flush=True)
+    ix.close()
+if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(dict(device=va.device_name(0), table=table), f, indent=1)

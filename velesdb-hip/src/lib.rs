@@ -916,6 +916,74 @@ impl HipHnswIndex {
         out
     }
 
+    /// The ids a caller's predicate matched as a device-side allow-list (`vdb_hip_index_filter_create`): an immutable snapshot of
+    /// the rows those ids have now (`negate`: every row present now except them).  Unknown and duplicate ids are ignored, rows
+    /// inserted later are not in it, rows removed later drop out of its results; `vacuum` and `file_load` make it stale (a search
+    /// with it then panics with the library's message).  `None` on a multi-device handle.  Drop it before the index.
+    #[must_use]
+    pub fn create_filter(&self, ids: &[u64], negate: bool) -> Option<HipFilter> {
+        let mut h: *mut std::os::raw::c_void = std::ptr::null_mut();
+        let mut matched: u64 = 0;
+        // SAFETY: `ids` is ids.len() u64s; both out pointers are valid.
+        let rc = unsafe { sys::vdb_hip_index_filter_create(self.h, ids.as_ptr(), ids.len() as u64, i32::from(negate), &mut matched, &mut h) };
+        if rc == sys::VDB_ERR_UNSUPPORTED {
+            return None;
+        }
+        check(rc);
+        Some(HipFilter { h, matched: matched as usize })
+    }
+
+    /// `search_batch_brute_force` among the filter's rows only (`vdb_hip_index_search_batch_filtered`): the exact top-k of the
+    /// allowed live rows — ids, ranks and score bits of an index that holds just those rows.  What the reference's
+    /// `_with_filter` searches (`collection/search/vector.rs:164-239`, `batch.rs:26-136`) approximate by over-fetching
+    /// ([`Self::search_filtered`] keeps that rule for the graph modes).
+    #[must_use]
+    pub fn search_batch_brute_force_filtered(&self, queries: &[&[f32]], k: usize, filter: &HipFilter) -> Vec<Vec<(u64, f32)>> {
+        for q in queries {
+            self.validate_dimension(q, "Query");
+        }
+        if queries.is_empty() {
+            return Vec::new();
+        }
+        if k == 0 {
+            return vec![Vec::new(); queries.len()];
+        }
+        let nq = queries.len();
+        let mut flat = Vec::with_capacity(nq * self.dimension);
+        for q in queries {
+            flat.extend_from_slice(q);
+        }
+        let mut ids = vec![0u64; nq * k];
+        let mut scores = vec![0f32; nq * k];
+        let mut counts = vec![0u32; nq];
+        // SAFETY: buffer sizes are nq*dim / nq*k / nq as the ABI requires; the filter handle is live (owned by `filter`).
+        check(unsafe {
+            sys::vdb_hip_index_search_batch_filtered(
+                self.h,
+                filter.h,
+                flat.as_ptr(),
+                nq as u32,
+                k as u32,
+                sys::VDB_SEARCH_BRUTE,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                counts.as_mut_ptr(),
+            )
+        });
+        (0..nq)
+            .map(|i| {
+                let c = counts[i] as usize;
+                (0..c).map(|j| (ids[i * k + j], scores[i * k + j])).collect()
+            })
+            .collect()
+    }
+
+    /// `search_brute_force` among the filter's rows only (one query).
+    #[must_use]
+    pub fn search_brute_force_filtered(&self, query: &[f32], k: usize, filter: &HipFilter) -> Vec<(u64, f32)> {
+        self.search_batch_brute_force_filtered(&[query], k, filter).pop().unwrap_or_default()
+    }
+
     /// Boxed as the trait object `Collection` holds: what a downstream crate's `hip` feature registers with the index factory
     /// hook of velesdb-core (see Cargo.toml: the dependency points from this crate to the core, never back).
     #[must_use]
@@ -984,6 +1052,33 @@ impl VectorIndex for HipNativeHnswIndex {
 
     fn metric(&self) -> DistanceMetric {
         VectorIndex::metric(&self.0)
+    }
+}
+
+/// An id allow-list of one [`HipHnswIndex`] (`vdb_hip_filter`), made by [`HipHnswIndex::create_filter`].  Immutable; any number of
+/// concurrent searches may use it.
+pub struct HipFilter {
+    h: *mut std::os::raw::c_void,
+    matched: usize,
+}
+
+// SAFETY: the filter is immutable after creation and the library reads it from any thread.
+unsafe impl Send for HipFilter {}
+// SAFETY: as above.
+unsafe impl Sync for HipFilter {}
+
+impl HipFilter {
+    /// Rows in the set (rows that are soft-deleted but still present count; searches drop them).
+    #[must_use]
+    pub fn matched(&self) -> usize {
+        self.matched
+    }
+}
+
+impl Drop for HipFilter {
+    fn drop(&mut self) {
+        // SAFETY: the handle was created by the library and is destroyed exactly once.
+        unsafe { sys::vdb_hip_filter_destroy(self.h) }
     }
 }
 

@@ -71,8 +71,9 @@ pub const VDB_OPT_KERNEL_TIMING: i32 = 4;
 pub const VDB_OPT_COMBINE_MAX_BATCH: i32 = 5;
 pub const VDB_OPT_COMBINE_WINDOW_US: i32 = 6;
 pub const VDB_OPT_COMBINE_INFLIGHT: i32 = 7;
+pub const VDB_OPT_FILTER_ROUTE: i32 = 8;
 #[allow(non_upper_case_globals)]
-pub const VDB_OPT_COUNT_: i32 = 8;
+pub const VDB_OPT_COUNT_: i32 = 9;
 
 // enum vdb_kernel_bit (vdb_hip_index_last_kernels)
 pub const VDB_KERNEL_SWEEP_VALU: i32 = 1;
@@ -91,6 +92,7 @@ pub const VDB_KERNEL_BITS_GEMM: i32 = 4096;
 pub const VDB_KERNEL_F16: i32 = 8192;
 pub const VDB_KERNEL_SWEEP_HALF_L2: i32 = 16384;
 pub const VDB_KERNEL_HNSW_HALF: i32 = 32768;
+pub const VDB_KERNEL_SWEEP_LISTED: i32 = 65536;
 
 pub const VDB_COMM_ID_BYTES: usize = 128;
 
@@ -128,6 +130,9 @@ extern "C" {
     pub fn vdb_hip_index_search_rerank(idx: *mut VdbHipIndex, queries_rowmajor: *const f32, nq: u32, k: u32, rerank_k: u32, ef: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_index_search_multi_entry(idx: *mut VdbHipIndex, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, num_probes: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_index_search_batch_dev(idx: *mut VdbHipIndex, d_queries: *const f32, nq: u32, k: u32, ef: u32, mode: i32, d_out_ids: *mut u64, d_out_scores: *mut f32, d_out_n: *mut u32, stream: *mut c_void) -> i32;
+    pub fn vdb_hip_index_filter_create(idx: *mut VdbHipIndex, ids: *const u64, n_ids: u64, negate: i32, matched: *mut u64, out: *mut *mut c_void) -> i32;
+    pub fn vdb_hip_filter_destroy(f: *mut c_void);
+    pub fn vdb_hip_index_search_batch_filtered(idx: *mut VdbHipIndex, f: *const c_void, queries_rowmajor: *const f32, nq: u32, k: u32, mode: i32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_batch_distance(device: i32, metric: i32, kind: i32, query: *const f32, vecs_rowmajor: *const f32, n: u64, dim: u32, out: *mut f32) -> i32;
     pub fn vdb_hip_batch_distance_dev(metric: i32, kind: i32, d_query: *const f32, d_vecs_rowmajor: *const f32, n: u64, dim: u32, d_out: *mut f32, stream: *mut c_void) -> i32;
     pub fn vdb_hip_batch_norm(device: i32, vecs_rowmajor: *const f32, n: u64, dim: u32, out: *mut f32) -> i32;

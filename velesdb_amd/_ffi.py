@@ -25,6 +25,11 @@ VDB_ERR_OOM = -6
 VDB_ERR_UNSUPPORTED = -7
 VDB_ERR_STATE = -8
 
+# enum vdb_option / vdb_kernel_bit members of the filtered exact search (vdb_hip_index_search_batch_filtered)
+VDB_OPT_FILTER_ROUTE = 8
+VDB_OPT_COUNT_ = 9
+VDB_KERNEL_SWEEP_LISTED = 65536
+
 # every function include/velesdb_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _u32, _u64, _f32 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float
 _pi32, _pu32, _pu64, _pf32 = C.POINTER(_i32), C.POINTER(_u32), C.POINTER(_u64), C.POINTER(_f32)
@@ -70,6 +75,9 @@ SIGNATURES = {
     "vdb_hip_index_search_multi_entry": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "vdb_hip_index_search_rerank": (_i32, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "vdb_hip_index_search_batch_dev": (_i32, [_vp, _vp, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _vp]),
+    "vdb_hip_index_filter_create": (_i32, [_vp, _vp, _u64, _i32, _pu64, C.POINTER(_vp)]),
+    "vdb_hip_filter_destroy": (None, [_vp]),
+    "vdb_hip_index_search_batch_filtered": (_i32, [_vp, _vp, _vp, _u32, _u32, _i32, _vp, _vp, _vp]),
     "vdb_hip_batch_distance": (_i32, [_i32, _i32, _i32, _vp, _vp, _u64, _u32, _vp]),
     "vdb_hip_batch_distance_dev": (_i32, [_i32, _i32, _vp, _vp, _u64, _u32, _vp, _vp]),
     "vdb_hip_index_load_reference_files": (_i32, [_vp, C.c_char_p, C.c_char_p]),

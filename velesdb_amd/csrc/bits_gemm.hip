@@ -173,7 +173,7 @@ uint32_t bits_gemm_chunk(const vdb_hip_index* ix, uint32_t nq_left, uint32_t k) 
 int32_t brute_bits_gemm_dev(vdb_hip_index* ix, int metric, const uint8_t* img, const float* cnt, const uint32_t* qbits, uint32_t nqg, uint32_t k,
                             uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
   const bool hib = metric == VDB_JACCARD;
-  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  const uint8_t* alive = search_alive(ix);
   const uint32_t n = (uint32_t)ix->n_rows, stride = bits_image_stride(ix->dim), dim2 = stride / 2;  // the kernel's unit: two bytes
   // Launch schedule: the sample seed over the first rows (bounds only), then the four-bit GEMM in launches of growing size (gemm_schedule,
   // vdb_kernels.hpp); every launch starts from the k-th best key over all rows before it

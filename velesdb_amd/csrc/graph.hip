@@ -89,6 +89,7 @@ int32_t vdb_hip_index_load_reference_files(vdb_hip_index* ix, const char* dir, c
   std::lock_guard<vdb::IndexMutex> g(ix->mu);
   if (ix->n_rows != 0) return fail(VDB_ERR_STATE, "load_reference_files needs an empty index");
   VDB_ENTER(ix);
+  ix->row_epoch++;  // the rows get new numbers: filters created before this are stale
   const std::string vp = std::string(dir) + "/" + basename + ".vectors";
   const std::string gp = std::string(dir) + "/" + basename + ".graph";
   // Everything is parsed and validated into locals first; the index is only touched once both files are known to be

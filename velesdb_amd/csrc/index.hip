@@ -12,6 +12,7 @@
 #include "vdb_probe_env.hpp"
 #include "vdb_kernels.hpp"
 #include "vdb_select_stage.hpp"
+#include "vdb_filter_route.hpp"
 
 namespace vdb {
 
@@ -53,6 +54,7 @@ int64_t opt_value(const vdb_hip_index* ix, int32_t option) {
     case VDB_OPT_COMBINE_MAX_BATCH: return ix->opt[option] >= 0 ? ix->opt[option] : kOptDefaultCombineMaxBatch;
     case VDB_OPT_COMBINE_WINDOW_US: return ix->opt[option] >= 0 ? ix->opt[option] : kOptDefaultCombineWindowUs;
     case VDB_OPT_COMBINE_INFLIGHT: return ix->opt[option] >= 0 ? ix->opt[option] : kOptDefaultCombineInflight;
+    case VDB_OPT_FILTER_ROUTE: return ix->opt[option] > 0 ? ix->opt[option] : 0;  // 0 = auto (vdb_filter_route.hpp)
     default: return -1;
   }
 }
@@ -516,6 +518,8 @@ int blocks_for(const vdb_hip_index* ix, int B, uint32_t ngroups) {
 
 // HnswIndex::search_brute_force (search.rs:176-219) for nq device-resident queries.
 // Outputs are device buffers; nothing synchronises.
+static int32_t brute_filtered_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
+                                  float* d_scores, uint32_t* d_n, hipStream_t st);
 static int32_t brute_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k,
                          uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
   if (nq == 0) return VDB_OK;
@@ -523,8 +527,13 @@ static int32_t brute_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride,
     VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
     return VDB_OK;
   }
+  // a filtered call (vdb_hip_index_search_batch_filtered) picks its route first; on the mask-substitution route it comes back here
+  // with the call's row mask in place of the soft-delete flags
+  if (ix->flt && !ix->alive_override) return brute_filtered_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  // ... and keeps the selection stage only while enough rows are allowed for its seed sample (vdb_filter_route.hpp)
+  const bool sel_ok = !ix->flt || filter_keeps_selection(ix->flt->count, ix->n_rows);
   const bool hib = higher_is_better_host(ix->metric);
-  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  const uint8_t* alive = search_alive(ix);
   if (is_bits_metric(ix->metric)) {
     if ((size_t)4 * k * 8 + (size_t)ix->words * 4 + 32 > 60 * 1024)
       return fail(VDB_ERR_UNSUPPORTED, "k too large for the fused top-k path");
@@ -641,14 +650,14 @@ static int32_t brute_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride,
     // large Cosine / DotProduct batches over a large corpus: split-bf16 selection + exact re-scoring + proof (same bits
     // as the exact matrix-core kernel below, which remains the fallback for unproven queries and every other shape)
     // ... and with 10 < k <= 128: the WIDE selection (sweep_wide.hip) — no block-local lists, every row above the bound is a candidate
-    if ((mfma_nqt || ix->metric == VDB_EUCLIDEAN) && q0 >= euclid_skip_until && select_level_wide(ix, nq - q0, k)) {
+    if (sel_ok && (mfma_nqt || ix->metric == VDB_EUCLIDEAN) && q0 >= euclid_skip_until && select_level_wide(ix, nq - q0, k)) {
       const uint32_t nqg = select_chunk(nq - q0);
       const int32_t rcw = brute_wide_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nqg, k, d_ids + (size_t)q0 * k, d_scores + (size_t)q0 * k, d_n + q0, st);
       if (rcw != VDB_OK) return rcw;
       q0 += nqg;
       continue;
     }
-    const int sel_level = mfma_nqt ? select_level(ix, nq - q0, k) : 0;
+    const int sel_level = (sel_ok && mfma_nqt) ? select_level(ix, nq - q0, k) : 0;
     if (sel_level) {
       const uint32_t nqg = select_chunk(nq - q0);
       const int32_t rcs = brute_split_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nqg, k, d_ids + (size_t)q0 * k,
@@ -660,7 +669,7 @@ static int32_t brute_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride,
     // Euclidean batches, first choice: the selection stage of the Cosine / DotProduct batches over the augmented form
     // s = q.v - |v|^2 / 2 (bf16 matrix pipe, canonical re-scoring, proof, unproven queries gathered on the device — no host
     // synchronisation); the f32 matrix-core path below remains for the shapes it does not take and for handles it parks
-    if (ix->metric == VDB_EUCLIDEAN && q0 >= euclid_skip_until && select_level_l2(ix, nq - q0, k)) {
+    if (sel_ok && ix->metric == VDB_EUCLIDEAN && q0 >= euclid_skip_until && select_level_l2(ix, nq - q0, k)) {
       const uint32_t nqg = select_chunk(nq - q0);
       const int32_t rcs = brute_split_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nqg, k, d_ids + (size_t)q0 * k,
                                           d_scores + (size_t)q0 * k, d_n + q0, st, 2);
@@ -914,6 +923,83 @@ static int32_t brute_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride,
   return VDB_OK;
 }
 
+// does VDB_SEARCH_BRUTE with this k run in oracle mode M on this handle?  (vdb_hip_index_sweep_arith_mode)
+static bool sweep_mode_m(const vdb_hip_index* ix, uint32_t k) {
+  return opt_engine(ix) == 1 && (ix->metric == VDB_COSINE || ix->metric == VDB_DOT) && sweep_mfma_lds_bytes(1, k, ix->dim) <= 160 * 1024;
+}
+
+// vdb_hip_index_search_batch_filtered: exact top-k among the rows of ix->flt that are alive now.  Two routes, same bits.
+static int32_t brute_filtered_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
+                                  float* d_scores, uint32_t* d_n, hipStream_t st) {
+  const RowFilter* f = ix->flt;
+  if (f->count == 0) {  // the empty filter: no row can answer
+    VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
+    return VDB_OK;
+  }
+  const bool mode_m = sweep_mode_m(ix, k);
+  ListedPlan lp;
+  if (!is_bits_metric(ix->metric)) sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, nq, ix->n_cus, &lp);
+  if (filter_route(opt_value(ix, VDB_OPT_FILTER_ROUTE), lp.blocks > 0, f->count, ix->n_rows, nq) == kFilterRouteListed) {
+    const bool hib = higher_is_better_host(ix->metric);
+    for (uint32_t q0 = 0; q0 < nq;) {
+      sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, nq - q0, ix->n_cus, &lp);
+      if (ix->s_part_keys.reserve((size_t)lp.nq_pass * lp.blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+      ListedArgs a{};
+      a.rows = ix->rows.as<float>();
+      a.norms = ix->norms.as<float>();
+      a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+      a.list = f->list.as<uint32_t>();
+      a.queries = d_q + (size_t)q0 * q_stride;
+      a.part_keys = ix->s_part_keys.as<uint64_t>();
+      a.row_stride = ix->row_stride;
+      a.q_stride = q_stride;
+      a.count = (uint32_t)f->count;
+      a.dim = ix->dim;
+      a.nq = lp.nq_pass;
+      a.k = k;
+      ix->last_kernels |= VDB_KERNEL_SWEEP_LISTED;
+      EventPair* ev = next_events(ix);
+      if (ev) (void)hipEventRecord(ev->a, st);
+      const hipError_t le = launch_sweep_listed(ix->metric, mode_m, lp, a, st);
+      if (le != hipSuccess) return fail(VDB_ERR_HIP, std::string("listed sweep launch: ") + hipGetErrorString(le));
+      if (ev) (void)hipEventRecord(ev->b, st);
+      MergeArgs m{};
+      m.part_keys = a.part_keys;
+      m.ext_ids = ix->ext_ids.as<uint64_t>();
+      m.out_ids = d_ids + (size_t)q0 * k;
+      m.out_scores = d_scores + (size_t)q0 * k;
+      m.out_n = d_n + q0;
+      m.n_lists = (uint32_t)lp.blocks;
+      m.k = k;
+      launch_merge(hib, m, lp.nq_pass, st);
+      q0 += lp.nq_pass;
+    }
+    VDB_HIP(hipGetLastError());
+    return VDB_OK;
+  }
+  // mask substitution: mask = filter AND alive, n_rows bytes written per call into this context's scratch (nothing is cached between
+  // calls or shared between contexts); rows past the filter's row count (inserted since) get 0
+  const size_t mask_cap = (size_t)ix->capacity + kRowSlack;  // (what the row arrays hold: a tile kernel may look past n_rows)
+  if (ix->s_flt_mask.cap < mask_cap) {
+    if (ix->s_flt_mask.reserve(mask_cap, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "filter mask scratch");
+    VDB_HIP(hipMemsetAsync(ix->s_flt_mask.p, 0, ix->s_flt_mask.cap, st));
+  }
+  launch_filter_mask(f->bitmap.as<uint32_t>(), (uint32_t)f->n_rows, ix->any_dead ? ix->alive.as<uint8_t>() : nullptr, ix->s_flt_mask.as<uint8_t>(),
+                     (uint32_t)ix->n_rows, st);
+  VDB_HIP(hipGetLastError());
+  // the handle's adaptive selection state (park-after-failure counters, the verdict sequence it has seen) is for its unfiltered
+  // batches: a filtered call reads it and leaves it as it was (its own verdicts are not posted: select_stage.hip)
+  const uint32_t seen = ix->sel_seq_seen, h16 = ix->sel16_hold, hw = ix->wide_hold, hl2 = ix->l2_hold;
+  ix->alive_override = ix->s_flt_mask.as<uint8_t>();
+  const int32_t rc = brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  ix->alive_override = nullptr;
+  ix->sel_seq_seen = seen;
+  ix->sel16_hold = h16;
+  ix->wide_hold = hw;
+  ix->l2_hold = hl2;
+  return rc;
+}
+
 static uint32_t balanced_ef(uint32_t k) { return std::max<uint32_t>(128, k * 4); }  // params.rs:313
 
 // dispatch of search_with_quality (search.rs:59-94) for device-resident queries
@@ -1044,7 +1130,7 @@ std::vector<DevBuf*> index_buffers(vdb_hip_index* ix) {
       &ix->sq8_codes, &ix->sq8_min, &ix->sq8_max, &ix->sq8_nsq, &ix->sign_bits,  // storage modes
       &ix->sq8_img, &ix->sq8_nrm, &ix->sq8_seed, &ix->sq8_rho,              // SQ8 selection images
       &ix->bits_img, &ix->bits_cnt,                                         // four-bit image of the bit rows (Hamming / Jaccard GEMM)
-      &ix->s_queries, &ix->s_part_keys, &ix->s_part_cnt, &ix->s_out, &ix->s_qbits, &ix->s_tickets,
+      &ix->s_queries, &ix->s_part_keys, &ix->s_part_cnt, &ix->s_out, &ix->s_qbits, &ix->s_tickets, &ix->s_flt_mask,
       &ix->s_misc, &ix->s_fb_keys, &ix->s_seed, &ix->s_visited, &ix->s_vlog, &ix->s_stats, &ix->s_build_stats, &ix->s_levels, &ix->s_req_keys,
       &ix->s_req_vals, &ix->s_sort_tmp};
   for (auto& L : ix->layers) {
@@ -1200,6 +1286,20 @@ int32_t search_to_device(vdb_hip_index* ix, const float* queries, uint32_t nq, u
   return VDB_OK;
 }
 
+// search_to_device in VDB_SEARCH_BRUTE restricted to a filter's rows.  The filter must belong to this handle (generation) and to its
+// present row numbering (row_epoch): anything else is an error, never a result.
+int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k) {
+  const vdb_hip_index* p = primary_of(ix);
+  if (f->generation != p->generation) return fail(VDB_ERR_INVALID_ARG, "filtered search: the filter was created on another index");
+  if (f->row_epoch != p->row_epoch)
+    return fail(VDB_ERR_STATE, "filtered search: the index renumbered its rows (vacuum / load) after the filter was created");
+  if (f->n_rows > ix->n_rows) return fail(VDB_ERR_STATE, "filtered search: the filter names rows the index does not hold");
+  ix->flt = f;
+  const int32_t rc = search_to_device(ix, queries, nq, k, 0, VDB_SEARCH_BRUTE, 0, nullptr);
+  ix->flt = nullptr;
+  return rc;
+}
+
 }  // namespace vdb
 
 using namespace vdb;
@@ -1322,6 +1422,10 @@ int32_t vdb_hip_index_set_option(vdb_hip_index* ix, int32_t option, int64_t valu
           break;
         case VDB_OPT_COMBINE_INFLIGHT:
           if (value > 7) return fail(VDB_ERR_INVALID_ARG, "combined batches in flight: 0 (by kind of search) .. 7");
+          v = (int32_t)value;
+          break;
+        case VDB_OPT_FILTER_ROUTE:
+          if (value > 2) return fail(VDB_ERR_INVALID_ARG, "filter route: 0 (auto), 1 (listed sweep) or 2 (mask substitution)");
           v = (int32_t)value;
           break;
         default: v = value ? 1 : 0; break;
@@ -1678,6 +1782,63 @@ int32_t vdb_hip_index_tombstone_count(const vdb_hip_index* ix, uint64_t* n) {
 // hash-map order and inserts them with rayon (non-deterministic); here: ascending old internal index, the
 // deterministic batch-synchronous construction (vdb_hip_index_insert_batch_parallel).  Quantised / bf16 copies are
 // re-encoded with the rows.
+// ---- filtered exact search: the filter object (include/velesdb_hip.h) ----
+int32_t vdb_hip_index_filter_create(vdb_hip_index* ix, const uint64_t* ids, uint64_t n_ids, int32_t negate, uint64_t* matched,
+                                    void** out) {
+  return vdb::guarded([&]() -> int32_t {
+  if (out) *out = nullptr;
+  if (matched) *matched = 0;
+  if (!ix || !out || (n_ids && !ids)) return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filter_create");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filter_create: not available on a member of a process group");
+  std::lock_guard<vdb::IndexMutex> g(ix->mu);
+  VDB_ENTER_READONLY(ix);
+  const uint64_t n = ix->n_rows;
+  std::vector<uint32_t> bits((n + 31) / 32, 0u);
+  for (uint64_t i = 0; i < n_ids; i++) {  // unknown ids are ignored, a duplicate sets its bit again
+    auto it = ix->id_to_idx.find(ids[i]);
+    if (it != ix->id_to_idx.end() && it->second < n) bits[it->second >> 5] |= 1u << (it->second & 31);
+  }
+  if (negate) {  // every row present now except these
+    for (auto& w : bits) w = ~w;
+    if (n % 32) bits.back() &= (1u << (n % 32)) - 1u;
+  }
+  std::vector<uint32_t> list;
+  for (uint64_t wi = 0; wi < bits.size(); wi++)
+    for (uint32_t w = bits[wi]; w; w &= w - 1) list.push_back((uint32_t)(wi * 32 + (uint64_t)__builtin_ctz(w)));
+  struct Del {
+    void operator()(RowFilter* f) const { vdb_hip_filter_destroy(f); }
+  };
+  std::unique_ptr<RowFilter, Del> f(new RowFilter());
+  f->device = ix->device;
+  f->generation = ix->generation;
+  f->row_epoch = ix->row_epoch;
+  f->n_rows = n;
+  f->count = list.size();
+  hipError_t e = hipSuccess;
+  if (!bits.empty() && (e = f->bitmap.reserve(bits.size() * 4, false, ix->stream)) == hipSuccess)
+    e = hipMemcpyAsync(f->bitmap.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, ix->stream);
+  if (e == hipSuccess && !list.empty() && (e = f->list.reserve(list.size() * 4, false, ix->stream)) == hipSuccess)
+    e = hipMemcpyAsync(f->list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, ix->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ix->stream);  // bits / list are locals; searches on other streams may use the filter at once
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? VDB_ERR_OOM : VDB_ERR_HIP, std::string("filter_create: ") + hipGetErrorString(e));
+  if (matched) *matched = f->count;
+  *out = f.release();
+  return VDB_OK;
+  });
+}
+
+void vdb_hip_filter_destroy(void* filter) {
+  RowFilter* f = static_cast<RowFilter*>(filter);
+  if (!f) return;
+  if (f->bitmap.p || f->list.p) {
+    (void)hipSetDevice(f->device);
+    f->bitmap.release();
+    f->list.release();
+  }
+  delete f;
+}
+
 int32_t vdb_hip_index_vacuum(vdb_hip_index* ix, uint64_t* count) {
   return vdb::guarded([&]() -> int32_t {
   if (!ix) return fail(VDB_ERR_INVALID_ARG, "null argument");
@@ -1687,6 +1848,7 @@ int32_t vdb_hip_index_vacuum(vdb_hip_index* ix, uint64_t* count) {
   const uint64_t n_old = ix->n_rows, n_live = ix->live;
   if (count) *count = n_live;
   if (n_live == 0) return VDB_OK;  // vacuum.rs:123-125: nothing to rebuild
+  ix->row_epoch++;  // the rows are renumbered below: filters created before this are stale
   // 1. snapshot of the active vectors (vacuum.rs:115-121)
   std::vector<float> all((size_t)n_old * ix->dim);
   VDB_HIP(hipMemcpy2DAsync(all.data(), (size_t)ix->dim * 4, ix->rows.p, ix->row_stride * 4, (size_t)ix->dim * 4, n_old,

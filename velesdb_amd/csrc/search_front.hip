@@ -83,6 +83,16 @@ static int32_t search_direct(vdb_hip_index* handle, const float* queries, uint32
       [&](vdb_hip_index* ix) { deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n); });
 }
 
+// vdb_hip_index_search_batch_filtered: always a launch of its own — callers with different filters must not share one, so a
+// filtered call never queues at the combining front
+static int32_t search_filtered_direct(vdb_hip_index* handle, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k,
+                                      uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  return run_search(
+      handle, nq, k, 0, VDB_SEARCH_BRUTE, 0,
+      [&](vdb_hip_index* ix) { return search_filtered_to_device(ix, f, queries, nq, k); },
+      [&](vdb_hip_index* ix) { deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n); });
+}
+
 // the leader's part: one launch for `batch` (same shape; batch[0] is the leader's own request)
 static void run_batch(vdb_hip_index* handle, CombineReq* const* reqs, size_t n_reqs) {
   struct Span {
@@ -192,6 +202,21 @@ int32_t vdb_hip_index_search_batch(vdb_hip_index* ix, const float* queries, uint
                                    int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
   return vdb::guarded([&]() -> int32_t {
   return search_batch_host(ix, queries, nq, k, ef, mode, 0, out_ids, out_scores, out_n);
+  });
+}
+
+// the `_with_filter` searches of the collection layer (collection/search/vector.rs:164-239, batch.rs:26-136) with the ids the
+// caller's predicate matched: exact top-k among exactly those rows (include/velesdb_hip.h)
+int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* ix, const void* filter, const float* queries, uint32_t nq, uint32_t k,
+                                            int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  return vdb::guarded([&]() -> int32_t {
+  const RowFilter* f = static_cast<const RowFilter*>(filter);
+  if (!ix || !f || (nq && (!queries || !out_n)) || (nq && k && (!out_ids || !out_scores))) return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filtered search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered search: not available on a member of a process group");
+  if (mode != VDB_SEARCH_BRUTE) return fail(VDB_ERR_UNSUPPORTED, "filtered search: VDB_SEARCH_BRUTE only (the graph and quantised modes keep the over-fetch rule)");
+  if (nq == 0) return VDB_OK;
+  return search_filtered_direct(ix, f, queries, nq, k, out_ids, out_scores, out_n);
   });
 }
 

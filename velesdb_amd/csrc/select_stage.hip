@@ -45,7 +45,7 @@ static bool gemm_bf16_glds_enabled() {
 // sweep_half_l2.hip for every batch size — query tiles of 16 (4 / 1 where LDS or the batch is smaller), the corpus re-read per tile
 static int32_t brute_half_l2_dev(vdb_hip_index* ix, const uint16_t* rows16, bool f16, const float* d_q, uint64_t q_stride, uint32_t nq,
                                  uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
-  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  const uint8_t* alive = search_alive(ix);
   ix->last_kernels |= VDB_KERNEL_SWEEP_HALF_L2;
   for (uint32_t q0 = 0; q0 < nq;) {
     const uint32_t rem = nq - q0;
@@ -100,7 +100,7 @@ int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
   const float* norms16 = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
   if (ix->metric == VDB_EUCLIDEAN) return brute_half_l2_dev(ix, rows16, f16, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
   if (f16) ix->last_kernels |= VDB_KERNEL_F16;
-  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  const uint8_t* alive = search_alive(ix);
   for (uint32_t q0 = 0; q0 < nq;) {
     const uint32_t rem = nq - q0;
     // large batches over a large corpus: the 256 x 256 LDS-DMA kernel (sweep_gemm_bf16.hip).  Its thresholds are seeded:
@@ -533,7 +533,7 @@ int32_t brute_split_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, 
   if (rc != VDB_OK) return rc;
   ix->last_select_level = level;
   ix->last_kernels |= (level < 2 ? VDB_KERNEL_SELECT_SPLIT : VDB_KERNEL_SELECT_BF16) | VDB_KERNEL_GEMM_F32;  // (exact seed sweep)
-  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  const uint8_t* alive = search_alive(ix);
   const uint32_t n = (uint32_t)ix->n_rows, dim = ix->dim, K2 = level >= 2 ? kSelect16Pool : kSplitPool;
   const uint32_t dim_a = l2 ? dim + 64 : dim, dim_s = dim + 4;  // augmented image / f32 seed widths (Euclidean)
   const uint32_t ks = std::min<uint32_t>(kGemmBf16MaxK, k + 3);  // rows a selection block keeps per query (sweep_split.hip)
@@ -798,7 +798,7 @@ int32_t brute_split_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, 
   fin.out_n = d_n;
   fin.nq = nqg;
   fin.k = k;
-  if (ix->sel_stats) {
+  if (ix->sel_stats && !ix->alive_override) {  // (a filtered call's verdicts say nothing about the handle's data: not posted)
     fin.stats_host = ix->sel_stats;
     fin.stats_seq = ++ix->sel_seq;
     fin.stats_level = sq8 ? 3u : (l2 ? 5u : (uint32_t)level);
@@ -983,7 +983,7 @@ int32_t brute_wide_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
   const uint32_t sel_dim = l2 ? dim_a : ix->dim;  // the k-extent the selection kernel and the seed contract over
   ix->last_select_level = 4;
   ix->last_kernels |= VDB_KERNEL_SELECT_BF16;
-  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  const uint8_t* alive = search_alive(ix);
   const uint32_t n = (uint32_t)ix->n_rows, dim = ix->dim;
   // The seed: a SAMPLE of the first rows, the k-th best of its keys is the first bound (any k rows with approximate scores >= A' prove
   // tau = A' - 2 delta; the selection launches sweep the sample rows again, which is what lets the sample drop rows).
@@ -1163,7 +1163,7 @@ int32_t brute_wide_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
     fq.out_n = d_n;
     fq.nq = nqg;
     fq.k = k;
-    if (ix->sel_stats) {
+    if (ix->sel_stats && !ix->alive_override) {
       fq.stats_host = ix->sel_stats;
       fq.stats_seq = ++ix->sel_seq;
       fq.stats_level = 4u;
@@ -1257,7 +1257,7 @@ int32_t brute_wide_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
   fin.out_n = d_n;
   fin.nq = nqg;
   fin.k = k;
-  if (ix->sel_stats) {
+  if (ix->sel_stats && !ix->alive_override) {  // (a filtered call's verdicts say nothing about the handle's data: not posted)
     fin.stats_host = ix->sel_stats;
     fin.stats_seq = ++ix->sel_seq;
     fin.stats_level = 4u;

@@ -86,6 +86,18 @@ struct EventPair {
   hipEvent_t a = nullptr, b = nullptr;
 };
 
+// an id allow-list (vdb_hip_filter of include/velesdb_hip.h — an untyped pointer at the boundary): an immutable snapshot of internal
+// rows of one handle at one row numbering
+struct RowFilter {
+  int device = 0;
+  uint64_t generation = 0;  // the handle's identity ...
+  uint64_t row_epoch = 0;   // ... and its row numbering at creation
+  uint64_t n_rows = 0;      // the handle's row count at creation (rows at or past it are not in the filter)
+  uint64_t count = 0;       // rows in the set
+  DevBuf bitmap;            // [ceil(n_rows / 32)] u32, bit r % 32 of word r / 32
+  DevBuf list;              // [count] u32, ascending internal rows
+};
+
 struct ShardGroup;  // shard_group.hip: the children of a multi-device handle
 struct ProcComm;    // shard_group.hip: this process's membership of a one-process-per-GPU shard group (RCCL)
 void shard_group_free(ShardGroup*);
@@ -175,7 +187,7 @@ struct vdb_hip_index {
   // large exact Cosine / DotProduct batch and kept up to date from then on
   vdb::DevBuf rows_split;
   // per-handle options (vdb_hip_index_set_option): -1 = follow the process-wide default (vdb_hip_set_*)
-  int32_t opt[VDB_OPT_COUNT_] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  int32_t opt[VDB_OPT_COUNT_] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
   bool split_enabled = false;
   bool sel_norms = false;    // canonical f32 norms are kept for every row whatever the metric (selection levels 1 / 2)
   // level 2 (plain bf16 selection) adaptivity: the verdict counts of finished batches arrive in pinned host memory
@@ -224,10 +236,17 @@ struct vdb_hip_index {
   std::vector<uint8_t> idx_live;
   uint64_t live = 0;
   bool any_dead = false;
+  // rows are renumbered on an existing handle (vacuum, load_*): filters created before that are stale (primary only)
+  uint64_t row_epoch = 0;
+  // filtered exact search (vdb_hip_index_search_batch_filtered), per search context and per call: the call's filter, and — mask
+  // substitution — the row mask `filter AND alive` that stands in for `alive` on every tier (search_alive below); s_flt_mask owns it
+  const vdb::RowFilter* flt = nullptr;
+  const uint8_t* alive_override = nullptr;
   bool raw_ef = false;  // transient, under the exclusive lock: the running call is NativeHnsw-level (search_multi_entry) — its ef is used as given
 
   // scratch
   vdb::DevBuf s_queries, s_part_keys, s_part_cnt, s_qbits, s_misc;
+  vdb::DevBuf s_flt_mask;  // [capacity + slack] u8: the row mask of a filtered call on the mask-substitution route (n_rows bytes written per call)
   vdb::DevBuf s_tickets;  // [2] u32, zero between calls: the block tickets of the one-launch packed-bit search (sweep_bits_fused)
   // results of a host-pointer search: ONE allocation [ids nq*k u64 | scores nq*k f32 | n nq u32] (reserve_out), so that one
   // copy brings everything back; the three views point into it
@@ -290,6 +309,12 @@ struct vdb_hip_index {
 
 namespace vdb {
 static inline vdb_hip_index* primary_of(vdb_hip_index* ix) { return ix->primary ? ix->primary : ix; }
+// the per-row mask a search honours: the filtered call's (filter AND alive) when one is set, else the soft-delete flags once a row died
+static inline const uint8_t* search_alive(const vdb_hip_index* ix) {
+  return ix->alive_override ? ix->alive_override : (ix->any_dead ? ix->alive.as<uint8_t>() : nullptr);
+}
+// filtered exact search (index.hip): the caller holds ix->mu shared and leased the context `ix`
+int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k);
 // rows per index: the tiled kernels count whole 256-row tiles of [0, n) in 32 bits — (n + 255) / 256 must not wrap
 // (tests/gemm_schedule_model.cpp walks the launch schedule up to this limit)
 constexpr uint64_t kMaxRowsPerIndex = 0xFFFFFE00ull;  // 2^32 - 512

@@ -261,6 +261,29 @@ hipError_t launch_sweep_half_l2(bool f16, int B, const uint16_t* rows, uint64_t 
                                 uint64_t q_stride, uint64_t* part_keys, uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks,
                                 hipStream_t st);
 void launch_merge(bool higher_is_better, const MergeArgs& m, uint32_t nq, hipStream_t st);
+// sweep_listed.hip — filtered exact search: the sweep over a LIST of rows, and the row mask of the other route
+struct ListedArgs {
+  const float* rows;      // [n_rows][row_stride] f32
+  const float* norms;     // canonical row norms (Cosine)
+  const uint8_t* alive;   // nullable
+  const uint32_t* list;   // [count] ascending internal rows
+  const float* queries;   // [nq][q_stride]
+  uint64_t* part_keys;    // [nq][blocks][k]
+  uint64_t row_stride, q_stride;
+  uint32_t count, dim, nq, k;
+};
+struct ListedPlan {
+  int blocks = 0;         // 0: the listed kernel cannot take this shape (its k-lists / queries do not fit the LDS)
+  uint32_t nq_pass = 0;   // queries per pass over the list
+  uint32_t per_block = 0; // mode M: 64-row tiles per block; mode C: row groups per block
+  size_t lds = 0;
+  int B = 0;              // mode C: queries per wave pass (1, 4, 8)
+};
+// mode_m: one k-ordered fmaf chain per (row, query) (oracle mode M) — else the canonical lane chains + butterfly (mode C)
+void sweep_listed_plan(bool mode_m, uint32_t dim, uint32_t k, uint32_t count, uint32_t nq_left, int n_cus, ListedPlan* p);
+hipError_t launch_sweep_listed(int metric, bool mode_m, const ListedPlan& p, const ListedArgs& a, hipStream_t st);
+// mask[r] = bit r of `bitmap` (r < f_rows) && (alive ? alive[r] : 1), r < n_rows
+void launch_filter_mask(const uint32_t* bitmap, uint32_t f_rows, const uint8_t* alive, uint8_t* mask, uint32_t n_rows, hipStream_t st);
 void launch_max_norm(const float* norms, uint32_t n_rows, uint32_t* out_bits, hipStream_t st);  // bits of max |v| (NaN propagates)
 // ---- exact f32 Cosine / Dot batches through split-bf16 selection + exact re-scoring + proof (sweep_split.hip) ----
 constexpr uint32_t kSplitPool = 32;  // candidates per query that are re-scored exactly (level 1: split selection)

@@ -35,6 +35,11 @@ KERNEL_F16, KERNEL_SWEEP_HALF_L2 = 1 << 13, 1 << 14
 # graph search over the f16 / bf16 copy of the rows (VDB_SEARCH_HNSW_F16 / _BF16) and its kernel family
 MODE_HNSW_F16, MODE_HNSW_BF16 = 8, 9
 KERNEL_HNSW_HALF = 1 << 15
+# filtered exact search (HnswIndex.create_filter / search_batch_brute_force_filtered): the route option (0 auto, 1 listed sweep,
+# 2 mask substitution) and the listed sweep's kernel bit
+OPT_FILTER_ROUTE = _ffi.VDB_OPT_FILTER_ROUTE
+FILTER_ROUTE_AUTO, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK = 0, 1, 2
+KERNEL_SWEEP_LISTED = _ffi.VDB_KERNEL_SWEEP_LISTED
 SHARD_REPLICA, SHARD_RANGE = 0, 1
 COMM_ID_BYTES = 128
 
@@ -93,6 +98,32 @@ def set_split_selector(level) -> None:
     selection for 10 < k <= 128), level 1 as the fallback level; 3 (the library's default) = level 2 with the WIDE selection at every
     k <= 128.  Results are identical at every level."""
     check(lib().vdb_hip_set_split_selector(int(level)))
+
+
+class Filter:
+    """An id allow-list of one index (vdb_hip_filter): an immutable snapshot of the rows the given ids had when it was created.
+    `matched` = rows in the set.  Close it (or leave its `with` block) before the index is closed."""
+
+    def __init__(self, handle, matched: int):
+        self._h = handle
+        self.matched = matched
+
+    def close(self) -> None:
+        if self._h:
+            lib().vdb_hip_filter_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class HnswIndex:
@@ -410,6 +441,36 @@ class HnswIndex:
             qs = qs.reshape(1, -1)
         self._validate(qs)
         return self._search_raw(qs, k, 0, MODE_BRUTE)
+
+    def create_filter(self, ids, negate: bool = False) -> Filter:
+        """The ids a caller's predicate matched, as a device-side allow-list (negate: every row present now except them).  Unknown
+        and duplicate ids are ignored; rows inserted later are not in it, rows removed later drop out of its results; vacuum() and
+        load make it stale (searches then raise with VDB_ERR_STATE)."""
+        a = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        h, m = C.c_void_p(), C.c_uint64(0)
+        check(lib().vdb_hip_index_filter_create(self._h, _ptr(a) if a.size else None, a.size, 1 if negate else 0, C.byref(m), C.byref(h)))
+        return Filter(h, int(m.value))
+
+    def search_batch_brute_force_filtered(self, queries, k: int, flt: Filter, mode: int = MODE_BRUTE):
+        """search_batch_brute_force among the filter's rows only: the exact top-k of the allowed live rows — ids, ranks and score
+        bits of an index that holds just those rows (what the reference's `_with_filter` searches approximate by over-fetching,
+        collection/search/vector.rs:164-239).  numpy outputs."""
+        qs = _f32(queries)
+        if qs.ndim == 1:
+            qs = qs.reshape(1, -1)
+        self._validate(qs)
+        nq, kk = qs.shape[0], max(k, 1)
+        ids = np.empty((nq, kk), dtype=np.uint64)
+        sc = np.empty((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        check(lib().vdb_hip_index_search_batch_filtered(self._h, flt._h if flt is not None else None, _ptr(qs), nq, k, mode, _ptr(ids),
+                                                        _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
+
+    def search_brute_force_filtered(self, query, k: int, flt: Filter) -> List[Tuple[int, float]]:
+        """search_brute_force among the filter's rows only (one query)."""
+        ids, sc, cnt = self.search_batch_brute_force_filtered(_f32(query).reshape(1, -1), k, flt)
+        return self._tuples(ids[0], sc[0], cnt[0])
 
     def insert_batch_sequential(self, vectors: Iterable[Tuple[int, Sequence[float]]]) -> int:
         """batch.rs:128-149."""
