@@ -312,6 +312,35 @@ void vdb_hip_filter_destroy(void* f);
  * call (it does not go through the combining front) and leaves the handle's adaptive selection state as it found it. */
 int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* idx, const void* f, const float* queries_rowmajor, uint32_t nq,
                                             uint32_t k, int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+/* Filtered GRAPH search: VDB_SEARCH_HNSW with the allow-list consulted inside the walk (hnsw_filtered.hip).
+ * allowed(r) = r < the filter's row count, its bit r set, row r alive at search time (the rules above).  The greedy descent over the
+ * upper layers is unfiltered (rejected nodes navigate); layer 0 is search_layer (native/graph.rs:438-520) with ONE change: `results`
+ * receives allowed nodes only, `candidates` and `visited` what they receive today — furthest = the largest distance among the (at
+ * most ef) allowed results, f32::MAX while there are none; a neighbour is pushed to candidates when `dist < furthest ||
+ * results.len() < ef` and to results when it is also allowed.  Answer: the first min(k, results.len()) results, ids through the id
+ * map, scores through transform_score — no post-drop.  ef as VDB_SEARCH_HNSW (0 = Balanced max(128, 4k); max(ef, k)); mode C
+ * arithmetic; ties by (total-order(distance), internal row).  With a filter that allows every row the call IS VDB_SEARCH_HNSW: ids,
+ * score bits, out_n and the search counters.
+ * Cost: while fewer than ef allowed nodes are known the walk admits every node it sees, so its candidate list — LDS, per query in
+ * flight — grows with 1 / density, and a query whose list would pass the largest one allowed is answered EXACTLY instead: top-k of
+ * the allowed live rows by (total-order(distance), row), distances by the walk's own function (same score bits for the same id).
+ * The largest list = what 160 KB of LDS hold at the graph's neighbour-list length, lowered by max_list when non-zero.
+ * route 0 (auto): the whole call takes the exact pass when matched < ef, or when the density-sized list
+ *   64-rounded(2 * ef * rows / matched + 64) exceeds the largest list; otherwise it walks with that list, re-runs queries that
+ *   overflow it with four times the room up to the largest list, and answers those that still overflow exactly, one by one.  The
+ *   factor 2 and the `matched < ef` cut are STATED GUESSES, nothing is measured (tools/filter_probe.py, graph leg).
+ * route 1 (walk): always the walk; a query that overflows the largest list fails the call with VDB_ERR_UNSUPPORTED.
+ * route 2: the exact pass for every query.
+ * out_route (nullable, [nq]): 1 = the walk answered, 2 = the exact pass, 0 = nothing ran (empty filter, k = 0, empty graph: out_n = 0).
+ * A query's route depends on the query, the filter, ef and max_list — never on the other queries of the call.
+ * mode other than VDB_SEARCH_HNSW, multi-device handles and process-group members: VDB_ERR_UNSUPPORTED; f == NULL or route outside
+ * 0..2: VDB_ERR_INVALID_ARG; a filter of another handle: VDB_ERR_INVALID_ARG; a stale filter or no graph: VDB_ERR_STATE.  Host
+ * pointers only; a launch of its own (no combining front).  vdb_hip_index_last_kernels: VDB_KERNEL_HNSW_FILTERED and / or
+ * VDB_KERNEL_FILTER_RANK; vdb_hip_index_last_search_stats: per query the counters of its last walk attempt plus the rows its exact
+ * pass evaluated (n_dist only), summed over the call. */
+int32_t vdb_hip_index_search_graph_filtered(vdb_hip_index* idx, const void* f, const float* queries_rowmajor, uint32_t nq,
+                                            uint32_t k, uint32_t ef, int32_t mode, int32_t route, uint32_t max_list,
+                                            uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route);
 
 /* ---- DistanceEngine::batch_distance / GpuAccelerator::batch_{cosine_similarity,
  * euclidean_distance,dot_product} (native/distance.rs:21-24; gpu_backend.rs:157,355,397) ----
@@ -485,7 +514,9 @@ enum vdb_kernel_bit {
                                       bit — SWEEP_MFMA_BF16 / GEMM_BF16 / GEMM_BF16_GLDS then name the f16 instance of that kernel      */
   VDB_KERNEL_SWEEP_HALF_L2 = 16384, /* sweep_topk_half_l2 (Euclidean difference chain over the f16 / bf16 rows)                       */
   VDB_KERNEL_HNSW_HALF = 32768,    /* hnsw_search_half_kernel (VDB_SEARCH_HNSW_F16 / _BF16; VDB_KERNEL_F16 next to it for the f16 instance) */
-  VDB_KERNEL_SWEEP_LISTED = 65536  /* sweep_topk_listed / sweep_topk_listed_m (vdb_hip_index_search_batch_filtered, the listed route) */
+  VDB_KERNEL_SWEEP_LISTED = 65536, /* sweep_topk_listed / sweep_topk_listed_m (vdb_hip_index_search_batch_filtered, the listed route) */
+  VDB_KERNEL_HNSW_FILTERED = 131072, /* hnsw_search_filtered_kernel (vdb_hip_index_search_graph_filtered, the walk)                    */
+  VDB_KERNEL_FILTER_RANK = 262144  /* filter_rank_kernel (vdb_hip_index_search_graph_filtered, the exact pass)                       */
 };
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same

@@ -11,6 +11,13 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
   --rider: HnswIndex.search_filtered (the over-fetch rule) for one query with the number of results it actually returned
   (needs the graph: build_graph over every row first — minutes at 1 M rows, off by default).
 
+  --graph: the GRAPH leg instead (vdb_hip_index_search_graph_filtered) over the bench's graph shape (--rows x --dim,
+  M 32, ef_construction 400, built here with build_graph: minutes at 1 M rows): densities 1 ... 1/1024, --graph-nq queries, k = 10;
+  per density queries/s, recall@10 against the exact filtered answer (route 2) and the mean n_dist per query of the auto, walk and
+  exact routes, with the over-fetch rule through plain VDB_SEARCH_HNSW (k' = max(4k, k + 10), post-filtered on the host) as the
+  baseline, its recall and the share of queries it answers short.  This table is what would replace the two guesses of the
+  auto rule (the factor 2 of the density-sized list, the `matched < ef` cut).  NO RUN OF IT IS RECORDED YET.
+
 Every figure is the median of --repeats blocks, each block the mean over enough calls to last ~--block-ms; the spread is
 (max - min) / median over the blocks.  Not part of the product or the test-suite."""
 import argparse
@@ -36,6 +43,10 @@ p.add_argument("--repeats", type=int, default=5)
 p.add_argument("--block-ms", type=float, default=40.0)
 p.add_argument("--gather-tbs", type=float, default=5.7, help="whole-row gather rate to compare one-query listed calls with, TB/s")
 p.add_argument("--rider", action="store_true")
+p.add_argument("--graph", action="store_true", help="the filtered graph search leg instead of the exact one")
+p.add_argument("--graph-nq", type=int, default=1024)
+p.add_argument("--ef", type=int, default=128)
+p.add_argument("--densities", default="1,0.5,0.25,0.125,0.0625,0.03125,0.015625,0.0078125,0.00390625,0.001953125,0.0009765625")
 p.add_argument("--out", default="")
 a = p.parse_args()
 dev = torch.device("cuda", 0)
@@ -75,8 +86,59 @@ def measure(fn):
     return med, (max(blocks) - min(blocks)) / med
 
 
+def graph_leg():
+    rows_out = []
+    for mname in a.metrics.split(","):
+        ix = build(METRICS[mname])
+        ix.set_option(va.OPT_COMBINE_MAX_BATCH, 0)
+        t0 = time.perf_counter()
+        ix.build_graph(0)
+        print(f"# {mname}: graph over {a.rows} rows in {time.perf_counter() - t0:.1f} s", flush=True)
+        rng = np.random.default_rng(7)
+        Q = rng.standard_normal((a.graph_nq, a.dim)).astype(np.float32)
+        kk = max(4 * a.k, a.k + 10)
+        for dens in [float(x) for x in a.densities.split(",")]:
+            count = max(1, int(a.rows * dens))
+            allowed = np.sort(rng.choice(a.rows, size=count, replace=False)).astype(np.uint64)
+            mask = np.zeros(a.rows, dtype=bool)
+            mask[allowed.astype(np.int64)] = True
+            with ix.create_filter(allowed) as flt:
+                row = dict(leg="graph", metric=mname, rows=a.rows, dim=a.dim, k=a.k, ef=a.ef, nq=a.graph_nq, density=dens, count=count)
+                (eid, _, ecnt), _ = ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=va.ROUTE_EXACT)
+                truth = [set(eid[i, :ecnt[i]].tolist()) for i in range(a.graph_nq)]
+
+                def recall(ids, cnt):
+                    return float(np.mean([len(truth[i] & set(ids[i][:cnt[i]])) / max(1, len(truth[i])) for i in range(a.graph_nq)]))
+                for name, route in (("auto", va.ROUTE_AUTO), ("walk", va.ROUTE_WALK), ("exact", va.ROUTE_EXACT)):
+                    try:
+                        (ids, _, cnt), routes = ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route)
+                    except va.VelesHipError as e:  # the walk route refuses queries whose list would not fit
+                        row[name + "_error"] = str(e)
+                        continue
+                    row[name + "_n_dist"] = ix.last_search_stats()[0] / a.graph_nq
+                    row[name + "_walked"] = float(np.mean(routes == 1))
+                    row[name + "_recall"] = recall(ids.tolist(), cnt.tolist())
+                    ms, sp = measure(lambda: ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route))
+                    row[name + "_qps"], row[name + "_spread"] = a.graph_nq / (ms * 1e-3), sp
+                # the over-fetch rule: plain VDB_SEARCH_HNSW at k' = max(4k, k + 10), the caller drops what the filter rejects
+                pid, _, pcnt = ix._search_raw(Q, kk, 0, va.MODE_HNSW)
+                row["overfetch_n_dist"] = ix.last_search_stats()[0] / a.graph_nq
+                kept = [[int(x) for x in pid[i, :pcnt[i]] if mask[int(x)]][:a.k] for i in range(a.graph_nq)]
+                row["overfetch_recall"] = recall(kept, [len(x) for x in kept])
+                row["overfetch_short"] = float(np.mean([len(x) < min(a.k, count) for x in kept]))
+                ms, sp = measure(lambda: ix._search_raw(Q, kk, 0, va.MODE_HNSW))
+                row["overfetch_qps"], row["overfetch_spread"] = a.graph_nq / (ms * 1e-3), sp
+                rows_out.append(row)
+                print(json.dumps(row), flush=True)
+        ix.close()
+    return rows_out
+
+
 table = []
-for mname in a.metrics.split(","):
+if a.graph:
+    table = graph_leg()
+    a.metrics = ""
+for mname in [m for m in a.metrics.split(",") if m]:
     ix = build(METRICS[mname])
     ix.set_option(va.OPT_COMBINE_MAX_BATCH, 0)  # the unfiltered yardstick launches alone too
     rng = np.random.default_rng(7)

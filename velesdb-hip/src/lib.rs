@@ -984,6 +984,72 @@ impl HipHnswIndex {
         self.search_batch_brute_force_filtered(&[query], k, filter).pop().unwrap_or_default()
     }
 
+    /// Graph search with the filter consulted inside the walk (`vdb_hip_index_search_graph_filtered`): layer 0 keeps allowed live
+    /// rows only in its result set while every node still navigates, so a selective filter still returns `k` results where the
+    /// over-fetch rule of [`Self::search_filtered`] comes back short.  `route`: 0 auto (the walk, or the exact pass for queries
+    /// whose candidate list would not fit), 1 walk, 2 exact pass; `max_list` lowers the largest candidate list (0: what the
+    /// LDS holds).  Returns the results and, per query, the route that answered (1 walk, 2 exact pass, 0 nothing ran).
+    #[must_use]
+    pub fn search_batch_graph_filtered(
+        &self,
+        queries: &[&[f32]],
+        k: usize,
+        quality: SearchQuality,
+        filter: &HipFilter,
+        route: i32,
+        max_list: u32,
+    ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
+        for q in queries {
+            self.validate_dimension(q, "Query");
+        }
+        if queries.is_empty() {
+            return (Vec::new(), Vec::new());
+        }
+        let nq = queries.len();
+        if k == 0 {
+            return (vec![Vec::new(); nq], vec![0; nq]);
+        }
+        let mut flat = Vec::with_capacity(nq * self.dimension);
+        for q in queries {
+            flat.extend_from_slice(q);
+        }
+        let mut ids = vec![0u64; nq * k];
+        let mut scores = vec![0f32; nq * k];
+        let mut counts = vec![0u32; nq];
+        let mut routes = vec![0u32; nq];
+        // SAFETY: buffer sizes are nq*dim / nq*k / nq / nq as the ABI requires; the filter handle is live (owned by `filter`).
+        check(unsafe {
+            sys::vdb_hip_index_search_graph_filtered(
+                self.h,
+                filter.h,
+                flat.as_ptr(),
+                nq as u32,
+                k as u32,
+                quality.ef_search(k) as u32,
+                sys::VDB_SEARCH_HNSW,
+                route,
+                max_list,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                counts.as_mut_ptr(),
+                routes.as_mut_ptr(),
+            )
+        });
+        let out = (0..nq)
+            .map(|i| {
+                let c = counts[i] as usize;
+                (0..c).map(|j| (ids[i * k + j], scores[i * k + j])).collect()
+            })
+            .collect();
+        (out, routes)
+    }
+
+    /// [`Self::search_batch_graph_filtered`] for one query on the auto route.
+    #[must_use]
+    pub fn search_graph_filtered(&self, query: &[f32], k: usize, quality: SearchQuality, filter: &HipFilter) -> Vec<(u64, f32)> {
+        self.search_batch_graph_filtered(&[query], k, quality, filter, 0, 0).0.pop().unwrap_or_default()
+    }
+
     /// Boxed as the trait object `Collection` holds: what a downstream crate's `hip` feature registers with the index factory
     /// hook of velesdb-core (see Cargo.toml: the dependency points from this crate to the core, never back).
     #[must_use]

@@ -29,6 +29,9 @@ VDB_ERR_STATE = -8
 VDB_OPT_FILTER_ROUTE = 8
 VDB_OPT_COUNT_ = 9
 VDB_KERNEL_SWEEP_LISTED = 65536
+# ... and of the filtered graph search (vdb_hip_index_search_graph_filtered): the walk and the exact pass
+VDB_KERNEL_HNSW_FILTERED = 131072
+VDB_KERNEL_FILTER_RANK = 262144
 
 # every function include/velesdb_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _u32, _u64, _f32 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float
@@ -78,6 +81,7 @@ SIGNATURES = {
     "vdb_hip_index_filter_create": (_i32, [_vp, _vp, _u64, _i32, _pu64, C.POINTER(_vp)]),
     "vdb_hip_filter_destroy": (None, [_vp]),
     "vdb_hip_index_search_batch_filtered": (_i32, [_vp, _vp, _vp, _u32, _u32, _i32, _vp, _vp, _vp]),
+    "vdb_hip_index_search_graph_filtered": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_batch_distance": (_i32, [_i32, _i32, _i32, _vp, _vp, _u64, _u32, _vp]),
     "vdb_hip_batch_distance_dev": (_i32, [_i32, _i32, _vp, _vp, _u64, _u32, _vp, _vp]),
     "vdb_hip_index_load_reference_files": (_i32, [_vp, C.c_char_p, C.c_char_p]),

@@ -1,0 +1,683 @@
+// hnsw_filtered.hip — filtered graph search (vdb_hip_index_search_graph_filtered): NativeHnsw::search
+// (native/graph.rs:251-270) with an id allow-list consulted where a node enters the RESULT set.
+//
+// Semantics.  allowed(r) = r < the filter's row count, its bit r set, row r alive now.  The greedy descent (graph.rs:405-428) is
+// unchanged: rejected nodes navigate.  Layer 0 is search_layer (graph.rs:438-520) with one change — `results` receives allowed
+// nodes only; `candidates` and `visited` receive what they receive today.  With every row allowed this IS VDB_SEARCH_HNSW: ids,
+// score bits, out_n, n_dist and n_expand.
+//
+// Single-list form.  The sorted LDS list of hnsw_walk_body (vdb_hnsw_device.hpp) holds candidates and results together; the flag
+// byte of an entry gets a second bit, "allowed", set at insert from the filter bitmap AND the alive flags (one dword load per
+// admitted neighbour).  results = the first ef allowed entries; the ef-th one is the PIVOT: `furthest` is its distance,
+// "results.len() < ef" is "no pivot".  Behind an insert the entries whose distance is greater than the pivot's are dropped (ties
+// stay, list_truncate's raw compare): whatever the reference pops behind them fails graph.rs:474 at once.  Nothing is dropped while
+// there is no pivot — so a selective filter makes the list long, and it is bounded: an entry that falls off a full list and that
+// the two-heap form still needs (an unexpanded candidate; or an allowed entry while the results are not full) sets the overflow
+// flag, the query finishes anyway and reports out_n = 0xFFFFFFFF; the host re-runs it with more room or answers it exactly.
+//
+// filter_rank_kernel is that exact answer: top-k of the allowed live rows by (total-order(distance), row), the distances from the
+// walk's own DIST::eval — bit for bit what the walk reports for the same row.
+//
+// Algorithmic HBM bytes per query: walk n_dist * dim * 4 + n_expand * M0 * 4 + (admitted neighbours) * 4 for the bitmap words;
+// exact pass matched * (dim * 4 + 4).  Nothing here is measured: tools/filter_probe.py has the graph leg.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "vdb_filter_route.hpp"
+#include "vdb_hnsw_device.hpp"
+#include "vdb_index.hpp"
+
+namespace vdb {
+
+struct HnswFilteredArgs {
+  HnswSearchArgs s;           // (s.nq = the queries of THIS launch; s.stats unused)
+  const uint32_t* f_bitmap;   // bit r % 32 of word r / 32, f_rows bits
+  const uint32_t* f_list;     // [f_count] ascending rows (the exact pass)
+  uint32_t f_rows, f_count;
+  const uint32_t* qmap;       // nullable: launch slot -> query index (re-runs and the exact pass of single queries)
+  unsigned long long* qstats; // [nq_total][2]: the walk WRITES a query's n_dist / n_expand, the exact pass ADDS its rows to n_dist
+};
+
+constexpr uint32_t kFlagExpanded = 1u, kFlagAllowed = 2u;
+
+// list_insert (vdb_hnsw_device.hpp) with the new entry's flag given and the lost entry reported: lost = 1 when an entry fell off
+// (the key itself when it sorts behind a full list), lost_flag = its flags
+__device__ __forceinline__ void flist_insert(lds_vu64* keys, lds_vu8* flags, uint32_t& cnt, uint32_t cap, uint64_t key, uint32_t flag,
+                                             int lane, uint32_t& lost, uint32_t& lost_flag) {
+  lost = 0;
+  lost_flag = 0;
+  uint32_t pos = 0;
+  for (uint32_t c = 0; c < cnt; c += 64) {
+    const uint32_t e = c + lane;
+    const bool less = e < cnt && keys[e] < key;
+    pos += (uint32_t)__popcll(__ballot(less));
+  }
+  if (pos >= cap) {
+    lost = 1;
+    lost_flag = flag;
+    return;
+  }
+  if (cnt == cap) {
+    lost = 1;
+    lost_flag = flags[cap - 1];
+  }
+  const uint32_t newcnt = cnt < cap ? cnt + 1 : cap;
+  if (newcnt - 1 > pos) {
+    const uint32_t span = newcnt - 1 - pos;
+    for (int32_t c = (int32_t)((span - 1) / 64) * 64; c >= 0; c -= 64) {
+      const uint32_t e = pos + (uint32_t)c + lane;
+      const bool mv = e < newcnt - 1;
+      const uint64_t v = mv ? keys[e] : 0;
+      const uint8_t f = mv ? flags[e] : (uint8_t)0;
+      if (mv) {
+        keys[e + 1] = v;
+        flags[e + 1] = f;
+      }
+    }
+  }
+  if (lane == 0) {
+    keys[pos] = key;
+    flags[pos] = (uint8_t)flag;
+  }
+  cnt = newcnt;
+}
+
+// position of the ef-th allowed entry (ef >= 1), kNoIndex while there are fewer
+__device__ __forceinline__ uint32_t find_pivot(lds_vu8* flags, uint32_t cnt, uint32_t ef, int lane) {
+  uint32_t seen = 0;
+  for (uint32_t c = 0; c < cnt; c += 64) {
+    const uint32_t e = c + lane;
+    const uint64_t m = __ballot(e < cnt && (flags[e] & kFlagAllowed) != 0);
+    const uint32_t n = (uint32_t)__popcll(m);
+    if (seen + n >= ef) {
+      const uint32_t need = ef - seen - 1;  // set bits in front of the one we want
+      const uint64_t hit = __ballot(((m >> lane) & 1ull) != 0 && (uint32_t)__popcll(m & lt_mask(lane)) == need);
+      return c + (uint32_t)__ffsll((long long)hit) - 1;
+    }
+    seen += n;
+  }
+  return kNoIndex;
+}
+
+// entries behind the pivot stay only up to the last one whose distance is not greater than the pivot's
+__device__ __forceinline__ void pivot_truncate(lds_vu64* keys, uint32_t& cnt, uint32_t pivot, int lane) {
+  if (pivot == kNoIndex || cnt <= pivot + 1) return;
+  const uint64_t wk = keys[pivot];
+  uint32_t last = pivot;
+  for (uint32_t c = pivot + 1; c < cnt; c += 64) {
+    const uint32_t e = c + lane;
+    const bool stay = e < cnt && !(key_dist(keys[e]) > key_dist(wk));  // negation of graph.rs:474's raw compare
+    const uint64_t mask = __ballot(stay);
+    if (mask) last = c + 63u - (uint32_t)__clzll((long long)mask);
+  }
+  cnt = last + 1;
+}
+
+__device__ __forceinline__ uint32_t row_allowed(const HnswFilteredArgs& fa, uint32_t r) {  // r wave-uniform
+  if (r >= fa.f_rows) return 0u;
+  if (((fa.f_bitmap[r >> 5] >> (r & 31)) & 1u) == 0u) return 0u;
+  if (fa.s.alive && fa.s.alive[r] == 0) return 0u;
+  return kFlagAllowed;
+}
+
+// R rows per wave and distance step: 8; 4 at four 256-dimension chunks per lane and for Euclidean at three (the half walk's lever,
+// hnsw_half.hip: with 8 the Euclidean 768-dimension walk kept 20 bytes per lane in scratch memory; the group size does not change
+// a bit, reduce_rows)
+template <int METRIC, int CPL>
+using FiltDist = WalkDistF32<METRIC, CPL, 4, ((CPL == 4 || (CPL == 3 && METRIC == kEuclidean)) ? 4 : 8)>;
+
+// LDS: hnsw_lds_bytes' layout — keys[cap] u64 | nb_id[nbmax] | nb_d[nbmax] | ctl[4] | flags[cap] u8 (padded) | query scratch
+template <int METRIC, int CPL>
+__global__ __launch_bounds__(256, 4) void hnsw_search_filtered_kernel(HnswFilteredArgs fa) {
+  const HnswSearchArgs& a = fa.s;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = lane_id();
+  const int wib = (int)rfl(threadIdx.x >> 6);
+  const uint32_t cap = a.cap, nbmax = a.nbmax, ef = a.ef;
+  lds_vu64* keys = (lds_vu64*)(lds_void_p)(smem);
+  lds_vu32* nb_id = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8);
+  lds_vf32* nb_d = (lds_vf32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 4);
+  lds_vu32* ctl = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8);
+  lds_vu8* flags = (lds_vu8*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8 + 16);
+  const size_t qoff = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+  uint32_t* vis = a.visited + (size_t)blockIdx.x * a.vis_words;
+  uint32_t* vlog = a.vlog + (size_t)blockIdx.x * a.vlog_cap;
+  FiltDist<METRIC, CPL> dist;
+  dist.init(a, smem + qoff);
+
+  for (uint32_t slot = blockIdx.x; slot < a.nq; slot += gridDim.x) {
+    const uint32_t qi = fa.qmap ? fa.qmap[slot] : slot;
+    dist.load_query(a.queries + (size_t)qi * a.q_stride, lane);
+    __syncthreads();
+
+    // ---- leader state (wave 0; wave-uniform) ----
+    uint32_t cnt = 0, pivot = kNoIndex;
+    uint32_t n_dist = 0, n_expand = 0, logn = 0, overflow = 0, m_prev = 0;
+    int phase = P_START;
+    int layer = (int)a.max_layer;
+    uint32_t cur = a.entry_point;
+    float best_d = 0.0f;
+
+    // one admitted node: flag, insert, pivot, what fell off, truncation
+    auto admit = [&](float d, uint32_t node) {
+      uint32_t lost, lost_flag;
+      flist_insert(keys, flags, cnt, cap, make_key<false>(d, node), row_allowed(fa, node), lane, lost, lost_flag);
+      pivot = find_pivot(flags, cnt, ef, lane);
+      if (lost && ((lost_flag & kFlagExpanded) == 0 || ((lost_flag & kFlagAllowed) != 0 && pivot == kNoIndex))) overflow = 1;
+      pivot_truncate(keys, cnt, pivot, lane);
+    };
+
+    for (;;) {
+      if (wib == 0) {
+        bool ready = false;
+        uint32_t m = 0, done = 0;
+        while (!ready) {
+          if (phase == P_START) {
+            if (lane == 0) nb_id[0] = cur;
+            m = 1;
+            ready = true;
+            phase = layer > 0 ? P_G_ENTRY : P_Z_ENTRY;
+          } else if (phase == P_G_ENTRY) {
+            best_d = rflf(nb_d[0]);
+            n_dist += 1;
+            phase = P_G_LOAD;
+          } else if (phase == P_G_LOAD) {
+            const HnswLayerRef L = a.layers[layer];
+            uint32_t nc = rfl(L.cnt[cur]);
+            nc = min(nc, min(L.stride, nbmax));
+            for (uint32_t base = 0; base < nc; base += 64) {
+              const uint32_t t = base + lane;
+              if (t < nc) nb_id[t] = L.nbr[(size_t)cur * L.stride + t];
+            }
+            if (nc == 0) {
+              phase = P_G_DONE;
+            } else {
+              m = nc;
+              ready = true;
+              phase = P_G_SCAN;
+            }
+          } else if (phase == P_G_SCAN) {
+            n_dist += m_prev;
+            // sequential scan with strict `<` == first index attaining the minimum, if below best (graph.rs:413-421)
+            float mn = 0.0f;
+            uint32_t besti = 0xFFFFFFFFu;
+            for (uint32_t base = 0; base < m_prev; base += 64) {
+              const uint32_t t = base + lane;
+              const float d = t < m_prev ? nb_d[t] : 0.0f;
+              const bool ok = t < m_prev && d < best_d;  // raw compare: NaN never improves
+              const uint64_t okm = __ballot(ok);
+              if (okm) {
+                float v = ok ? d : __uint_as_float(0x7F800000u);
+#pragma unroll
+                for (int s = 32; s >= 1; s >>= 1) v = fminf(v, shx(v, s));
+                v = rflf(v);
+                if (besti == 0xFFFFFFFFu || v < mn) {
+                  const uint64_t eq = __ballot(ok && d == v);
+                  besti = base + (uint32_t)__ffsll((long long)eq) - 1;
+                  mn = v;
+                }
+              }
+            }
+            if (besti != 0xFFFFFFFFu) {
+              cur = rfl(nb_id[besti]);
+              best_d = rflf(nb_d[besti]);
+              phase = P_G_LOAD;
+            } else {
+              phase = P_G_DONE;
+            }
+          } else if (phase == P_G_DONE) {
+            layer -= 1;
+            phase = P_START;
+          } else if (phase == P_Z_ENTRY) {
+            // graph.rs:463-468: the entry point is evaluated, pushed to candidates, marked visited — and to results only if allowed
+            const float d = rflf(nb_d[0]);
+            const uint32_t ep = rfl(nb_id[0]);
+            n_dist += 1;
+            admit(d, ep);
+            if (lane == 0) {
+              atomicOr(&vis[ep >> 5], 1u << (ep & 31));
+              if (a.vlog_cap) vlog[0] = ep;
+            }
+            logn = 1;
+            phase = P_Z_POP;
+          } else if (phase == P_Z_POP) {
+            uint32_t idx = kNoIndex;
+            for (uint32_t c = 0; c < cnt; c += 64) {
+              const uint32_t e = c + lane;
+              const uint64_t un = __ballot(e < cnt && (flags[e] & kFlagExpanded) == 0);
+              if (un) {
+                idx = c + (uint32_t)__ffsll((long long)un) - 1;
+                break;
+              }
+            }
+            if (idx == kNoIndex) {
+              phase = P_FINISH;  // candidates empty (graph.rs:471)
+            } else {
+              const uint64_t ckey = keys[idx];
+              // graph.rs:474 with furthest = the pivot's distance and results.len() >= ef = "there is a pivot"
+              if (pivot != kNoIndex && key_dist(ckey) > key_dist(keys[pivot])) {
+                phase = P_FINISH;
+              } else {
+                if (lane == 0) flags[idx] = (uint8_t)(flags[idx] | kFlagExpanded);
+                n_expand += 1;
+                const uint32_t cnode = (uint32_t)ckey;
+                const HnswLayerRef L = a.layers[0];
+                const uint32_t lim = min(L.stride, nbmax);
+                uint32_t nc = rfl(L.cnt[cnode]);
+                nc = min(nc, lim);
+                for (uint32_t base = 0; base < nc; base += 64) {
+                  const uint32_t t = base + lane;
+                  const bool valid = t < nc;
+                  uint32_t nb = 0;
+                  bool newly = false;
+                  if (valid) {
+                    nb = L.nbr[(size_t)cnode * L.stride + t];
+                    const uint32_t bit = 1u << (nb & 31);
+                    newly = (atomicOr(&vis[nb >> 5], bit) & bit) == 0;  // visited.insert (graph.rs:499)
+                  }
+                  const uint64_t mask = __ballot(newly);
+                  const uint32_t before = (uint32_t)__popcll(mask & lt_mask(lane));
+                  if (newly) {
+                    nb_id[m + before] = nb;  // (m + before < nc <= nbmax)
+                    if (logn + before < a.vlog_cap) vlog[logn + before] = nb;
+                  }
+                  m += (uint32_t)__popcll(mask);
+                  logn += (uint32_t)__popcll(mask);
+                }
+                if (m != 0) {
+                  ready = true;
+                  phase = P_Z_ADMIT;
+                }
+              }
+            }
+          } else if (phase == P_Z_ADMIT) {
+            n_dist += m_prev;
+            for (uint32_t base = 0; base < m_prev; base += 64) {
+              const uint32_t t = base + lane;
+              const float d = t < m_prev ? nb_d[t] : 0.0f;
+              // pre-filter against the bound at chunk start: it only falls while the result set is full (there is a pivot), so a
+              // neighbour rejected now would be rejected at its turn too
+              const float far0 = pivot != kNoIndex ? key_dist(keys[pivot]) : 0.0f;
+              uint64_t mask = __ballot(t < m_prev && (pivot == kNoIndex || d < far0));
+              while (mask) {
+                const int src = __ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const float dj = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(d), src));
+                if (pivot == kNoIndex || dj < key_dist(keys[pivot])) admit(dj, nb_id[base + src]);  // graph.rs:503
+              }
+            }
+            phase = P_Z_POP;
+          } else {  // P_FINISH
+            done = 1;
+            ready = true;
+          }
+        }
+        if (lane == 0) {
+          ctl[0] = m;
+          ctl[1] = done;
+          ctl[2] = logn;
+        }
+        m_prev = m;
+      }
+      __syncthreads();
+      const uint32_t m = ctl[0];
+      if (ctl[1]) break;
+      dist.eval(m, nb_id, nb_d, lane, wib, false);
+      __syncthreads();
+    }
+
+    // ---- results: the first k allowed entries in list order (all of them are alive: the flag says so), scores through
+    // transform_score; NaN / ~0 padding and out_n as the unfiltered walk ----
+    if (wib == 0) {
+      uint32_t outn = 0;
+      for (uint32_t base = 0; base < cnt && outn < a.k; base += 64) {
+        const uint32_t e = base + lane;
+        const bool al = e < cnt && (flags[e] & kFlagAllowed) != 0;
+        const uint64_t mask = __ballot(al);
+        const uint32_t p = outn + (uint32_t)__popcll(mask & lt_mask(lane));
+        if (al && p < a.k) {
+          const uint64_t key = keys[e];
+          const uint32_t node = (uint32_t)key;
+          a.out_ids[(size_t)qi * a.k + p] = a.ext_ids ? a.ext_ids[node] : (uint64_t)node;
+          a.out_scores[(size_t)qi * a.k + p] = transform_score_dev(METRIC, key_dist(key));
+        }
+        outn = min(a.k, outn + (uint32_t)__popcll(mask));
+      }
+      for (uint32_t e = outn + lane; e < a.k; e += 64) {
+        a.out_ids[(size_t)qi * a.k + e] = ~0ull;
+        a.out_scores[(size_t)qi * a.k + e] = __uint_as_float(0x7FC00000u);
+      }
+      if (lane == 0) {
+        a.out_n[qi] = overflow ? 0xFFFFFFFFu : outn;
+        fa.qstats[(size_t)qi * 2] = n_dist;
+        fa.qstats[(size_t)qi * 2 + 1] = n_expand;
+      }
+    }
+    // ---- undo the visited bits of this query ----
+    const uint32_t nlog = ctl[2];
+    if (nlog <= a.vlog_cap) {
+      for (uint32_t i = threadIdx.x; i < nlog; i += 256) vis[vlog[i] >> 5] = 0;
+    } else {
+      for (uint64_t i = threadIdx.x; i < a.vis_words; i += 256) vis[i] = 0;
+    }
+    __syncthreads();
+  }
+}
+
+// The exact pass: one block per query over the filter's ascending row list in chunks of nbmax — dead rows skipped, distances by
+// the walk's DIST::eval, the k best by (total-order(distance), row) in the same LDS list (a.cap >= k entries), results in the
+// walk's format.  Adds the rows it evaluated to the query's n_dist.
+template <int METRIC, int CPL>
+__global__ __launch_bounds__(256, 4) void filter_rank_kernel(HnswFilteredArgs fa) {
+  const HnswSearchArgs& a = fa.s;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = lane_id();
+  const int wib = (int)rfl(threadIdx.x >> 6);
+  const uint32_t cap = a.cap, nbmax = a.nbmax, k = a.k;
+  lds_vu64* keys = (lds_vu64*)(lds_void_p)(smem);
+  lds_vu32* nb_id = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8);
+  lds_vf32* nb_d = (lds_vf32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 4);
+  lds_vu32* ctl = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8);
+  lds_vu8* flags = (lds_vu8*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8 + 16);
+  const size_t qoff = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+  FiltDist<METRIC, CPL> dist;
+  dist.init(a, smem + qoff);
+
+  for (uint32_t slot = blockIdx.x; slot < a.nq; slot += gridDim.x) {
+    const uint32_t qi = fa.qmap ? fa.qmap[slot] : slot;
+    dist.load_query(a.queries + (size_t)qi * a.q_stride, lane);
+    __syncthreads();
+    uint32_t cnt = 0, n_eval = 0, at = 0, m_prev = 0;  // leader state (wave 0; wave-uniform)
+    for (;;) {
+      if (wib == 0) {
+        // the chunk evaluated last: keys below the k-th best (or anything while the list is short) enter in row order
+        for (uint32_t base = 0; base < m_prev; base += 64) {
+          const uint32_t t = base + lane;
+          const uint64_t key = t < m_prev ? make_key<false>(nb_d[t], nb_id[t]) : kKeyInvalid;
+          uint64_t mask = __ballot(t < m_prev && (cnt < k || key < keys[k - 1]));
+          while (mask) {
+            const int src = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const uint64_t kj = readlane64(key, src);
+            if (cnt < k || kj < keys[k - 1]) {
+              uint32_t lost, lost_flag;
+              flist_insert(keys, flags, cnt, k, kj, 0u, lane, lost, lost_flag);
+            }
+          }
+        }
+        n_eval += m_prev;
+        // the next chunk: up to nbmax list entries, the live ones compacted in order
+        uint32_t m = 0;
+        while (m == 0 && at < fa.f_count) {
+          const uint32_t lim = min(nbmax, fa.f_count - at);
+          for (uint32_t base = 0; base < lim; base += 64) {
+            const uint32_t t = base + lane;
+            uint32_t row = 0;
+            bool ok = false;
+            if (t < lim) {
+              row = fa.f_list[at + t];
+              ok = row < a.n_rows && (!a.alive || a.alive[row] != 0);
+            }
+            const uint64_t mask = __ballot(ok);
+            if (ok) nb_id[m + (uint32_t)__popcll(mask & lt_mask(lane))] = row;  // (< lim <= nbmax)
+            m += (uint32_t)__popcll(mask);
+          }
+          at += lim;
+        }
+        if (lane == 0) {
+          ctl[0] = m;
+          ctl[1] = m == 0 ? 1u : 0u;
+        }
+        m_prev = m;
+      }
+      __syncthreads();
+      const uint32_t m = ctl[0];
+      if (ctl[1]) break;
+      dist.eval(m, nb_id, nb_d, lane, wib, false);
+      __syncthreads();
+    }
+    if (wib == 0) {
+      for (uint32_t e = lane; e < k; e += 64) {
+        uint64_t id = ~0ull;
+        float sc = __uint_as_float(0x7FC00000u);
+        if (e < cnt) {
+          const uint64_t key = keys[e];
+          const uint32_t node = (uint32_t)key;
+          id = a.ext_ids ? a.ext_ids[node] : (uint64_t)node;
+          sc = transform_score_dev(METRIC, key_dist(key));
+        }
+        a.out_ids[(size_t)qi * k + e] = id;
+        a.out_scores[(size_t)qi * k + e] = sc;
+      }
+      if (lane == 0) {
+        a.out_n[qi] = cnt;
+        fa.qstats[(size_t)qi * 2] += n_eval;
+      }
+    }
+    __syncthreads();  // (ctl, the list: read by everybody before the next query's leader rewrites them)
+  }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+template <bool RANK, int METRIC, int CPL>
+static hipError_t launch_fk(const HnswFilteredArgs& fa, int slots, size_t lds, hipStream_t st) {
+  auto kern = RANK ? filter_rank_kernel<METRIC, CPL> : hnsw_search_filtered_kernel<METRIC, CPL>;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  // resident blocks per CU of THIS instantiation: a larger grid would queue whole blocks behind the persistent ones — and the
+  // walk's visited bitmaps are sized for `slots` blocks
+  int occ = 0;
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, lds);
+  if (e != hipSuccess) return e;
+  occ = std::max(1, std::min(occ, 4));
+  const int grid = (int)std::min<int64_t>((int64_t)slots, (int64_t)fa.s.n_cus * occ);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, fa);
+  return hipGetLastError();
+}
+template <bool RANK, int METRIC>
+static hipError_t launch_fk_cpl(const HnswFilteredArgs& fa, int slots, size_t lds, hipStream_t st) {
+  switch (sweep_cpl_for_dim(fa.s.dim)) {
+    case 1: return launch_fk<RANK, METRIC, 1>(fa, slots, lds, st);
+    case 2: return launch_fk<RANK, METRIC, 2>(fa, slots, lds, st);
+    case 3: return launch_fk<RANK, METRIC, 3>(fa, slots, lds, st);
+    case 4: return launch_fk<RANK, METRIC, 4>(fa, slots, lds, st);
+    default: return launch_fk<RANK, METRIC, 0>(fa, slots, lds, st);
+  }
+}
+template <bool RANK>
+static hipError_t launch_filtered(const HnswFilteredArgs& fa, int slots, size_t lds, hipStream_t st) {
+  switch (fa.s.metric) {
+    case kCosine: return launch_fk_cpl<RANK, kCosine>(fa, slots, lds, st);
+    case kEuclidean: return launch_fk_cpl<RANK, kEuclidean>(fa, slots, lds, st);
+    case kDot: return launch_fk_cpl<RANK, kDot>(fa, slots, lds, st);
+    case kHamming: return launch_fk<RANK, kHamming, 0>(fa, slots, lds, st);
+    default: return launch_fk<RANK, kJaccard, 0>(fa, slots, lds, st);
+  }
+}
+
+// the largest list (entries) whose launch stays inside 160 KB of LDS at this nbmax: hnsw_search_prepare's limit
+static uint32_t largest_list(uint32_t nbmax, uint32_t dim, uint32_t words, int metric) {
+  uint64_t cap = (160 * 1024) / 9 / 64 * 64;
+  while (cap && hnsw_lds_bytes((uint32_t)cap, nbmax, dim, words, metric) > 160 * 1024) cap -= 64;
+  return (uint32_t)cap;
+}
+
+// vdb_hip_index_search_graph_filtered on a leased context (ix->mu shared, by the caller): the queries up, the walk with its
+// re-runs, the exact pass for what is left, the result block back in ix->h_out (reserve_out's layout).  routes: host, [nq].
+int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k, uint32_t ef,
+                                        int32_t route, uint32_t max_list, uint32_t* routes) {
+  int32_t rc = filter_check(ix, f);
+  if (rc != VDB_OK) return rc;
+  if (!ix->graph_valid) return fail(VDB_ERR_STATE, "HNSW graph not built for all rows (use the exact filtered search or build it)");
+  hipStream_t st = ix->stream;
+  ix->ev_used = 0;
+  ix->sel_ev_used = 0;
+  ix->last_select_level = 0;
+  ix->split_flags_n = 0;
+  ix->last_kernels = 0;
+  ix->last_n_dist = ix->last_n_expand = ix->last_pf_hits = 0;
+  ix->stats_pending = false;
+  const size_t kk = std::max<uint32_t>(k, 1);
+  rc = reserve_out(ix, nq, kk, st);
+  if (rc != VDB_OK) return rc;
+  if (ix->h_out.reserve(ix->s_out_bytes) != hipSuccess) return fail(VDB_ERR_OOM, "pinned result staging");
+  uint32_t* d_n = ix->s_out_n.as<uint32_t>();
+  const size_t n_off = (size_t)((unsigned char*)ix->s_out_n.p - (unsigned char*)ix->s_out.p);
+  uint32_t* h_n = reinterpret_cast<uint32_t*>(ix->h_out.as<unsigned char>() + n_off);
+  if (routes) std::memset(routes, 0, (size_t)nq * 4);
+  // graph.rs:252-255: no entry point => empty; an empty filter or k = 0 cannot answer either — no launch
+  if (f->count == 0 || k == 0 || ix->n_rows == 0 || ix->entry_point < 0 || ix->graph_nodes == 0) {
+    std::memset(h_n, 0, (size_t)nq * 4);
+    return VDB_OK;
+  }
+  if (ix->layers.size() > (size_t)kMaxLayers) return fail(VDB_ERR_UNSUPPORTED, "more than 16 graph layers");
+  if (ef == 0) ef = std::max<uint32_t>(128, k * 4);  // Balanced, params.rs:313
+  ef = std::max(ef, k);                               // SearchQuality::Custom(ef) = max(ef, k), params.rs:317
+
+  HnswFilteredArgs fa{};
+  HnswSearchArgs& a = fa.s;
+  uint32_t nbmax = 0;
+  for (size_t l = 0; l < ix->layers.size(); l++) {
+    a.layers[l].nbr = ix->layers[l].nbr.as<uint32_t>();
+    a.layers[l].cnt = ix->layers[l].cnt.as<uint32_t>();
+    a.layers[l].stride = ix->layers[l].stride;
+    nbmax = std::max(nbmax, ix->layers[l].stride);
+  }
+  nbmax = (nbmax + 63) / 64 * 64;
+  uint32_t cap_max = largest_list(nbmax, ix->dim, ix->words, ix->metric);
+  if (max_list) cap_max = std::min(cap_max, max_list);
+  const FilterGraphPlan plan = filter_graph_route(route, ef, f->count, ix->n_rows, cap_max);
+  const std::string limits = " (route " + std::to_string(route) + ", max_list " + std::to_string(max_list) + ", ef " + std::to_string(ef) + ")";
+  if (plan.route == kFgRefuse)
+    return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: the smallest candidate list does not fit the largest list allowed" + limits);
+
+  // queries up (pinned staging), per-query counters and the slot map behind them
+  rc = stage_queries(ix, queries, 0, nq, nq);
+  if (rc != VDB_OK) return rc;
+  if (ix->s_queries.reserve((size_t)nq * ix->row_stride * 4, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "search scratch");
+  const size_t qs_bytes = (size_t)nq * 16;
+  if (ix->s_fgraph.reserve(qs_bytes + (size_t)nq * 4, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "filtered graph scratch");
+  VDB_HIP(hipMemcpyAsync(ix->s_queries.p, ix->h_in.p, (size_t)nq * ix->row_stride * 4, hipMemcpyHostToDevice, st));
+  VDB_HIP(hipMemsetAsync(ix->s_fgraph.p, 0, qs_bytes, st));
+  uint32_t* d_qmap = reinterpret_cast<uint32_t*>(ix->s_fgraph.as<unsigned char>() + qs_bytes);
+
+  a.rows = ix->rows.as<float>();
+  a.norms = ix->norms.as<float>();
+  a.bits = ix->bits.as<uint32_t>();
+  a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  a.ext_ids = ix->ext_ids.as<uint64_t>();
+  a.queries = ix->s_queries.as<float>();
+  a.row_stride = ix->row_stride;
+  a.q_stride = ix->row_stride;
+  a.out_ids = ix->s_out_ids.as<uint64_t>();
+  a.out_scores = ix->s_out_scores.as<float>();
+  a.out_n = d_n;
+  a.dim = ix->dim;
+  a.words = ix->words;
+  a.n_rows = (uint32_t)ix->n_rows;
+  a.k = k;
+  a.ef = ef;
+  a.nbmax = nbmax;
+  a.vlog_cap = kVlogCap;
+  a.max_layer = ix->max_layer;
+  a.entry_point = (uint32_t)ix->entry_point;
+  a.metric = ix->metric;
+  a.n_cus = (uint32_t)ix->n_cus;
+  fa.f_bitmap = f->bitmap.as<uint32_t>();
+  fa.f_list = f->list.as<uint32_t>();
+  fa.f_rows = (uint32_t)f->n_rows;
+  fa.f_count = (uint32_t)f->count;
+  fa.qstats = ix->s_fgraph.as<unsigned long long>();
+
+  auto fetch = [&]() -> int32_t {
+    VDB_HIP(hipMemcpyAsync(ix->h_out.p, ix->s_out.p, ix->s_out_bytes, hipMemcpyDeviceToHost, st));
+    VDB_HIP(hipStreamSynchronize(st));
+    return VDB_OK;
+  };
+  // the queries of a launch: all of them (no map), or the listed ones
+  auto set_queries = [&](const std::vector<uint32_t>* which) -> int32_t {
+    fa.qmap = nullptr;
+    a.nq = nq;
+    if (which) {
+      VDB_HIP(hipMemcpyAsync(d_qmap, which->data(), which->size() * 4, hipMemcpyHostToDevice, st));
+      VDB_HIP(hipStreamSynchronize(st));  // (`which` is host memory)
+      fa.qmap = d_qmap;
+      a.nq = (uint32_t)which->size();
+    }
+    return VDB_OK;
+  };
+
+  std::vector<uint32_t> left;  // queries still without an answer (empty + all = every query)
+  bool all = true;
+  if (plan.route == kFgWalk) {
+    for (uint64_t cap = plan.cap;;) {
+      a.cap = (uint32_t)cap;
+      const size_t lds = hnsw_lds_bytes(a.cap, nbmax, ix->dim, ix->words, ix->metric);
+      if (lds > 160 * 1024) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: candidate list beyond the LDS" + limits);
+      rc = set_queries(all ? nullptr : &left);
+      if (rc != VDB_OK) return rc;
+      const int per_cu = (int)std::min<size_t>(4, std::max<size_t>(1, (160 * 1024) / lds));
+      const int slots = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * per_cu);
+      rc = ensure_traversal_scratch(ix, st, slots);
+      if (rc != VDB_OK) return rc;
+      a.visited = ix->s_visited.as<uint32_t>();
+      a.vlog = ix->s_vlog.as<uint32_t>();
+      a.vis_words = ix->vis_words;
+      const hipError_t e = launch_filtered<false>(fa, slots, lds, st);
+      if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filtered hnsw_search launch: ") + hipGetErrorString(e));
+      ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED;
+      rc = fetch();
+      if (rc != VDB_OK) return rc;
+      std::vector<uint32_t> over;
+      if (all) {
+        for (uint32_t i = 0; i < nq; i++) {
+          if (h_n[i] == 0xFFFFFFFFu) over.push_back(i);
+          if (routes) routes[i] = kFgWalk;
+        }
+      } else {
+        for (uint32_t i : left)
+          if (h_n[i] == 0xFFFFFFFFu) over.push_back(i);
+      }
+      left.swap(over);
+      all = false;
+      if (left.empty() || cap >= cap_max) break;
+      cap = std::min<uint64_t>(cap * 4, cap_max);  // search_block's rule: four times the room
+    }
+    if (!left.empty() && route == kFgWalk)
+      return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: " + std::to_string(left.size()) + " queries overflow the largest candidate list (" +
+                                           std::to_string(cap_max) + " entries)" + limits);
+  }
+  if (all || !left.empty()) {  // the exact pass: the whole call, or the queries the largest list could not hold
+    a.cap = (uint32_t)fg_round64(k);
+    const size_t lds = hnsw_lds_bytes(a.cap, nbmax, ix->dim, ix->words, ix->metric);
+    if (lds > 160 * 1024) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: k too large for the LDS-resident result list");
+    rc = set_queries(all ? nullptr : &left);
+    if (rc != VDB_OK) return rc;
+    const int slots = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * 4);
+    const hipError_t e = launch_filtered<true>(fa, slots, lds, st);
+    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filter_rank launch: ") + hipGetErrorString(e));
+    ix->last_kernels |= VDB_KERNEL_FILTER_RANK;
+    rc = fetch();
+    if (rc != VDB_OK) return rc;
+    if (routes) {
+      if (all)
+        for (uint32_t i = 0; i < nq; i++) routes[i] = kFgExact;
+      else
+        for (uint32_t i : left) routes[i] = kFgExact;
+    }
+  }
+  // the call's counters: every query's last walk attempt plus the rows its exact pass evaluated
+  std::vector<unsigned long long> qs((size_t)nq * 2);
+  VDB_HIP(hipMemcpyAsync(qs.data(), ix->s_fgraph.p, qs_bytes, hipMemcpyDeviceToHost, st));
+  VDB_HIP(hipStreamSynchronize(st));
+  for (uint32_t i = 0; i < nq; i++) {
+    ix->last_n_dist += qs[(size_t)i * 2];
+    ix->last_n_expand += qs[(size_t)i * 2 + 1];
+  }
+  return VDB_OK;
+}
+
+}  // namespace vdb

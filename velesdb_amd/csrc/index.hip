@@ -1131,7 +1131,7 @@ std::vector<DevBuf*> index_buffers(vdb_hip_index* ix) {
       &ix->sq8_img, &ix->sq8_nrm, &ix->sq8_seed, &ix->sq8_rho,              // SQ8 selection images
       &ix->bits_img, &ix->bits_cnt,                                         // four-bit image of the bit rows (Hamming / Jaccard GEMM)
       &ix->s_queries, &ix->s_part_keys, &ix->s_part_cnt, &ix->s_out, &ix->s_qbits, &ix->s_tickets, &ix->s_flt_mask,
-      &ix->s_misc, &ix->s_fb_keys, &ix->s_seed, &ix->s_visited, &ix->s_vlog, &ix->s_stats, &ix->s_build_stats, &ix->s_levels, &ix->s_req_keys,
+      &ix->s_misc, &ix->s_fgraph, &ix->s_fb_keys, &ix->s_seed, &ix->s_visited, &ix->s_vlog, &ix->s_stats, &ix->s_build_stats, &ix->s_levels, &ix->s_req_keys,
       &ix->s_req_vals, &ix->s_sort_tmp};
   for (auto& L : ix->layers) {
     v.push_back(&L.nbr);
@@ -1288,12 +1288,17 @@ int32_t search_to_device(vdb_hip_index* ix, const float* queries, uint32_t nq, u
 
 // search_to_device in VDB_SEARCH_BRUTE restricted to a filter's rows.  The filter must belong to this handle (generation) and to its
 // present row numbering (row_epoch): anything else is an error, never a result.
-int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k) {
+int32_t filter_check(vdb_hip_index* ix, const RowFilter* f) {
   const vdb_hip_index* p = primary_of(ix);
   if (f->generation != p->generation) return fail(VDB_ERR_INVALID_ARG, "filtered search: the filter was created on another index");
   if (f->row_epoch != p->row_epoch)
     return fail(VDB_ERR_STATE, "filtered search: the index renumbered its rows (vacuum / load) after the filter was created");
   if (f->n_rows > ix->n_rows) return fail(VDB_ERR_STATE, "filtered search: the filter names rows the index does not hold");
+  return VDB_OK;
+}
+int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k) {
+  const int32_t rcf = filter_check(ix, f);
+  if (rcf != VDB_OK) return rcf;
   ix->flt = f;
   const int32_t rc = search_to_device(ix, queries, nq, k, 0, VDB_SEARCH_BRUTE, 0, nullptr);
   ix->flt = nullptr;

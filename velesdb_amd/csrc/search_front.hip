@@ -93,6 +93,16 @@ static int32_t search_filtered_direct(vdb_hip_index* handle, const RowFilter* f,
       [&](vdb_hip_index* ix) { deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n); });
 }
 
+// vdb_hip_index_search_graph_filtered: a launch (or a few) of its own on a leased context, like the exact filtered call
+static int32_t search_graph_filtered_direct(vdb_hip_index* handle, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k,
+                                            uint32_t ef, int32_t route, uint32_t max_list, uint64_t* out_ids, float* out_scores,
+                                            uint32_t* out_n, uint32_t* out_route) {
+  return run_search(
+      handle, nq, k, ef, VDB_SEARCH_HNSW, 0,
+      [&](vdb_hip_index* ix) { return search_graph_filtered_to_device(ix, f, queries, nq, k, ef, route, max_list, out_route); },
+      [&](vdb_hip_index* ix) { deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n); });
+}
+
 // the leader's part: one launch for `batch` (same shape; batch[0] is the leader's own request)
 static void run_batch(vdb_hip_index* handle, CombineReq* const* reqs, size_t n_reqs) {
   struct Span {
@@ -217,6 +227,22 @@ int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* ix, const void* filte
   if (mode != VDB_SEARCH_BRUTE) return fail(VDB_ERR_UNSUPPORTED, "filtered search: VDB_SEARCH_BRUTE only (the graph and quantised modes keep the over-fetch rule)");
   if (nq == 0) return VDB_OK;
   return search_filtered_direct(ix, f, queries, nq, k, out_ids, out_scores, out_n);
+  });
+}
+
+// VDB_SEARCH_HNSW with the allow-list consulted inside the walk, and the exact pass behind it (hnsw_filtered.hip)
+int32_t vdb_hip_index_search_graph_filtered(vdb_hip_index* ix, const void* filter, const float* queries, uint32_t nq, uint32_t k,
+                                            uint32_t ef, int32_t mode, int32_t route, uint32_t max_list, uint64_t* out_ids,
+                                            float* out_scores, uint32_t* out_n, uint32_t* out_route) {
+  return vdb::guarded([&]() -> int32_t {
+  const RowFilter* f = static_cast<const RowFilter*>(filter);
+  if (!ix || !f || (nq && (!queries || !out_n)) || (nq && k && (!out_ids || !out_scores))) return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filtered graph search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  if (mode != VDB_SEARCH_HNSW) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: VDB_SEARCH_HNSW only (no filtered walk over the half / int8 images)");
+  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
+  if (nq == 0) return VDB_OK;
+  return search_graph_filtered_direct(ix, f, queries, nq, k, ef, route, max_list, out_ids, out_scores, out_n, out_route);
   });
 }
 

@@ -1,5 +1,7 @@
-// vdb_filter_route.hpp — which route a filtered exact call takes (vdb_hip_index_search_batch_filtered).
-// Pure host logic without a HIP header: tests/filter_route_model.cpp compiles it alone and walks its boundaries.
+// vdb_filter_route.hpp — which route a filtered exact call takes (vdb_hip_index_search_batch_filtered) and which a
+// filtered graph call takes (vdb_hip_index_search_graph_filtered).
+// Pure host logic without a HIP header: tests/filter_route_model.cpp and tests/filter_graph_route_model.cpp compile it alone and
+// walk its boundaries.
 #pragma once
 #include <stdint.h>
 
@@ -24,5 +26,40 @@ static inline int filter_route(int64_t opt, bool listed_available, uint64_t coun
 // than 1/16 of the rows allowed the seed sample holds too few live rows to give k keys a bound (16 384 sample rows, one key per 64
 // rows: 256 keys, 16 of them live at 1/16), so those calls go straight to the exact kernels — which serve any mask.
 static inline bool filter_keeps_selection(uint64_t count, uint64_t n_rows) { return count * 16 >= n_rows; }
+
+// ---- filtered graph search (vdb_hip_index_search_graph_filtered): walk or exact pass, and the walk's first list ----
+enum FilterGraphRoute : int { kFgRefuse = -1, kFgAuto = 0, kFgWalk = 1, kFgExact = 2 };
+struct FilterGraphPlan {
+  int route;      // kFgWalk, kFgExact, or kFgRefuse (route = walk and not even the smallest list fits cap_max)
+  uint32_t cap;   // kFgWalk: the capacity of the first attempt (entries)
+};
+static inline uint64_t fg_round64(uint64_t v) { return (v + 63) / 64 * 64; }
+// the list of the unfiltered walk (hnsw_search_prepare): ef results + room for candidates that tie with the furthest one
+static inline uint64_t fg_min_list(uint32_t ef_eff) {
+  return fg_round64((uint64_t)ef_eff + (ef_eff / 2 > 64 ? (uint64_t)ef_eff / 2 : 64));
+}
+// the density-sized list: while fewer than ef allowed nodes are known the walk admits everything, about ef * n_rows / matched
+// nodes; twice that plus one chunk.  ~0 when it cannot fit any list (ef_eff > cap_max: the product below then stays far inside 64 bits)
+static inline uint64_t fg_sized_list(uint32_t ef_eff, uint64_t matched, uint64_t n_rows, uint32_t cap_max) {
+  if (matched == 0 || ef_eff > cap_max) return ~0ull;
+  const uint64_t s = fg_round64(2ull * ef_eff * n_rows / matched + 64);
+  const uint64_t m = fg_min_list(ef_eff);
+  return s > m ? s : m;
+}
+// route: the caller's (0 auto, 1 walk, 2 exact pass); ef_eff = max(ef, k) after the Balanced rule; matched = rows in the filter;
+// cap_max = the largest list the launch can hold (160 KB of LDS at its nbmax, lowered by the caller's max_list).
+// Auto is a STATED GUESS, not a measurement — the factor 2 and the `matched < ef_eff` cut: tools/filter_probe.py's graph leg is
+// what would settle them.
+static inline FilterGraphPlan filter_graph_route(int route, uint32_t ef_eff, uint64_t matched, uint64_t n_rows, uint32_t cap_max) {
+  if (route == kFgExact || matched == 0) return FilterGraphPlan{kFgExact, 0};
+  const uint64_t sized = fg_sized_list(ef_eff, matched, n_rows, cap_max);
+  if (route == kFgWalk) {
+    if (fg_min_list(ef_eff) > cap_max) return FilterGraphPlan{kFgRefuse, 0};
+    return FilterGraphPlan{kFgWalk, (uint32_t)(sized < cap_max ? sized : cap_max)};
+  }
+  if (matched < ef_eff) return FilterGraphPlan{kFgExact, 0};  // the walk could never fill its result set
+  if (sized > cap_max) return FilterGraphPlan{kFgExact, 0};
+  return FilterGraphPlan{kFgWalk, (uint32_t)sized};
+}
 
 }  // namespace vdb

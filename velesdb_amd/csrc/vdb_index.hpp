@@ -247,6 +247,7 @@ struct vdb_hip_index {
   // scratch
   vdb::DevBuf s_queries, s_part_keys, s_part_cnt, s_qbits, s_misc;
   vdb::DevBuf s_flt_mask;  // [capacity + slack] u8: the row mask of a filtered call on the mask-substitution route (n_rows bytes written per call)
+  vdb::DevBuf s_fgraph;    // filtered graph search (hnsw_filtered.hip): [nq][2] u64 per-query counters | [nq] u32 launch slot -> query
   vdb::DevBuf s_tickets;  // [2] u32, zero between calls: the block tickets of the one-launch packed-bit search (sweep_bits_fused)
   // results of a host-pointer search: ONE allocation [ids nq*k u64 | scores nq*k f32 | n nq u32] (reserve_out), so that one
   // copy brings everything back; the three views point into it
@@ -315,6 +316,12 @@ static inline const uint8_t* search_alive(const vdb_hip_index* ix) {
 }
 // filtered exact search (index.hip): the caller holds ix->mu shared and leased the context `ix`
 int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k);
+// the filter belongs to this handle (generation) and to its present row numbering (row_epoch): anything else is an error
+int32_t filter_check(vdb_hip_index* ix, const RowFilter* f);
+// filtered graph search (hnsw_filtered.hip): same locking; the result block ends in ix->h_out, routes[nq] (host, nullable) says per
+// query 1 = walk, 2 = exact pass, 0 = nothing was launched
+int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k, uint32_t ef,
+                                        int32_t route, uint32_t max_list, uint32_t* routes);
 // rows per index: the tiled kernels count whole 256-row tiles of [0, n) in 32 bits — (n + 255) / 256 must not wrap
 // (tests/gemm_schedule_model.cpp walks the launch schedule up to this limit)
 constexpr uint64_t kMaxRowsPerIndex = 0xFFFFFE00ull;  // 2^32 - 512

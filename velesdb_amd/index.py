@@ -40,6 +40,10 @@ KERNEL_HNSW_HALF = 1 << 15
 OPT_FILTER_ROUTE = _ffi.VDB_OPT_FILTER_ROUTE
 FILTER_ROUTE_AUTO, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK = 0, 1, 2
 KERNEL_SWEEP_LISTED = _ffi.VDB_KERNEL_SWEEP_LISTED
+# filtered graph search (HnswIndex.search_batch_filtered_graph): the route of a call / of a query, and the two kernel families
+ROUTE_AUTO, ROUTE_WALK, ROUTE_EXACT = 0, 1, 2
+KERNEL_HNSW_FILTERED = _ffi.VDB_KERNEL_HNSW_FILTERED
+KERNEL_FILTER_RANK = _ffi.VDB_KERNEL_FILTER_RANK
 SHARD_REPLICA, SHARD_RANGE = 0, 1
 COMM_ID_BYTES = 128
 
@@ -466,6 +470,25 @@ class HnswIndex:
         check(lib().vdb_hip_index_search_batch_filtered(self._h, flt._h if flt is not None else None, _ptr(qs), nq, k, mode, _ptr(ids),
                                                         _ptr(sc), _ptr(cnt)))
         return ids, sc, cnt
+
+    def search_batch_filtered_graph(self, queries, k: int, flt: Filter, ef: int = 0, route: int = ROUTE_AUTO, max_list: int = 0,
+                                    mode: int = MODE_HNSW):
+        """Graph search with the filter consulted inside the walk (vdb_hip_index_search_graph_filtered): layer 0 keeps allowed live
+        rows only in its result set, every node still navigates.  route: ROUTE_AUTO (walk, or the exact pass where the walk's
+        candidate list could not hold the query), ROUTE_WALK, ROUTE_EXACT; max_list lowers the largest candidate list (0 = what
+        the LDS holds).  Returns ((ids, scores, counts), routes): numpy outputs, routes[q] = 1 walk / 2 exact pass / 0 nothing ran."""
+        qs = _f32(queries)
+        if qs.ndim == 1:
+            qs = qs.reshape(1, -1)
+        self._validate(qs)
+        nq, kk = qs.shape[0], max(k, 1)
+        ids = np.empty((nq, kk), dtype=np.uint64)
+        sc = np.empty((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        routes = np.zeros(nq, dtype=np.uint32)
+        check(lib().vdb_hip_index_search_graph_filtered(self._h, flt._h if flt is not None else None, _ptr(qs), nq, k, ef, mode, route,
+                                                        max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
+        return (ids, sc, cnt), routes
 
     def search_brute_force_filtered(self, query, k: int, flt: Filter) -> List[Tuple[int, float]]:
         """search_brute_force among the filter's rows only (one query)."""
