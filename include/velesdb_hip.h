@@ -341,6 +341,27 @@ int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* idx, const void* f, c
 int32_t vdb_hip_index_search_graph_filtered(vdb_hip_index* idx, const void* f, const float* queries_rowmajor, uint32_t nq,
                                             uint32_t k, uint32_t ef, int32_t mode, int32_t route, uint32_t max_list,
                                             uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route);
+/* One filter PER QUERY in one graph call: the collection layer's search_batch_with_filters (collection/search/batch.rs:26-115;
+ * DESIGN 4.1i).  filters = n_filters distinct filter handles of this index; filter_of_query[i] in 0..n_filters-1 names query i's
+ * filter, filter_of_query[i] == n_filters = query i has NO filter, defined as a filter created at the moment of the call with
+ * negate = 1 and no ids (every row present now; dead rows are dropped inside the walk).  n_filters == 0 with filters == NULL is
+ * legal: every query is unfiltered.
+ * THE CONTRACT: query i gets, bit for bit, what vdb_hip_index_search_graph_filtered returns for that query ALONE with its filter and
+ * the same k, ef, route, max_list — ids, ranks, score bits, out_n, padding, out_route[i], and its share of the search counters
+ * (vdb_hip_index_last_search_stats = the sum of the single calls' counters).  A query's answer and route never depend on its
+ * companions or on its position in the batch: a query with an empty filter gets out_n = 0 and route 0 while the others are
+ * answered.  Queries whose candidate lists differ in size share launches (at most four walk launches per attempt round, one launch
+ * for every exact pass of the call).  route 1: a query that overflows the largest list fails the WHOLE call with
+ * VDB_ERR_UNSUPPORTED (the message says how many did).
+ * Errors, checked for every filter of the table before anything runs: a NULL table entry or a filter of another handle, a
+ * filter_of_query value > n_filters, route outside 0..2: VDB_ERR_INVALID_ARG; a stale filter or no graph: VDB_ERR_STATE; mode other
+ * than VDB_SEARCH_HNSW, multi-device handles and process-group members: VDB_ERR_UNSUPPORTED.  The outputs are untouched on error.
+ * Host pointers only; launches of its own (no combining front).  vdb_hip_index_last_kernels: VDB_KERNEL_HNSW_FILTERED and / or
+ * VDB_KERNEL_FILTER_RANK (the per-query kernels are instances of those families). */
+int32_t vdb_hip_index_search_graph_filters(vdb_hip_index* idx, void** filters, uint32_t n_filters,
+                                           const uint32_t* filter_of_query, const float* queries_rowmajor, uint32_t nq,
+                                           uint32_t k, uint32_t ef, int32_t mode, int32_t route, uint32_t max_list,
+                                           uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route);
 
 /* ---- DistanceEngine::batch_distance / GpuAccelerator::batch_{cosine_similarity,
  * euclidean_distance,dot_product} (native/distance.rs:21-24; gpu_backend.rs:157,355,397) ----

@@ -17,6 +17,11 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
   exact routes, with the over-fetch rule through plain VDB_SEARCH_HNSW (k' = max(4k, k + 10), post-filtered on the host) as the
   baseline, its recall and the share of queries it answers short.  This table is what would replace the two guesses of the
   auto rule (the factor 2 of the density-sized list, the `matched < ef` cut).  NO RUN OF IT IS RECORDED YET.
+  --graph --per-query F: the PER-QUERY leg instead (vdb_hip_index_search_graph_filters): at each density F distinct
+  random filters of that density, the --graph-nq queries dealt round-robin over them; one call of search_batch_with_filters against
+  the same queries as F calls of search_batch_filtered_graph, one per filter — what a caller does today with the same library, timed
+  in the same run, the spread of the blocks beside each.  Also n_dist per query of both (they must agree: the same walks), and the
+  launches each side needs AT LEAST (first attempts by LDS class plus one exact pass; re-runs are not visible from outside).
 
 Every figure is the median of --repeats blocks, each block the mean over enough calls to last ~--block-ms; the spread is
 (max - min) / median over the blocks.  Not part of the product or the test-suite."""
@@ -45,6 +50,7 @@ p.add_argument("--gather-tbs", type=float, default=5.7, help="whole-row gather r
 p.add_argument("--rider", action="store_true")
 p.add_argument("--graph", action="store_true", help="the filtered graph search leg instead of the exact one")
 p.add_argument("--graph-nq", type=int, default=1024)
+p.add_argument("--per-query", type=int, default=0, help="with --graph: F distinct filters per density in one call against F single-filter calls")
 p.add_argument("--ef", type=int, default=128)
 p.add_argument("--densities", default="1,0.5,0.25,0.125,0.0625,0.03125,0.015625,0.0078125,0.00390625,0.001953125,0.0009765625")
 p.add_argument("--out", default="")
@@ -134,9 +140,63 @@ def graph_leg():
     return rows_out
 
 
+def per_query_leg():
+    F, rows_out = a.per_query, []
+    for mname in a.metrics.split(","):
+        ix = build(METRICS[mname])
+        ix.set_option(va.OPT_COMBINE_MAX_BATCH, 0)
+        t0 = time.perf_counter()
+        ix.build_graph(0)
+        print(f"# {mname}: graph over {a.rows} rows in {time.perf_counter() - t0:.1f} s", flush=True)
+        rng = np.random.default_rng(7)
+        Q = rng.standard_normal((a.graph_nq, a.dim)).astype(np.float32)
+        of = np.arange(a.graph_nq) % F
+        parts = [np.flatnonzero(of == j) for j in range(F)]
+        Qs = [np.ascontiguousarray(Q[p]) for p in parts]
+        for dens in [float(x) for x in a.densities.split(",")]:
+            count = max(1, int(a.rows * dens))
+            flts = [ix.create_filter(np.sort(rng.choice(a.rows, size=count, replace=False)).astype(np.uint64)) for _ in range(F)]
+            per_q = [flts[j] for j in of]
+            row = dict(leg="per_query", metric=mname, rows=a.rows, dim=a.dim, k=a.k, ef=a.ef, nq=a.graph_nq, filters=F, density=dens, count=count)
+
+            def one_call():
+                return ix.search_batch_with_filters(Q, a.k, per_q, ef=a.ef)
+
+            def single_calls():
+                return [ix.search_batch_filtered_graph(Qs[j], a.k, flts[j], ef=a.ef) for j in range(F) if len(parts[j])]
+            (ids, sc, cnt), routes = one_call()
+            row["n_dist"] = ix.last_search_stats()[0] / a.graph_nq
+            row["walked"] = float(np.mean(routes == 1))
+            nd, exact_calls = 0, 0
+            for j in range(F):  # the answers agree bit for bit (a probe that times different answers measures nothing)
+                if not len(parts[j]):
+                    continue
+                (i1, s1, c1), r1 = ix.search_batch_filtered_graph(Qs[j], a.k, flts[j], ef=a.ef)
+                nd += ix.last_search_stats()[0]
+                exact_calls += bool(np.any(r1 == 2))
+                assert np.array_equal(i1, ids[parts[j]]) and np.array_equal(s1.view(np.uint32), sc[parts[j]].view(np.uint32)), (mname, dens, j)
+                assert np.array_equal(c1, cnt[parts[j]]) and np.array_equal(r1, routes[parts[j]]), (mname, dens, j)
+            row["single_n_dist"] = nd / a.graph_nq
+            # every filter of a density has the same size, so the same first list: one walk launch for the call, one per single call
+            used = sum(1 for p in parts if len(p))
+            row["launches_at_least"] = int(np.any(routes == 1)) + int(np.any(routes == 2))
+            row["single_launches_at_least"] = (used if np.any(routes == 1) else 0) + exact_calls
+            ms, sp = measure(one_call)
+            row["ms"], row["spread"], row["qps"] = ms, sp, a.graph_nq / (ms * 1e-3)
+            ms1, sp1 = measure(single_calls)
+            row["single_ms"], row["single_spread"], row["single_qps"] = ms1, sp1, a.graph_nq / (ms1 * 1e-3)
+            row["single_over_one_call"] = ms1 / ms
+            for f in flts:
+                f.close()
+            rows_out.append(row)
+            print(json.dumps(row), flush=True)
+        ix.close()
+    return rows_out
+
+
 table = []
 if a.graph:
-    table = graph_leg()
+    table = per_query_leg() if a.per_query > 0 else graph_leg()
     a.metrics = ""
 for mname in [m for m in a.metrics.split(",") if m]:
     ix = build(METRICS[mname])

@@ -1044,6 +1044,92 @@ impl HipHnswIndex {
         (out, routes)
     }
 
+    /// [`Self::search_batch_graph_filtered`] with one optional filter PER QUERY in one call (`vdb_hip_index_search_graph_filters`;
+    /// `Collection::search_batch_with_filters`, collection/search/batch.rs:26-115).  `None` = no filter: every row present now.
+    /// Query `i` gets bit for bit what [`Self::search_batch_graph_filtered`] returns for it alone with its filter, whatever its
+    /// companions are.  The filter table is built by identity of the `HipFilter` objects.
+    ///
+    /// # Panics
+    /// When `filters.len() != queries.len()` ("Queries count … does not match filters count …", as the reference).
+    #[must_use]
+    pub fn search_batch_with_filters(
+        &self,
+        queries: &[&[f32]],
+        k: usize,
+        quality: SearchQuality,
+        filters: &[Option<&HipFilter>],
+        route: i32,
+        max_list: u32,
+    ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
+        assert!(
+            queries.len() == filters.len(),
+            "Queries count ({}) does not match filters count ({})",
+            queries.len(),
+            filters.len()
+        );
+        for q in queries {
+            self.validate_dimension(q, "Query");
+        }
+        if queries.is_empty() {
+            return (Vec::new(), Vec::new());
+        }
+        let nq = queries.len();
+        if k == 0 {
+            return (vec![Vec::new(); nq], vec![0; nq]);
+        }
+        // the table of distinct handles; `None` is numbered behind it once its length is known
+        let mut table: Vec<*mut c_void> = Vec::new();
+        let slots: Vec<Option<usize>> = filters
+            .iter()
+            .map(|f| {
+                f.map(|f| {
+                    table.iter().position(|t| *t == f.h).unwrap_or_else(|| {
+                        table.push(f.h);
+                        table.len() - 1
+                    })
+                })
+            })
+            .collect();
+        let none = table.len() as u32;
+        let fq: Vec<u32> = slots.iter().map(|s| s.map_or(none, |at| at as u32)).collect();
+        let mut flat = Vec::with_capacity(nq * self.dimension);
+        for q in queries {
+            flat.extend_from_slice(q);
+        }
+        let mut ids = vec![0u64; nq * k];
+        let mut scores = vec![0f32; nq * k];
+        let mut counts = vec![0u32; nq];
+        let mut routes = vec![0u32; nq];
+        // SAFETY: buffer sizes are n_filters / nq / nq*dim / nq*k / nq as the ABI requires; every handle of the table is live
+        // (borrowed from `filters`); the library does not write through the table.
+        check(unsafe {
+            sys::vdb_hip_index_search_graph_filters(
+                self.h,
+                if table.is_empty() { std::ptr::null_mut() } else { table.as_mut_ptr() },
+                none,
+                fq.as_ptr(),
+                flat.as_ptr(),
+                nq as u32,
+                k as u32,
+                quality.ef_search(k) as u32,
+                sys::VDB_SEARCH_HNSW,
+                route,
+                max_list,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                counts.as_mut_ptr(),
+                routes.as_mut_ptr(),
+            )
+        });
+        let out = (0..nq)
+            .map(|i| {
+                let c = counts[i] as usize;
+                (0..c).map(|j| (ids[i * k + j], scores[i * k + j])).collect()
+            })
+            .collect();
+        (out, routes)
+    }
+
     /// [`Self::search_batch_graph_filtered`] for one query on the auto route.
     #[must_use]
     pub fn search_graph_filtered(&self, query: &[f32], k: usize, quality: SearchQuality, filter: &HipFilter) -> Vec<(u64, f32)> {

@@ -136,6 +136,7 @@ extern "C" {
     pub fn vdb_hip_filter_destroy(f: *mut c_void);
     pub fn vdb_hip_index_search_batch_filtered(idx: *mut VdbHipIndex, f: *const c_void, queries_rowmajor: *const f32, nq: u32, k: u32, mode: i32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filtered(idx: *mut VdbHipIndex, f: *const c_void, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, mode: i32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
+    pub fn vdb_hip_index_search_graph_filters(idx: *mut VdbHipIndex, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, mode: i32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
     pub fn vdb_hip_batch_distance(device: i32, metric: i32, kind: i32, query: *const f32, vecs_rowmajor: *const f32, n: u64, dim: u32, out: *mut f32) -> i32;
     pub fn vdb_hip_batch_distance_dev(metric: i32, kind: i32, d_query: *const f32, d_vecs_rowmajor: *const f32, n: u64, dim: u32, d_out: *mut f32, stream: *mut c_void) -> i32;
     pub fn vdb_hip_batch_norm(device: i32, vecs_rowmajor: *const f32, n: u64, dim: u32, out: *mut f32) -> i32;

@@ -18,6 +18,11 @@
 // filter_rank_kernel is that exact answer: top-k of the allowed live rows by (total-order(distance), row), the distances from the
 // walk's own DIST::eval — bit for bit what the walk reports for the same row.
 //
+// One filter per query (vdb_hip_index_search_graph_filters): hnsw_search_filters_kernel / filters_rank_kernel are the
+// same two bodies with the filter taken from a per-slot descriptor instead of the argument struct; a launch's LDS layout follows its
+// PHYSICAL list capacity, every query's list logic its own LOGICAL one, so queries with lists of different sizes share launches and
+// each computes what it computes alone.
+//
 // Algorithmic HBM bytes per query: walk n_dist * dim * 4 + n_expand * M0 * 4 + (admitted neighbours) * 4 for the bitmap words;
 // exact pass matched * (dim * 4 + 4).  Nothing here is measured: tools/filter_probe.py has the graph leg.
 #include <algorithm>
@@ -39,7 +44,63 @@ struct HnswFilteredArgs {
   unsigned long long* qstats; // [nq_total][2]: the walk WRITES a query's n_dist / n_expand, the exact pass ADDS its rows to n_dist
 };
 
+// one filter per query (vdb_hip_index_search_graph_filters): a table of n_filters + 1 descriptors — the last one is "no
+// filter": null bitmap and list, rows = count = the index's rows now — and one FiltersSlot (vdb_filter_route.hpp) per launch slot
+struct FilterDesc {
+  const uint32_t* bitmap;
+  const uint32_t* list;
+  uint32_t rows, count;
+};
+struct HnswFiltersArgs {
+  HnswSearchArgs s;           // (s.nq = the slots of THIS launch; s.cap = its PHYSICAL list capacity: the LDS layout)
+  const FilterDesc* descs;    // [n_filters + 1]
+  const FiltersSlot* slots;   // [s.nq]
+  unsigned long long* qstats; // as HnswFilteredArgs::qstats
+};
+
 constexpr uint32_t kFlagExpanded = 1u, kFlagAllowed = 2u;
+
+// What a workgroup knows about the query of its launch slot: the filter, the query's index in the call and the LOGICAL capacity of
+// its list (<= the launch's physical s.cap; all list logic of the query runs on it).  Every field is wave-uniform.
+// (the two arrays as global-memory pointers by type: a pointer that was LOADED — the descriptor's — is a generic one to the
+// compiler, and reads through it would take the flat path)
+typedef const __attribute__((address_space(1))) uint32_t* glb_u32_p;
+struct SlotFilter {
+  glb_u32_p bitmap;
+  glb_u32_p list;
+  uint32_t rows, count, qi, cap;
+};
+// where the bodies below find it — the call's one filter in the argument struct ...
+struct OneFilterSrc {
+  static constexpr bool kOpen = false;  // there is always a bitmap and a list
+  const HnswFilteredArgs& fa;
+  __device__ __forceinline__ SlotFilter load(uint32_t slot) const {
+    return SlotFilter{(glb_u32_p)fa.f_bitmap, (glb_u32_p)fa.f_list, fa.f_rows, fa.f_count, fa.qmap ? fa.qmap[slot] : slot, fa.s.cap};
+  }
+};
+__device__ __forceinline__ glb_u32_p uniform_ptr(const uint32_t* p) {
+  const uint64_t v = (uint64_t)p;
+  return (glb_u32_p)(((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | (uint64_t)rfl((uint32_t)v));
+}
+// ... or the slot's descriptor, loaded once per query into scalar registers (rfl as for wib): the per-neighbour bitmap test stays
+// one dword load from a scalar base
+struct SlotTableSrc {
+  static constexpr bool kOpen = true;  // a null bitmap / list = every row below `rows`
+  const HnswFiltersArgs& fa;
+  __device__ __forceinline__ SlotFilter load(uint32_t slot) const {
+    const FiltersSlot s = fa.slots[slot];
+    const uint32_t fi = rfl(s.filter);
+    const FilterDesc d = fa.descs[fi];
+    SlotFilter f;
+    f.bitmap = uniform_ptr(d.bitmap);
+    f.list = uniform_ptr(d.list);
+    f.rows = rfl(d.rows);
+    f.count = rfl(d.count);
+    f.qi = rfl(s.query);
+    f.cap = min(rfl(s.cap), fa.s.cap);  // (never past the layout, whatever the table says)
+    return f;
+  }
+};
 
 // list_insert (vdb_hnsw_device.hpp) with the new entry's flag given and the lost entry reported: lost = 1 when an entry fell off
 // (the key itself when it sorts behind a full list), lost_flag = its flags
@@ -114,10 +175,11 @@ __device__ __forceinline__ void pivot_truncate(lds_vu64* keys, uint32_t& cnt, ui
   cnt = last + 1;
 }
 
-__device__ __forceinline__ uint32_t row_allowed(const HnswFilteredArgs& fa, uint32_t r) {  // r wave-uniform
-  if (r >= fa.f_rows) return 0u;
-  if (((fa.f_bitmap[r >> 5] >> (r & 31)) & 1u) == 0u) return 0u;
-  if (fa.s.alive && fa.s.alive[r] == 0) return 0u;
+template <bool OPEN>
+__device__ __forceinline__ uint32_t row_allowed(const SlotFilter& f, const uint8_t* alive, uint32_t r) {  // r wave-uniform
+  if (r >= f.rows) return 0u;
+  if (!(OPEN && f.bitmap == nullptr) && ((f.bitmap[r >> 5] >> (r & 31)) & 1u) == 0u) return 0u;
+  if (alive && alive[r] == 0) return 0u;
   return kFlagAllowed;
 }
 
@@ -128,13 +190,13 @@ template <int METRIC, int CPL>
 using FiltDist = WalkDistF32<METRIC, CPL, 4, ((CPL == 4 || (CPL == 3 && METRIC == kEuclidean)) ? 4 : 8)>;
 
 // LDS: hnsw_lds_bytes' layout — keys[cap] u64 | nb_id[nbmax] | nb_d[nbmax] | ctl[4] | flags[cap] u8 (padded) | query scratch
-template <int METRIC, int CPL>
-__global__ __launch_bounds__(256, 4) void hnsw_search_filtered_kernel(HnswFilteredArgs fa) {
-  const HnswSearchArgs& a = fa.s;
+// (the walk of both kernel families below: SRC says where the slot's filter comes from)
+template <int METRIC, int CPL, class SRC>
+__device__ __forceinline__ void filtered_walk_body(const HnswSearchArgs& a, unsigned long long* qstats, const SRC src) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
   const int wib = (int)rfl(threadIdx.x >> 6);
-  const uint32_t cap = a.cap, nbmax = a.nbmax, ef = a.ef;
+  const uint32_t cap = a.cap, nbmax = a.nbmax, ef = a.ef;  // cap: the launch's physical capacity, the layout only
   lds_vu64* keys = (lds_vu64*)(lds_void_p)(smem);
   lds_vu32* nb_id = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8);
   lds_vf32* nb_d = (lds_vf32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 4);
@@ -147,7 +209,8 @@ __global__ __launch_bounds__(256, 4) void hnsw_search_filtered_kernel(HnswFilter
   dist.init(a, smem + qoff);
 
   for (uint32_t slot = blockIdx.x; slot < a.nq; slot += gridDim.x) {
-    const uint32_t qi = fa.qmap ? fa.qmap[slot] : slot;
+    const SlotFilter f = src.load(slot);
+    const uint32_t qi = f.qi;
     dist.load_query(a.queries + (size_t)qi * a.q_stride, lane);
     __syncthreads();
 
@@ -162,7 +225,7 @@ __global__ __launch_bounds__(256, 4) void hnsw_search_filtered_kernel(HnswFilter
     // one admitted node: flag, insert, pivot, what fell off, truncation
     auto admit = [&](float d, uint32_t node) {
       uint32_t lost, lost_flag;
-      flist_insert(keys, flags, cnt, cap, make_key<false>(d, node), row_allowed(fa, node), lane, lost, lost_flag);
+      flist_insert(keys, flags, cnt, f.cap, make_key<false>(d, node), row_allowed<SRC::kOpen>(f, a.alive, node), lane, lost, lost_flag);
       pivot = find_pivot(flags, cnt, ef, lane);
       if (lost && ((lost_flag & kFlagExpanded) == 0 || ((lost_flag & kFlagAllowed) != 0 && pivot == kNoIndex))) overflow = 1;
       pivot_truncate(keys, cnt, pivot, lane);
@@ -350,8 +413,8 @@ __global__ __launch_bounds__(256, 4) void hnsw_search_filtered_kernel(HnswFilter
       }
       if (lane == 0) {
         a.out_n[qi] = overflow ? 0xFFFFFFFFu : outn;
-        fa.qstats[(size_t)qi * 2] = n_dist;
-        fa.qstats[(size_t)qi * 2 + 1] = n_expand;
+        qstats[(size_t)qi * 2] = n_dist;
+        qstats[(size_t)qi * 2 + 1] = n_expand;
       }
     }
     // ---- undo the visited bits of this query ----
@@ -365,12 +428,21 @@ __global__ __launch_bounds__(256, 4) void hnsw_search_filtered_kernel(HnswFilter
   }
 }
 
+template <int METRIC, int CPL>
+__global__ __launch_bounds__(256, 4) void hnsw_search_filtered_kernel(HnswFilteredArgs fa) {
+  filtered_walk_body<METRIC, CPL>(fa.s, fa.qstats, OneFilterSrc{fa});
+}
+// one filter per query: the slot's descriptor instead of the call's filter
+template <int METRIC, int CPL>
+__global__ __launch_bounds__(256, 4) void hnsw_search_filters_kernel(HnswFiltersArgs fa) {
+  filtered_walk_body<METRIC, CPL>(fa.s, fa.qstats, SlotTableSrc{fa});
+}
+
 // The exact pass: one block per query over the filter's ascending row list in chunks of nbmax — dead rows skipped, distances by
 // the walk's DIST::eval, the k best by (total-order(distance), row) in the same LDS list (a.cap >= k entries), results in the
 // walk's format.  Adds the rows it evaluated to the query's n_dist.
-template <int METRIC, int CPL>
-__global__ __launch_bounds__(256, 4) void filter_rank_kernel(HnswFilteredArgs fa) {
-  const HnswSearchArgs& a = fa.s;
+template <int METRIC, int CPL, class SRC>
+__device__ __forceinline__ void filter_rank_body(const HnswSearchArgs& a, unsigned long long* qstats, const SRC src) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
   const int wib = (int)rfl(threadIdx.x >> 6);
@@ -385,7 +457,8 @@ __global__ __launch_bounds__(256, 4) void filter_rank_kernel(HnswFilteredArgs fa
   dist.init(a, smem + qoff);
 
   for (uint32_t slot = blockIdx.x; slot < a.nq; slot += gridDim.x) {
-    const uint32_t qi = fa.qmap ? fa.qmap[slot] : slot;
+    const SlotFilter f = src.load(slot);
+    const uint32_t qi = f.qi;
     dist.load_query(a.queries + (size_t)qi * a.q_stride, lane);
     __syncthreads();
     uint32_t cnt = 0, n_eval = 0, at = 0, m_prev = 0;  // leader state (wave 0; wave-uniform)
@@ -409,14 +482,14 @@ __global__ __launch_bounds__(256, 4) void filter_rank_kernel(HnswFilteredArgs fa
         n_eval += m_prev;
         // the next chunk: up to nbmax list entries, the live ones compacted in order
         uint32_t m = 0;
-        while (m == 0 && at < fa.f_count) {
-          const uint32_t lim = min(nbmax, fa.f_count - at);
+        while (m == 0 && at < f.count) {
+          const uint32_t lim = min(nbmax, f.count - at);
           for (uint32_t base = 0; base < lim; base += 64) {
             const uint32_t t = base + lane;
             uint32_t row = 0;
             bool ok = false;
             if (t < lim) {
-              row = fa.f_list[at + t];
+              row = (SRC::kOpen && f.list == nullptr) ? at + t : f.list[at + t];  // (no filter: the rows themselves)
               ok = row < a.n_rows && (!a.alive || a.alive[row] != 0);
             }
             const uint64_t mask = __ballot(ok);
@@ -452,17 +525,31 @@ __global__ __launch_bounds__(256, 4) void filter_rank_kernel(HnswFilteredArgs fa
       }
       if (lane == 0) {
         a.out_n[qi] = cnt;
-        fa.qstats[(size_t)qi * 2] += n_eval;
+        qstats[(size_t)qi * 2] += n_eval;
       }
     }
     __syncthreads();  // (ctl, the list: read by everybody before the next query's leader rewrites them)
   }
 }
 
+template <int METRIC, int CPL>
+__global__ __launch_bounds__(256, 4) void filter_rank_kernel(HnswFilteredArgs fa) {
+  filter_rank_body<METRIC, CPL>(fa.s, fa.qstats, OneFilterSrc{fa});
+}
+template <int METRIC, int CPL>
+__global__ __launch_bounds__(256, 4) void filters_rank_kernel(HnswFiltersArgs fa) {
+  filter_rank_body<METRIC, CPL>(fa.s, fa.qstats, SlotTableSrc{fa});
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------
 template <bool RANK, int METRIC, int CPL>
-static hipError_t launch_fk(const HnswFilteredArgs& fa, int slots, size_t lds, hipStream_t st) {
-  auto kern = RANK ? filter_rank_kernel<METRIC, CPL> : hnsw_search_filtered_kernel<METRIC, CPL>;
+static auto kernel_of(const HnswFilteredArgs&) { return RANK ? filter_rank_kernel<METRIC, CPL> : hnsw_search_filtered_kernel<METRIC, CPL>; }
+template <bool RANK, int METRIC, int CPL>
+static auto kernel_of(const HnswFiltersArgs&) { return RANK ? filters_rank_kernel<METRIC, CPL> : hnsw_search_filters_kernel<METRIC, CPL>; }
+
+template <bool RANK, int METRIC, int CPL, class ARGS>
+static hipError_t launch_fk(const ARGS& fa, int slots, size_t lds, hipStream_t st) {
+  auto kern = kernel_of<RANK, METRIC, CPL>(fa);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -477,8 +564,8 @@ static hipError_t launch_fk(const HnswFilteredArgs& fa, int slots, size_t lds, h
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, fa);
   return hipGetLastError();
 }
-template <bool RANK, int METRIC>
-static hipError_t launch_fk_cpl(const HnswFilteredArgs& fa, int slots, size_t lds, hipStream_t st) {
+template <bool RANK, int METRIC, class ARGS>
+static hipError_t launch_fk_cpl(const ARGS& fa, int slots, size_t lds, hipStream_t st) {
   switch (sweep_cpl_for_dim(fa.s.dim)) {
     case 1: return launch_fk<RANK, METRIC, 1>(fa, slots, lds, st);
     case 2: return launch_fk<RANK, METRIC, 2>(fa, slots, lds, st);
@@ -487,8 +574,8 @@ static hipError_t launch_fk_cpl(const HnswFilteredArgs& fa, int slots, size_t ld
     default: return launch_fk<RANK, METRIC, 0>(fa, slots, lds, st);
   }
 }
-template <bool RANK>
-static hipError_t launch_filtered(const HnswFilteredArgs& fa, int slots, size_t lds, hipStream_t st) {
+template <bool RANK, class ARGS>
+static hipError_t launch_filtered(const ARGS& fa, int slots, size_t lds, hipStream_t st) {
   switch (fa.s.metric) {
     case kCosine: return launch_fk_cpl<RANK, kCosine>(fa, slots, lds, st);
     case kEuclidean: return launch_fk_cpl<RANK, kEuclidean>(fa, slots, lds, st);
@@ -503,6 +590,43 @@ static uint32_t largest_list(uint32_t nbmax, uint32_t dim, uint32_t words, int m
   uint64_t cap = (160 * 1024) / 9 / 64 * 64;
   while (cap && hnsw_lds_bytes((uint32_t)cap, nbmax, dim, words, metric) > 160 * 1024) cap -= 64;
   return (uint32_t)cap;
+}
+
+// the graph of a launch: every layer's lists; returns nbmax (the longest neighbour list, 64-rounded)
+static uint32_t walk_args_graph(const vdb_hip_index* ix, HnswSearchArgs& a) {
+  uint32_t nbmax = 0;
+  for (size_t l = 0; l < ix->layers.size(); l++) {
+    a.layers[l].nbr = ix->layers[l].nbr.as<uint32_t>();
+    a.layers[l].cnt = ix->layers[l].cnt.as<uint32_t>();
+    a.layers[l].stride = ix->layers[l].stride;
+    nbmax = std::max(nbmax, ix->layers[l].stride);
+  }
+  return (nbmax + 63) / 64 * 64;
+}
+// ... and everything else a launch reads from the index and the context (queries in s_queries, results in s_out_*)
+static void walk_args_index(vdb_hip_index* ix, HnswSearchArgs& a, uint32_t k, uint32_t ef, uint32_t nbmax, uint32_t* d_n) {
+  a.rows = ix->rows.as<float>();
+  a.norms = ix->norms.as<float>();
+  a.bits = ix->bits.as<uint32_t>();
+  a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  a.ext_ids = ix->ext_ids.as<uint64_t>();
+  a.queries = ix->s_queries.as<float>();
+  a.row_stride = ix->row_stride;
+  a.q_stride = ix->row_stride;
+  a.out_ids = ix->s_out_ids.as<uint64_t>();
+  a.out_scores = ix->s_out_scores.as<float>();
+  a.out_n = d_n;
+  a.dim = ix->dim;
+  a.words = ix->words;
+  a.n_rows = (uint32_t)ix->n_rows;
+  a.k = k;
+  a.ef = ef;
+  a.nbmax = nbmax;
+  a.vlog_cap = kVlogCap;
+  a.max_layer = ix->max_layer;
+  a.entry_point = (uint32_t)ix->entry_point;
+  a.metric = ix->metric;
+  a.n_cus = (uint32_t)ix->n_cus;
 }
 
 // vdb_hip_index_search_graph_filtered on a leased context (ix->mu shared, by the caller): the queries up, the walk with its
@@ -539,14 +663,7 @@ int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, c
 
   HnswFilteredArgs fa{};
   HnswSearchArgs& a = fa.s;
-  uint32_t nbmax = 0;
-  for (size_t l = 0; l < ix->layers.size(); l++) {
-    a.layers[l].nbr = ix->layers[l].nbr.as<uint32_t>();
-    a.layers[l].cnt = ix->layers[l].cnt.as<uint32_t>();
-    a.layers[l].stride = ix->layers[l].stride;
-    nbmax = std::max(nbmax, ix->layers[l].stride);
-  }
-  nbmax = (nbmax + 63) / 64 * 64;
+  const uint32_t nbmax = walk_args_graph(ix, a);
   uint32_t cap_max = largest_list(nbmax, ix->dim, ix->words, ix->metric);
   if (max_list) cap_max = std::min(cap_max, max_list);
   const FilterGraphPlan plan = filter_graph_route(route, ef, f->count, ix->n_rows, cap_max);
@@ -564,28 +681,7 @@ int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, c
   VDB_HIP(hipMemsetAsync(ix->s_fgraph.p, 0, qs_bytes, st));
   uint32_t* d_qmap = reinterpret_cast<uint32_t*>(ix->s_fgraph.as<unsigned char>() + qs_bytes);
 
-  a.rows = ix->rows.as<float>();
-  a.norms = ix->norms.as<float>();
-  a.bits = ix->bits.as<uint32_t>();
-  a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
-  a.ext_ids = ix->ext_ids.as<uint64_t>();
-  a.queries = ix->s_queries.as<float>();
-  a.row_stride = ix->row_stride;
-  a.q_stride = ix->row_stride;
-  a.out_ids = ix->s_out_ids.as<uint64_t>();
-  a.out_scores = ix->s_out_scores.as<float>();
-  a.out_n = d_n;
-  a.dim = ix->dim;
-  a.words = ix->words;
-  a.n_rows = (uint32_t)ix->n_rows;
-  a.k = k;
-  a.ef = ef;
-  a.nbmax = nbmax;
-  a.vlog_cap = kVlogCap;
-  a.max_layer = ix->max_layer;
-  a.entry_point = (uint32_t)ix->entry_point;
-  a.metric = ix->metric;
-  a.n_cus = (uint32_t)ix->n_cus;
+  walk_args_index(ix, a, k, ef, nbmax, d_n);
   fa.f_bitmap = f->bitmap.as<uint32_t>();
   fa.f_list = f->list.as<uint32_t>();
   fa.f_rows = (uint32_t)f->n_rows;
@@ -669,6 +765,171 @@ int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, c
         for (uint32_t i : left) routes[i] = kFgExact;
     }
   }
+  // the call's counters: every query's last walk attempt plus the rows its exact pass evaluated
+  std::vector<unsigned long long> qs((size_t)nq * 2);
+  VDB_HIP(hipMemcpyAsync(qs.data(), ix->s_fgraph.p, qs_bytes, hipMemcpyDeviceToHost, st));
+  VDB_HIP(hipStreamSynchronize(st));
+  for (uint32_t i = 0; i < nq; i++) {
+    ix->last_n_dist += qs[(size_t)i * 2];
+    ix->last_n_expand += qs[(size_t)i * 2 + 1];
+  }
+  return VDB_OK;
+}
+
+// vdb_hip_index_search_graph_filters: one filter per query.  Query i computes what the function above computes for it
+// alone — its own plan, its own ladder of capacities, the exact pass behind it — and only shares launches with its companions:
+// filters_walk_ladders (vdb_filter_route.hpp) groups every round into at most four launches by LDS footprint, and every exact pass
+// of the call is one launch.  filters: [n_filters] handles, non-null; fq: [nq] values in 0..n_filters, n_filters = no filter.
+int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
+                                       const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
+                                       uint32_t* routes) {
+  int32_t rc;
+  for (uint32_t j = 0; j < n_filters; j++)
+    if ((rc = filter_check(ix, filters[j])) != VDB_OK) return rc;
+  if (!ix->graph_valid) return fail(VDB_ERR_STATE, "HNSW graph not built for all rows (use the exact filtered search or build it)");
+  hipStream_t st = ix->stream;
+  ix->ev_used = 0;
+  ix->sel_ev_used = 0;
+  ix->last_select_level = 0;
+  ix->split_flags_n = 0;
+  ix->last_kernels = 0;
+  ix->last_n_dist = ix->last_n_expand = ix->last_pf_hits = 0;
+  ix->stats_pending = false;
+  const size_t kk = std::max<uint32_t>(k, 1);
+  rc = reserve_out(ix, nq, kk, st);
+  if (rc != VDB_OK) return rc;
+  if (ix->h_out.reserve(ix->s_out_bytes) != hipSuccess) return fail(VDB_ERR_OOM, "pinned result staging");
+  uint32_t* d_n = ix->s_out_n.as<uint32_t>();
+  unsigned char* h_base = ix->h_out.as<unsigned char>();
+  uint32_t* h_n = reinterpret_cast<uint32_t*>(h_base + (size_t)((unsigned char*)ix->s_out_n.p - (unsigned char*)ix->s_out.p));
+  std::memset(routes, 0, (size_t)nq * 4);
+  // a query nothing runs for (an empty filter; k = 0; an empty graph): out_n = 0 and padding, written on the host at the end
+  auto blank = [&]() {
+    uint64_t* h_ids = reinterpret_cast<uint64_t*>(h_base);
+    uint32_t* h_sc = reinterpret_cast<uint32_t*>(h_base + (size_t)nq * kk * 8);
+    for (uint32_t i = 0; i < nq; i++) {
+      if (routes[i] != 0) continue;
+      h_n[i] = 0;
+      for (size_t e = 0; e < (size_t)k; e++) {
+        h_ids[(size_t)i * k + e] = ~0ull;
+        h_sc[(size_t)i * k + e] = 0x7FC00000u;
+      }
+    }
+  };
+  if (k == 0 || ix->n_rows == 0 || ix->entry_point < 0 || ix->graph_nodes == 0) {
+    blank();
+    return VDB_OK;
+  }
+  if (ix->layers.size() > (size_t)kMaxLayers) return fail(VDB_ERR_UNSUPPORTED, "more than 16 graph layers");
+  if (ef == 0) ef = std::max<uint32_t>(128, k * 4);  // Balanced, params.rs:313
+  ef = std::max(ef, k);                               // SearchQuality::Custom(ef) = max(ef, k), params.rs:317
+
+  HnswFiltersArgs fa{};
+  HnswSearchArgs& a = fa.s;
+  const uint32_t nbmax = walk_args_graph(ix, a);
+  uint32_t cap_max = largest_list(nbmax, ix->dim, ix->words, ix->metric);
+  if (max_list) cap_max = std::min(cap_max, max_list);
+  const std::string limits = " (route " + std::to_string(route) + ", max_list " + std::to_string(max_list) + ", ef " + std::to_string(ef) + ")";
+  auto lds_of = [&](uint32_t cap) -> uint64_t { return hnsw_lds_bytes(cap, nbmax, ix->dim, ix->words, ix->metric); };
+
+  // the descriptor table (the last entry: no filter) and every query's own plan
+  std::vector<FilterDesc> descs(n_filters + 1);
+  for (uint32_t j = 0; j < n_filters; j++)
+    descs[j] = FilterDesc{filters[j]->bitmap.as<uint32_t>(), filters[j]->list.as<uint32_t>(), (uint32_t)filters[j]->n_rows, (uint32_t)filters[j]->count};
+  descs[n_filters] = FilterDesc{nullptr, nullptr, (uint32_t)ix->n_rows, (uint32_t)ix->n_rows};
+  std::vector<FiltersSlot> first, exact;
+  for (uint32_t i = 0; i < nq; i++) {
+    const uint64_t matched = descs[fq[i]].count;
+    if (matched == 0) continue;  // (route 0: nothing runs for this query)
+    const FilterGraphPlan plan = filter_graph_route(route, ef, matched, ix->n_rows, cap_max);
+    if (plan.route == kFgRefuse)
+      return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: the smallest candidate list does not fit the largest list allowed" + limits);
+    if (plan.route == kFgWalk) {
+      first.push_back(FiltersSlot{i, fq[i], plan.cap, 0});
+      routes[i] = kFgWalk;
+    } else {
+      exact.push_back(FiltersSlot{i, fq[i], 0, 0});
+    }
+  }
+  if (first.empty() && exact.empty()) {
+    blank();
+    return VDB_OK;
+  }
+
+  // queries up (pinned staging); counters, descriptors and the slot table behind each other in the context's scratch
+  rc = stage_queries(ix, queries, 0, nq, nq);
+  if (rc != VDB_OK) return rc;
+  if (ix->s_queries.reserve((size_t)nq * ix->row_stride * 4, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "search scratch");
+  const size_t qs_bytes = (size_t)nq * 16, desc_bytes = descs.size() * sizeof(FilterDesc), slot_bytes = (size_t)nq * sizeof(FiltersSlot);
+  if (ix->s_fgraph.reserve(qs_bytes + desc_bytes + slot_bytes, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "filtered graph scratch");
+  VDB_HIP(hipMemcpyAsync(ix->s_queries.p, ix->h_in.p, (size_t)nq * ix->row_stride * 4, hipMemcpyHostToDevice, st));
+  VDB_HIP(hipMemsetAsync(ix->s_fgraph.p, 0, qs_bytes, st));
+  FilterDesc* d_descs = reinterpret_cast<FilterDesc*>(ix->s_fgraph.as<unsigned char>() + qs_bytes);
+  FiltersSlot* d_slots = reinterpret_cast<FiltersSlot*>(ix->s_fgraph.as<unsigned char>() + qs_bytes + desc_bytes);
+  VDB_HIP(hipMemcpyAsync(d_descs, descs.data(), desc_bytes, hipMemcpyHostToDevice, st));  // (`descs` outlives every synchronisation below)
+  walk_args_index(ix, a, k, ef, nbmax, d_n);
+  fa.descs = d_descs;
+  fa.qstats = ix->s_fgraph.as<unsigned long long>();
+
+  auto fetch = [&]() -> int32_t {
+    VDB_HIP(hipMemcpyAsync(ix->h_out.p, ix->s_out.p, ix->s_out_bytes, hipMemcpyDeviceToHost, st));
+    VDB_HIP(hipStreamSynchronize(st));
+    return VDB_OK;
+  };
+  // one round of walks: its slot table up, its launches behind each other, one fetch (`slots` is host memory that lives until
+  // the round's synchronisation)
+  auto run_round = [&](const FiltersSlot* slots, uint32_t n, const FiltersLaunch* launches, uint32_t n_launches, unsigned char* over) -> int {
+    VDB_HIP(hipMemcpyAsync(d_slots, slots, (size_t)n * sizeof(FiltersSlot), hipMemcpyHostToDevice, st));
+    int most = 0;
+    for (uint32_t l = 0; l < n_launches; l++)
+      most = std::max(most, (int)std::min<int64_t>((int64_t)launches[l].count, (int64_t)ix->n_cus * (int64_t)launches[l].per_cu));
+    int32_t r = ensure_traversal_scratch(ix, st, most);  // (once, in front of the round: the launches share the bitmaps in stream order)
+    if (r != VDB_OK) return r;
+    a.visited = ix->s_visited.as<uint32_t>();
+    a.vlog = ix->s_vlog.as<uint32_t>();
+    a.vis_words = ix->vis_words;
+    for (uint32_t l = 0; l < n_launches; l++) {
+      const FiltersLaunch& L = launches[l];
+      a.cap = L.cap;
+      a.nq = L.count;
+      fa.slots = d_slots + L.begin;
+      const size_t lds = lds_of(a.cap);
+      if (lds > kFgLdsBudget) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: candidate list beyond the LDS" + limits);
+      const int slots_l = (int)std::min<int64_t>((int64_t)L.count, (int64_t)ix->n_cus * (int64_t)L.per_cu);
+      const hipError_t e = launch_filtered<false>(fa, slots_l, lds, st);
+      if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filtered hnsw_search launch: ") + hipGetErrorString(e));
+    }
+    ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED;
+    r = fetch();
+    if (r != VDB_OK) return r;
+    for (uint32_t i = 0; i < n; i++) over[i] = h_n[slots[i].query] == 0xFFFFFFFFu;
+    return VDB_OK;
+  };
+  std::vector<FiltersSlot> left;
+  rc = filters_walk_ladders(first, cap_max, lds_of, run_round, &left);
+  if (rc != VDB_OK) return rc;
+  if (!left.empty() && route == kFgWalk)
+    return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: " + std::to_string(left.size()) + " queries overflow the largest candidate list (" +
+                                         std::to_string(cap_max) + " entries)" + limits);
+  exact.insert(exact.end(), left.begin(), left.end());
+  if (!exact.empty()) {  // every exact pass of the call in one launch: the whole-route ones and what the largest list could not hold
+    std::sort(exact.begin(), exact.end(), [](const FiltersSlot& x, const FiltersSlot& y) { return x.query < y.query; });
+    a.cap = (uint32_t)fg_round64(k);
+    for (FiltersSlot& s : exact) s.cap = a.cap;
+    const size_t lds = lds_of(a.cap);
+    if (lds > kFgLdsBudget) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: k too large for the LDS-resident result list");
+    VDB_HIP(hipMemcpyAsync(d_slots, exact.data(), exact.size() * sizeof(FiltersSlot), hipMemcpyHostToDevice, st));
+    a.nq = (uint32_t)exact.size();
+    fa.slots = d_slots;
+    const int slots_l = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * 4);
+    const hipError_t e = launch_filtered<true>(fa, slots_l, lds, st);
+    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filters_rank launch: ") + hipGetErrorString(e));
+    ix->last_kernels |= VDB_KERNEL_FILTER_RANK;
+    rc = fetch();
+    if (rc != VDB_OK) return rc;
+    for (const FiltersSlot& s : exact) routes[s.query] = kFgExact;
+  }
+  blank();
   // the call's counters: every query's last walk attempt plus the rows its exact pass evaluated
   std::vector<unsigned long long> qs((size_t)nq * 2);
   VDB_HIP(hipMemcpyAsync(qs.data(), ix->s_fgraph.p, qs_bytes, hipMemcpyDeviceToHost, st));

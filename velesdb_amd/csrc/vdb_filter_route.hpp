@@ -1,9 +1,12 @@
 // vdb_filter_route.hpp — which route a filtered exact call takes (vdb_hip_index_search_batch_filtered) and which a
-// filtered graph call takes (vdb_hip_index_search_graph_filtered).
-// Pure host logic without a HIP header: tests/filter_route_model.cpp and tests/filter_graph_route_model.cpp compile it alone and
-// walk its boundaries.
+// filtered graph call takes (vdb_hip_index_search_graph_filtered), and which queries of a call with one filter per
+// query share a launch (vdb_hip_index_search_graph_filters).
+// Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_graph_route_model.cpp and
+// tests/filters_plan_model.cpp compile it alone and walk its boundaries.
 #pragma once
 #include <stdint.h>
+
+#include <vector>
 
 namespace vdb {
 
@@ -60,6 +63,81 @@ static inline FilterGraphPlan filter_graph_route(int route, uint32_t ef_eff, uin
   if (matched < ef_eff) return FilterGraphPlan{kFgExact, 0};  // the walk could never fill its result set
   if (sized > cap_max) return FilterGraphPlan{kFgExact, 0};
   return FilterGraphPlan{kFgWalk, (uint32_t)sized};
+}
+
+// ---- one filter per query (vdb_hip_index_search_graph_filters): which queries share a launch ----
+// Every query keeps the plan filter_graph_route gives ITS filter and climbs ITS OWN ladder — first list plan.cap, four times the
+// room while it overflows, cap_max last, then the exact pass: the sequence the single-filter host loop runs.  Only the grouping into
+// launches looks at the other queries, and a launch changes nothing a query computes: the kernel sizes the LDS layout by the
+// launch's PHYSICAL capacity and runs all list logic of a query on its own LOGICAL one.
+struct FiltersSlot {   // one launch slot (device layout, 16 bytes)
+  uint32_t query, filter, cap, pad;  // cap: the query's logical list capacity in this attempt
+};
+struct FiltersLaunch {
+  uint32_t begin, count;  // slots [begin, begin + count) of the round's grouped slot array
+  uint32_t cap;           // physical capacity: the largest logical one of the group
+  uint32_t per_cu;        // walks a CU holds at that footprint (1..4)
+};
+constexpr uint64_t kFgLdsBudget = 160 * 1024;
+// walks per CU at an LDS footprint: the rule of the single-filter loop
+static inline uint32_t fg_per_cu(uint64_t lds) {
+  const uint64_t n = lds ? kFgLdsBudget / lds : 4;
+  return (uint32_t)(n > 4 ? 4 : (n < 1 ? 1 : n));
+}
+// the next step of a query's ladder after an overflow at `cap`; 0 = the ladder is over (the exact pass, or the refusal of route 1)
+static inline uint32_t fg_ladder_next(uint32_t cap, uint32_t cap_max) {
+  if (cap >= cap_max) return 0;
+  const uint64_t n = (uint64_t)cap * 4;
+  return (uint32_t)(n < cap_max ? n : cap_max);
+}
+// One round (the first attempts, or the re-runs): `in[n]` grouped into at most four launches by fg_per_cu(lds_of(cap)), fullest CUs
+// first, the order of `in` kept inside a group.  out[n] receives the grouped slots; returns the number of launches.
+template <class LdsOf>
+static inline uint32_t filters_plan_round(const FiltersSlot* in, uint32_t n, FiltersSlot* out, FiltersLaunch launches[4], LdsOf&& lds_of) {
+  uint32_t n_launch = 0, at = 0;
+  for (uint32_t pc = 4; pc >= 1; pc--) {
+    FiltersLaunch l{at, 0, 0, pc};
+    for (uint32_t i = 0; i < n; i++) {
+      if (fg_per_cu(lds_of(in[i].cap)) != pc) continue;
+      out[at++] = in[i];
+      l.count++;
+      if (in[i].cap > l.cap) l.cap = in[i].cap;
+    }
+    if (l.count) launches[n_launch++] = l;
+  }
+  return n_launch;
+}
+// The ladders of a call.  `round` = the first attempts (cap = the query's plan.cap).  run(slots, n, launches, n_launches, over)
+// runs one round and sets over[i] != 0 for every slot whose list overflowed; a non-zero return ends the call with that value.
+// Queries whose ladder is over land in *leftover with the capacity of their last attempt.
+template <class LdsOf, class Run>
+static inline int filters_walk_ladders(std::vector<FiltersSlot> round, uint32_t cap_max, LdsOf&& lds_of, Run&& run,
+                                       std::vector<FiltersSlot>* leftover) {
+  std::vector<FiltersSlot> grouped, next;
+  std::vector<unsigned char> over;
+  while (!round.empty()) {
+    const uint32_t n = (uint32_t)round.size();
+    FiltersLaunch launches[4];
+    grouped.resize(n);
+    const uint32_t nl = filters_plan_round(round.data(), n, grouped.data(), launches, lds_of);
+    over.assign(n, 0);
+    const int rc = run((const FiltersSlot*)grouped.data(), n, (const FiltersLaunch*)launches, nl, over.data());
+    if (rc != 0) return rc;
+    next.clear();
+    for (uint32_t i = 0; i < n; i++) {
+      if (!over[i]) continue;
+      FiltersSlot s = grouped[i];
+      const uint32_t nc = fg_ladder_next(s.cap, cap_max);
+      if (nc) {
+        s.cap = nc;
+        next.push_back(s);
+      } else {
+        leftover->push_back(s);
+      }
+    }
+    round.swap(next);
+  }
+  return 0;
 }
 
 }  // namespace vdb

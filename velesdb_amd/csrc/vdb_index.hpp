@@ -247,7 +247,7 @@ struct vdb_hip_index {
   // scratch
   vdb::DevBuf s_queries, s_part_keys, s_part_cnt, s_qbits, s_misc;
   vdb::DevBuf s_flt_mask;  // [capacity + slack] u8: the row mask of a filtered call on the mask-substitution route (n_rows bytes written per call)
-  vdb::DevBuf s_fgraph;    // filtered graph search (hnsw_filtered.hip): [nq][2] u64 per-query counters | [nq] u32 launch slot -> query
+  vdb::DevBuf s_fgraph;    // filtered graph search (hnsw_filtered.hip): [nq][2] u64 per-query counters | [nq] u32 launch slot -> query (per-query filters: | descriptors | slots)
   vdb::DevBuf s_tickets;  // [2] u32, zero between calls: the block tickets of the one-launch packed-bit search (sweep_bits_fused)
   // results of a host-pointer search: ONE allocation [ids nq*k u64 | scores nq*k f32 | n nq u32] (reserve_out), so that one
   // copy brings everything back; the three views point into it
@@ -322,6 +322,11 @@ int32_t filter_check(vdb_hip_index* ix, const RowFilter* f);
 // query 1 = walk, 2 = exact pass, 0 = nothing was launched
 int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k, uint32_t ef,
                                         int32_t route, uint32_t max_list, uint32_t* routes);
+// one filter per query (hnsw_filtered.hip): filters[n_filters] checked handles, fq[nq] in 0..n_filters (n_filters = no
+// filter); same locking, result block and routes
+int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
+                                       const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
+                                       uint32_t* routes);
 // rows per index: the tiled kernels count whole 256-row tiles of [0, n) in 32 bits — (n + 255) / 256 must not wrap
 // (tests/gemm_schedule_model.cpp walks the launch schedule up to this limit)
 constexpr uint64_t kMaxRowsPerIndex = 0xFFFFFE00ull;  // 2^32 - 512

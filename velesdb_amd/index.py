@@ -490,6 +490,34 @@ class HnswIndex:
                                                         max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
         return (ids, sc, cnt), routes
 
+    def search_batch_with_filters(self, queries, k: int, filters, ef: int = 0, route: int = ROUTE_AUTO, max_list: int = 0):
+        """search_batch_filtered_graph with one optional filter PER QUERY in one call (vdb_hip_index_search_graph_filters; the
+        collection layer's search_batch_with_filters).  filters: a sequence of Optional[Filter], one per query; None = no filter
+        (every row present now).  Query i gets bit for bit what search_batch_filtered_graph returns for it alone with its filter,
+        whatever its companions are.  Returns ((ids, scores, counts), routes)."""
+        qs = _f32(queries)
+        if qs.ndim == 1:
+            qs = qs.reshape(1, -1)
+        self._validate(qs)
+        filters = list(filters)
+        nq, kk = qs.shape[0], max(k, 1)
+        if len(filters) != nq:
+            raise ValueError(f"Queries count ({nq}) does not match filters count ({len(filters)})")
+        table, slot_of = [], {}  # distinct filters by object identity; index len(table) = no filter
+        for f in filters:
+            if f is not None and id(f) not in slot_of:
+                slot_of[id(f)] = len(table)
+                table.append(f)
+        fq = np.array([len(table) if f is None else slot_of[id(f)] for f in filters], dtype=np.uint32)
+        handles = (C.c_void_p * max(len(table), 1))(*[f._h for f in table])
+        ids = np.empty((nq, kk), dtype=np.uint64)
+        sc = np.empty((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        routes = np.zeros(nq, dtype=np.uint32)
+        check(lib().vdb_hip_index_search_graph_filters(self._h, handles if table else None, len(table), _ptr(fq), _ptr(qs), nq, k, ef,
+                                                       MODE_HNSW, route, max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
+        return (ids, sc, cnt), routes
+
     def search_brute_force_filtered(self, query, k: int, flt: Filter) -> List[Tuple[int, float]]:
         """search_brute_force among the filter's rows only (one query)."""
         ids, sc, cnt = self.search_batch_brute_force_filtered(_f32(query).reshape(1, -1), k, flt)
