@@ -15,6 +15,10 @@ from oracle import pyoracle as po
 
 VECTORS_HEADER = 16  # u32 version = 1 | u64 count | u32 dim, little-endian; then count * dim raw f32 (backend_adapter.rs:199-215)
 SHAPES = [(3000, 96, 8, 60), (1500, 768, 16, 100), (1200, 37, 6, 40)]  # (n, dim, M, efc): CPL 0 (dim % 256), CPL 3, dim % 4 != 0
+# the register-chunk instances CPL 1 / 2 / 4, then dims whose query lives in LDS scratch (1 536, the default max_dimensions 4 096,
+# and dim % 4 != 0 above the register layout): tests/test_gpu_large_dim_features.py, tests/test_gpu_int8.py
+LARGE_SHAPES = [(1500, 256, 8, 60), (1500, 512, 8, 60), (1500, 1024, 8, 60),
+                (1200, 1536, 8, 60), (1000, 4096, 8, 40), (1000, 4099, 6, 40)]
 KEF = [(10, 64), (1, 16), (25, 50), (10, 300)]                        # ef > 192: the LDS list
 NQ = 20
 PO_METRIC = {hr.COSINE: po.COSINE, hr.EUCLIDEAN: po.EUCLIDEAN, hr.DOT: po.DOT}

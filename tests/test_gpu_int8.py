@@ -19,7 +19,9 @@ def bits(a):
 
 
 @pytest.mark.parametrize("metric", [DM.Cosine, DM.Euclidean, DM.DotProduct])
-@pytest.mark.parametrize("n,dim,M,efc", [(3000, 96, 8, 60), (1500, 768, 16, 100), (1200, 37, 6, 40)])
+# (the last four: the register-chunk instances CPL 1 / 2 / 4 — dim 1 024 is the walk's limit — and the generic layout just under it)
+@pytest.mark.parametrize("n,dim,M,efc", [(3000, 96, 8, 60), (1500, 768, 16, 100), (1200, 37, 6, 40),
+                                         (1500, 256, 8, 60), (1500, 512, 8, 60), (1500, 1024, 8, 60), (1200, 1000, 8, 60)])
 def test_int8_traversal_bit_exact(tmp_path, metric, n, dim, M, efc):
     rng = np.random.default_rng(n + dim)
     rows = rng.standard_normal((n, dim)).astype(np.float32)

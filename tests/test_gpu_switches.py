@@ -48,6 +48,10 @@ ONE_LAUNCH = ["tests/test_gpu_round5_parity.py", "-k", "one_launch and (300000 o
 # (everything of test_gpu_split.py that leaves queries unproven as well: near-duplicate clusters, NaN / inf rows, level parking)
 SPLIT_ALL = ["tests/test_gpu_split.py", "-k", "not 1000000 and not 300000 and not 150001"]
 WIDE = ["tests/test_gpu_wide_k.py", "-k", "vs_oracle or adversarial"]
+# (the f32 walk at CPL 1 / 2 / 4 and with the query in LDS scratch: the latency-mode kernel's instances no test of GRAPH reaches.  No
+# kernel bit tells the latency-mode kernel from the throughput one: three of the test's four (k, ef) pairs take it under the switch,
+# ef 300 — the LDS list — stays on the throughput kernel by design)
+GRAPH_LARGE = ["tests/test_gpu_large_dim_features.py", "-k", "f32_walk_at_the_large_shapes"]
 
 CASES = [
     ({"VELESDB_BF16_PP": "0"}, SPLIT),
@@ -57,6 +61,8 @@ CASES = [
     ({"VELESDB_HNSW_LATENCY_MODE": "0"}, GRAPH),
     ({"VELESDB_HNSW_LATENCY_MODE": "2"}, GRAPH),
     ({"VELESDB_HNSW_LATENCY_MODE": "3"}, GRAPH),
+    ({"VELESDB_HNSW_LATENCY_MODE": "2"}, GRAPH_LARGE),
+    ({"VELESDB_HNSW_LATENCY_MODE": "3"}, GRAPH_LARGE),
     ({"VELESDB_HNSW_VIS_LDS": "1"}, GRAPH),
     ({"VELESDB_HNSW_PREFETCH_IDS": "1"}, GRAPH),
     ({"VELESDB_INT8_VIS_LDS": "1"}, INT8),

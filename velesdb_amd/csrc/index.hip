@@ -244,6 +244,12 @@ uint32_t last_kernels_of_this_thread(vdb_hip_index* ix) {
   if (tl_kernels_valid && tl_ctx_owner == ix && tl_ctx_gen == ix->generation) return tl_kernels;
   return last_context(ix)->last_kernels;
 }
+// ... and the same for the counters of a search that had them on the host when its lease ended (the filtered graph calls; the plain
+// walks leave them on the device until a getter asks, and stay with the context): tests/test_gpu_filtered_graph.py
+// ::test_four_threads_with_four_filters_get_what_they_get_alone read a neighbour's n_dist / n_expand, once
+static thread_local bool tl_stats_valid = false;
+static thread_local uint64_t tl_n_dist = 0, tl_n_expand = 0, tl_pf_hits = 0;
+static bool stats_of_this_thread(const vdb_hip_index* ix) { return tl_stats_valid && tl_ctx_owner == ix && tl_ctx_gen == ix->generation; }
 void note_last_kernels(uint32_t mask) {  // (behind note_last_context: a search the combining front had another thread run)
   tl_kernels = mask;
   tl_kernels_valid = true;
@@ -253,6 +259,7 @@ void note_last_context(vdb_hip_index* handle, vdb_hip_index* ctx) {
   tl_ctx_owner = handle;
   tl_ctx_gen = handle->generation;
   tl_kernels_valid = false;
+  tl_stats_valid = false;
 }
 
 // the primary + up to seven clones.  A context owns scratch and a stream; its graph-walk scratch is sized by the calls it has
@@ -308,6 +315,12 @@ CtxLease::~CtxLease() {
   if (tl_ctx == ctx) {
     tl_kernels = ctx->last_kernels;
     tl_kernels_valid = true;
+    tl_stats_valid = !ctx->stats_pending;
+    if (tl_stats_valid) {
+      tl_n_dist = ctx->last_n_dist;
+      tl_n_expand = ctx->last_n_expand;
+      tl_pf_hits = ctx->last_pf_hits;
+    }
   }
   ctx->ctx_mu.unlock();
 }
@@ -2159,6 +2172,11 @@ int32_t vdb_hip_index_last_search_stats(vdb_hip_index* ix, uint64_t* n_dist, uin
     return VDB_OK;
   }
   std::shared_lock<vdb::IndexMutex> g(ix->mu);
+  if (stats_of_this_thread(ix)) {  // taken when this thread's lease ended: the context may serve another thread by now
+    if (n_dist) *n_dist = tl_n_dist;
+    if (n_expand) *n_expand = tl_n_expand;
+    return VDB_OK;
+  }
     ix = last_context(ix);  // the search context that served this thread's last search (the handle itself unless searches overlapped)
     std::lock_guard<std::mutex> cg(ix->ctx_mu);
   if (ix->stats_pending) {
@@ -2186,6 +2204,10 @@ int32_t vdb_hip_index_last_prefetch_hits(vdb_hip_index* ix, uint64_t* hits) {
     return VDB_OK;
   }
   std::shared_lock<vdb::IndexMutex> g(ix->mu);
+  if (stats_of_this_thread(ix)) {
+    *hits = tl_pf_hits;
+    return VDB_OK;
+  }
   ix = last_context(ix);
   std::lock_guard<std::mutex> cg(ix->ctx_mu);
   if (ix->stats_pending) {
