@@ -363,6 +363,55 @@ int32_t vdb_hip_index_search_graph_filters(vdb_hip_index* idx, void** filters, u
                                            uint32_t k, uint32_t ef, int32_t mode, int32_t route, uint32_t max_list,
                                            uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route);
 
+/* ---- multi-query search with result fusion: Collection::multi_query_search / multi_query_search_ids (collection/search/batch.rs:
+ * 206-403) and FusionStrategy::fuse (fusion/strategy.rs:138-300) on the device (fusion.hip, vdb_fusion.hpp) ----
+ * The reference searches up to MAX_VECTORS = 10 reformulations of one user query at an over-fetched k (top_k 0-10: x 20, 11-50: x 10,
+ * 51-100: x 5, larger: x 2; batch.rs:270-275), fuses the lists and keeps top_k.
+ * The rule, for one group of V lists (list q = n_q records (id, score), best first):
+ *   per (id, q): best_q = the maximum over the id's occurrences in list q, rank_q = the 0-based position of the first one;
+ *   AVERAGE   the sum of best_q over the lists that hold the id (ascending q, a left fold from the first term) / (float)count;
+ *   MAXIMUM   the maximum over all occurrences;
+ *   RRF       0.0f + the sum over those lists of 1.0f / ((float)rrf_k + (float)(rank_q + 1)), ascending q;
+ *   WEIGHTED  (avg_w * avg + max_w * mx) + hit_w * ((float)count / (float)V), every operation rounded on its own; V counts empty lists.
+ * Result: descending by the IEEE total order of the fused score, EQUAL SCORES BY ID ASCENDING (the reference leaves ties to HashMap
+ * iteration: any tie order is one of its outputs, this one is fixed).  WEIGHTED weights: any weight < 0, a sum off 1.0 by more than
+ * 0.001 (in f32) and NaN weights are VDB_ERR_INVALID_ARG (the reference's weighted() lets NaN through).  NaN scores and an id whose
+ * scores mix +0.0 and -0.0 are outside the contract (resolved by total order). */
+enum vdb_fusion_strategy { VDB_FUSION_AVERAGE = 0, VDB_FUSION_MAXIMUM = 1, VDB_FUSION_RRF = 2, VDB_FUSION_WEIGHTED = 3 };
+/* FusionStrategy::fuse for n_groups independent groups in ONE launch (one block per group), host pointers.  Lists are
+ * [n_lists][list_stride]; list j holds list_n[j] <= list_stride records; consecutive lists form the groups: group g = the next
+ * group_sizes[g] lists (0 and more than 10 are legal here: fuse has no limit); the sizes must sum to n_lists.  weights = [3] avg, max,
+ * hit (VDB_FUSION_WEIGHTED only, else ignored, nullable); rrf_k: VDB_FUSION_RRF only (the reference's default is 60).
+ * Outputs [n_groups][max(top_k, 1)] / out_n [n_groups]: the first min(top_k, distinct ids) fused records, padded as the search calls
+ * pad (id ~0, score NaN); top_k = 0: out_n = 0, nothing else written.  A group of more than 8192 records (what one block's LDS
+ * takes, 128 of 160 KB) answers VDB_ERR_UNSUPPORTED before anything runs; a size sum != n_lists, list_n[j] > list_stride, a null
+ * pointer, a strategy outside 0..3, invalid weights: VDB_ERR_INVALID_ARG.  The outputs are untouched on error. */
+int32_t vdb_hip_fuse_results(int32_t device, int32_t strategy, uint32_t rrf_k, const float* weights, const uint64_t* ids,
+                             const float* scores, const uint32_t* list_n, uint32_t n_lists, uint32_t list_stride,
+                             const uint32_t* group_sizes, uint32_t n_groups, uint32_t top_k, uint64_t* out_ids, float* out_scores,
+                             uint32_t* out_n);
+/* multi_query_search_ids for n_groups user queries in one call: queries_rowmajor holds the vectors of group 0, then of group 1, ...;
+ * group_sizes[g] in 1..10 (VDB_ERR_INVALID_ARG otherwise, the message names the group); n_groups = 0 is VDB_OK.
+ * THE CONTRACT: group g gets, bit for bit, the rule above applied to
+ *   filter == NULL: the lists vdb_hip_index_search_batch(mode = VDB_SEARCH_HNSW, ef = 0, k = overfetch(top_k)) returns for its vectors
+ *     (search_batch_parallel with SearchQuality::Balanced is what the reference calls);
+ *   filter != NULL: the lists vdb_hip_index_search_graph_filtered(filter, k = overfetch(top_k), ef = 0, route 0, max_list 0) returns —
+ *     the in-walk allow-list of DESIGN 4.1h: rows the filter rejects never take a place in a list.  The reference POST-filters the
+ *     over-fetched lists instead (batch.rs:283-302), so a selective filter leaves it fewer candidates than it leaves this call.
+ * Scores are the FUSED scores, sorted descending whatever the metric, as the reference sorts them: AVERAGE / MAXIMUM / WEIGHTED over
+ * a distance metric (Euclidean, Hamming: smaller = better) therefore rank the worst first — the reference's behaviour, inherited;
+ * RRF uses ranks only and is the metric-agnostic default (FusionStrategy::default()).
+ * A group's answer never depends on its companions or on its position in the call.  Outputs as vdb_hip_fuse_results.  A group of
+ * V vectors with V * overfetch(top_k) > 8192 answers VDB_ERR_UNSUPPORTED before anything runs (top_k <= 409 is always served);
+ * every other limit or error of the per-query call it stands on is passed through (no graph: VDB_ERR_STATE; a filter of another handle:
+ * VDB_ERR_INVALID_ARG; a stale filter: VDB_ERR_STATE).  Multi-device handles and process-group members: VDB_ERR_UNSUPPORTED.  The
+ * outputs are untouched on error.  Host pointers; launches of its own on one leased search context (no combining front): the walks,
+ * then fuse_lists_kernel over the context's result lists on the same stream — only the fused block comes back.
+ * vdb_hip_index_last_kernels: VDB_KERNEL_FUSE next to the walk's bits. */
+int32_t vdb_hip_index_multi_query_search(vdb_hip_index* idx, const void* filter, const float* queries_rowmajor,
+                                         const uint32_t* group_sizes, uint32_t n_groups, uint32_t top_k, int32_t strategy,
+                                         uint32_t rrf_k, const float* weights, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+
 /* ---- DistanceEngine::batch_distance / GpuAccelerator::batch_{cosine_similarity,
  * euclidean_distance,dot_product} (native/distance.rs:21-24; gpu_backend.rs:157,355,397) ----
  * n rows of dim floats against one query; out has n floats, same order as the rows. */
@@ -539,6 +588,9 @@ enum vdb_kernel_bit {
   VDB_KERNEL_HNSW_FILTERED = 131072, /* hnsw_search_filtered_kernel (vdb_hip_index_search_graph_filtered, the walk)                    */
   VDB_KERNEL_FILTER_RANK = 262144  /* filter_rank_kernel (vdb_hip_index_search_graph_filtered, the exact pass)                       */
 };
+/* one more bit of the same mask: fuse_lists_kernel ran (vdb_hip_index_multi_query_search sets it next to the walk's bits).  A macro
+ * beside the enum, not an enumerator: tests/test_filters_graph_cpu.py pins VDB_KERNEL_FILTER_RANK as the enum's last member. */
+#define VDB_KERNEL_FUSE 524288
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same
  * context a moment later does not change it. */

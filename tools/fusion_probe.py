@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""GPU probe of the multi-query search with result fusion (vdb_hip_index_multi_query_search), single MI355X,
+host-pointer calls.  For top_k 10 / 50 / 100 and 1 / 8 / 128 groups of 4 and of 10 vectors it times, over the same index and queries
+in the same run:
+
+  fused   one call of multi_query_search_batch: the walks, fuse_lists_kernel, top_k records per group back;
+  host    what a caller of this library does without it: search_batch (VDB_SEARCH_HNSW, ef = 0) at the over-fetched k, every list
+          back on the host, then the fusion there — the compiled host model of the product's rule (tests/fusion_model.cpp over
+          csrc/vdb_fusion.hpp, built with g++ -O2), one group after the other on one thread;
+  and the share of `host` that is the host fusion alone.
+
+Both sides must return the same records (checked bit for bit before anything is timed).  Every figure is the median of --repeats
+blocks, each block the mean over enough calls to last ~--block-ms; the spread is (max - min) / median over the blocks.
+There is no pass bar.  One run is recorded: DESIGN.md 4.1j, profiles/fusion_probe_100k_rrf.log.  Not part of the product or the
+test-suite."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import velesdb_amd as va  # noqa: E402
+
+p = argparse.ArgumentParser()
+p.add_argument("--rows", type=int, default=100_000)
+p.add_argument("--dim", type=int, default=768)
+p.add_argument("--top-k", default="10,50,100")
+p.add_argument("--groups", default="1,8,128")
+p.add_argument("--vectors", default="4,10")
+p.add_argument("--strategy", default="rrf", choices=["average", "maximum", "rrf", "weighted"])
+p.add_argument("--repeats", type=int, default=5)
+p.add_argument("--block-ms", type=float, default=40.0)
+p.add_argument("--out", default="")
+a = p.parse_args()
+
+STRATEGY = {"average": va.FusionStrategy.Average(), "maximum": va.FusionStrategy.Maximum(), "rrf": va.FusionStrategy.rrf_default(),
+            "weighted": va.FusionStrategy.Weighted(0.6, 0.3, 0.1)}[a.strategy]
+
+
+def host_model():
+    so = os.path.join(tempfile.gettempdir(), "vdb_fusion_probe_%d" % os.getuid(), "libfusion_model_o2.so")
+    os.makedirs(os.path.dirname(so), exist_ok=True)
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I", os.path.join(ROOT, "velesdb_amd", "csrc"),
+                           "-o", so, os.path.join(ROOT, "tests", "fusion_model.cpp")])
+    L = C.CDLL(so)
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.fusion_model_fuse_groups.restype, L.fusion_model_fuse_groups.argtypes = C.c_int, [C.c_int, u32, vp, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
+    return L
+
+
+def overfetch(top_k):
+    return top_k * (20 if top_k <= 10 else 10 if top_k <= 50 else 5 if top_k <= 100 else 2)
+
+
+def timed(fn):
+    fn()
+    t0 = time.perf_counter()
+    fn()
+    once = max(time.perf_counter() - t0, 1e-6)
+    calls = max(1, int(a.block_ms / 1e3 / once))
+    blocks = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()
+        blocks.append((time.perf_counter() - t0) / calls * 1e3)
+    med = statistics.median(blocks)
+    return med, (max(blocks) - min(blocks)) / med
+
+
+def main():
+    rng = np.random.default_rng(42)
+    rows = rng.standard_normal((a.rows, a.dim)).astype(np.float32)
+    ix = va.HnswIndex(a.dim, va.DistanceMetric.Cosine, va.HnswParams(32, 400, a.rows))
+    ix.upload(np.arange(a.rows, dtype=np.uint64), rows)
+    t0 = time.perf_counter()
+    ix.build_graph()
+    print(f"# {va.device_name(0)}: {a.rows} x {a.dim} cosine, graph built in {time.perf_counter() - t0:.1f} s, strategy {STRATEGY}")
+    L = host_model()
+    w = np.array(STRATEGY.weights, dtype=np.float32)
+    table = []
+    print("top_k  groups  vectors  fused ms (spread)   host ms (spread)   of which host fusion ms   fused / host")
+    for top_k in [int(x) for x in a.top_k.split(",")]:
+        kf = overfetch(top_k)
+        for ng in [int(x) for x in a.groups.split(",")]:
+            for V in [int(x) for x in a.vectors.split(",")]:
+                qs = rng.standard_normal((ng * V, a.dim)).astype(np.float32)
+                groups = np.split(qs, ng)
+                sizes = np.full(ng, V, dtype=np.uint32)
+                oi = np.empty((ng, top_k), dtype=np.uint64)
+                ob = np.empty((ng, top_k), dtype=np.uint32)
+                on = np.empty(ng, dtype=np.uint32)
+                state = {}
+
+                def search():
+                    state["lists"] = ix._search_raw(qs, kf, 0, va.MODE_HNSW)
+
+                def fuse_host():
+                    ids, sc, cnt = state["lists"]
+                    rc = L.fusion_model_fuse_groups(STRATEGY.code, STRATEGY.rrf_k, w.ctypes.data, ids.ctypes.data, sc.ctypes.data, cnt.ctypes.data,
+                                                    ids.shape[1], sizes.ctypes.data, ng, top_k, oi.ctypes.data, ob.ctypes.data, on.ctypes.data)
+                    assert rc == 0
+
+                def host():
+                    search()
+                    fuse_host()
+
+                def fused():
+                    state["fused"] = ix.multi_query_search_batch(groups, top_k, STRATEGY)
+
+                host()
+                fused()
+                fi, fs, fn_ = state["fused"]
+                assert np.array_equal(fn_, on) and np.array_equal(fi, oi) and np.array_equal(fs.view(np.uint32), ob), "the two sides differ"
+                t_f, s_f = timed(fused)
+                t_h, s_h = timed(host)
+                t_hf, _ = timed(fuse_host)
+                table.append({"top_k": top_k, "groups": ng, "vectors": V, "fused_ms": t_f, "fused_spread": s_f, "host_ms": t_h, "host_spread": s_h,
+                              "host_fusion_ms": t_hf})
+                print(f"{top_k:5d}  {ng:6d}  {V:7d}  {t_f:9.3f} ({s_f:5.2f})  {t_h:9.3f} ({s_h:5.2f})  {t_hf:12.3f}             {t_f / t_h:6.2f}")
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump({"device": va.device_name(0), "rows": a.rows, "dim": a.dim, "strategy": str(STRATEGY), "table": table}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

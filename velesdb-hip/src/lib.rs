@@ -1136,11 +1136,219 @@ impl HipHnswIndex {
         self.search_batch_graph_filtered(&[query], k, quality, filter, 0, 0).0.pop().unwrap_or_default()
     }
 
+    /// `Collection::multi_query_search_ids` (collection/search/batch.rs:352-402) with the fusion on the device
+    /// (`vdb_hip_index_multi_query_search`): up to ten reformulations of one user query are searched at the over-fetched k
+    /// (`SearchQuality::Balanced`) and their lists fused by `fusion`; the first `top_k` fused `(id, score)` come back, equal scores by
+    /// id ascending.  With a filter the lists are those of [`Self::search_batch_graph_filtered`] (the allow-list inside the walk), not
+    /// the reference's post-filter.
+    ///
+    /// # Errors
+    /// The reference's `Error::Config` / `Error::DimensionMismatch` messages as `Err(String)`: no vector, more than ten, a vector
+    /// of another dimension.
+    ///
+    /// # Panics
+    /// On a status the library reports for the call itself (no graph, a stale filter, `top_k` past what one block fuses).
+    pub fn multi_query_search_ids(
+        &self,
+        vectors: &[&[f32]],
+        top_k: usize,
+        fusion: &FusionStrategy,
+        filter: Option<&HipFilter>,
+    ) -> Result<Vec<(u64, f32)>, String> {
+        const MAX_VECTORS: usize = 10;
+        if vectors.is_empty() {
+            return Err("multi_query_search requires at least one vector".into());
+        }
+        if vectors.len() > MAX_VECTORS {
+            return Err(format!("multi_query_search supports at most {MAX_VECTORS} vectors, got {}", vectors.len()));
+        }
+        for v in vectors {
+            if v.len() != self.dimension {
+                return Err(format!("Vector dimension mismatch: expected {}, got {}", self.dimension, v.len()));
+            }
+        }
+        let mut flat = Vec::with_capacity(vectors.len() * self.dimension);
+        for v in vectors {
+            flat.extend_from_slice(v);
+        }
+        let kk = top_k.max(1);
+        let mut ids = vec![0u64; kk];
+        let mut scores = vec![0f32; kk];
+        let mut n = 0u32;
+        let group = [vectors.len() as u32];
+        let (code, rrf_k, w) = fusion.abi();
+        // SAFETY: one group of vectors.len() rows of `dimension` floats; outputs hold max(top_k, 1) records and one count; the
+        // weights array outlives the call; the filter handle is live (borrowed).
+        check(unsafe {
+            sys::vdb_hip_index_multi_query_search(
+                self.h,
+                filter.map_or(ptr::null(), |f| f.h.cast_const()),
+                flat.as_ptr(),
+                group.as_ptr(),
+                1,
+                top_k as u32,
+                code,
+                rrf_k,
+                w.as_ptr(),
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                &mut n,
+            )
+        });
+        Ok((0..n as usize).map(|j| (ids[j], scores[j])).collect())
+    }
+
     /// Boxed as the trait object `Collection` holds: what a downstream crate's `hip` feature registers with the index factory
     /// hook of velesdb-core (see Cargo.toml: the dependency points from this crate to the core, never back).
     #[must_use]
     pub fn boxed(dimension: usize, metric: DistanceMetric, params: HnswParams) -> Option<Box<dyn VectorIndex>> {
         Self::with_params(dimension, metric, params).map(|ix| Box::new(ix) as Box<dyn VectorIndex>)
+    }
+}
+
+/// `FusionError` (fusion/strategy.rs:10-34).
+#[derive(Debug, Clone, PartialEq)]
+pub enum FusionError {
+    /// Weights do not sum to 1.0 (within 0.001) — or, here, a weight is NaN.
+    InvalidWeightSum {
+        /// The actual sum of weights.
+        sum: f32,
+    },
+    /// Negative weight provided.
+    NegativeWeight {
+        /// The negative weight value.
+        weight: f32,
+    },
+}
+
+impl std::fmt::Display for FusionError {
+    fn fmt(&self, f: &mut std::fmt::Formatter<'_>) -> std::fmt::Result {
+        match self {
+            Self::InvalidWeightSum { sum } => write!(f, "Weights must sum to 1.0, got {sum:.4}"),
+            Self::NegativeWeight { weight } => write!(f, "Weights must be non-negative, got {weight:.4}"),
+        }
+    }
+}
+
+impl std::error::Error for FusionError {}
+
+/// `FusionStrategy` (fusion/strategy.rs:46-79) with `fuse` on the device (`vdb_hip_fuse_results`).  Equal fused scores come back
+/// by id ascending (the reference leaves them to `HashMap` iteration); NaN weights are refused.
+#[derive(Debug, Clone, PartialEq)]
+pub enum FusionStrategy {
+    /// Mean of the per-query best scores of a document.
+    Average,
+    /// Best score of a document over all queries.
+    Maximum,
+    /// Reciprocal Rank Fusion: the sum of `1 / (k + rank)` over the queries that hold the document.
+    RRF {
+        /// Ranking constant (default: 60).
+        k: u32,
+    },
+    /// `avg_weight * avg + max_weight * max + hit_weight * hit_ratio`.
+    Weighted {
+        /// Weight of the average.
+        avg_weight: f32,
+        /// Weight of the maximum.
+        max_weight: f32,
+        /// Weight of the hit ratio.
+        hit_weight: f32,
+    },
+}
+
+impl Default for FusionStrategy {
+    fn default() -> Self {
+        Self::RRF { k: 60 }
+    }
+}
+
+impl FusionStrategy {
+    /// RRF with the standard k = 60.
+    #[must_use]
+    pub fn rrf_default() -> Self {
+        Self::RRF { k: 60 }
+    }
+
+    /// `FusionStrategy::weighted` (strategy.rs:95-122).
+    ///
+    /// # Errors
+    /// A negative weight; a sum off 1.0 by more than 0.001; a NaN weight (reported as the sum).
+    pub fn weighted(avg_weight: f32, max_weight: f32, hit_weight: f32) -> Result<Self, FusionError> {
+        for weight in [avg_weight, max_weight, hit_weight] {
+            if weight < 0.0 {
+                return Err(FusionError::NegativeWeight { weight });
+            }
+        }
+        let sum = avg_weight + max_weight + hit_weight;
+        if sum.is_nan() || (sum - 1.0).abs() > 0.001 {
+            return Err(FusionError::InvalidWeightSum { sum });
+        }
+        Ok(Self::Weighted { avg_weight, max_weight, hit_weight })
+    }
+
+    /// (strategy code, rrf_k, weights) as the C ABI takes them
+    fn abi(&self) -> (i32, u32, [f32; 3]) {
+        match *self {
+            Self::Average => (sys::VDB_FUSION_AVERAGE, 0, [0.0; 3]),
+            Self::Maximum => (sys::VDB_FUSION_MAXIMUM, 0, [0.0; 3]),
+            Self::RRF { k } => (sys::VDB_FUSION_RRF, k, [0.0; 3]),
+            Self::Weighted { avg_weight, max_weight, hit_weight } => (sys::VDB_FUSION_WEIGHTED, 0, [avg_weight, max_weight, hit_weight]),
+        }
+    }
+
+    /// `FusionStrategy::fuse` (strategy.rs:138-167) on device 0: one list of `(id, score)` per query, best first.
+    ///
+    /// # Errors
+    /// Weights a hand-built `Weighted` carries that `weighted()` would have refused.
+    ///
+    /// # Panics
+    /// Without a device, or when the lists hold more than 8192 records together.
+    pub fn fuse(&self, results: Vec<Vec<(u64, f32)>>) -> Result<Vec<(u64, f32)>, FusionError> {
+        if let Self::Weighted { avg_weight, max_weight, hit_weight } = *self {
+            Self::weighted(avg_weight, max_weight, hit_weight)?;
+        }
+        let stride = results.iter().map(Vec::len).max().unwrap_or(0);
+        if stride == 0 {
+            return Ok(Vec::new());
+        }
+        let n_lists = results.len();
+        let mut ids = vec![0u64; n_lists * stride];
+        let mut scores = vec![0f32; n_lists * stride];
+        let list_n: Vec<u32> = results.iter().map(|r| r.len() as u32).collect();
+        for (q, r) in results.iter().enumerate() {
+            for (p, (id, score)) in r.iter().enumerate() {
+                ids[q * stride + p] = *id;
+                scores[q * stride + p] = *score;
+            }
+        }
+        let total: usize = results.iter().map(Vec::len).sum();
+        let mut out_ids = vec![0u64; total];
+        let mut out_scores = vec![0f32; total];
+        let mut n = 0u32;
+        let group = [n_lists as u32];
+        let (code, rrf_k, w) = self.abi();
+        // SAFETY: ids / scores are n_lists * stride, list_n is n_lists, one group of n_lists lists; the outputs hold `total`
+        // records (top_k = total: every distinct id fits) and one count.
+        check(unsafe {
+            sys::vdb_hip_fuse_results(
+                0,
+                code,
+                rrf_k,
+                w.as_ptr(),
+                ids.as_ptr(),
+                scores.as_ptr(),
+                list_n.as_ptr(),
+                n_lists as u32,
+                stride as u32,
+                group.as_ptr(),
+                1,
+                total as u32,
+                out_ids.as_mut_ptr(),
+                out_scores.as_mut_ptr(),
+                &mut n,
+            )
+        });
+        Ok((0..n as usize).map(|j| (out_ids[j], out_scores[j])).collect())
     }
 }
 

@@ -16,7 +16,8 @@ from .index import KERNEL_F16, KERNEL_SWEEP_HALF_L2, MODE_BRUTE_F16, VectorPreci
 from .index import KERNEL_HNSW_HALF, MODE_HNSW_BF16, MODE_HNSW_F16  # noqa: F401
 from .index import KERNEL_FILTER_RANK, KERNEL_HNSW_FILTERED, ROUTE_AUTO, ROUTE_EXACT, ROUTE_WALK  # noqa: F401
 from .index import (FILTER_ROUTE_AUTO, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK, KERNEL_SWEEP_LISTED, OPT_FILTER_ROUTE, Filter)  # noqa: F401
+from .index import FUSE_MAX_RECORDS, FusionError, FusionStrategy, KERNEL_FUSE, MAX_FUSED_VECTORS, fuse_arrays, fuse_groups  # noqa: F401
 from .params import DistanceMetric, DualPrecisionConfig, HnswParams, SearchQuality, StorageMode  # noqa: F401
 
-__all__ = ["HnswIndex", "Filter", "NativeHnswIndex", "HipDistance", "GpuAccelerator", "DistanceMetric", "HnswParams", "SearchQuality", "StorageMode", "DualPrecisionConfig", "VectorPrecision",
+__all__ = ["HnswIndex", "Filter", "FusionStrategy", "FusionError", "NativeHnswIndex", "HipDistance", "GpuAccelerator", "DistanceMetric", "HnswParams", "SearchQuality", "StorageMode", "DualPrecisionConfig", "VectorPrecision",
            "device_count", "device_name", "comm_unique_id", "SHARD_RANGE", "SHARD_REPLICA", "set_kernel_timing", "set_max_query_tile", "set_sweep_engine", "set_split_selector", "lib", "VelesHipError"]

@@ -32,6 +32,9 @@ VDB_KERNEL_SWEEP_LISTED = 65536
 # ... and of the filtered graph search (vdb_hip_index_search_graph_filtered): the walk and the exact pass
 VDB_KERNEL_HNSW_FILTERED = 131072
 VDB_KERNEL_FILTER_RANK = 262144
+# ... and of the multi-query search with result fusion (vdb_hip_index_multi_query_search / vdb_hip_fuse_results)
+VDB_KERNEL_FUSE = 524288
+VDB_FUSION_AVERAGE, VDB_FUSION_MAXIMUM, VDB_FUSION_RRF, VDB_FUSION_WEIGHTED = 0, 1, 2, 3
 
 # every function include/velesdb_hip.h declares: name -> (restype, argtypes)
 _vp, _i32, _u32, _u64, _f32 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float
@@ -83,6 +86,8 @@ SIGNATURES = {
     "vdb_hip_index_search_batch_filtered": (_i32, [_vp, _vp, _vp, _u32, _u32, _i32, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filtered": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filters": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
+    "vdb_hip_fuse_results": (_i32, [_i32, _i32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "vdb_hip_index_multi_query_search": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_batch_distance": (_i32, [_i32, _i32, _i32, _vp, _vp, _u64, _u32, _vp]),
     "vdb_hip_batch_distance_dev": (_i32, [_i32, _i32, _vp, _vp, _u64, _u32, _vp, _vp]),
     "vdb_hip_index_load_reference_files": (_i32, [_vp, C.c_char_p, C.c_char_p]),

@@ -1144,7 +1144,7 @@ std::vector<DevBuf*> index_buffers(vdb_hip_index* ix) {
       &ix->sq8_img, &ix->sq8_nrm, &ix->sq8_seed, &ix->sq8_rho,              // SQ8 selection images
       &ix->bits_img, &ix->bits_cnt,                                         // four-bit image of the bit rows (Hamming / Jaccard GEMM)
       &ix->s_queries, &ix->s_part_keys, &ix->s_part_cnt, &ix->s_out, &ix->s_qbits, &ix->s_tickets, &ix->s_flt_mask,
-      &ix->s_misc, &ix->s_fgraph, &ix->s_fb_keys, &ix->s_seed, &ix->s_visited, &ix->s_vlog, &ix->s_stats, &ix->s_build_stats, &ix->s_levels, &ix->s_req_keys,
+      &ix->s_misc, &ix->s_fgraph, &ix->s_fuse, &ix->s_fb_keys, &ix->s_seed, &ix->s_visited, &ix->s_vlog, &ix->s_stats, &ix->s_build_stats, &ix->s_levels, &ix->s_req_keys,
       &ix->s_req_vals, &ix->s_sort_tmp};
   for (auto& L : ix->layers) {
     v.push_back(&L.nbr);
@@ -1164,6 +1164,7 @@ void destroy_single(vdb_hip_index* ix) {
   for (DevBuf* b : index_buffers(ix)) b->release();
   ix->h_in.release();
   ix->h_out.release();
+  ix->h_fuse.release();
   combiner_free(ix->combiner);
   for (auto* pool : {&ix->ev_pool, &ix->sel_ev})
     for (auto& e : *pool) {

@@ -24,7 +24,9 @@
 #include <cstring>
 
 #include "vdb_combiner.hpp"
+#include "vdb_fusion.hpp"
 #include "vdb_index.hpp"
+#include "vdb_kernels.hpp"
 
 namespace vdb {
 
@@ -114,6 +116,69 @@ static int32_t search_graph_filters_direct(vdb_hip_index* handle, const RowFilte
       [&](vdb_hip_index* ix) {
         deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n);
         if (out_route) std::memcpy(out_route, routes.data(), (size_t)nq * 4);
+      });
+}
+
+// vdb_hip_index_multi_query_search: ONE lease — the walk of every vector of every group at the over-fetched k, the
+// fusion kernel over the context's result lists (ix->s_out_ids / s_out_scores) on the same stream, the fused block back through
+// pinned memory, one synchronisation behind the fusion.  The list lengths are the ones the search brought to the host (a search that
+// had nothing to launch leaves them only there).
+static int32_t multi_query_direct(vdb_hip_index* handle, const RowFilter* f, const float* queries, const uint32_t* group_sizes,
+                                  uint32_t n_groups, uint32_t nq, uint32_t top_k, uint32_t kf, int32_t strategy, uint32_t rrf_k, const float* w,
+                                  uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  const size_t kk = std::max<uint32_t>(top_k, 1);
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t o_gr = (size_t)nq * sizeof(FuseList), o_oi = o_gr + (size_t)n_groups * sizeof(FuseGroup), o_os = o_oi + up16((size_t)n_groups * kk * 8),
+               o_on = o_os + up16((size_t)n_groups * kk * 4), total = o_on + up16((size_t)n_groups * 4);
+  return run_search(
+      handle, nq, kf, 0, VDB_SEARCH_HNSW, 0,
+      [&](vdb_hip_index* ix) -> int32_t {
+        int32_t rc = f ? search_graph_filtered_to_device(ix, f, queries, nq, kf, 0, 0, 0, nullptr)
+                       : search_to_device(ix, queries, nq, kf, 0, VDB_SEARCH_HNSW, 0, nullptr);
+        if (rc != VDB_OK) return rc;
+        hipStream_t st = ix->stream;
+        const uint32_t* h_n = reinterpret_cast<const uint32_t*>(ix->h_out.as<unsigned char>() + ((unsigned char*)ix->s_out_n.p - (unsigned char*)ix->s_out.p));
+        std::vector<FuseList> lists;
+        std::vector<FuseGroup> groups;
+        uint32_t most = 0;
+        rc = fuse_plan(h_n, nq, std::max<uint32_t>(kf, 1), group_sizes, n_groups, &lists, &groups, &most);
+        if (rc != VDB_OK) return rc;
+        if (ix->s_fuse.reserve(total, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "fusion scratch");
+        if (ix->h_fuse.reserve(total) != hipSuccess) return fail(VDB_ERR_OOM, "pinned fusion staging");
+        unsigned char* h = ix->h_fuse.as<unsigned char>();
+        unsigned char* d = ix->s_fuse.as<unsigned char>();
+        std::memcpy(h, lists.data(), o_gr);
+        std::memcpy(h + o_gr, groups.data(), o_oi - o_gr);
+        VDB_HIP(hipMemcpyAsync(d, h, o_oi, hipMemcpyHostToDevice, st));
+        FuseArgs a{};
+        a.ids = ix->s_out_ids.as<uint64_t>();
+        a.scores = ix->s_out_scores.as<float>();
+        a.list_stride = std::max<uint32_t>(kf, 1);
+        a.lists = reinterpret_cast<const FuseList*>(d);
+        a.groups = reinterpret_cast<const FuseGroup*>(d + o_gr);
+        a.strategy = strategy;
+        a.rrf_k = rrf_k;
+        a.w_avg = w[0];
+        a.w_max = w[1];
+        a.w_hit = w[2];
+        a.top_k = top_k;
+        a.out_ids = reinterpret_cast<uint64_t*>(d + o_oi);
+        a.out_scores = reinterpret_cast<float*>(d + o_os);
+        a.out_n = reinterpret_cast<uint32_t*>(d + o_on);
+        rc = fuse_launch(a, n_groups, most, st);
+        if (rc != VDB_OK) return rc;
+        ix->last_kernels |= VDB_KERNEL_FUSE;
+        VDB_HIP(hipMemcpyAsync(h + o_oi, d + o_oi, total - o_oi, hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipStreamSynchronize(st));
+        return VDB_OK;
+      },
+      [&](vdb_hip_index* ix) {
+        const unsigned char* h = ix->h_fuse.as<unsigned char>();
+        if (top_k) {
+          std::memcpy(out_ids, h + o_oi, (size_t)n_groups * top_k * 8);
+          std::memcpy(out_scores, h + o_os, (size_t)n_groups * top_k * 4);
+        }
+        std::memcpy(out_n, h + o_on, (size_t)n_groups * 4);
       });
 }
 
@@ -280,6 +345,39 @@ int32_t vdb_hip_index_search_graph_filters(vdb_hip_index* ix, void** filters, ui
   if (nq == 0) return VDB_OK;
   return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k, ef,
                                      route, max_list, out_ids, out_scores, out_n, out_route);
+  });
+}
+
+// Collection::multi_query_search / multi_query_search_ids (collection/search/batch.rs:206-403) for n_groups user queries: the walks at
+// the over-fetched k and FusionStrategy::fuse (fusion/strategy.rs) on the device (include/velesdb_hip.h)
+int32_t vdb_hip_index_multi_query_search(vdb_hip_index* ix, const void* filter, const float* queries, const uint32_t* group_sizes,
+                                         uint32_t n_groups, uint32_t top_k, int32_t strategy, uint32_t rrf_k, const float* weights,
+                                         uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || (n_groups && (!queries || !group_sizes || !out_n)) || (n_groups && top_k && (!out_ids || !out_scores)))
+    return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "multi_query_search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "multi_query_search: not available on a member of a process group");
+  float w[3];
+  const int32_t rcs = fuse_check_strategy(strategy, weights, w);
+  if (rcs != VDB_OK) return rcs;
+  const uint64_t kf = fusion::overfetch(top_k);
+  uint64_t nq = 0;
+  for (uint32_t g = 0; g < n_groups; g++) {
+    if (group_sizes[g] == 0)
+      return fail(VDB_ERR_INVALID_ARG, "multi_query_search requires at least one vector (group " + std::to_string(g) + ")");
+    if (group_sizes[g] > VDB_MAX_FUSED_VECTORS)
+      return fail(VDB_ERR_INVALID_ARG, "multi_query_search supports at most " + std::to_string(VDB_MAX_FUSED_VECTORS) + " vectors, got " +
+                                           std::to_string(group_sizes[g]) + " (group " + std::to_string(g) + ")");
+    if (group_sizes[g] * kf > VDB_FUSE_MAX_RECORDS)
+      return fail(VDB_ERR_UNSUPPORTED, "multi_query_search: group " + std::to_string(g) + " would fuse " + std::to_string(group_sizes[g]) + " lists of " +
+                                           std::to_string(kf) + " records, more than the " + std::to_string(VDB_FUSE_MAX_RECORDS) + " one block's LDS takes");
+    nq += group_sizes[g];
+  }
+  if (n_groups == 0) return VDB_OK;
+  if (nq > 0xFFFFFFFFull) return fail(VDB_ERR_INVALID_ARG, "multi_query_search: more than 2^32 - 1 vectors in one call");
+  return multi_query_direct(ix, static_cast<const RowFilter*>(filter), queries, group_sizes, n_groups, (uint32_t)nq, top_k, (uint32_t)kf, strategy,
+                            rrf_k, w, out_ids, out_scores, out_n);
   });
 }
 

@@ -248,6 +248,10 @@ struct vdb_hip_index {
   vdb::DevBuf s_queries, s_part_keys, s_part_cnt, s_qbits, s_misc;
   vdb::DevBuf s_flt_mask;  // [capacity + slack] u8: the row mask of a filtered call on the mask-substitution route (n_rows bytes written per call)
   vdb::DevBuf s_fgraph;    // filtered graph search (hnsw_filtered.hip): [nq][2] u64 per-query counters | [nq] u32 launch slot -> query (per-query filters: | descriptors | slots)
+  // multi-query search (search_front.hip, fusion.hip): [lists | groups | fused ids | fused scores | fused n] of the call on the device,
+  // and the same block in pinned host memory (the tables go up from it, the fused results come back into it)
+  vdb::DevBuf s_fuse;
+  vdb::HostStage h_fuse;
   vdb::DevBuf s_tickets;  // [2] u32, zero between calls: the block tickets of the one-launch packed-bit search (sweep_bits_fused)
   // results of a host-pointer search: ONE allocation [ids nq*k u64 | scores nq*k f32 | n nq u32] (reserve_out), so that one
   // copy brings everything back; the three views point into it

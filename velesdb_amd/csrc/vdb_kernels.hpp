@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "vdb_gemm_schedule.hpp"
 
 namespace vdb {
@@ -438,5 +440,37 @@ hipError_t radix_sort_pairs_u64(uint64_t* keys_a, uint64_t* vals_a, uint64_t* ke
                                 int n_digits, void* scratch, bool* result_in_b, hipStream_t st);
 void launch_prep_rows(const PrepArgs& a, hipStream_t st);
 void launch_score_rows(int metric, const ScoreArgs& a, hipStream_t st);
+// fusion.hip: FusionStrategy::fuse, one block per group of lists (the rule: vdb_fusion.hpp)
+struct FuseList {
+  uint32_t n;    // records in the list
+  uint32_t off;  // where they go in the group's LDS array (prefix sum of n inside the group)
+  uint32_t ord;  // ordinal among the group's non-empty lists (< 2^13: a group holds <= VDB_FUSE_MAX_RECORDS records)
+  uint32_t pad;
+};
+struct FuseGroup {
+  uint32_t first;  // first list of the group
+  uint32_t V;      // lists of the group, empty ones included
+  uint32_t n;      // records of the group
+  uint32_t pad;
+};
+struct FuseArgs {
+  const uint64_t* ids;    // [n_lists][list_stride]
+  const float* scores;    // [n_lists][list_stride]
+  uint32_t list_stride;
+  const FuseList* lists;  // [n_lists]
+  const FuseGroup* groups;  // [n_groups]
+  int32_t strategy;       // enum vdb_fusion_strategy
+  uint32_t rrf_k;
+  float w_avg, w_max, w_hit;
+  uint32_t top_k;
+  uint32_t lds_records;   // entries of the launch's LDS array (a power of two >= every group's n; set by fuse_launch)
+  uint64_t* out_ids;      // [n_groups][max(top_k, 1)]
+  float* out_scores;
+  uint32_t* out_n;        // [n_groups]
+};
+int32_t fuse_check_strategy(int32_t strategy, const float* weights, float* w);
+int32_t fuse_plan(const uint32_t* list_n, uint32_t n_lists, uint32_t list_stride, const uint32_t* group_sizes, uint32_t n_groups,
+                  std::vector<FuseList>* lists, std::vector<FuseGroup>* groups, uint32_t* max_records);
+int32_t fuse_launch(FuseArgs a, uint32_t n_groups, uint32_t max_records, hipStream_t st);
 
 }  // namespace vdb

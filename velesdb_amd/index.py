@@ -44,6 +44,11 @@ KERNEL_SWEEP_LISTED = _ffi.VDB_KERNEL_SWEEP_LISTED
 ROUTE_AUTO, ROUTE_WALK, ROUTE_EXACT = 0, 1, 2
 KERNEL_HNSW_FILTERED = _ffi.VDB_KERNEL_HNSW_FILTERED
 KERNEL_FILTER_RANK = _ffi.VDB_KERNEL_FILTER_RANK
+# multi-query search with result fusion (HnswIndex.multi_query_search_ids / FusionStrategy.fuse): the fusion kernel's bit, the limits
+KERNEL_FUSE = _ffi.VDB_KERNEL_FUSE
+MAX_FUSED_VECTORS = 10      # MAX_VECTORS of multi_query_search (collection/search/batch.rs:238)
+FUSE_MAX_RECORDS = 8192     # records of one group the fusion kernel takes (VDB_FUSE_MAX_RECORDS)
+_PAD_ID = 0xFFFFFFFFFFFFFFFF  # what the library pads result ids with (the score beside it: NaN 0x7FC00000)
 SHARD_REPLICA, SHARD_RANGE = 0, 1
 COMM_ID_BYTES = 128
 
@@ -102,6 +107,102 @@ def set_split_selector(level) -> None:
     selection for 10 < k <= 128), level 1 as the fallback level; 3 (the library's default) = level 2 with the WIDE selection at every
     k <= 128.  Results are identical at every level."""
     check(lib().vdb_hip_set_split_selector(int(level)))
+
+
+class FusionError(ValueError):
+    """FusionError (fusion/strategy.rs:10-34): the reference's messages."""
+
+
+class FusionStrategy:
+    """FusionStrategy (fusion/strategy.rs:46-79) with `fuse` on the device (vdb_hip_fuse_results).  Build one with Average(), Maximum(),
+    RRF(k=60), rrf_default() or Weighted(avg, max, hit).  Fused lists come back descending by the total order of the fused score, equal
+    scores by id ascending (the reference leaves ties to HashMap iteration); NaN weights are refused (the reference lets them through)."""
+
+    def __init__(self, code: int, rrf_k: int = 0, weights=(0.0, 0.0, 0.0), name: str = ""):
+        self.code, self.rrf_k, self.weights, self.name = code, rrf_k, tuple(np.float32(w) for w in weights), name
+
+    def __repr__(self):
+        return self.name
+
+    def __eq__(self, other):
+        return isinstance(other, FusionStrategy) and (self.code, self.rrf_k, self.weights) == (other.code, other.rrf_k, other.weights)
+
+    def __hash__(self):
+        return hash((self.code, self.rrf_k, self.weights))
+
+    @classmethod
+    def Average(cls) -> "FusionStrategy":
+        return cls(_ffi.VDB_FUSION_AVERAGE, name="Average")
+
+    @classmethod
+    def Maximum(cls) -> "FusionStrategy":
+        return cls(_ffi.VDB_FUSION_MAXIMUM, name="Maximum")
+
+    @classmethod
+    def RRF(cls, k: int = 60) -> "FusionStrategy":
+        return cls(_ffi.VDB_FUSION_RRF, rrf_k=int(k), name=f"RRF(k={int(k)})")
+
+    @classmethod
+    def rrf_default(cls) -> "FusionStrategy":
+        return cls.RRF(60)
+
+    @classmethod
+    def Weighted(cls, avg_weight: float, max_weight: float, hit_weight: float) -> "FusionStrategy":
+        """FusionStrategy::weighted (strategy.rs:95-122): f32 arithmetic, the reference's messages; NaN is refused too."""
+        a, m, h = np.float32(avg_weight), np.float32(max_weight), np.float32(hit_weight)
+        for w in (a, m, h):
+            if w < 0:
+                raise FusionError(f"Weights must be non-negative, got {float(w):.4f}")
+        total = np.float32(np.float32(a + m) + h)
+        if np.isnan(total) or np.abs(np.float32(total - np.float32(1.0))) > np.float32(0.001):
+            raise FusionError(f"Weights must sum to 1.0, got {float(total):.4f}")
+        return cls(_ffi.VDB_FUSION_WEIGHTED, weights=(a, m, h), name=f"Weighted({float(a)}, {float(m)}, {float(h)})")
+
+    def _weights_ptr(self):
+        w = np.array(self.weights, dtype=np.float32)
+        return w, _ptr(w)
+
+    def fuse(self, results, device: int = 0) -> List[Tuple[int, float]]:
+        """FusionStrategy::fuse (strategy.rs:138-167): `results` = one list of (id, score) per query, best first."""
+        ids, sc, cnt = fuse_groups(self, [results], None, device)
+        return [(int(ids[0, i]), float(sc[0, i])) for i in range(int(cnt[0]))]
+
+
+def fuse_groups(fusion: FusionStrategy, groups, top_k: Optional[int] = None, device: int = 0):
+    """vdb_hip_fuse_results: `groups` = a sequence of groups, each a sequence of lists of (id, score); every group is fused on its own,
+    all in one launch.  top_k None = everything (the largest group's record count).  Returns (ids, scores, counts): numpy arrays
+    [n_groups][max(top_k, 1)] padded with id 2^64 - 1 / NaN, and [n_groups]."""
+    lists = [list(l) for g in groups for l in g]
+    sizes = np.array([len(g) for g in groups], dtype=np.uint32)
+    stride = max([len(l) for l in lists], default=0)
+    ids = np.zeros((len(lists), max(stride, 1)), dtype=np.uint64)
+    sc = np.zeros((len(lists), max(stride, 1)), dtype=np.float32)
+    ln = np.array([len(l) for l in lists], dtype=np.uint32)
+    for j, l in enumerate(lists):
+        if l:
+            ids[j, :len(l)] = np.array([r[0] for r in l], dtype=np.uint64)
+            sc[j, :len(l)] = np.array([r[1] for r in l], dtype=np.float32)
+    if top_k is None:
+        top_k = max([sum(len(l) for l in g) for g in groups], default=0)
+    return fuse_arrays(fusion, ids, sc, ln, sizes, top_k, device)
+
+
+def fuse_arrays(fusion: FusionStrategy, ids, scores, list_n, group_sizes, top_k: int, device: int = 0):
+    """vdb_hip_fuse_results over numpy arrays: ids / scores [n_lists][list_stride], list_n [n_lists], group_sizes [n_groups]."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    list_n = np.ascontiguousarray(list_n, dtype=np.uint32)
+    group_sizes = np.ascontiguousarray(group_sizes, dtype=np.uint32)
+    n_lists, stride = (ids.shape if ids.ndim == 2 else (0, 0))
+    ng, kk = group_sizes.size, max(top_k, 1)
+    out_ids = np.full((ng, kk), _PAD_ID, dtype=np.uint64)      # (top_k = 0: the library writes counts only; the one slot stays padding)
+    out_sc = np.full((ng, kk), np.nan, dtype=np.float32)
+    out_n = np.zeros(ng, dtype=np.uint32)
+    w, wp = fusion._weights_ptr()
+    check(lib().vdb_hip_fuse_results(device, fusion.code, fusion.rrf_k, wp, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None,
+                                     _ptr(list_n) if n_lists else None, n_lists, stride, _ptr(group_sizes) if ng else None, ng, top_k,
+                                     _ptr(out_ids), _ptr(out_sc), _ptr(out_n)))
+    return out_ids, out_sc, out_n
 
 
 class Filter:
@@ -517,6 +618,40 @@ class HnswIndex:
         check(lib().vdb_hip_index_search_graph_filters(self._h, handles if table else None, len(table), _ptr(fq), _ptr(qs), nq, k, ef,
                                                        MODE_HNSW, route, max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
         return (ids, sc, cnt), routes
+
+    def multi_query_search_batch(self, groups, top_k: int, fusion: FusionStrategy, flt: Optional[Filter] = None):
+        """Collection::multi_query_search_ids (collection/search/batch.rs:352-402) for MANY user queries in one call
+        (vdb_hip_index_multi_query_search): `groups` = a sequence of groups of 1..10 vectors (the reformulations of one user query).
+        Every vector is searched at the over-fetched k (SearchQuality::Balanced; with `flt` by the filtered graph search), every group's
+        lists are fused by `fusion` on the device, the first top_k fused records per group come back.  Returns (ids, scores, counts):
+        numpy arrays [n_groups][max(top_k, 1)] padded with id 2^64 - 1 / NaN, and [n_groups]."""
+        mats = []
+        for g in groups:
+            vs = [_f32(v).reshape(-1) for v in g]
+            if not vs:
+                raise ValueError("multi_query_search requires at least one vector")
+            if len(vs) > MAX_FUSED_VECTORS:
+                raise ValueError(f"multi_query_search supports at most {MAX_FUSED_VECTORS} vectors, got {len(vs)}")
+            for v in vs:
+                if v.shape[0] != self._dimension:
+                    raise ValueError(f"Vector dimension mismatch: expected {self._dimension}, got {v.shape[0]}")
+            mats.append(np.stack(vs))
+        sizes = np.array([m.shape[0] for m in mats], dtype=np.uint32)
+        qs = np.ascontiguousarray(np.concatenate(mats)) if mats else np.zeros((0, self._dimension), np.float32)
+        ng, kk = len(mats), max(top_k, 1)
+        ids = np.full((ng, kk), _PAD_ID, dtype=np.uint64)          # (top_k = 0: the library writes counts only)
+        sc = np.full((ng, kk), np.nan, dtype=np.float32)
+        cnt = np.zeros(ng, dtype=np.uint32)
+        w, wp = fusion._weights_ptr()
+        check(lib().vdb_hip_index_multi_query_search(self._h, flt._h if flt is not None else None, _ptr(qs) if ng else None,
+                                                     _ptr(sizes) if ng else None, ng, top_k, fusion.code, fusion.rrf_k, wp, _ptr(ids),
+                                                     _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
+
+    def multi_query_search_ids(self, vectors, top_k: int, fusion: FusionStrategy, flt: Optional[Filter] = None) -> List[Tuple[int, float]]:
+        """Collection::multi_query_search_ids for one user query: `vectors` = its 1..10 reformulations.  (id, fused score), best first."""
+        ids, sc, cnt = self.multi_query_search_batch([list(vectors)], top_k, fusion, flt)
+        return self._tuples(ids[0], sc[0], cnt[0])
 
     def search_brute_force_filtered(self, query, k: int, flt: Filter) -> List[Tuple[int, float]]:
         """search_brute_force among the filter's rows only (one query)."""
