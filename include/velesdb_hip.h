@@ -362,6 +362,30 @@ int32_t vdb_hip_index_search_graph_filters(vdb_hip_index* idx, void** filters, u
                                            const uint32_t* filter_of_query, const float* queries_rowmajor, uint32_t nq,
                                            uint32_t k, uint32_t ef, int32_t mode, int32_t route, uint32_t max_list,
                                            uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route);
+/* vdb_hip_index_search_graph_filters over the HALF-PRECISION image of the rows (hnsw_filtered.hip): mode is
+ * VDB_SEARCH_HNSW_F16 or VDB_SEARCH_HNSW_BF16.  Everything vdb_hip_index_search_graph_filters promises holds — the filter table,
+ * "no filter" = n_filters, allowed(r), routes 0 / 1 / 2, max_list, out_route, padding, a query's independence from its companions
+ * and its position, the summed counters — with every distance of the walk AND of the exact pass taken as the plain
+ * VDB_SEARCH_HNSW_F16 / _BF16 walk takes it: between the query rounded to the precision and the row's image, mode C summation order,
+ * the Cosine EPSILON rule.  A row has the same score bits on either route.  One filter for a whole call is a table of one.
+ * Two corollaries:
+ *   - with no query filtered (n_filters = 0, or "no filter" everywhere) on a handle without dead rows the call IS
+ *     vdb_hip_index_search_batch(mode): ids, score bits, out_n, n_dist and n_expand;
+ *   - on a handle whose f32 rows already equal their image (rows inserted already rounded), with queries already rounded, the call
+ *     equals vdb_hip_index_search_graph_filters(VDB_SEARCH_HNSW) bit for bit, routes and counters included — DotProduct and Euclidean
+ *     on any data, Cosine when no norm is below f32::EPSILON.
+ * The route plan, the list sizes, the attempt rounds and the largest list are the f32 call's (the lists hold f32 distances and the
+ * query scratch is f32); a visited node costs 2 * stride bytes (+ 4 for the Cosine norm) instead of 4 * stride.
+ * Errors, all checked before anything runs, the outputs untouched: mode other than VDB_SEARCH_HNSW_F16 / _BF16, Hamming / Jaccard
+ * handles, multi-device handles and process-group members: VDB_ERR_UNSUPPORTED; no image of that precision
+ * (vdb_hip_index_enable_half_precision): VDB_ERR_STATE, as modes 8 / 9 of vdb_hip_index_search_batch; a NULL table entry, a filter of
+ * another handle, a filter_of_query value > n_filters, route outside 0..2: VDB_ERR_INVALID_ARG; a stale filter or no graph:
+ * VDB_ERR_STATE.  vdb_hip_index_last_kernels: VDB_KERNEL_HNSW_FILTERED and / or VDB_KERNEL_FILTER_RANK together with
+ * VDB_KERNEL_HNSW_HALF, plus VDB_KERNEL_F16 for f16.  The two calls above keep refusing modes 8 and 9. */
+int32_t vdb_hip_index_search_graph_filters_half(vdb_hip_index* idx, int32_t mode, void** filters, uint32_t n_filters,
+                                                const uint32_t* filter_of_query, const float* queries_rowmajor, uint32_t nq,
+                                                uint32_t k, uint32_t ef, int32_t route, uint32_t max_list, uint64_t* out_ids,
+                                                float* out_scores, uint32_t* out_n, uint32_t* out_route);
 
 /* ---- multi-query search with result fusion: Collection::multi_query_search / multi_query_search_ids (collection/search/batch.rs:
  * 206-403) and FusionStrategy::fuse (fusion/strategy.rs:138-300) on the device (fusion.hip, vdb_fusion.hpp) ----

@@ -17,6 +17,13 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
   exact routes, with the over-fetch rule through plain VDB_SEARCH_HNSW (k' = max(4k, k + 10), post-filtered on the host) as the
   baseline, its recall and the share of queries it answers short.  This table is what would replace the two guesses of the
   auto rule (the factor 2 of the density-sized list, the `matched < ef` cut).  NO RUN OF IT IS RECORDED YET.
+  --graph --precision f16|bf16: the three filtered routes go through vdb_hip_index_search_graph_filters_half over that
+  image of the rows (enable_half_precision on the same handle); the exact-route truth and the over-fetch baseline stay f32.  Every
+  route also gets its ALGORITHMIC bytes per query, n_dist * row bytes + n_expand * M0 * 4 + admitted * 4 with row bytes =
+  2 * stride (+ 4 for the Cosine norm) over an image and 4 * stride over the f32 rows, the strides taken as the dimension rounded
+  up to 8 elements, and `admitted` (one bitmap word per admitted neighbour, not visible from outside) bounded by n_dist.
+  Beside every route the f32 filtered call on the same handle (`f32_<route>_*`), its timing blocks alternating with the image's.
+  One run of it is recorded: profiles/filter_probe_half_f16_100k.json (100 K x 768, densities 0.5 and 0.1).
   --graph --per-query F: the PER-QUERY leg instead (vdb_hip_index_search_graph_filters): at each density F distinct
   random filters of that density, the --graph-nq queries dealt round-robin over them; one call of search_batch_with_filters against
   the same queries as F calls of search_batch_filtered_graph, one per filter — what a caller does today with the same library, timed
@@ -51,6 +58,7 @@ p.add_argument("--rider", action="store_true")
 p.add_argument("--graph", action="store_true", help="the filtered graph search leg instead of the exact one")
 p.add_argument("--graph-nq", type=int, default=1024)
 p.add_argument("--per-query", type=int, default=0, help="with --graph: F distinct filters per density in one call against F single-filter calls")
+p.add_argument("--precision", default="f32", choices=["f32", "f16", "bf16"], help="with --graph: the rows the filtered walk reads")
 p.add_argument("--ef", type=int, default=128)
 p.add_argument("--densities", default="1,0.5,0.25,0.125,0.0625,0.03125,0.015625,0.0078125,0.00390625,0.001953125,0.0009765625")
 p.add_argument("--out", default="")
@@ -92,11 +100,41 @@ def measure(fn):
     return med, (max(blocks) - min(blocks)) / med
 
 
+def measure_pair(fa, fb):
+    """measure() for two calls whose blocks alternate (a, b, a, b, ...): both see the same clocks and the same neighbours"""
+    for _ in range(3):
+        fa()
+        fb()
+    t0 = time.perf_counter()
+    fa()
+    fb()
+    one = max((time.perf_counter() - t0) / 2, 1e-6)
+    iters = int(min(200, max(3, a.block_ms * 1e-3 / one)))
+    blocks = ([], [])
+    for _ in range(a.repeats):
+        for which, fn in enumerate((fa, fb)):
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            blocks[which].append((time.perf_counter() - t0) / iters * 1e3)
+    return tuple((statistics.median(b), (max(b) - min(b)) / statistics.median(b)) for b in blocks)
+
+
 def graph_leg():
     rows_out = []
+    half_mode = {"f16": va.MODE_HNSW_F16, "bf16": va.MODE_HNSW_BF16}.get(a.precision)
+    stride, m0 = (a.dim + 7) // 8 * 8, 2 * 32
     for mname in a.metrics.split(","):
         ix = build(METRICS[mname])
         ix.set_option(va.OPT_COMBINE_MAX_BATCH, 0)
+        if half_mode is not None:
+            ix.enable_half_precision(va.VectorPrecision.F16 if a.precision == "f16" else va.VectorPrecision.BF16)
+        row_bytes = 4 * stride if half_mode is None else 2 * stride + (4 if mname == "cosine" else 0)
+
+        def filtered(Q, flt, route):
+            if half_mode is None:
+                return ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route)
+            return ix.search_batch_filtered_graph_half(Q, a.k, flt, half_mode, ef=a.ef, route=route)
         t0 = time.perf_counter()
         ix.build_graph(0)
         print(f"# {mname}: graph over {a.rows} rows in {time.perf_counter() - t0:.1f} s", flush=True)
@@ -109,7 +147,8 @@ def graph_leg():
             mask = np.zeros(a.rows, dtype=bool)
             mask[allowed.astype(np.int64)] = True
             with ix.create_filter(allowed) as flt:
-                row = dict(leg="graph", metric=mname, rows=a.rows, dim=a.dim, k=a.k, ef=a.ef, nq=a.graph_nq, density=dens, count=count)
+                row = dict(leg="graph", metric=mname, precision=a.precision, rows=a.rows, dim=a.dim, k=a.k, ef=a.ef, nq=a.graph_nq,
+                           density=dens, count=count)
                 (eid, _, ecnt), _ = ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=va.ROUTE_EXACT)
                 truth = [set(eid[i, :ecnt[i]].tolist()) for i in range(a.graph_nq)]
 
@@ -117,14 +156,25 @@ def graph_leg():
                     return float(np.mean([len(truth[i] & set(ids[i][:cnt[i]])) / max(1, len(truth[i])) for i in range(a.graph_nq)]))
                 for name, route in (("auto", va.ROUTE_AUTO), ("walk", va.ROUTE_WALK), ("exact", va.ROUTE_EXACT)):
                     try:
-                        (ids, _, cnt), routes = ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route)
+                        (ids, _, cnt), routes = filtered(Q, flt, route)
                     except va.VelesHipError as e:  # the walk route refuses queries whose list would not fit
                         row[name + "_error"] = str(e)
                         continue
-                    row[name + "_n_dist"] = ix.last_search_stats()[0] / a.graph_nq
+                    n_dist, n_expand = ix.last_search_stats()[:2]
+                    row[name + "_n_dist"] = n_dist / a.graph_nq
+                    row[name + "_algo_bytes"] = (n_dist * row_bytes + n_expand * m0 * 4 + n_dist * 4) / a.graph_nq
                     row[name + "_walked"] = float(np.mean(routes == 1))
                     row[name + "_recall"] = recall(ids.tolist(), cnt.tolist())
-                    ms, sp = measure(lambda: ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route))
+                    if half_mode is None:
+                        ms, sp = measure(lambda: filtered(Q, flt, route))
+                    else:  # the f32 filtered walk of the same build on the same handle, blocks alternating
+                        ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route)
+                        fd, fe = ix.last_search_stats()[:2]
+                        row["f32_" + name + "_n_dist"] = fd / a.graph_nq
+                        row["f32_" + name + "_algo_bytes"] = (fd * 4 * stride + fe * m0 * 4 + fd * 4) / a.graph_nq
+                        (ms, sp), (fms, fsp) = measure_pair(lambda: filtered(Q, flt, route),
+                                                            lambda: ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route))
+                        row["f32_" + name + "_qps"], row["f32_" + name + "_spread"] = a.graph_nq / (fms * 1e-3), fsp
                     row[name + "_qps"], row[name + "_spread"] = a.graph_nq / (ms * 1e-3), sp
                 # the over-fetch rule: plain VDB_SEARCH_HNSW at k' = max(4k, k + 10), the caller drops what the filter rejects
                 pid, _, pcnt = ix._search_raw(Q, kk, 0, va.MODE_HNSW)

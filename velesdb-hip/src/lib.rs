@@ -1061,6 +1061,43 @@ impl HipHnswIndex {
         route: i32,
         max_list: u32,
     ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
+        self.filters_call(queries, k, quality, filters, VectorPrecision::F32, route, max_list)
+    }
+
+    /// [`Self::search_batch_with_filters`] over the half-precision image of the rows (`vdb_hip_index_search_graph_filters_half`;
+    /// [`Self::enable_half_precision`] first): same filters, routes, lists and outputs, every distance of the walk and of the exact
+    /// pass taken as [`Self::search_batch_half_graph`] takes it — the query rounded to `precision` against the row's image.  With no
+    /// query filtered the call is the plain half-precision graph search.  `VectorPrecision::F32` is
+    /// [`Self::search_batch_with_filters`].
+    ///
+    /// # Panics
+    /// When `filters.len() != queries.len()`.
+    #[must_use]
+    pub fn search_batch_with_filters_half(
+        &self,
+        queries: &[&[f32]],
+        k: usize,
+        quality: SearchQuality,
+        filters: &[Option<&HipFilter>],
+        precision: VectorPrecision,
+        route: i32,
+        max_list: u32,
+    ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
+        self.filters_call(queries, k, quality, filters, precision, route, max_list)
+    }
+
+    // one filter per query over the f32 rows or a half image: the table, the buffers and the call
+    #[allow(clippy::too_many_arguments)]
+    fn filters_call(
+        &self,
+        queries: &[&[f32]],
+        k: usize,
+        quality: SearchQuality,
+        filters: &[Option<&HipFilter>],
+        precision: VectorPrecision,
+        route: i32,
+        max_list: u32,
+    ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
         assert!(
             queries.len() == filters.len(),
             "Queries count ({}) does not match filters count ({})",
@@ -1102,24 +1139,45 @@ impl HipHnswIndex {
         let mut routes = vec![0u32; nq];
         // SAFETY: buffer sizes are n_filters / nq / nq*dim / nq*k / nq as the ABI requires; every handle of the table is live
         // (borrowed from `filters`); the library does not write through the table.
+        let table_p = if table.is_empty() { std::ptr::null_mut() } else { table.as_mut_ptr() };
+        let ef = quality.ef_search(k) as u32;
         check(unsafe {
-            sys::vdb_hip_index_search_graph_filters(
-                self.h,
-                if table.is_empty() { std::ptr::null_mut() } else { table.as_mut_ptr() },
-                none,
-                fq.as_ptr(),
-                flat.as_ptr(),
-                nq as u32,
-                k as u32,
-                quality.ef_search(k) as u32,
-                sys::VDB_SEARCH_HNSW,
-                route,
-                max_list,
-                ids.as_mut_ptr(),
-                scores.as_mut_ptr(),
-                counts.as_mut_ptr(),
-                routes.as_mut_ptr(),
-            )
+            match precision {
+                VectorPrecision::F32 => sys::vdb_hip_index_search_graph_filters(
+                    self.h,
+                    table_p,
+                    none,
+                    fq.as_ptr(),
+                    flat.as_ptr(),
+                    nq as u32,
+                    k as u32,
+                    ef,
+                    sys::VDB_SEARCH_HNSW,
+                    route,
+                    max_list,
+                    ids.as_mut_ptr(),
+                    scores.as_mut_ptr(),
+                    counts.as_mut_ptr(),
+                    routes.as_mut_ptr(),
+                ),
+                half => sys::vdb_hip_index_search_graph_filters_half(
+                    self.h,
+                    if half == VectorPrecision::F16 { sys::VDB_SEARCH_HNSW_F16 } else { sys::VDB_SEARCH_HNSW_BF16 },
+                    table_p,
+                    none,
+                    fq.as_ptr(),
+                    flat.as_ptr(),
+                    nq as u32,
+                    k as u32,
+                    ef,
+                    route,
+                    max_list,
+                    ids.as_mut_ptr(),
+                    scores.as_mut_ptr(),
+                    counts.as_mut_ptr(),
+                    routes.as_mut_ptr(),
+                ),
+            }
         });
         let out = (0..nq)
             .map(|i| {

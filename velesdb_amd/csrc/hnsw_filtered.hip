@@ -23,8 +23,12 @@
 // PHYSICAL list capacity, every query's list logic its own LOGICAL one, so queries with lists of different sizes share launches and
 // each computes what it computes alone.
 //
+// Over the half-precision images (vdb_hip_index_search_graph_filters_half): hnsw_search_filters_half_kernel /
+// filters_rank_half_kernel are the same two bodies in the per-query form with the half walk's distance phase (WalkDistHalf,
+// hnsw_half.hip) — the query rounded to the precision against the row's f16 / bf16 image, n_dist * (2 * stride [+ 4 Cosine]) row bytes.
+//
 // Algorithmic HBM bytes per query: walk n_dist * dim * 4 + n_expand * M0 * 4 + (admitted neighbours) * 4 for the bitmap words;
-// exact pass matched * (dim * 4 + 4).  Nothing here is measured: tools/filter_probe.py has the graph leg.
+// exact pass matched * (dim * 4 + 4).  Measured once, at one shape, f16 beside f32: tools/filter_probe.py has the graph leg.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -188,10 +192,17 @@ __device__ __forceinline__ uint32_t row_allowed(const SlotFilter& f, const uint8
 // a bit, reduce_rows)
 template <int METRIC, int CPL>
 using FiltDist = WalkDistF32<METRIC, CPL, 4, ((CPL == 4 || (CPL == 3 && METRIC == kEuclidean)) ? 4 : 8)>;
+// ... and over the f16 / bf16 image (vdb_hip_index_search_graph_filters_half): the half walk's distance phase
+// (hnsw_half.hip) under the same two bodies.  A row group holds R x CPL x 2 registers, half of FiltDist's: 8 rows everywhere but
+// at four chunks per lane, hnsw_half.hip's own rule (DESIGN 4.1k has the resource table)
+template <int METRIC, int CPL>
+constexpr int kFiltHalfRows = (CPL == 4 ? 4 : 8);
+template <int METRIC, int CPL, bool F16>
+using FiltDistHalf = WalkDistHalf<METRIC, CPL, 4, kFiltHalfRows<METRIC, CPL>, F16>;
 
 // LDS: hnsw_lds_bytes' layout — keys[cap] u64 | nb_id[nbmax] | nb_d[nbmax] | ctl[4] | flags[cap] u8 (padded) | query scratch
-// (the walk of both kernel families below: SRC says where the slot's filter comes from)
-template <int METRIC, int CPL, class SRC>
+// (the walk of the kernel families below: SRC says where the slot's filter comes from, DIST which rows the distances are taken over)
+template <int METRIC, int CPL, class SRC, class DIST = FiltDist<METRIC, CPL>>
 __device__ __forceinline__ void filtered_walk_body(const HnswSearchArgs& a, unsigned long long* qstats, const SRC src) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
@@ -205,7 +216,7 @@ __device__ __forceinline__ void filtered_walk_body(const HnswSearchArgs& a, unsi
   const size_t qoff = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
   uint32_t* vis = a.visited + (size_t)blockIdx.x * a.vis_words;
   uint32_t* vlog = a.vlog + (size_t)blockIdx.x * a.vlog_cap;
-  FiltDist<METRIC, CPL> dist;
+  DIST dist;
   dist.init(a, smem + qoff);
 
   for (uint32_t slot = blockIdx.x; slot < a.nq; slot += gridDim.x) {
@@ -437,11 +448,17 @@ template <int METRIC, int CPL>
 __global__ __launch_bounds__(256, 4) void hnsw_search_filters_kernel(HnswFiltersArgs fa) {
   filtered_walk_body<METRIC, CPL>(fa.s, fa.qstats, SlotTableSrc{fa});
 }
+// ... over the half image: a.rows = the image, a.row_stride in half elements, a.norms of the rounded rows; the queries stay f32 and
+// are rounded at load
+template <int METRIC, int CPL, bool F16>
+__global__ __launch_bounds__(256, 4) void hnsw_search_filters_half_kernel(HnswFiltersArgs fa) {
+  filtered_walk_body<METRIC, CPL, SlotTableSrc, FiltDistHalf<METRIC, CPL, F16>>(fa.s, fa.qstats, SlotTableSrc{fa});
+}
 
 // The exact pass: one block per query over the filter's ascending row list in chunks of nbmax — dead rows skipped, distances by
 // the walk's DIST::eval, the k best by (total-order(distance), row) in the same LDS list (a.cap >= k entries), results in the
 // walk's format.  Adds the rows it evaluated to the query's n_dist.
-template <int METRIC, int CPL, class SRC>
+template <int METRIC, int CPL, class SRC, class DIST = FiltDist<METRIC, CPL>>
 __device__ __forceinline__ void filter_rank_body(const HnswSearchArgs& a, unsigned long long* qstats, const SRC src) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
@@ -453,7 +470,7 @@ __device__ __forceinline__ void filter_rank_body(const HnswSearchArgs& a, unsign
   lds_vu32* ctl = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8);
   lds_vu8* flags = (lds_vu8*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8 + 16);
   const size_t qoff = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
-  FiltDist<METRIC, CPL> dist;
+  DIST dist;
   dist.init(a, smem + qoff);
 
   for (uint32_t slot = blockIdx.x; slot < a.nq; slot += gridDim.x) {
@@ -540,16 +557,29 @@ template <int METRIC, int CPL>
 __global__ __launch_bounds__(256, 4) void filters_rank_kernel(HnswFiltersArgs fa) {
   filter_rank_body<METRIC, CPL>(fa.s, fa.qstats, SlotTableSrc{fa});
 }
+template <int METRIC, int CPL, bool F16>
+__global__ __launch_bounds__(256, 4) void filters_rank_half_kernel(HnswFiltersArgs fa) {
+  filter_rank_body<METRIC, CPL, SlotTableSrc, FiltDistHalf<METRIC, CPL, F16>>(fa.s, fa.qstats, SlotTableSrc{fa});
+}
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-template <bool RANK, int METRIC, int CPL>
-static auto kernel_of(const HnswFilteredArgs&) { return RANK ? filter_rank_kernel<METRIC, CPL> : hnsw_search_filtered_kernel<METRIC, CPL>; }
-template <bool RANK, int METRIC, int CPL>
-static auto kernel_of(const HnswFiltersArgs&) { return RANK ? filters_rank_kernel<METRIC, CPL> : hnsw_search_filters_kernel<METRIC, CPL>; }
+// (ROWS: FiltersRows — the half images exist in the per-query form only)
+template <bool RANK, int METRIC, int CPL, int ROWS>
+static auto kernel_of(const HnswFilteredArgs&) {
+  static_assert(ROWS == kFiltersF32, "one-filter form: f32 rows and packed bits only");
+  return RANK ? filter_rank_kernel<METRIC, CPL> : hnsw_search_filtered_kernel<METRIC, CPL>;
+}
+template <bool RANK, int METRIC, int CPL, int ROWS>
+static auto kernel_of(const HnswFiltersArgs&) {
+  if constexpr (ROWS == kFiltersF32)
+    return RANK ? filters_rank_kernel<METRIC, CPL> : hnsw_search_filters_kernel<METRIC, CPL>;
+  else
+    return RANK ? filters_rank_half_kernel<METRIC, CPL, ROWS == kFiltersF16> : hnsw_search_filters_half_kernel<METRIC, CPL, ROWS == kFiltersF16>;
+}
 
-template <bool RANK, int METRIC, int CPL, class ARGS>
+template <bool RANK, int METRIC, int CPL, int ROWS, class ARGS>
 static hipError_t launch_fk(const ARGS& fa, int slots, size_t lds, hipStream_t st) {
-  auto kern = kernel_of<RANK, METRIC, CPL>(fa);
+  auto kern = kernel_of<RANK, METRIC, CPL, ROWS>(fa);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -564,25 +594,37 @@ static hipError_t launch_fk(const ARGS& fa, int slots, size_t lds, hipStream_t s
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, fa);
   return hipGetLastError();
 }
-template <bool RANK, int METRIC, class ARGS>
+template <bool RANK, int METRIC, int ROWS, class ARGS>
 static hipError_t launch_fk_cpl(const ARGS& fa, int slots, size_t lds, hipStream_t st) {
   switch (sweep_cpl_for_dim(fa.s.dim)) {
-    case 1: return launch_fk<RANK, METRIC, 1>(fa, slots, lds, st);
-    case 2: return launch_fk<RANK, METRIC, 2>(fa, slots, lds, st);
-    case 3: return launch_fk<RANK, METRIC, 3>(fa, slots, lds, st);
-    case 4: return launch_fk<RANK, METRIC, 4>(fa, slots, lds, st);
-    default: return launch_fk<RANK, METRIC, 0>(fa, slots, lds, st);
+    case 1: return launch_fk<RANK, METRIC, 1, ROWS>(fa, slots, lds, st);
+    case 2: return launch_fk<RANK, METRIC, 2, ROWS>(fa, slots, lds, st);
+    case 3: return launch_fk<RANK, METRIC, 3, ROWS>(fa, slots, lds, st);
+    case 4: return launch_fk<RANK, METRIC, 4, ROWS>(fa, slots, lds, st);
+    default: return launch_fk<RANK, METRIC, 0, ROWS>(fa, slots, lds, st);
   }
 }
-template <bool RANK, class ARGS>
+template <bool RANK, int ROWS = kFiltersF32, class ARGS>
 static hipError_t launch_filtered(const ARGS& fa, int slots, size_t lds, hipStream_t st) {
   switch (fa.s.metric) {
-    case kCosine: return launch_fk_cpl<RANK, kCosine>(fa, slots, lds, st);
-    case kEuclidean: return launch_fk_cpl<RANK, kEuclidean>(fa, slots, lds, st);
-    case kDot: return launch_fk_cpl<RANK, kDot>(fa, slots, lds, st);
-    case kHamming: return launch_fk<RANK, kHamming, 0>(fa, slots, lds, st);
-    default: return launch_fk<RANK, kJaccard, 0>(fa, slots, lds, st);
+    case kCosine: return launch_fk_cpl<RANK, kCosine, ROWS>(fa, slots, lds, st);
+    case kEuclidean: return launch_fk_cpl<RANK, kEuclidean, ROWS>(fa, slots, lds, st);
+    case kDot: return launch_fk_cpl<RANK, kDot, ROWS>(fa, slots, lds, st);
+    default: break;
   }
+  if constexpr (ROWS == kFiltersF32) {
+    if (fa.s.metric == kHamming) return launch_fk<RANK, kHamming, 0, ROWS>(fa, slots, lds, st);
+    return launch_fk<RANK, kJaccard, 0, ROWS>(fa, slots, lds, st);
+  } else {
+    return hipErrorInvalidValue;  // (no image of packed bits: refused in front of the call)
+  }
+}
+// the per-query form over the rows the call names
+template <bool RANK>
+static hipError_t launch_filters_rows(const HnswFiltersArgs& fa, int rows, int slots, size_t lds, hipStream_t st) {
+  if (rows == kFiltersF16) return launch_filtered<RANK, kFiltersF16>(fa, slots, lds, st);
+  if (rows == kFiltersBF16) return launch_filtered<RANK, kFiltersBF16>(fa, slots, lds, st);
+  return launch_filtered<RANK>(fa, slots, lds, st);
 }
 
 // the largest list (entries) whose launch stays inside 160 KB of LDS at this nbmax: hnsw_search_prepare's limit
@@ -782,8 +824,16 @@ int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, c
 // of the call is one launch.  filters: [n_filters] handles, non-null; fq: [nq] values in 0..n_filters, n_filters = no filter.
 int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                        const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
-                                       uint32_t* routes) {
+                                       uint32_t* routes, int half) {
   int32_t rc;
+  // (the statuses of the plain half walk, hnsw_search_half_dev)
+  if (half == kFiltersF16 && !ix->f16_enabled)
+    return fail(VDB_ERR_STATE, "f16 filtered graph search: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
+  if (half == kFiltersBF16 && !ix->bf16_enabled)
+    return fail(VDB_ERR_STATE, "bf16 filtered graph search: call vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16) first");
+  if (half != kFiltersF32 && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search: Cosine, DotProduct and Euclidean only");
+  const uint32_t half_kernels = half == kFiltersF32 ? 0u : (VDB_KERNEL_HNSW_HALF | (half == kFiltersF16 ? VDB_KERNEL_F16 : 0u));
   for (uint32_t j = 0; j < n_filters; j++)
     if ((rc = filter_check(ix, filters[j])) != VDB_OK) return rc;
   if (!ix->graph_valid) return fail(VDB_ERR_STATE, "HNSW graph not built for all rows (use the exact filtered search or build it)");
@@ -868,6 +918,13 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   FiltersSlot* d_slots = reinterpret_cast<FiltersSlot*>(ix->s_fgraph.as<unsigned char>() + qs_bytes + desc_bytes);
   VDB_HIP(hipMemcpyAsync(d_descs, descs.data(), desc_bytes, hipMemcpyHostToDevice, st));  // (`descs` outlives every synchronisation below)
   walk_args_index(ix, a, k, ef, nbmax, d_n);
+  if (half != kFiltersF32) {  // the image instead of the f32 rows, as hnsw_search_half_dev: same fields, the stride in half elements
+    const bool f16 = half == kFiltersF16;
+    a.rows = reinterpret_cast<const float*>(f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>());
+    a.norms = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
+    a.row_stride = ix->bf16_stride;
+    a.bits = nullptr;
+  }
   fa.descs = d_descs;
   fa.qstats = ix->s_fgraph.as<unsigned long long>();
 
@@ -896,10 +953,10 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
       const size_t lds = lds_of(a.cap);
       if (lds > kFgLdsBudget) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: candidate list beyond the LDS" + limits);
       const int slots_l = (int)std::min<int64_t>((int64_t)L.count, (int64_t)ix->n_cus * (int64_t)L.per_cu);
-      const hipError_t e = launch_filtered<false>(fa, slots_l, lds, st);
+      const hipError_t e = launch_filters_rows<false>(fa, half, slots_l, lds, st);
       if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filtered hnsw_search launch: ") + hipGetErrorString(e));
     }
-    ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED;
+    ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED | half_kernels;
     r = fetch();
     if (r != VDB_OK) return r;
     for (uint32_t i = 0; i < n; i++) over[i] = h_n[slots[i].query] == 0xFFFFFFFFu;
@@ -922,9 +979,9 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
     a.nq = (uint32_t)exact.size();
     fa.slots = d_slots;
     const int slots_l = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * 4);
-    const hipError_t e = launch_filtered<true>(fa, slots_l, lds, st);
+    const hipError_t e = launch_filters_rows<true>(fa, half, slots_l, lds, st);
     if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filters_rank launch: ") + hipGetErrorString(e));
-    ix->last_kernels |= VDB_KERNEL_FILTER_RANK;
+    ix->last_kernels |= VDB_KERNEL_FILTER_RANK | half_kernels;
     rc = fetch();
     if (rc != VDB_OK) return rc;
     for (const FiltersSlot& s : exact) routes[s.query] = kFgExact;

@@ -105,14 +105,15 @@ static int32_t search_graph_filtered_direct(vdb_hip_index* handle, const RowFilt
       [&](vdb_hip_index* ix) { deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n); });
 }
 
-// vdb_hip_index_search_graph_filters: the same, one filter per query; the routes travel with the results (nothing is written on error)
+// vdb_hip_index_search_graph_filters: the same, one filter per query; the routes travel with the results (nothing is written on error).
+// half: the rows of the walk (FiltersRows; vdb_hip_index_search_graph_filters_half)
 static int32_t search_graph_filters_direct(vdb_hip_index* handle, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                            const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
-                                           uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route) {
+                                           uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route, int half = kFiltersF32) {
   std::vector<uint32_t> routes(nq, 0u);
   return run_search(
       handle, nq, k, ef, VDB_SEARCH_HNSW, 0,
-      [&](vdb_hip_index* ix) { return search_graph_filters_to_device(ix, filters, n_filters, fq, queries, nq, k, ef, route, max_list, routes.data()); },
+      [&](vdb_hip_index* ix) { return search_graph_filters_to_device(ix, filters, n_filters, fq, queries, nq, k, ef, route, max_list, routes.data(), half); },
       [&](vdb_hip_index* ix) {
         deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n);
         if (out_route) std::memcpy(out_route, routes.data(), (size_t)nq * 4);
@@ -345,6 +346,35 @@ int32_t vdb_hip_index_search_graph_filters(vdb_hip_index* ix, void** filters, ui
   if (nq == 0) return VDB_OK;
   return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k, ef,
                                      route, max_list, out_ids, out_scores, out_n, out_route);
+  });
+}
+
+// the same call over the f16 / bf16 image of the rows: a symbol of its own — the two calls above keep refusing the
+// half modes, which is their documented contract
+int32_t vdb_hip_index_search_graph_filters_half(vdb_hip_index* ix, int32_t mode, void** filters, uint32_t n_filters,
+                                                const uint32_t* filter_of_query, const float* queries, uint32_t nq, uint32_t k, uint32_t ef,
+                                                int32_t route, uint32_t max_list, uint64_t* out_ids, float* out_scores, uint32_t* out_n,
+                                                uint32_t* out_route) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || (n_filters && !filters) || (nq && (!queries || !out_n || !filter_of_query)) || (nq && k && (!out_ids || !out_scores)))
+    return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filtered graph search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  if (mode != VDB_SEARCH_HNSW_F16 && mode != VDB_SEARCH_HNSW_BF16)
+    return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search: VDB_SEARCH_HNSW_F16 or VDB_SEARCH_HNSW_BF16");
+  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search: Cosine, DotProduct and Euclidean only");
+  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
+  for (uint32_t j = 0; j < n_filters; j++)
+    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: filter " + std::to_string(j) + " of the table is null");
+  for (uint32_t i = 0; i < nq; i++)
+    if (filter_of_query[i] > n_filters)
+      return fail(VDB_ERR_INVALID_ARG, "filtered graph search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
+                                           " of a table of " + std::to_string(n_filters));
+  if (nq == 0) return VDB_OK;
+  return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k, ef,
+                                     route, max_list, out_ids, out_scores, out_n, out_route,
+                                     mode == VDB_SEARCH_HNSW_F16 ? kFiltersF16 : kFiltersBF16);
   });
 }
 

@@ -619,6 +619,43 @@ class HnswIndex:
                                                        MODE_HNSW, route, max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
         return (ids, sc, cnt), routes
 
+    def search_batch_with_filters_half(self, queries, k: int, filters, mode: int, ef: int = 0, route: int = ROUTE_AUTO,
+                                       max_list: int = 0):
+        """search_batch_with_filters over the half-precision image of the rows (vdb_hip_index_search_graph_filters_half): mode is
+        MODE_HNSW_F16 or MODE_HNSW_BF16 (enable_half_precision first).  Same filters, routes, lists and outputs; every distance of
+        the walk and of the exact pass is the one search_batch(mode) takes — the query rounded to the precision against the row's
+        image.  With no query filtered the call is search_batch(mode).  Returns ((ids, scores, counts), routes)."""
+        qs = _f32(queries)
+        if qs.ndim == 1:
+            qs = qs.reshape(1, -1)
+        self._validate(qs)
+        filters = list(filters)
+        nq, kk = qs.shape[0], max(k, 1)
+        if len(filters) != nq:
+            raise ValueError(f"Queries count ({nq}) does not match filters count ({len(filters)})")
+        table, slot_of = [], {}  # distinct filters by object identity; index len(table) = no filter
+        for f in filters:
+            if f is not None and id(f) not in slot_of:
+                slot_of[id(f)] = len(table)
+                table.append(f)
+        fq = np.array([len(table) if f is None else slot_of[id(f)] for f in filters], dtype=np.uint32)
+        handles = (C.c_void_p * max(len(table), 1))(*[f._h for f in table])
+        ids = np.empty((nq, kk), dtype=np.uint64)
+        sc = np.empty((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        routes = np.zeros(nq, dtype=np.uint32)
+        check(lib().vdb_hip_index_search_graph_filters_half(self._h, mode, handles if table else None, len(table), _ptr(fq), _ptr(qs), nq,
+                                                            k, ef, route, max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
+        return (ids, sc, cnt), routes
+
+    def search_batch_filtered_graph_half(self, queries, k: int, flt: Filter, mode: int, ef: int = 0, route: int = ROUTE_AUTO,
+                                         max_list: int = 0):
+        """search_batch_filtered_graph over the half-precision image: search_batch_with_filters_half with `flt` for every query (a
+        table of one)."""
+        qs = _f32(queries)
+        nq = 1 if qs.ndim == 1 else qs.shape[0]
+        return self.search_batch_with_filters_half(qs, k, [flt] * nq, mode, ef=ef, route=route, max_list=max_list)
+
     def multi_query_search_batch(self, groups, top_k: int, fusion: FusionStrategy, flt: Optional[Filter] = None):
         """Collection::multi_query_search_ids (collection/search/batch.rs:352-402) for MANY user queries in one call
         (vdb_hip_index_multi_query_search): `groups` = a sequence of groups of 1..10 vectors (the reformulations of one user query).
