@@ -214,6 +214,20 @@ int32_t vdb_hip_index_enable_bf16(vdb_hip_index* idx);
  * images).  On Cosine / DotProduct, VDB_PRECISION_BF16 is vdb_hip_index_enable_bf16 (which keeps refusing Euclidean handles).  A
  * multi-device handle forwards the call to every shard. */
 int32_t vdb_hip_index_enable_half_precision(vdb_hip_index* idx, int32_t precision);
+/* The graph precision: the row format every distance of graph CONSTRUCTION is taken over from this call on (insert, insert_batch,
+ * insert_batch_parallel, build_graph, the rebuild inside vacuum).  VDB_PRECISION_F32 (the default): the f32 rows.  VDB_PRECISION_F16 /
+ * _BF16: the distance between two nodes is half_precision::{dot_product, cosine_similarity, euclidean_distance}
+ * (half_precision.rs:199-287) over their two image rows, reported as DistanceEngine::distance reports it; the inserted node's query is
+ * its own image row dequantised (exact), its Cosine norm the stored norm of the rounded row.  The graph is then the one the
+ * reference's sequential / batch-synchronous insert builds over the dequantised rows, link for link — the graph modes 8 / 9 and the
+ * filtered half walks are meant to run on.  Needs the matching image (vdb_hip_index_enable_half_precision; VDB_ERR_STATE otherwise, as
+ * modes 8 / 9); VDB_ERR_UNSUPPORTED on Hamming / Jaccard and multi-device handles, VDB_ERR_INVALID_ARG for an unknown precision; a
+ * refused call changes nothing.  Allowed at any time, also on a graph that has nodes or was loaded from files: a change of precision
+ * recomputes the cached neighbour distances in the new precision before the next insert (back-link pruning ranks by them).  Searches
+ * are unaffected; filters stay valid; vacuum keeps the precision.  NOT persisted: neither the reference's file formats nor the index
+ * directory has a field for it — a loaded handle starts at VDB_PRECISION_F32, call this again after a load. */
+int32_t vdb_hip_index_set_graph_precision(vdb_hip_index* idx, int32_t precision);
+int32_t vdb_hip_index_graph_precision(const vdb_hip_index* idx, int32_t* precision);
 /* links every row that is not in the graph yet (rows that arrived through upload/upload_dev), same
  * schedule as insert_batch_parallel; afterwards the HNSW search modes are available. */
 int32_t vdb_hip_index_build_graph(vdb_hip_index* idx, uint32_t max_batch);

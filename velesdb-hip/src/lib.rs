@@ -756,6 +756,26 @@ impl HipHnswIndex {
         check(unsafe { sys::vdb_hip_index_enable_half_precision(self.h, precision as i32) });
     }
 
+    /// The row format every distance of graph construction is taken over from now on (`insert`, `insert_batch_*`, `build_graph`,
+    /// the rebuild inside `vacuum`): `F32` (the default) or, after [`Self::enable_half_precision`] with the same precision, `F16` /
+    /// `BF16` — the image the half walks read.  Allowed on a graph that has nodes.  Not persisted: a loaded index starts at `F32`.
+    pub fn set_graph_precision(&self, precision: VectorPrecision) {
+        // SAFETY: live handle.
+        check(unsafe { sys::vdb_hip_index_set_graph_precision(self.h, precision as i32) });
+    }
+
+    /// The graph precision set with [`Self::set_graph_precision`].
+    pub fn graph_precision(&self) -> VectorPrecision {
+        let mut p: i32 = 0;
+        // SAFETY: live handle; `p` outlives the call.
+        check(unsafe { sys::vdb_hip_index_graph_precision(self.h, &mut p) });
+        match p {
+            sys::VDB_PRECISION_F16 => VectorPrecision::F16,
+            sys::VDB_PRECISION_BF16 => VectorPrecision::BF16,
+            _ => VectorPrecision::F32,
+        }
+    }
+
     fn search_batch_mode(&self, queries: &[&[f32]], k: usize, ef: usize, mode: i32) -> Vec<Vec<(u64, f32)>> {
         if queries.is_empty() || k == 0 {
             return queries.iter().map(|_| Vec::new()).collect();

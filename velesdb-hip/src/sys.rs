@@ -125,6 +125,8 @@ extern "C" {
     pub fn vdb_hip_index_get_quantized(idx: *mut VdbHipIndex, id: u64, out: *mut u8, cap: usize, len: *mut usize) -> i32;
     pub fn vdb_hip_index_enable_bf16(idx: *mut VdbHipIndex) -> i32;
     pub fn vdb_hip_index_enable_half_precision(idx: *mut VdbHipIndex, precision: i32) -> i32;
+    pub fn vdb_hip_index_set_graph_precision(idx: *mut VdbHipIndex, precision: i32) -> i32;
+    pub fn vdb_hip_index_graph_precision(idx: *const VdbHipIndex, precision: *mut i32) -> i32;
     pub fn vdb_hip_index_build_graph(idx: *mut VdbHipIndex, max_batch: u32) -> i32;
     pub fn vdb_hip_index_upload(idx: *mut VdbHipIndex, ids: *const u64, vecs_rowmajor: *const f32, n: u64, inserted: *mut u64) -> i32;
     pub fn vdb_hip_index_upload_dev(idx: *mut VdbHipIndex, id_base: u64, d_vecs_rowmajor: *const f32, n: u64, stream: *mut c_void) -> i32;

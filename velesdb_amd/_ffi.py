@@ -63,6 +63,8 @@ SIGNATURES = {
     "vdb_hip_index_build_graph": (_i32, [_vp, _u32]),
     "vdb_hip_index_enable_bf16": (_i32, [_vp]),
     "vdb_hip_index_enable_half_precision": (_i32, [_vp, _i32]),
+    "vdb_hip_index_set_graph_precision": (_i32, [_vp, _i32]),
+    "vdb_hip_index_graph_precision": (_i32, [_vp, _pi32]),
     "vdb_hip_index_set_storage_mode": (_i32, [_vp, _i32]),
     "vdb_hip_index_get_quantized": (_i32, [_vp, _u64, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vdb_hip_index_train_quantizer": (_i32, [_vp, _u32]),

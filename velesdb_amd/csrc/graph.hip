@@ -206,6 +206,7 @@ int32_t vdb_hip_index_load_reference_files(vdb_hip_index* ix, const char* dir, c
   ix->M0 = M0;
   ix->efc = efc;
   ix->ndist_valid = false;  // the files carry no distances; recomputed before the first insert
+  ix->graph_precision = VDB_PRECISION_F32;  // nor a graph precision: a loaded handle starts at F32 (vdb_hip_index_set_graph_precision)
   ix->entry_point = count ? (int64_t)ep : -1;
   ix->max_layer = max_layer;
   ix->graph_nodes = count;

@@ -25,6 +25,12 @@
 //   next to the lists (every one of them was produced by a search: d(a,b) and d(b,a) are bit-identical
 //   in the canonical arithmetic), so pruning needs no vector reads at all: the reference recomputes
 //   max_conn+1 distances per full back-link, 4 160 row reads per inserted node at M0 = 64.
+//
+// Row formats: the handle's graph precision (vdb_hip_index_set_graph_precision) says what every distance of construction is taken
+// over — the f32 rows / packed bits (hnsw_insert_kernel, hnsw_ndist_kernel) or the f16 / bf16 image (hnsw_insert_half_kernel,
+// hnsw_ndist_half_kernel: half_precision::* over two image rows in mode C's order, i.e. bit for bit the f32 construction over the
+// dequantised rows).  One body per kernel, the distance phase a type (BuildDistF32 / BuildDistHalf below).  The cache of kernel B is
+// valid for ONE precision: a change of precision refills it (graph_fill_ndist) before the next insert.
 #include <algorithm>
 #include <cmath>
 
@@ -83,10 +89,55 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 }  // namespace
 
-// LDS: keys[cap] u64 | nb_id, nb_d, nbx, sel [nbmax] u32 each | ctl[8] u32 | flags[cap] u8 (pad 16) | query scratch
+// ---- the distance phase of construction, a type as in hnsw_walk_body: how row `qrow` of the storage becomes the query (registers, or
+// the LDS scratch behind the lists) and eval(m, nb_id, nb_d) with all four waves.  Everything else of the two kernels below — phases,
+// candidate list, visited log, select_neighbors, link requests, counters — is one text for every row format.
+// The f32 rows (Cosine / Euclidean / DotProduct, canonical arithmetic) and the packed bits (Hamming / Jaccard).  Their query load
+// stays written out in the bodies (the `!DIST::HALF` branches): taken through a function here, the same statements cost
+// hnsw_ndist_kernel<0, 3> three registers and with them a wave per SIMD.
 template <int METRIC, int CPL>
-__global__ __launch_bounds__(256) void hnsw_insert_kernel(HnswInsertArgs a) {
-  constexpr bool BITS = (METRIC == kHamming || METRIC == kJaccard);
+struct BuildDistF32 {
+  static constexpr bool HALF = false, BITS = (METRIC == kHamming || METRIC == kJaccard);
+  static constexpr int kMetric = METRIC, kCpl = CPL, NQ = CPL > 0 ? CPL : 1;
+  static __device__ __forceinline__ void eval(const DistCtx& dc, const float4 (&q)[NQ], float qnorm, const float* qgen, const uint32_t* qbits,
+                                              uint32_t m, lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib) {
+    if (BITS)
+      dist_phase_bits<METRIC>(dc, qbits, m, nb_id, nb_d);
+    else
+      dist_phase_f32<METRIC, CPL>(dc, q, qnorm, qgen, m, nb_id, nb_d, lane, wib);
+  }
+};
+
+// the f16 / bf16 image of the rows (graph precision F16 / BF16): dc.rows = the image, dc.row_stride in half elements, dc.norms = the
+// norms of the ROUNDED rows (what hnsw_search_half_dev sets).  The query is the node's own image row dequantised — exact, nothing is
+// rounded twice — and its Cosine norm the stored norm of the rounded row.  Row groups as in hnsw_half.hip: 8 rows, 4 at CPL 4
+// (the group size does not change a bit: reduce_rows).
+template <int METRIC, int CPL, bool F16>
+struct BuildDistHalf {
+  static constexpr bool HALF = true, BITS = false;
+  static constexpr bool LDS_QUERY = CPL == 0;  // load_row wrote the LDS scratch: the caller's barrier follows
+  static constexpr int kMetric = METRIC, kCpl = CPL, NQ = CPL > 0 ? CPL : 1;
+  // every thread of the block
+  static __device__ __forceinline__ void load_row(const DistCtx& dc, uint32_t qrow, float4 (&q)[NQ], float& qnorm, float* qgen, int d4,
+                                                  int lane) {
+    const uint16_t* qp = reinterpret_cast<const uint16_t*>(dc.rows) + (size_t)qrow * dc.row_stride;
+    if (CPL > 0) {
+#pragma unroll
+      for (int c = 0; c < CPL; c++) q[c] = half4_to_f32<F16>(ld_half4(qp + (size_t)(c * 64 + lane) * 4));
+    } else {
+      for (int i = threadIdx.x; i < d4 * 4; i += 256) qgen[i] = half1_to_f32<F16>(qp[i]);  // (4 * d4 <= row_stride; the padding is zero)
+    }
+    if (METRIC == kCosine) qnorm = dc.norms[qrow];
+  }
+  static __device__ __forceinline__ void eval(const DistCtx& dc, const float4 (&q)[NQ], float qnorm, const float* qgen, const uint32_t*,
+                                              uint32_t m, lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib) {
+    dist_phase_half<METRIC, CPL, 4, (CPL == 4 ? 4 : 8), F16>(dc, q, qnorm, qgen, m, nb_id, nb_d, lane, wib);
+  }
+};
+
+// LDS: keys[cap] u64 | nb_id, nb_d, nbx, sel [nbmax] u32 each | ctl[8] u32 | flags[cap] u8 (pad 16) | query scratch
+template <class DIST>
+__device__ __forceinline__ void hnsw_insert_body(const HnswInsertArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
   const int wib = (int)rfl(threadIdx.x >> 6);
@@ -110,7 +161,7 @@ __global__ __launch_bounds__(256) void hnsw_insert_kernel(HnswInsertArgs a) {
   for (uint32_t bi = blockIdx.x; bi < a.B; bi += gridDim.x) {
     const uint32_t x = a.first + bi;
     const int lx = (int)a.levels[bi];
-    float4 q[CPL > 0 ? CPL : 1];
+    float4 q[DIST::NQ];
     float qnorm = 0.0f;
     uint32_t qrow_loaded = kNone;
 
@@ -415,26 +466,26 @@ __global__ __launch_bounds__(256) void hnsw_insert_kernel(HnswInsertArgs a) {
       }
       const uint32_t qrow = ctl[3];
       if (qrow != qrow_loaded) {  // block-uniform
-        if (BITS) {
+        if constexpr (DIST::HALF) {
+          DIST::load_row(dc, qrow, q, qnorm, qgen, d4, lane);
+          if constexpr (DIST::LDS_QUERY) __syncthreads();
+        } else if (DIST::BITS) {
           for (uint32_t w = threadIdx.x; w < dc.words; w += 256) qbits[w] = dc.bits[(size_t)qrow * dc.words + w];
           __syncthreads();
-        } else if (CPL > 0) {
+        } else if (DIST::kCpl > 0) {
           const float* qp = dc.rows + (size_t)qrow * dc.row_stride;
 #pragma unroll
-          for (int c = 0; c < CPL; c++) q[c] = ld4(qp + (size_t)(c * 64 + lane) * 4);
-          if (METRIC == kCosine) qnorm = dc.norms[qrow];
+          for (int c = 0; c < DIST::kCpl; c++) q[c] = ld4(qp + (size_t)(c * 64 + lane) * 4);
+          if (DIST::kMetric == kCosine) qnorm = dc.norms[qrow];
         } else {
           const float* qp = dc.rows + (size_t)qrow * dc.row_stride;
           for (int i = threadIdx.x; i < d4 * 4; i += 256) qgen[i] = qp[i];  // row padding is zero
-          if (METRIC == kCosine) qnorm = dc.norms[qrow];
+          if (DIST::kMetric == kCosine) qnorm = dc.norms[qrow];
           __syncthreads();
         }
         qrow_loaded = qrow;
       }
-      if (BITS)
-        dist_phase_bits<METRIC>(dc, qbits, m, nb_id, nb_d);
-      else
-        dist_phase_f32<METRIC, CPL>(dc, q, qnorm, qgen, m, nb_id, nb_d, lane, wib);
+      DIST::eval(dc, q, qnorm, qgen, qbits, m, nb_id, nb_d, lane, wib);
       __syncthreads();
     }
     if (a.stats && threadIdx.x == 0) {
@@ -445,6 +496,16 @@ __global__ __launch_bounds__(256) void hnsw_insert_kernel(HnswInsertArgs a) {
     }
     __syncthreads();
   }
+}
+
+template <int METRIC, int CPL>
+__global__ __launch_bounds__(256) void hnsw_insert_kernel(HnswInsertArgs a) {
+  hnsw_insert_body<BuildDistF32<METRIC, CPL>>(a);
+}
+// graph precision F16 / BF16: every distance of the insert over the image (Cosine / Euclidean / DotProduct)
+template <int METRIC, int CPL, bool F16>
+__global__ __launch_bounds__(256) void hnsw_insert_half_kernel(HnswInsertArgs a) {
+  hnsw_insert_body<BuildDistHalf<METRIC, CPL, F16>>(a);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -528,9 +589,8 @@ struct HnswNdistArgs {
   HnswLayerMut layer;
   uint32_t n_nodes, nbmax;
 };
-template <int METRIC, int CPL>
-__global__ __launch_bounds__(256) void hnsw_ndist_kernel(HnswNdistArgs a) {
-  constexpr bool BITS = (METRIC == kHamming || METRIC == kJaccard);
+template <class DIST>
+__device__ __forceinline__ void hnsw_ndist_body(const HnswNdistArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
   const int wib = (int)rfl(threadIdx.x >> 6);
@@ -544,29 +604,36 @@ __global__ __launch_bounds__(256) void hnsw_ndist_kernel(HnswNdistArgs a) {
     const uint32_t c = min(a.layer.cnt[node], a.layer.stride);
     if (c == 0) continue;  // block-uniform
     for (uint32_t t = threadIdx.x; t < c; t += 256) nb_id[t] = a.layer.nbr[(size_t)node * a.layer.stride + t];
-    float4 q[CPL > 0 ? CPL : 1];
+    float4 q[DIST::NQ];
     float qnorm = 0.0f;
-    if (BITS) {
+    if constexpr (DIST::HALF) {
+      DIST::load_row(dc, node, q, qnorm, qgen, d4, lane);
+    } else if (DIST::BITS) {
       for (uint32_t w = threadIdx.x; w < dc.words; w += 256) qbits[w] = dc.bits[(size_t)node * dc.words + w];
-    } else if (CPL > 0) {
+    } else if (DIST::kCpl > 0) {
       const float* qp = dc.rows + (size_t)node * dc.row_stride;
 #pragma unroll
-      for (int cc = 0; cc < CPL; cc++) q[cc] = ld4(qp + (size_t)(cc * 64 + lane) * 4);
-      if (METRIC == kCosine) qnorm = dc.norms[node];
+      for (int cc = 0; cc < DIST::kCpl; cc++) q[cc] = ld4(qp + (size_t)(cc * 64 + lane) * 4);
+      if (DIST::kMetric == kCosine) qnorm = dc.norms[node];
     } else {
       const float* qp = dc.rows + (size_t)node * dc.row_stride;
       for (int i = threadIdx.x; i < d4 * 4; i += 256) qgen[i] = qp[i];
-      if (METRIC == kCosine) qnorm = dc.norms[node];
+      if (DIST::kMetric == kCosine) qnorm = dc.norms[node];
     }
     __syncthreads();
-    if (BITS)
-      dist_phase_bits<METRIC>(dc, qbits, c, nb_id, nb_d);
-    else
-      dist_phase_f32<METRIC, CPL>(dc, q, qnorm, qgen, c, nb_id, nb_d, lane, wib);
+    DIST::eval(dc, q, qnorm, qgen, qbits, c, nb_id, nb_d, lane, wib);
     __syncthreads();
     for (uint32_t t = threadIdx.x; t < c; t += 256) a.layer.ndist[(size_t)node * a.layer.stride + t] = nb_d[t];
     __syncthreads();
   }
+}
+template <int METRIC, int CPL>
+__global__ __launch_bounds__(256) void hnsw_ndist_kernel(HnswNdistArgs a) {
+  hnsw_ndist_body<BuildDistF32<METRIC, CPL>>(a);
+}
+template <int METRIC, int CPL, bool F16>
+__global__ __launch_bounds__(256) void hnsw_ndist_half_kernel(HnswNdistArgs a) {
+  hnsw_ndist_body<BuildDistHalf<METRIC, CPL, F16>>(a);
 }
 
 // ---- host side -----------------------------------------------------------------------------
@@ -595,7 +662,48 @@ static hipError_t launch_ndist_t(const HnswNdistArgs& a, int blocks, size_t lds,
   return hipGetLastError();
 }
 
-#define VDB_DISPATCH_METRIC_CPL(FN, metric, dim, ...)                                   \
+template <int METRIC, int CPL, bool F16>
+static hipError_t launch_insert_half_t(const HnswInsertArgs& a, int slots, size_t lds, hipStream_t st) {
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hnsw_insert_half_kernel<METRIC, CPL, F16>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((hnsw_insert_half_kernel<METRIC, CPL, F16>), dim3(slots), dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+template <int METRIC, int CPL, bool F16>
+static hipError_t launch_ndist_half_t(const HnswNdistArgs& a, int blocks, size_t lds, hipStream_t st) {
+  hipLaunchKernelGGL((hnsw_ndist_half_kernel<METRIC, CPL, F16>), dim3(blocks), dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+// the half families: Cosine / Euclidean / DotProduct x CPL 0-4 x f16 / bf16 (FN<METRIC, CPL, F16>)
+#define VDB_DISPATCH_HALF_CPL_(FN, M_, F16_, cpl_, ...)          \
+  switch (cpl_) {                                                \
+    case 1: return FN<M_, 1, F16_>(__VA_ARGS__);                 \
+    case 2: return FN<M_, 2, F16_>(__VA_ARGS__);                 \
+    case 3: return FN<M_, 3, F16_>(__VA_ARGS__);                 \
+    case 4: return FN<M_, 4, F16_>(__VA_ARGS__);                 \
+    default: return FN<M_, 0, F16_>(__VA_ARGS__);                \
+  }
+#define VDB_DISPATCH_HALF_METRIC_(FN, metric, F16_, cpl_, ...)                          \
+  switch (metric) {                                                                     \
+    case kCosine: VDB_DISPATCH_HALF_CPL_(FN, kCosine, F16_, cpl_, __VA_ARGS__)          \
+    case kEuclidean: VDB_DISPATCH_HALF_CPL_(FN, kEuclidean, F16_, cpl_, __VA_ARGS__)    \
+    default: VDB_DISPATCH_HALF_CPL_(FN, kDot, F16_, cpl_, __VA_ARGS__)                  \
+  }
+#define VDB_DISPATCH_HALF(FN, metric, dim, f16, ...)                                    \
+  [&]() -> hipError_t {                                                                 \
+    const int cpl_ = sweep_cpl_for_dim(dim);                                            \
+    if (f16) {                                                                          \
+      VDB_DISPATCH_HALF_METRIC_(FN, metric, true, cpl_, __VA_ARGS__)                    \
+    } else {                                                                            \
+      VDB_DISPATCH_HALF_METRIC_(FN, metric, false, cpl_, __VA_ARGS__)                   \
+    }                                                                                   \
+  }()
+
+#define VDB_DISPATCH_METRIC_CPL(FN, metric, dim, ...)                                 \
   [&]() -> hipError_t {                                                                 \
     const int cpl_ = sweep_cpl_for_dim(dim);                                            \
     switch (metric) {                                                                   \
@@ -662,10 +770,30 @@ uint32_t build_batch_size(uint64_t linked, uint32_t max_batch) {
   return (uint32_t)b;
 }
 
-// distance cache of a loaded graph (one-off, before the first insert into it)
+// The rows construction takes its distances over: the handle's graph precision (vdb_hip_index_set_graph_precision).  F16 / BF16:
+// the image, its stride in half elements and the norms of the rounded rows — what hnsw_search_half_dev hands the walk.
+static int32_t build_dist_ctx(vdb_hip_index* ix, DistCtx* dc) {
+  if (ix->graph_precision == VDB_PRECISION_F32) {
+    *dc = DistCtx{ix->rows.as<float>(), ix->norms.as<float>(), ix->bits.as<uint32_t>(), ix->row_stride, ix->dim, ix->words};
+    return VDB_OK;
+  }
+  const bool f16 = ix->graph_precision == VDB_PRECISION_F16;
+  // (set_graph_precision checked the image and the metric; an image is never dropped, and every row is converted as it arrives)
+  if (!(f16 ? ix->f16_enabled : ix->bf16_enabled) || (f16 ? ix->f16_rows : ix->bf16_rows) < ix->n_rows)
+    return fail(VDB_ERR_STATE, "graph construction: the half-precision image of the graph precision does not cover every row");
+  *dc = DistCtx{reinterpret_cast<const float*>(f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>()),
+                f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>(), nullptr, ix->bf16_stride, ix->dim, 0};
+  return VDB_OK;
+}
+
+// distance cache of a graph that has none in the graph precision (loaded from files, or the precision changed): before the next
+// insert into it
 int32_t graph_fill_ndist(vdb_hip_index* ix) {
   if (ix->ndist_valid) return VDB_OK;
   hipStream_t st = ix->stream;
+  DistCtx dc{};
+  const int32_t rdc = build_dist_ctx(ix, &dc);
+  if (rdc != VDB_OK) return rdc;
   for (size_t l = 0; l < ix->layers.size(); l++) {
     GraphLayer& L = ix->layers[l];
     hipError_t e = L.ndist.reserve(std::max<size_t>(ix->capacity * L.stride * 4, 4), false, st);
@@ -674,8 +802,7 @@ int32_t graph_fill_ndist(vdb_hip_index* ix) {
   if (ix->graph_nodes) {
     for (size_t l = 0; l < ix->layers.size(); l++) {
       HnswNdistArgs a{};
-      a.dc = DistCtx{ix->rows.as<float>(), ix->norms.as<float>(), ix->bits.as<uint32_t>(), ix->row_stride, ix->dim,
-                     ix->words};
+      a.dc = dc;
       HnswLayerMut lm[kMaxLayers] = {};
       fill_layers(ix, lm, nullptr);
       a.layer = lm[l];
@@ -687,7 +814,10 @@ int32_t graph_fill_ndist(vdb_hip_index* ix) {
       else if (sweep_cpl_for_dim(ix->dim) == 0)
         lds += (size_t)((ix->dim + 3) / 4) * 16;
       const int blocks = (int)std::min<uint64_t>(ix->graph_nodes, (uint64_t)ix->n_cus * 8);
-      hipError_t e = VDB_DISPATCH_METRIC_CPL(launch_ndist_t, ix->metric, ix->dim, a, blocks, lds, st);
+      hipError_t e = ix->graph_precision == VDB_PRECISION_F32
+                         ? VDB_DISPATCH_METRIC_CPL(launch_ndist_t, ix->metric, ix->dim, a, blocks, lds, st)
+                         : VDB_DISPATCH_HALF(launch_ndist_half_t, ix->metric, ix->dim, ix->graph_precision == VDB_PRECISION_F16, a, blocks,
+                                             lds, st);
       if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("ndist launch: ") + hipGetErrorString(e));
     }
   }
@@ -725,8 +855,9 @@ static int32_t graph_insert_rows_impl(vdb_hip_index* ix, uint64_t first, uint64_
   HnswInsertArgs a{};
   uint32_t max_stride = 0;
   fill_layers(ix, a.layers, &max_stride);
-  a.dc = DistCtx{ix->rows.as<float>(), ix->norms.as<float>(), ix->bits.as<uint32_t>(), ix->row_stride, ix->dim,
-                 ix->words};
+  rc = build_dist_ctx(ix, &a.dc);
+  if (rc != VDB_OK) return rc;
+  const bool half = ix->graph_precision != VDB_PRECISION_F32, half_f16 = ix->graph_precision == VDB_PRECISION_F16;
   const uint32_t ef = std::max<uint32_t>(ix->efc, 1);
   a.ef = ef;
   uint64_t cap = (uint64_t)ef + std::max<uint64_t>(64, ef / 2);
@@ -793,7 +924,8 @@ static int32_t graph_insert_rows_impl(vdb_hip_index* ix, uint64_t first, uint64_
         VDB_HIP(hipMemsetAsync(d_req_n, 0, 8, st));  // request counter + overflow flags
         VDB_HIP(hipMemsetAsync(keys_in, 0xFF, (size_t)nreq * 8, st));
         const int slots = (int)std::min<uint64_t>(b, (uint64_t)ix->n_cus * per_cu);
-        e = VDB_DISPATCH_METRIC_CPL(launch_insert_t, ix->metric, ix->dim, a, slots, lds, st);
+        e = half ? VDB_DISPATCH_HALF(launch_insert_half_t, ix->metric, ix->dim, half_f16, a, slots, lds, st)
+                 : VDB_DISPATCH_METRIC_CPL(launch_insert_t, ix->metric, ix->dim, a, slots, lds, st);
         if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("insert launch: ") + hipGetErrorString(e));
         // The insert kernel only writes the NEW nodes' own lists and the request buffer (back-links are applied by the
         // link kernel below), so a batch can be repeated.  Candidates tied with the worst result stay in the list

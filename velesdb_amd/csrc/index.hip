@@ -221,6 +221,7 @@ static void copy_data_fields(vdb_hip_index* c, const vdb_hip_index* p) {
   c->live = p->live;
   c->any_dead = p->any_dead;
   c->ndist_valid = p->ndist_valid;
+  c->graph_precision = p->graph_precision;
   copy_image_fields(c, p);
 }
 static thread_local vdb_hip_index* tl_ctx = nullptr;        // the context of this thread's last search ...
@@ -1682,6 +1683,43 @@ int32_t vdb_hip_index_enable_half_precision(vdb_hip_index* ix, int32_t precision
   if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
     return fail(VDB_ERR_UNSUPPORTED, "half precision: Cosine, DotProduct and Euclidean only");
   return enable_half_locked(ix, precision);
+  });
+}
+
+// The row format graph construction takes its distances over (hnsw_build.hip build_dist_ctx).  A change invalidates the cached
+// neighbour distances: graph_fill_ndist recomputes them in the new precision before the next insert (back-link pruning ranks by them,
+// the reference recomputes a full list's distances from the vectors it holds at every prune).  Not persisted.
+int32_t vdb_hip_index_set_graph_precision(vdb_hip_index* ix, int32_t precision) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix) return fail(VDB_ERR_INVALID_ARG, "null argument");
+  if (precision != VDB_PRECISION_F32 && precision != VDB_PRECISION_F16 && precision != VDB_PRECISION_BF16)
+    return fail(VDB_ERR_INVALID_ARG, "bad vector precision");
+  VDB_NO_GROUP(ix, "set_graph_precision");
+  std::lock_guard<vdb::IndexMutex> g(ix->mu);
+  if (precision != VDB_PRECISION_F32) {
+    if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+      return fail(VDB_ERR_UNSUPPORTED, "half-precision graph construction: Cosine, DotProduct and Euclidean only");
+    // (the statuses of the half walks, hnsw_half.hip)
+    if (precision == VDB_PRECISION_F16 && !ix->f16_enabled)
+      return fail(VDB_ERR_STATE, "f16 graph precision: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
+    if (precision == VDB_PRECISION_BF16 && !ix->bf16_enabled)
+      return fail(VDB_ERR_STATE, "bf16 graph precision: call vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16) first");
+  }
+  VDB_ENTER(ix);
+  if (precision != ix->graph_precision) {
+    ix->graph_precision = precision;
+    ix->ndist_valid = false;
+  }
+  mark_changed(ix);
+  return VDB_OK;
+  });
+}
+int32_t vdb_hip_index_graph_precision(const vdb_hip_index* ix, int32_t* precision) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || !precision) return fail(VDB_ERR_INVALID_ARG, "null argument");
+  std::shared_lock<vdb::IndexMutex> g(ix->mu);  // (a pure read: searches go on)
+  *precision = ix->graph_precision;
+  return VDB_OK;
   });
 }
 

@@ -505,6 +505,11 @@ __device__ __forceinline__ float4 half4_to_f32(const uint2& w) {
                 __uint_as_float(w.y & 0xFFFF0000u)};
 }
 __device__ __forceinline__ uint2 ld_half4(const uint16_t* p) { return *reinterpret_cast<const uint2*>(p); }
+template <bool F16>
+__device__ __forceinline__ float half1_to_f32(uint16_t h) {  // one half element as f32 (exact)
+  if (F16) return (float)__builtin_bit_cast(_Float16, h);
+  return __uint_as_float((uint32_t)h << 16);
+}
 
 // nb_id[0..m) -> nb_d[0..m) over the half image: half_precision::dot_product / cosine_similarity / euclidean_distance
 // (half_precision.rs:199-287) as DistanceEngine::distance reports them (-dot, 1 - cosine, the root).  The summation order is

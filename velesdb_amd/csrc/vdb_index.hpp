@@ -229,6 +229,9 @@ struct vdb_hip_index {
   uint32_t max_layer = 0;
   uint64_t graph_nodes = 0;  // nodes linked
   uint64_t rng_state = 0x5DEECE66D1A4B5B5ull;  // native/graph.rs:72
+  // the row format every distance of graph CONSTRUCTION is taken over (vdb_hip_index_set_graph_precision): the f32 rows, or the
+  // f16 / bf16 image (hnsw_build.hip build_dist_ctx).  Not persisted; vacuum keeps it.
+  int32_t graph_precision = VDB_PRECISION_F32;
 
   // id mappings (host)
   std::unordered_map<uint64_t, uint64_t> id_to_idx;

@@ -481,6 +481,19 @@ class HnswIndex:
         search_batch_brute_force_half: Cosine, DotProduct and Euclidean indexes; F16 and BF16 may both be enabled."""
         check(lib().vdb_hip_index_enable_half_precision(self._h, int(precision)))
 
+    def set_graph_precision(self, precision) -> None:
+        """The row format every distance of graph construction is taken over from now on (insert, insert_batch*, build_graph,
+        the rebuild inside vacuum): F32 (default) or — after enable_half_precision(precision) — F16 / BF16, the image the half
+        walks read.  The graph is then the reference's over the dequantised rows, link for link.  Allowed on a graph that has
+        nodes (the cached neighbour distances are recomputed in the new precision before the next insert).  Not persisted: a
+        loaded index starts at F32."""
+        check(lib().vdb_hip_index_set_graph_precision(self._h, int(precision)))
+
+    def graph_precision(self) -> VectorPrecision:
+        p = C.c_int32(0)
+        check(lib().vdb_hip_index_graph_precision(self._h, C.byref(p)))
+        return VectorPrecision(p.value)
+
     def search_batch_brute_force_half(self, queries, k: int, precision):
         """Exact scan over the half-precision copy of the rows with queries rounded the same way: half_precision::dot_product /
         cosine_similarity / euclidean_distance on VectorData::{F16, BF16} (half_precision.rs:199-287); numpy outputs like
