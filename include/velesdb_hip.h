@@ -371,7 +371,7 @@ int32_t vdb_hip_index_search_graph_filtered(vdb_hip_index* idx, const void* f, c
  * filter_of_query value > n_filters, route outside 0..2: VDB_ERR_INVALID_ARG; a stale filter or no graph: VDB_ERR_STATE; mode other
  * than VDB_SEARCH_HNSW, multi-device handles and process-group members: VDB_ERR_UNSUPPORTED.  The outputs are untouched on error.
  * Host pointers only; launches of its own (no combining front).  vdb_hip_index_last_kernels: VDB_KERNEL_HNSW_FILTERED and / or
- * VDB_KERNEL_FILTER_RANK (the per-query kernels are instances of those families). */
+ * VDB_KERNEL_FILTER_RANK (one kernel family serves this call and the one above). */
 int32_t vdb_hip_index_search_graph_filters(vdb_hip_index* idx, void** filters, uint32_t n_filters,
                                            const uint32_t* filter_of_query, const float* queries_rowmajor, uint32_t nq,
                                            uint32_t k, uint32_t ef, int32_t mode, int32_t route, uint32_t max_list,
@@ -623,8 +623,8 @@ enum vdb_kernel_bit {
   VDB_KERNEL_SWEEP_HALF_L2 = 16384, /* sweep_topk_half_l2 (Euclidean difference chain over the f16 / bf16 rows)                       */
   VDB_KERNEL_HNSW_HALF = 32768,    /* hnsw_search_half_kernel (VDB_SEARCH_HNSW_F16 / _BF16; VDB_KERNEL_F16 next to it for the f16 instance) */
   VDB_KERNEL_SWEEP_LISTED = 65536, /* sweep_topk_listed / sweep_topk_listed_m (vdb_hip_index_search_batch_filtered, the listed route) */
-  VDB_KERNEL_HNSW_FILTERED = 131072, /* hnsw_search_filtered_kernel (vdb_hip_index_search_graph_filtered, the walk)                    */
-  VDB_KERNEL_FILTER_RANK = 262144  /* filter_rank_kernel (vdb_hip_index_search_graph_filtered, the exact pass)                       */
+  VDB_KERNEL_HNSW_FILTERED = 131072, /* hnsw_search_filters_kernel (vdb_hip_index_search_graph_filtered / _filters, the walk)            */
+  VDB_KERNEL_FILTER_RANK = 262144  /* filters_rank_kernel (vdb_hip_index_search_graph_filtered / _filters, the exact pass)             */
 };
 /* one more bit of the same mask: fuse_lists_kernel ran (vdb_hip_index_multi_query_search sets it next to the walk's bits).  A macro
  * beside the enum, not an enumerator: tests/test_filters_graph_cpu.py pins VDB_KERNEL_FILTER_RANK as the enum's last member. */

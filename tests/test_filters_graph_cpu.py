@@ -1,7 +1,8 @@
 """One filter per query in one graph call (vdb_hip_index_search_graph_filters), the part that needs no GPU: the entry
 point agrees between the header, the ctypes table and the Rust raw bindings; the library exports it; the safe Rust wrapper and the
 Python method reach it; without a device the call fails with a status; and the launch plan (filters_plan_round /
-filters_walk_ladders in velesdb_amd/csrc/vdb_filter_route.hpp, compiled stand-alone) keeps every query on the ladder it climbs alone."""
+filters_walk_ladders in velesdb_amd/csrc/vdb_filter_route.hpp, compiled stand-alone) keeps every query on the ladder it climbs alone
+— and runs a call whose queries all share one filter as the one-filter call's own host loop ran it."""
 import ctypes as C
 import json
 import os
@@ -105,3 +106,8 @@ def test_launch_plan_keeps_every_query_on_its_own_ladder(tmp_path):
     # the generated calls reached what the plan is for: rounds of several launches, launches whose queries differ in list capacity,
     # re-runs, and calls that fail as a whole
     assert min(line["split_rounds"], line["mixed_launches"], line["rerun_rounds"], line["failed_calls"]) > 1000, line
+    # ... and the calls with every query on one filter — held to the host loop the one-filter call once had — reached re-runs, exact
+    # passes behind the largest list, whole-call exact passes and refusals
+    assert line["one_filter_cases"] > 10000, line
+    assert min(line["one_filter_rerun_rounds"], line["one_filter_exact_after_walk"], line["one_filter_exact_calls"],
+               line["one_filter_failed_calls"]) > 1000, line

@@ -6,6 +6,7 @@ the exact pass as a plain sort.  Everything is compared bit for bit — ids, ran
 call's n_dist / n_expand; there are no tolerances.  Shapes are those of tests/half_walk_ref.py (CPL 0, CPL 3, dim % 4 != 0), one
 oracle graph and one GPU handle per (metric, shape); the handle loads the oracle's dump, so both sides walk the same links.
 """
+import ctypes as C
 import os
 import threading
 
@@ -239,28 +240,38 @@ def test_routes(worlds, metric, shape):
 
 
 # ---- 4. per-query fallback -----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("metric", F32_METRICS)
-def test_queries_that_overflow_the_largest_list_take_the_exact_pass_alone(worlds, metric):
+def overflow_case(w):
     """Density 1/10, all of it at one end of the data: the 10 % of the rows with the largest first coordinate, and queries pushed
     along that coordinate by +30 ... -30 — towards the allowed rows a query fills its results at once, away from them it admits
-    most of the graph first.  max_list is chosen with the reference so that some but not all of the 20 queries overflow it."""
-    w, k, ef = worlds(metric, hw.SHAPES[0]), 10, 16
-    allowed = np.zeros(w.n, dtype=bool)
-    allowed[np.argsort(w.rows[:, 0])[-w.n // 10:]] = True
-    qs = w.qs.copy()
-    qs[:, 0] += np.resize(np.array([30, -30, 0, -4, -8, -2], dtype=np.float32), NQ)
-    ef_eff, matched = fw.ef_rule(k, ef), int(allowed.sum())
-    sized = fw.sized_list(ef_eff, matched, w.n)
-    chosen = None
-    for max_list in (4 * sized, 2 * sized, sized):  # (below `sized` the auto rule sends the whole call to the exact pass)
-        over = [protocol(w.G, q, k, ef_eff, allowed, sized, max_list)[1] for q in qs]
-        if 0 < sum(over) < NQ:
-            chosen = max_list
-            break
-    assert chosen is not None, "no list size splits the queries: the case is meaningless"
-    want = expect_call(w, allowed, k, ef, va.ROUTE_AUTO, max_list=chosen, qs=qs)
-    assert 1 in want[2] and 2 in want[2]
-    print(f"metric {metric}: max_list {chosen} (first list {sized}), routes {want[2]}")
+    most of the graph first.  max_list is chosen with the reference so that some but not all of the 20 queries overflow it.
+    -> (allowed, qs, k, ef, max_list, the reference's call); computed once per world"""
+    if getattr(w, "_overflow_case", None) is None:
+        k, ef = 10, 16
+        allowed = np.zeros(w.n, dtype=bool)
+        allowed[np.argsort(w.rows[:, 0])[-w.n // 10:]] = True
+        qs = w.qs.copy()
+        qs[:, 0] += np.resize(np.array([30, -30, 0, -4, -8, -2], dtype=np.float32), NQ)
+        ef_eff, matched = fw.ef_rule(k, ef), int(allowed.sum())
+        sized = fw.sized_list(ef_eff, matched, w.n)
+        chosen = None
+        for max_list in (4 * sized, 2 * sized, sized):  # (below `sized` the auto rule sends the whole call to the exact pass)
+            over = [protocol(w.G, q, k, ef_eff, allowed, sized, max_list)[1] for q in qs]
+            if 0 < sum(over) < NQ:
+                chosen = max_list
+                break
+        assert chosen is not None, "no list size splits the queries: the case is meaningless"
+        want = expect_call(w, allowed, k, ef, va.ROUTE_AUTO, max_list=chosen, qs=qs)
+        assert 1 in want[2] and 2 in want[2]
+        print(f"metric {w.metric}: max_list {chosen} (first list {sized}), routes {want[2]}")
+        w._overflow_case = (allowed, qs, k, ef, chosen, want)
+    return w._overflow_case
+
+
+@pytest.mark.parametrize("metric", F32_METRICS)
+def test_queries_that_overflow_the_largest_list_take_the_exact_pass_alone(worlds, metric):
+    """overflow_case: some queries of the call answer from the walk, the others overflow the largest list and take the exact pass"""
+    w = worlds(metric, hw.SHAPES[0])
+    allowed, qs, k, ef, chosen, want = overflow_case(w)
     with w.ix.create_filter(np.flatnonzero(allowed).astype(np.uint64)) as flt:
         out, routes = w.ix.search_batch_filtered_graph(qs, k, flt, ef=ef, route=va.ROUTE_AUTO, max_list=chosen)
         stats, kern = w.ix.last_search_stats(), w.ix.last_kernels()
@@ -274,6 +285,25 @@ def test_queries_that_overflow_the_largest_list_take_the_exact_pass_alone(worlds
         with pytest.raises(va.VelesHipError) as e:
             w.ix.search_batch_filtered_graph(qs, k, flt, ef=ef, route=va.ROUTE_WALK, max_list=chosen)
         assert e.value.code == UNSUPPORTED and "route" in str(e.value) and "max_list" in str(e.value)
+
+
+def test_call_without_out_route_gives_the_same_answer(worlds):
+    """out_route is nullable at the C level; multi-query fusion is the only caller inside the library that leaves it out.  The same
+    one-filter call with and without it — walks, re-runs and exact passes in one call (overflow_case) — gives the same ids, score
+    bits and out_n."""
+    from velesdb_amd import _ffi
+    w = worlds(po.COSINE, hw.SHAPES[0])
+    allowed, qs, k, ef, chosen, want = overflow_case(w)
+    with w.ix.create_filter(np.flatnonzero(allowed).astype(np.uint64)) as flt:
+        (ids, sc, cnt), routes = w.ix.search_batch_filtered_graph(qs, k, flt, ef=ef, route=va.ROUTE_AUTO, max_list=chosen)
+        assert routes.tolist() == want[2]
+        q32 = np.ascontiguousarray(qs, dtype=np.float32)
+        ids0, sc0, cnt0 = np.zeros((NQ, k), dtype=np.uint64), np.zeros((NQ, k), dtype=np.float32), np.full(NQ, 77, dtype=np.uint32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        rc = _ffi.lib().vdb_hip_index_search_graph_filtered(w.ix._h, flt._h, vp(q32), NQ, k, ef, va.MODE_HNSW, va.ROUTE_AUTO, chosen,
+                                                            vp(ids0), vp(sc0), vp(cnt0), None)
+        assert rc == 0, _ffi.last_error()
+        assert np.array_equal(ids0, ids) and np.array_equal(sc0.view(np.uint32), sc.view(np.uint32)) and np.array_equal(cnt0, cnt)
 
 
 # ---- 5. life cycle --------------------------------------------------------------------------------------------------------------------

@@ -2,8 +2,12 @@
 
 The contract under test: query i of a mixed batch gets, bit for bit, what search_batch_filtered_graph returns for that query ALONE
 with its filter and the same k, ef, route, max_list — ids, ranks, score bits, out_n, padding, its route, and its share of the call's
-n_dist / n_expand.  "No filter" is compared against create_filter([], negate=True).  So that the tests do not rest on the product
-alone, (k, ef) = (10, 64) is also checked against tests/filtered_walk_ref.py at the query's own ladder.  No tolerances anywhere.
+n_dist / n_expand.  "No filter" is compared against create_filter([], negate=True).  The one-query call goes through the same host
+path and the same kernels as the batch (the one-filter entry point is the per-query one with a table of one filter), so this is a
+batch held against its queries one at a time: what a query computes must not depend on its companions or on the launches it shares.
+So that the tests do not rest on the product alone, (k, ef) = (10, 64) is also checked against tests/filtered_walk_ref.py (a Python
+model, never the product) at the query's own ladder, as tests/test_gpu_filtered_graph.py checks the one-filter entry point.  No
+tolerances anywhere.
 Worlds (oracle graph, dump, GPU handle, the five named filters), the reference protocol and the shapes are those of
 tests/test_gpu_filtered_graph.py.
 """

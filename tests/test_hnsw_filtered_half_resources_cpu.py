@@ -1,5 +1,5 @@
 """What the compiler made of the filtered graph walk and its exact pass over the half-precision images (hnsw_filtered.hip, DESIGN
-4.1k), read from the built library like tests/test_hnsw_filtered_resources_cpu.py: every instance the dispatch can reach exists —
+4.1k), read from the built library like tests/test_hnsw_filters_resources_cpu.py: every instance the dispatch can reach exists —
 three metrics x CPL 0-4 x f16 / bf16 in the per-query form — and none of them uses scratch memory, spills a vector register or
 needs a dynamic stack; all of them keep the four 256-thread walks per CU the launch assumes."""
 import os

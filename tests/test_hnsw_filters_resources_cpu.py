@@ -1,8 +1,8 @@
-"""What the compiler made of the per-query forms of the filtered graph walk and its exact pass (hnsw_search_filters_kernel /
-filters_rank_kernel, hnsw_filtered.hip), read from the built library like tests/test_hnsw_filtered_resources_cpu.py:
-every instance the dispatch can reach exists, at four walks per CU, without scratch memory, vector spills or a dynamic stack — and
-the descriptor loads left the LDS state and the filter reads off the flat path.  The two single-filter families share their bodies
-with these and still meet the same pins."""
+"""What the compiler made of the filtered graph walk and its exact pass (hnsw_search_filters_kernel / filters_rank_kernel,
+hnsw_filtered.hip), read from the built library like tests/test_hnsw_half_resources_cpu.py: every instance the
+dispatch can reach exists, at four walks per CU, without scratch memory, vector spills or a dynamic stack — and the descriptor
+loads left the LDS state and the filter reads off the flat path.  These two families serve the one-filter call
+(vdb_hip_index_search_graph_filtered) as well: the families it once had of its own are gone from the library."""
 import os
 import sys
 
@@ -17,7 +17,7 @@ pytest.importorskip("msgpack")
 COSINE, EUCLIDEAN, DOT, HAMMING, JACCARD = 0, 1, 2, 3, 4
 INSTANCES = [(m, cpl) for m in (COSINE, EUCLIDEAN, DOT) for cpl in (0, 1, 2, 3, 4)] + [(HAMMING, 0), (JACCARD, 0)]
 NEW = ["hnsw_search_filters_kernel", "filters_rank_kernel"]
-OLD = ["hnsw_search_filtered_kernel", "filter_rank_kernel"]
+RETIRED = ["hnsw_search_filtered_kernel", "filter_rank_kernel"]
 
 
 @pytest.fixture(scope="module")
@@ -26,7 +26,7 @@ def kernels():
     return {k["name"]: k for k in kr.kernels()}
 
 
-@pytest.mark.parametrize("family", NEW + OLD)
+@pytest.mark.parametrize("family", NEW)
 def test_every_instance_exists_at_four_waves_without_scratch(kernels, family):
     fam = [n for n in kernels if kr.family(n) == family]
     want = {f"vdb::{family}<{m}, {cpl}>" for m, cpl in INSTANCES}
@@ -35,6 +35,10 @@ def test_every_instance_exists_at_four_waves_without_scratch(kernels, family):
         k = kernels[n]
         assert k["block"] == 256 and k["waves_per_simd"] >= 4, k
         assert k["scratch"] == 0 and k["vgpr_spill"] == 0 and not k["dynamic_stack"], k
+
+
+def test_the_one_filter_families_are_gone(kernels):
+    assert [n for n in kernels if kr.family(n) in RETIRED] == []
 
 
 @pytest.mark.skipif(not os.path.exists(kr.OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")

@@ -1,4 +1,4 @@
-// hnsw_filtered.hip — filtered graph search (vdb_hip_index_search_graph_filtered): NativeHnsw::search
+// hnsw_filtered.hip — filtered graph search (vdb_hip_index_search_graph_filtered / _filters): NativeHnsw::search
 // (native/graph.rs:251-270) with an id allow-list consulted where a node enters the RESULT set.
 //
 // Semantics.  allowed(r) = r < the filter's row count, its bit r set, row r alive now.  The greedy descent (graph.rs:405-428) is
@@ -15,16 +15,17 @@
 // the two-heap form still needs (an unexpanded candidate; or an allowed entry while the results are not full) sets the overflow
 // flag, the query finishes anyway and reports out_n = 0xFFFFFFFF; the host re-runs it with more room or answers it exactly.
 //
-// filter_rank_kernel is that exact answer: top-k of the allowed live rows by (total-order(distance), row), the distances from the
+// filters_rank_kernel is that exact answer: top-k of the allowed live rows by (total-order(distance), row), the distances from the
 // walk's own DIST::eval — bit for bit what the walk reports for the same row.
 //
-// One filter per query (vdb_hip_index_search_graph_filters): hnsw_search_filters_kernel / filters_rank_kernel are the
-// same two bodies with the filter taken from a per-slot descriptor instead of the argument struct; a launch's LDS layout follows its
-// PHYSICAL list capacity, every query's list logic its own LOGICAL one, so queries with lists of different sizes share launches and
-// each computes what it computes alone.
+// One kernel family, one host path.  hnsw_search_filters_kernel / filters_rank_kernel take every query's filter from a per-slot
+// descriptor (vdb_hip_index_search_graph_filters, DESIGN 4.1i: one filter per query); a launch's LDS layout follows its PHYSICAL
+// list capacity, every query's list logic its own LOGICAL one, so queries with lists of different sizes share launches and each
+// computes what it computes alone.  The one-filter call (vdb_hip_index_search_graph_filtered) is that path with a table of one
+// filter and every query on it: search_graph_filtered_to_device at the end of the file.
 //
 // Over the half-precision images (vdb_hip_index_search_graph_filters_half): hnsw_search_filters_half_kernel /
-// filters_rank_half_kernel are the same two bodies in the per-query form with the half walk's distance phase (WalkDistHalf,
+// filters_rank_half_kernel are the same two bodies with the half walk's distance phase (WalkDistHalf,
 // hnsw_half.hip) — the query rounded to the precision against the row's f16 / bf16 image, n_dist * (2 * stride [+ 4 Cosine]) row bytes.
 //
 // Algorithmic HBM bytes per query: walk n_dist * dim * 4 + n_expand * M0 * 4 + (admitted neighbours) * 4 for the bitmap words;
@@ -39,17 +40,8 @@
 
 namespace vdb {
 
-struct HnswFilteredArgs {
-  HnswSearchArgs s;           // (s.nq = the queries of THIS launch; s.stats unused)
-  const uint32_t* f_bitmap;   // bit r % 32 of word r / 32, f_rows bits
-  const uint32_t* f_list;     // [f_count] ascending rows (the exact pass)
-  uint32_t f_rows, f_count;
-  const uint32_t* qmap;       // nullable: launch slot -> query index (re-runs and the exact pass of single queries)
-  unsigned long long* qstats; // [nq_total][2]: the walk WRITES a query's n_dist / n_expand, the exact pass ADDS its rows to n_dist
-};
-
-// one filter per query (vdb_hip_index_search_graph_filters): a table of n_filters + 1 descriptors — the last one is "no
-// filter": null bitmap and list, rows = count = the index's rows now — and one FiltersSlot (vdb_filter_route.hpp) per launch slot
+// The filters of a call: a table of n_filters + 1 descriptors — the last one is "no filter": null bitmap and list, rows = count = the
+// index's rows now — and one FiltersSlot (vdb_filter_route.hpp) per launch slot
 struct FilterDesc {
   const uint32_t* bitmap;
   const uint32_t* list;
@@ -59,7 +51,7 @@ struct HnswFiltersArgs {
   HnswSearchArgs s;           // (s.nq = the slots of THIS launch; s.cap = its PHYSICAL list capacity: the LDS layout)
   const FilterDesc* descs;    // [n_filters + 1]
   const FiltersSlot* slots;   // [s.nq]
-  unsigned long long* qstats; // as HnswFilteredArgs::qstats
+  unsigned long long* qstats; // [nq][2]: the walk WRITES a query's n_dist / n_expand, the exact pass ADDS its rows to n_dist
 };
 
 constexpr uint32_t kFlagExpanded = 1u, kFlagAllowed = 2u;
@@ -74,37 +66,25 @@ struct SlotFilter {
   glb_u32_p list;
   uint32_t rows, count, qi, cap;
 };
-// where the bodies below find it — the call's one filter in the argument struct ...
-struct OneFilterSrc {
-  static constexpr bool kOpen = false;  // there is always a bitmap and a list
-  const HnswFilteredArgs& fa;
-  __device__ __forceinline__ SlotFilter load(uint32_t slot) const {
-    return SlotFilter{(glb_u32_p)fa.f_bitmap, (glb_u32_p)fa.f_list, fa.f_rows, fa.f_count, fa.qmap ? fa.qmap[slot] : slot, fa.s.cap};
-  }
-};
 __device__ __forceinline__ glb_u32_p uniform_ptr(const uint32_t* p) {
   const uint64_t v = (uint64_t)p;
   return (glb_u32_p)(((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | (uint64_t)rfl((uint32_t)v));
 }
-// ... or the slot's descriptor, loaded once per query into scalar registers (rfl as for wib): the per-neighbour bitmap test stays
-// one dword load from a scalar base
-struct SlotTableSrc {
-  static constexpr bool kOpen = true;  // a null bitmap / list = every row below `rows`
-  const HnswFiltersArgs& fa;
-  __device__ __forceinline__ SlotFilter load(uint32_t slot) const {
-    const FiltersSlot s = fa.slots[slot];
-    const uint32_t fi = rfl(s.filter);
-    const FilterDesc d = fa.descs[fi];
-    SlotFilter f;
-    f.bitmap = uniform_ptr(d.bitmap);
-    f.list = uniform_ptr(d.list);
-    f.rows = rfl(d.rows);
-    f.count = rfl(d.count);
-    f.qi = rfl(s.query);
-    f.cap = min(rfl(s.cap), fa.s.cap);  // (never past the layout, whatever the table says)
-    return f;
-  }
-};
+// the slot's descriptor, loaded once per query into scalar registers (rfl as for wib): the per-neighbour bitmap test stays one dword
+// load from a scalar base.  A null bitmap / list = every row below `rows`.
+__device__ __forceinline__ SlotFilter load_slot_filter(const HnswFiltersArgs& fa, uint32_t slot) {
+  const FiltersSlot s = fa.slots[slot];
+  const uint32_t fi = rfl(s.filter);
+  const FilterDesc d = fa.descs[fi];
+  SlotFilter f;
+  f.bitmap = uniform_ptr(d.bitmap);
+  f.list = uniform_ptr(d.list);
+  f.rows = rfl(d.rows);
+  f.count = rfl(d.count);
+  f.qi = rfl(s.query);
+  f.cap = min(rfl(s.cap), fa.s.cap);  // (never past the layout, whatever the table says)
+  return f;
+}
 
 // list_insert (vdb_hnsw_device.hpp) with the new entry's flag given and the lost entry reported: lost = 1 when an entry fell off
 // (the key itself when it sorts behind a full list), lost_flag = its flags
@@ -179,10 +159,9 @@ __device__ __forceinline__ void pivot_truncate(lds_vu64* keys, uint32_t& cnt, ui
   cnt = last + 1;
 }
 
-template <bool OPEN>
 __device__ __forceinline__ uint32_t row_allowed(const SlotFilter& f, const uint8_t* alive, uint32_t r) {  // r wave-uniform
   if (r >= f.rows) return 0u;
-  if (!(OPEN && f.bitmap == nullptr) && ((f.bitmap[r >> 5] >> (r & 31)) & 1u) == 0u) return 0u;
+  if (f.bitmap != nullptr && ((f.bitmap[r >> 5] >> (r & 31)) & 1u) == 0u) return 0u;
   if (alive && alive[r] == 0) return 0u;
   return kFlagAllowed;
 }
@@ -200,27 +179,23 @@ constexpr int kFiltHalfRows = (CPL == 4 ? 4 : 8);
 template <int METRIC, int CPL, bool F16>
 using FiltDistHalf = WalkDistHalf<METRIC, CPL, 4, kFiltHalfRows<METRIC, CPL>, F16>;
 
-// LDS: hnsw_lds_bytes' layout — keys[cap] u64 | nb_id[nbmax] | nb_d[nbmax] | ctl[4] | flags[cap] u8 (padded) | query scratch
-// (the walk of the kernel families below: SRC says where the slot's filter comes from, DIST which rows the distances are taken over)
-template <int METRIC, int CPL, class SRC, class DIST = FiltDist<METRIC, CPL>>
-__device__ __forceinline__ void filtered_walk_body(const HnswSearchArgs& a, unsigned long long* qstats, const SRC src) {
+// The walk of the kernel families below (LDS: WalkLds, vdb_hnsw_device.hpp); DIST says which rows the distances are taken over
+template <int METRIC, int CPL, class DIST = FiltDist<METRIC, CPL>>
+__device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa) {
+  const HnswSearchArgs& a = fa.s;
+  unsigned long long* qstats = fa.qstats;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
   const int wib = (int)rfl(threadIdx.x >> 6);
   const uint32_t cap = a.cap, nbmax = a.nbmax, ef = a.ef;  // cap: the launch's physical capacity, the layout only
-  lds_vu64* keys = (lds_vu64*)(lds_void_p)(smem);
-  lds_vu32* nb_id = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8);
-  lds_vf32* nb_d = (lds_vf32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 4);
-  lds_vu32* ctl = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8);
-  lds_vu8* flags = (lds_vu8*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8 + 16);
-  const size_t qoff = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+  const auto [keys, nb_id, nb_d, ctl, flags, qscratch] = WalkLds(smem, cap, nbmax);
   uint32_t* vis = a.visited + (size_t)blockIdx.x * a.vis_words;
   uint32_t* vlog = a.vlog + (size_t)blockIdx.x * a.vlog_cap;
   DIST dist;
-  dist.init(a, smem + qoff);
+  dist.init(a, qscratch);
 
   for (uint32_t slot = blockIdx.x; slot < a.nq; slot += gridDim.x) {
-    const SlotFilter f = src.load(slot);
+    const SlotFilter f = load_slot_filter(fa, slot);
     const uint32_t qi = f.qi;
     dist.load_query(a.queries + (size_t)qi * a.q_stride, lane);
     __syncthreads();
@@ -234,9 +209,10 @@ __device__ __forceinline__ void filtered_walk_body(const HnswSearchArgs& a, unsi
     float best_d = 0.0f;
 
     // one admitted node: flag, insert, pivot, what fell off, truncation
-    auto admit = [&](float d, uint32_t node) {
+    // (keys = keys: a structured binding cannot be captured in C++17)
+    auto admit = [&, keys = keys, flags = flags](float d, uint32_t node) {
       uint32_t lost, lost_flag;
-      flist_insert(keys, flags, cnt, f.cap, make_key<false>(d, node), row_allowed<SRC::kOpen>(f, a.alive, node), lane, lost, lost_flag);
+      flist_insert(keys, flags, cnt, f.cap, make_key<false>(d, node), row_allowed(f, a.alive, node), lane, lost, lost_flag);
       pivot = find_pivot(flags, cnt, ef, lane);
       if (lost && ((lost_flag & kFlagExpanded) == 0 || ((lost_flag & kFlagAllowed) != 0 && pivot == kNoIndex))) overflow = 1;
       pivot_truncate(keys, cnt, pivot, lane);
@@ -273,26 +249,7 @@ __device__ __forceinline__ void filtered_walk_body(const HnswSearchArgs& a, unsi
             }
           } else if (phase == P_G_SCAN) {
             n_dist += m_prev;
-            // sequential scan with strict `<` == first index attaining the minimum, if below best (graph.rs:413-421)
-            float mn = 0.0f;
-            uint32_t besti = 0xFFFFFFFFu;
-            for (uint32_t base = 0; base < m_prev; base += 64) {
-              const uint32_t t = base + lane;
-              const float d = t < m_prev ? nb_d[t] : 0.0f;
-              const bool ok = t < m_prev && d < best_d;  // raw compare: NaN never improves
-              const uint64_t okm = __ballot(ok);
-              if (okm) {
-                float v = ok ? d : __uint_as_float(0x7F800000u);
-#pragma unroll
-                for (int s = 32; s >= 1; s >>= 1) v = fminf(v, shx(v, s));
-                v = rflf(v);
-                if (besti == 0xFFFFFFFFu || v < mn) {
-                  const uint64_t eq = __ballot(ok && d == v);
-                  besti = base + (uint32_t)__ffsll((long long)eq) - 1;
-                  mn = v;
-                }
-              }
-            }
+            const uint32_t besti = greedy_scan(nb_d, m_prev, best_d, lane);
             if (besti != 0xFFFFFFFFu) {
               cur = rfl(nb_id[besti]);
               best_d = rflf(nb_d[besti]);
@@ -440,41 +397,33 @@ __device__ __forceinline__ void filtered_walk_body(const HnswSearchArgs& a, unsi
 }
 
 template <int METRIC, int CPL>
-__global__ __launch_bounds__(256, 4) void hnsw_search_filtered_kernel(HnswFilteredArgs fa) {
-  filtered_walk_body<METRIC, CPL>(fa.s, fa.qstats, OneFilterSrc{fa});
-}
-// one filter per query: the slot's descriptor instead of the call's filter
-template <int METRIC, int CPL>
 __global__ __launch_bounds__(256, 4) void hnsw_search_filters_kernel(HnswFiltersArgs fa) {
-  filtered_walk_body<METRIC, CPL>(fa.s, fa.qstats, SlotTableSrc{fa});
+  filtered_walk_body<METRIC, CPL>(fa);
 }
 // ... over the half image: a.rows = the image, a.row_stride in half elements, a.norms of the rounded rows; the queries stay f32 and
 // are rounded at load
 template <int METRIC, int CPL, bool F16>
 __global__ __launch_bounds__(256, 4) void hnsw_search_filters_half_kernel(HnswFiltersArgs fa) {
-  filtered_walk_body<METRIC, CPL, SlotTableSrc, FiltDistHalf<METRIC, CPL, F16>>(fa.s, fa.qstats, SlotTableSrc{fa});
+  filtered_walk_body<METRIC, CPL, FiltDistHalf<METRIC, CPL, F16>>(fa);
 }
 
 // The exact pass: one block per query over the filter's ascending row list in chunks of nbmax — dead rows skipped, distances by
 // the walk's DIST::eval, the k best by (total-order(distance), row) in the same LDS list (a.cap >= k entries), results in the
 // walk's format.  Adds the rows it evaluated to the query's n_dist.
-template <int METRIC, int CPL, class SRC, class DIST = FiltDist<METRIC, CPL>>
-__device__ __forceinline__ void filter_rank_body(const HnswSearchArgs& a, unsigned long long* qstats, const SRC src) {
+template <int METRIC, int CPL, class DIST = FiltDist<METRIC, CPL>>
+__device__ __forceinline__ void filter_rank_body(const HnswFiltersArgs& fa) {
+  const HnswSearchArgs& a = fa.s;
+  unsigned long long* qstats = fa.qstats;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id();
   const int wib = (int)rfl(threadIdx.x >> 6);
   const uint32_t cap = a.cap, nbmax = a.nbmax, k = a.k;
-  lds_vu64* keys = (lds_vu64*)(lds_void_p)(smem);
-  lds_vu32* nb_id = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8);
-  lds_vf32* nb_d = (lds_vf32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 4);
-  lds_vu32* ctl = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8);
-  lds_vu8* flags = (lds_vu8*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8 + 16);
-  const size_t qoff = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+  const auto [keys, nb_id, nb_d, ctl, flags, qscratch] = WalkLds(smem, cap, nbmax);
   DIST dist;
-  dist.init(a, smem + qoff);
+  dist.init(a, qscratch);
 
   for (uint32_t slot = blockIdx.x; slot < a.nq; slot += gridDim.x) {
-    const SlotFilter f = src.load(slot);
+    const SlotFilter f = load_slot_filter(fa, slot);
     const uint32_t qi = f.qi;
     dist.load_query(a.queries + (size_t)qi * a.q_stride, lane);
     __syncthreads();
@@ -506,7 +455,7 @@ __device__ __forceinline__ void filter_rank_body(const HnswSearchArgs& a, unsign
             uint32_t row = 0;
             bool ok = false;
             if (t < lim) {
-              row = (SRC::kOpen && f.list == nullptr) ? at + t : f.list[at + t];  // (no filter: the rows themselves)
+              row = f.list == nullptr ? at + t : f.list[at + t];  // (no filter: the rows themselves)
               ok = row < a.n_rows && (!a.alive || a.alive[row] != 0);
             }
             const uint64_t mask = __ballot(ok);
@@ -550,36 +499,27 @@ __device__ __forceinline__ void filter_rank_body(const HnswSearchArgs& a, unsign
 }
 
 template <int METRIC, int CPL>
-__global__ __launch_bounds__(256, 4) void filter_rank_kernel(HnswFilteredArgs fa) {
-  filter_rank_body<METRIC, CPL>(fa.s, fa.qstats, OneFilterSrc{fa});
-}
-template <int METRIC, int CPL>
 __global__ __launch_bounds__(256, 4) void filters_rank_kernel(HnswFiltersArgs fa) {
-  filter_rank_body<METRIC, CPL>(fa.s, fa.qstats, SlotTableSrc{fa});
+  filter_rank_body<METRIC, CPL>(fa);
 }
 template <int METRIC, int CPL, bool F16>
 __global__ __launch_bounds__(256, 4) void filters_rank_half_kernel(HnswFiltersArgs fa) {
-  filter_rank_body<METRIC, CPL, SlotTableSrc, FiltDistHalf<METRIC, CPL, F16>>(fa.s, fa.qstats, SlotTableSrc{fa});
+  filter_rank_body<METRIC, CPL, FiltDistHalf<METRIC, CPL, F16>>(fa);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-// (ROWS: FiltersRows — the half images exist in the per-query form only)
+// (ROWS: FiltersRows — the f32 rows and packed bits, or one of the half images)
 template <bool RANK, int METRIC, int CPL, int ROWS>
-static auto kernel_of(const HnswFilteredArgs&) {
-  static_assert(ROWS == kFiltersF32, "one-filter form: f32 rows and packed bits only");
-  return RANK ? filter_rank_kernel<METRIC, CPL> : hnsw_search_filtered_kernel<METRIC, CPL>;
-}
-template <bool RANK, int METRIC, int CPL, int ROWS>
-static auto kernel_of(const HnswFiltersArgs&) {
+static auto kernel_of() {
   if constexpr (ROWS == kFiltersF32)
     return RANK ? filters_rank_kernel<METRIC, CPL> : hnsw_search_filters_kernel<METRIC, CPL>;
   else
     return RANK ? filters_rank_half_kernel<METRIC, CPL, ROWS == kFiltersF16> : hnsw_search_filters_half_kernel<METRIC, CPL, ROWS == kFiltersF16>;
 }
 
-template <bool RANK, int METRIC, int CPL, int ROWS, class ARGS>
-static hipError_t launch_fk(const ARGS& fa, int slots, size_t lds, hipStream_t st) {
-  auto kern = kernel_of<RANK, METRIC, CPL, ROWS>(fa);
+template <bool RANK, int METRIC, int CPL, int ROWS>
+static hipError_t launch_fk(const HnswFiltersArgs& fa, int slots, size_t lds, hipStream_t st) {
+  auto kern = kernel_of<RANK, METRIC, CPL, ROWS>();
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -594,8 +534,8 @@ static hipError_t launch_fk(const ARGS& fa, int slots, size_t lds, hipStream_t s
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, fa);
   return hipGetLastError();
 }
-template <bool RANK, int METRIC, int ROWS, class ARGS>
-static hipError_t launch_fk_cpl(const ARGS& fa, int slots, size_t lds, hipStream_t st) {
+template <bool RANK, int METRIC, int ROWS>
+static hipError_t launch_fk_cpl(const HnswFiltersArgs& fa, int slots, size_t lds, hipStream_t st) {
   switch (sweep_cpl_for_dim(fa.s.dim)) {
     case 1: return launch_fk<RANK, METRIC, 1, ROWS>(fa, slots, lds, st);
     case 2: return launch_fk<RANK, METRIC, 2, ROWS>(fa, slots, lds, st);
@@ -604,8 +544,8 @@ static hipError_t launch_fk_cpl(const ARGS& fa, int slots, size_t lds, hipStream
     default: return launch_fk<RANK, METRIC, 0, ROWS>(fa, slots, lds, st);
   }
 }
-template <bool RANK, int ROWS = kFiltersF32, class ARGS>
-static hipError_t launch_filtered(const ARGS& fa, int slots, size_t lds, hipStream_t st) {
+template <bool RANK, int ROWS = kFiltersF32>
+static hipError_t launch_filtered(const HnswFiltersArgs& fa, int slots, size_t lds, hipStream_t st) {
   switch (fa.s.metric) {
     case kCosine: return launch_fk_cpl<RANK, kCosine, ROWS>(fa, slots, lds, st);
     case kEuclidean: return launch_fk_cpl<RANK, kEuclidean, ROWS>(fa, slots, lds, st);
@@ -619,7 +559,7 @@ static hipError_t launch_filtered(const ARGS& fa, int slots, size_t lds, hipStre
     return hipErrorInvalidValue;  // (no image of packed bits: refused in front of the call)
   }
 }
-// the per-query form over the rows the call names
+// ... over the rows the call names
 template <bool RANK>
 static hipError_t launch_filters_rows(const HnswFiltersArgs& fa, int rows, int slots, size_t lds, hipStream_t st) {
   if (rows == kFiltersF16) return launch_filtered<RANK, kFiltersF16>(fa, slots, lds, st);
@@ -629,199 +569,17 @@ static hipError_t launch_filters_rows(const HnswFiltersArgs& fa, int rows, int s
 
 // the largest list (entries) whose launch stays inside 160 KB of LDS at this nbmax: hnsw_search_prepare's limit
 static uint32_t largest_list(uint32_t nbmax, uint32_t dim, uint32_t words, int metric) {
-  uint64_t cap = (160 * 1024) / 9 / 64 * 64;
-  while (cap && hnsw_lds_bytes((uint32_t)cap, nbmax, dim, words, metric) > 160 * 1024) cap -= 64;
+  uint64_t cap = kFgLdsBudget / 9 / 64 * 64;
+  while (cap && hnsw_lds_bytes((uint32_t)cap, nbmax, dim, words, metric) > kFgLdsBudget) cap -= 64;
   return (uint32_t)cap;
 }
 
-// the graph of a launch: every layer's lists; returns nbmax (the longest neighbour list, 64-rounded)
-static uint32_t walk_args_graph(const vdb_hip_index* ix, HnswSearchArgs& a) {
-  uint32_t nbmax = 0;
-  for (size_t l = 0; l < ix->layers.size(); l++) {
-    a.layers[l].nbr = ix->layers[l].nbr.as<uint32_t>();
-    a.layers[l].cnt = ix->layers[l].cnt.as<uint32_t>();
-    a.layers[l].stride = ix->layers[l].stride;
-    nbmax = std::max(nbmax, ix->layers[l].stride);
-  }
-  return (nbmax + 63) / 64 * 64;
-}
-// ... and everything else a launch reads from the index and the context (queries in s_queries, results in s_out_*)
-static void walk_args_index(vdb_hip_index* ix, HnswSearchArgs& a, uint32_t k, uint32_t ef, uint32_t nbmax, uint32_t* d_n) {
-  a.rows = ix->rows.as<float>();
-  a.norms = ix->norms.as<float>();
-  a.bits = ix->bits.as<uint32_t>();
-  a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
-  a.ext_ids = ix->ext_ids.as<uint64_t>();
-  a.queries = ix->s_queries.as<float>();
-  a.row_stride = ix->row_stride;
-  a.q_stride = ix->row_stride;
-  a.out_ids = ix->s_out_ids.as<uint64_t>();
-  a.out_scores = ix->s_out_scores.as<float>();
-  a.out_n = d_n;
-  a.dim = ix->dim;
-  a.words = ix->words;
-  a.n_rows = (uint32_t)ix->n_rows;
-  a.k = k;
-  a.ef = ef;
-  a.nbmax = nbmax;
-  a.vlog_cap = kVlogCap;
-  a.max_layer = ix->max_layer;
-  a.entry_point = (uint32_t)ix->entry_point;
-  a.metric = ix->metric;
-  a.n_cus = (uint32_t)ix->n_cus;
-}
-
-// vdb_hip_index_search_graph_filtered on a leased context (ix->mu shared, by the caller): the queries up, the walk with its
-// re-runs, the exact pass for what is left, the result block back in ix->h_out (reserve_out's layout).  routes: host, [nq].
-int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k, uint32_t ef,
-                                        int32_t route, uint32_t max_list, uint32_t* routes) {
-  int32_t rc = filter_check(ix, f);
-  if (rc != VDB_OK) return rc;
-  if (!ix->graph_valid) return fail(VDB_ERR_STATE, "HNSW graph not built for all rows (use the exact filtered search or build it)");
-  hipStream_t st = ix->stream;
-  ix->ev_used = 0;
-  ix->sel_ev_used = 0;
-  ix->last_select_level = 0;
-  ix->split_flags_n = 0;
-  ix->last_kernels = 0;
-  ix->last_n_dist = ix->last_n_expand = ix->last_pf_hits = 0;
-  ix->stats_pending = false;
-  const size_t kk = std::max<uint32_t>(k, 1);
-  rc = reserve_out(ix, nq, kk, st);
-  if (rc != VDB_OK) return rc;
-  if (ix->h_out.reserve(ix->s_out_bytes) != hipSuccess) return fail(VDB_ERR_OOM, "pinned result staging");
-  uint32_t* d_n = ix->s_out_n.as<uint32_t>();
-  const size_t n_off = (size_t)((unsigned char*)ix->s_out_n.p - (unsigned char*)ix->s_out.p);
-  uint32_t* h_n = reinterpret_cast<uint32_t*>(ix->h_out.as<unsigned char>() + n_off);
-  if (routes) std::memset(routes, 0, (size_t)nq * 4);
-  // graph.rs:252-255: no entry point => empty; an empty filter or k = 0 cannot answer either — no launch
-  if (f->count == 0 || k == 0 || ix->n_rows == 0 || ix->entry_point < 0 || ix->graph_nodes == 0) {
-    std::memset(h_n, 0, (size_t)nq * 4);
-    return VDB_OK;
-  }
-  if (ix->layers.size() > (size_t)kMaxLayers) return fail(VDB_ERR_UNSUPPORTED, "more than 16 graph layers");
-  if (ef == 0) ef = std::max<uint32_t>(128, k * 4);  // Balanced, params.rs:313
-  ef = std::max(ef, k);                               // SearchQuality::Custom(ef) = max(ef, k), params.rs:317
-
-  HnswFilteredArgs fa{};
-  HnswSearchArgs& a = fa.s;
-  const uint32_t nbmax = walk_args_graph(ix, a);
-  uint32_t cap_max = largest_list(nbmax, ix->dim, ix->words, ix->metric);
-  if (max_list) cap_max = std::min(cap_max, max_list);
-  const FilterGraphPlan plan = filter_graph_route(route, ef, f->count, ix->n_rows, cap_max);
-  const std::string limits = " (route " + std::to_string(route) + ", max_list " + std::to_string(max_list) + ", ef " + std::to_string(ef) + ")";
-  if (plan.route == kFgRefuse)
-    return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: the smallest candidate list does not fit the largest list allowed" + limits);
-
-  // queries up (pinned staging), per-query counters and the slot map behind them
-  rc = stage_queries(ix, queries, 0, nq, nq);
-  if (rc != VDB_OK) return rc;
-  if (ix->s_queries.reserve((size_t)nq * ix->row_stride * 4, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "search scratch");
-  const size_t qs_bytes = (size_t)nq * 16;
-  if (ix->s_fgraph.reserve(qs_bytes + (size_t)nq * 4, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "filtered graph scratch");
-  VDB_HIP(hipMemcpyAsync(ix->s_queries.p, ix->h_in.p, (size_t)nq * ix->row_stride * 4, hipMemcpyHostToDevice, st));
-  VDB_HIP(hipMemsetAsync(ix->s_fgraph.p, 0, qs_bytes, st));
-  uint32_t* d_qmap = reinterpret_cast<uint32_t*>(ix->s_fgraph.as<unsigned char>() + qs_bytes);
-
-  walk_args_index(ix, a, k, ef, nbmax, d_n);
-  fa.f_bitmap = f->bitmap.as<uint32_t>();
-  fa.f_list = f->list.as<uint32_t>();
-  fa.f_rows = (uint32_t)f->n_rows;
-  fa.f_count = (uint32_t)f->count;
-  fa.qstats = ix->s_fgraph.as<unsigned long long>();
-
-  auto fetch = [&]() -> int32_t {
-    VDB_HIP(hipMemcpyAsync(ix->h_out.p, ix->s_out.p, ix->s_out_bytes, hipMemcpyDeviceToHost, st));
-    VDB_HIP(hipStreamSynchronize(st));
-    return VDB_OK;
-  };
-  // the queries of a launch: all of them (no map), or the listed ones
-  auto set_queries = [&](const std::vector<uint32_t>* which) -> int32_t {
-    fa.qmap = nullptr;
-    a.nq = nq;
-    if (which) {
-      VDB_HIP(hipMemcpyAsync(d_qmap, which->data(), which->size() * 4, hipMemcpyHostToDevice, st));
-      VDB_HIP(hipStreamSynchronize(st));  // (`which` is host memory)
-      fa.qmap = d_qmap;
-      a.nq = (uint32_t)which->size();
-    }
-    return VDB_OK;
-  };
-
-  std::vector<uint32_t> left;  // queries still without an answer (empty + all = every query)
-  bool all = true;
-  if (plan.route == kFgWalk) {
-    for (uint64_t cap = plan.cap;;) {
-      a.cap = (uint32_t)cap;
-      const size_t lds = hnsw_lds_bytes(a.cap, nbmax, ix->dim, ix->words, ix->metric);
-      if (lds > 160 * 1024) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: candidate list beyond the LDS" + limits);
-      rc = set_queries(all ? nullptr : &left);
-      if (rc != VDB_OK) return rc;
-      const int per_cu = (int)std::min<size_t>(4, std::max<size_t>(1, (160 * 1024) / lds));
-      const int slots = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * per_cu);
-      rc = ensure_traversal_scratch(ix, st, slots);
-      if (rc != VDB_OK) return rc;
-      a.visited = ix->s_visited.as<uint32_t>();
-      a.vlog = ix->s_vlog.as<uint32_t>();
-      a.vis_words = ix->vis_words;
-      const hipError_t e = launch_filtered<false>(fa, slots, lds, st);
-      if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filtered hnsw_search launch: ") + hipGetErrorString(e));
-      ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED;
-      rc = fetch();
-      if (rc != VDB_OK) return rc;
-      std::vector<uint32_t> over;
-      if (all) {
-        for (uint32_t i = 0; i < nq; i++) {
-          if (h_n[i] == 0xFFFFFFFFu) over.push_back(i);
-          if (routes) routes[i] = kFgWalk;
-        }
-      } else {
-        for (uint32_t i : left)
-          if (h_n[i] == 0xFFFFFFFFu) over.push_back(i);
-      }
-      left.swap(over);
-      all = false;
-      if (left.empty() || cap >= cap_max) break;
-      cap = std::min<uint64_t>(cap * 4, cap_max);  // search_block's rule: four times the room
-    }
-    if (!left.empty() && route == kFgWalk)
-      return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: " + std::to_string(left.size()) + " queries overflow the largest candidate list (" +
-                                           std::to_string(cap_max) + " entries)" + limits);
-  }
-  if (all || !left.empty()) {  // the exact pass: the whole call, or the queries the largest list could not hold
-    a.cap = (uint32_t)fg_round64(k);
-    const size_t lds = hnsw_lds_bytes(a.cap, nbmax, ix->dim, ix->words, ix->metric);
-    if (lds > 160 * 1024) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: k too large for the LDS-resident result list");
-    rc = set_queries(all ? nullptr : &left);
-    if (rc != VDB_OK) return rc;
-    const int slots = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * 4);
-    const hipError_t e = launch_filtered<true>(fa, slots, lds, st);
-    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filter_rank launch: ") + hipGetErrorString(e));
-    ix->last_kernels |= VDB_KERNEL_FILTER_RANK;
-    rc = fetch();
-    if (rc != VDB_OK) return rc;
-    if (routes) {
-      if (all)
-        for (uint32_t i = 0; i < nq; i++) routes[i] = kFgExact;
-      else
-        for (uint32_t i : left) routes[i] = kFgExact;
-    }
-  }
-  // the call's counters: every query's last walk attempt plus the rows its exact pass evaluated
-  std::vector<unsigned long long> qs((size_t)nq * 2);
-  VDB_HIP(hipMemcpyAsync(qs.data(), ix->s_fgraph.p, qs_bytes, hipMemcpyDeviceToHost, st));
-  VDB_HIP(hipStreamSynchronize(st));
-  for (uint32_t i = 0; i < nq; i++) {
-    ix->last_n_dist += qs[(size_t)i * 2];
-    ix->last_n_expand += qs[(size_t)i * 2 + 1];
-  }
-  return VDB_OK;
-}
-
-// vdb_hip_index_search_graph_filters: one filter per query.  Query i computes what the function above computes for it
-// alone — its own plan, its own ladder of capacities, the exact pass behind it — and only shares launches with its companions:
-// filters_walk_ladders (vdb_filter_route.hpp) groups every round into at most four launches by LDS footprint, and every exact pass
-// of the call is one launch.  filters: [n_filters] handles, non-null; fq: [nq] values in 0..n_filters, n_filters = no filter.
+// vdb_hip_index_search_graph_filters on a leased context (ix->mu shared, by the caller): one filter per query.  The
+// queries go up, every query gets its own plan (filter_graph_route on ITS filter), climbs its own ladder of capacities and takes the
+// exact pass behind it if the largest list could not hold it; the result block comes back in ix->h_out (reserve_out's layout).
+// Queries only share launches: filters_walk_ladders (vdb_filter_route.hpp) groups every round into at most four launches by LDS
+// footprint, and every exact pass of the call is one launch — so query i computes what it computes in a call of its own.
+// filters: [n_filters] handles, non-null; fq: [nq] values in 0..n_filters, n_filters = no filter; routes: host, [nq].
 int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                        const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
                                        uint32_t* routes, int half) {
@@ -866,7 +624,10 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
       }
     }
   };
-  if (k == 0 || ix->n_rows == 0 || ix->entry_point < 0 || ix->graph_nodes == 0) {
+  // graph.rs:252-255: no entry point => empty; k = 0 or filters that are all empty cannot answer either — no launch
+  bool matched_any = false;
+  for (uint32_t i = 0; i < nq; i++) matched_any |= fq[i] == n_filters ? ix->n_rows != 0 : filters[fq[i]]->count != 0;
+  if (!matched_any || k == 0 || ix->n_rows == 0 || ix->entry_point < 0 || ix->graph_nodes == 0) {
     blank();
     return VDB_OK;
   }
@@ -876,7 +637,7 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
 
   HnswFiltersArgs fa{};
   HnswSearchArgs& a = fa.s;
-  const uint32_t nbmax = walk_args_graph(ix, a);
+  const uint32_t nbmax = (walk_args_graph(ix, a) + 63) / 64 * 64;
   uint32_t cap_max = largest_list(nbmax, ix->dim, ix->words, ix->metric);
   if (max_list) cap_max = std::min(cap_max, max_list);
   const std::string limits = " (route " + std::to_string(route) + ", max_list " + std::to_string(max_list) + ", ef " + std::to_string(ef) + ")";
@@ -887,11 +648,13 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   for (uint32_t j = 0; j < n_filters; j++)
     descs[j] = FilterDesc{filters[j]->bitmap.as<uint32_t>(), filters[j]->list.as<uint32_t>(), (uint32_t)filters[j]->n_rows, (uint32_t)filters[j]->count};
   descs[n_filters] = FilterDesc{nullptr, nullptr, (uint32_t)ix->n_rows, (uint32_t)ix->n_rows};
+  std::vector<FilterGraphPlan> plans(descs.size());  // (a plan depends on the filter alone: one per table entry, not one per query)
+  for (size_t j = 0; j < descs.size(); j++) plans[j] = filter_graph_route(route, ef, descs[j].count, ix->n_rows, cap_max);
   std::vector<FiltersSlot> first, exact;
+  first.reserve(nq);
   for (uint32_t i = 0; i < nq; i++) {
-    const uint64_t matched = descs[fq[i]].count;
-    if (matched == 0) continue;  // (route 0: nothing runs for this query)
-    const FilterGraphPlan plan = filter_graph_route(route, ef, matched, ix->n_rows, cap_max);
+    if (descs[fq[i]].count == 0) continue;  // (route 0: nothing runs for this query)
+    const FilterGraphPlan plan = plans[fq[i]];
     if (plan.route == kFgRefuse)
       return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: the smallest candidate list does not fit the largest list allowed" + limits);
     if (plan.route == kFgWalk) {
@@ -901,23 +664,40 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
       exact.push_back(FiltersSlot{i, fq[i], 0, 0});
     }
   }
-  if (first.empty() && exact.empty()) {
-    blank();
-    return VDB_OK;
-  }
 
-  // queries up (pinned staging); counters, descriptors and the slot table behind each other in the context's scratch
-  rc = stage_queries(ix, queries, 0, nq, nq);
+  // The queries go up through pinned staging, and the descriptor table and the slot table of the coming launches travel behind them:
+  // same staging buffer, same device buffer, so the first upload of the call is ONE copy (what a call costs before its first launch
+  // shows in the one-query case) and no later one starts from pageable memory.  Whole staging rows, so the tables stay aligned.
+  const size_t row_bytes = (size_t)ix->row_stride * 4, q_bytes = (size_t)nq * row_bytes, qs_bytes = (size_t)nq * 16;
+  const size_t desc_bytes = descs.size() * sizeof(FilterDesc), slot_bytes = (size_t)nq * sizeof(FiltersSlot);
+  const uint32_t table_rows = (uint32_t)((desc_bytes + slot_bytes + row_bytes - 1) / row_bytes);
+  rc = stage_queries(ix, queries, 0, nq, nq + table_rows);
   if (rc != VDB_OK) return rc;
-  if (ix->s_queries.reserve((size_t)nq * ix->row_stride * 4, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "search scratch");
-  const size_t qs_bytes = (size_t)nq * 16, desc_bytes = descs.size() * sizeof(FilterDesc), slot_bytes = (size_t)nq * sizeof(FiltersSlot);
-  if (ix->s_fgraph.reserve(qs_bytes + desc_bytes + slot_bytes, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "filtered graph scratch");
-  VDB_HIP(hipMemcpyAsync(ix->s_queries.p, ix->h_in.p, (size_t)nq * ix->row_stride * 4, hipMemcpyHostToDevice, st));
+  if (ix->s_queries.reserve(q_bytes + table_rows * row_bytes, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "search scratch");
+  if (ix->s_fgraph.reserve(qs_bytes, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "filtered graph scratch");
   VDB_HIP(hipMemsetAsync(ix->s_fgraph.p, 0, qs_bytes, st));
-  FilterDesc* d_descs = reinterpret_cast<FilterDesc*>(ix->s_fgraph.as<unsigned char>() + qs_bytes);
-  FiltersSlot* d_slots = reinterpret_cast<FiltersSlot*>(ix->s_fgraph.as<unsigned char>() + qs_bytes + desc_bytes);
-  VDB_HIP(hipMemcpyAsync(d_descs, descs.data(), desc_bytes, hipMemcpyHostToDevice, st));  // (`descs` outlives every synchronisation below)
-  walk_args_index(ix, a, k, ef, nbmax, d_n);
+  unsigned char* h_up = ix->h_in.as<unsigned char>();
+  unsigned char* d_up = ix->s_queries.as<unsigned char>();
+  std::memcpy(h_up + q_bytes, descs.data(), desc_bytes);
+  FiltersSlot* d_slots = reinterpret_cast<FiltersSlot*>(d_up + q_bytes + desc_bytes);
+  size_t sent = 0;  // bytes of [queries | descriptors | slots] the device holds
+  // the slot table of the next launches (the staging copy of the last ones is free: their round was fetched)
+  auto slots_up = [&](const FiltersSlot* slots, size_t n) -> int32_t {
+    std::memcpy(h_up + q_bytes + desc_bytes, slots, n * sizeof(FiltersSlot));
+    const size_t from = sent ? q_bytes + desc_bytes : 0, to = q_bytes + desc_bytes + n * sizeof(FiltersSlot);
+    VDB_HIP(hipMemcpyAsync(d_up + from, h_up + from, to - from, hipMemcpyHostToDevice, st));
+    sent = to;
+    return VDB_OK;
+  };
+  walk_args_index(ix, a);
+  a.queries = ix->s_queries.as<float>();
+  a.q_stride = ix->row_stride;
+  a.out_ids = ix->s_out_ids.as<uint64_t>();
+  a.out_scores = ix->s_out_scores.as<float>();
+  a.out_n = d_n;
+  a.k = k;
+  a.ef = ef;
+  a.nbmax = nbmax;
   if (half != kFiltersF32) {  // the image instead of the f32 rows, as hnsw_search_half_dev: same fields, the stride in half elements
     const bool f16 = half == kFiltersF16;
     a.rows = reinterpret_cast<const float*>(f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>());
@@ -925,7 +705,7 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
     a.row_stride = ix->bf16_stride;
     a.bits = nullptr;
   }
-  fa.descs = d_descs;
+  fa.descs = reinterpret_cast<const FilterDesc*>(d_up + q_bytes);
   fa.qstats = ix->s_fgraph.as<unsigned long long>();
 
   auto fetch = [&]() -> int32_t {
@@ -933,14 +713,14 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
     VDB_HIP(hipStreamSynchronize(st));
     return VDB_OK;
   };
-  // one round of walks: its slot table up, its launches behind each other, one fetch (`slots` is host memory that lives until
-  // the round's synchronisation)
+  // one round of walks: its slot table up, its launches behind each other, one fetch
   auto run_round = [&](const FiltersSlot* slots, uint32_t n, const FiltersLaunch* launches, uint32_t n_launches, unsigned char* over) -> int {
-    VDB_HIP(hipMemcpyAsync(d_slots, slots, (size_t)n * sizeof(FiltersSlot), hipMemcpyHostToDevice, st));
+    int32_t r = slots_up(slots, n);
+    if (r != VDB_OK) return r;
     int most = 0;
     for (uint32_t l = 0; l < n_launches; l++)
       most = std::max(most, (int)std::min<int64_t>((int64_t)launches[l].count, (int64_t)ix->n_cus * (int64_t)launches[l].per_cu));
-    int32_t r = ensure_traversal_scratch(ix, st, most);  // (once, in front of the round: the launches share the bitmaps in stream order)
+    r = ensure_traversal_scratch(ix, st, most);  // (once, in front of the round: the launches share the bitmaps in stream order)
     if (r != VDB_OK) return r;
     a.visited = ix->s_visited.as<uint32_t>();
     a.vlog = ix->s_vlog.as<uint32_t>();
@@ -968,14 +748,17 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   if (!left.empty() && route == kFgWalk)
     return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: " + std::to_string(left.size()) + " queries overflow the largest candidate list (" +
                                          std::to_string(cap_max) + " entries)" + limits);
-  exact.insert(exact.end(), left.begin(), left.end());
-  if (!exact.empty()) {  // every exact pass of the call in one launch: the whole-route ones and what the largest list could not hold
+  if (!left.empty()) {  // (`exact` is in query order so far)
+    exact.insert(exact.end(), left.begin(), left.end());
     std::sort(exact.begin(), exact.end(), [](const FiltersSlot& x, const FiltersSlot& y) { return x.query < y.query; });
+  }
+  if (!exact.empty()) {  // every exact pass of the call in one launch: the whole-route ones and what the largest list could not hold
     a.cap = (uint32_t)fg_round64(k);
     for (FiltersSlot& s : exact) s.cap = a.cap;
     const size_t lds = lds_of(a.cap);
     if (lds > kFgLdsBudget) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: k too large for the LDS-resident result list");
-    VDB_HIP(hipMemcpyAsync(d_slots, exact.data(), exact.size() * sizeof(FiltersSlot), hipMemcpyHostToDevice, st));
+    rc = slots_up(exact.data(), exact.size());
+    if (rc != VDB_OK) return rc;
     a.nq = (uint32_t)exact.size();
     fa.slots = d_slots;
     const int slots_l = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * 4);
@@ -996,6 +779,17 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
     ix->last_n_expand += qs[(size_t)i * 2 + 1];
   }
   return VDB_OK;
+}
+
+// vdb_hip_index_search_graph_filtered: one filter for the whole call = a table of that filter with every query on it.
+// routes: host, [nq], nullable (multi_query_direct, search_front.hip, has no use for them).
+int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k, uint32_t ef,
+                                        int32_t route, uint32_t max_list, uint32_t* routes) {
+  const std::vector<uint32_t> fq(nq, 0u);
+  std::vector<uint32_t> r(nq, 0u);
+  const int32_t rc = search_graph_filters_to_device(ix, &f, 1, fq.data(), queries, nq, k, ef, route, max_list, r.data(), kFiltersF32);
+  if (rc == VDB_OK && routes) std::copy(r.begin(), r.end(), routes);
+  return rc;
 }
 
 }  // namespace vdb

@@ -528,14 +528,7 @@ int32_t hnsw_search_int8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_str
   const uint64_t ef = std::max<uint64_t>(ef_search, cand_k);  // dual_precision.rs:334
   HnswInt8Args A{};
   HnswSearchArgs& a = A.s;
-  uint32_t nbmax = 0;
-  for (size_t l = 0; l < ix->layers.size() && l < (size_t)kMaxLayers; l++) {
-    a.layers[l].nbr = ix->layers[l].nbr.as<uint32_t>();
-    a.layers[l].cnt = ix->layers[l].cnt.as<uint32_t>();
-    a.layers[l].stride = ix->layers[l].stride;
-    nbmax = std::max(nbmax, ix->layers[l].stride);
-  }
-  nbmax = (uint32_t)((std::max<uint64_t>(nbmax, cand_k) + 63) / 64 * 64);
+  const uint32_t nbmax = (uint32_t)((std::max<uint64_t>(walk_args_graph(ix, a), cand_k) + 63) / 64 * 64);
   uint64_t cap = ef + std::max<uint64_t>(64, ef * cap_mult / 2);
   cap = (cap + 63) / 64 * 64;
   // integer distances tie often: the register list (256 entries) is used for small ef only on the first attempt
@@ -553,13 +546,9 @@ int32_t hnsw_search_int8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_str
   int32_t rcs = ensure_traversal_scratch(ix, st);
   if (rcs != VDB_OK) return rcs;
   VDB_HIP(hipMemsetAsync(ix->s_stats.p, 0, 24, st));
-  a.rows = ix->rows.as<float>();
-  a.norms = ix->norms.as<float>();
+  walk_args_index(ix, a);
   a.bits = nullptr;
-  a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
-  a.ext_ids = ix->ext_ids.as<uint64_t>();
   a.queries = d_q;
-  a.row_stride = ix->row_stride;
   a.q_stride = q_stride;
   a.visited = ix->s_visited.as<uint32_t>();
   a.vlog = ix->s_vlog.as<uint32_t>();
@@ -568,19 +557,11 @@ int32_t hnsw_search_int8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_str
   a.out_scores = d_scores;
   a.out_n = d_n;
   a.stats = ix->s_stats.as<unsigned long long>();
-  a.dim = ix->dim;
-  a.words = ix->words;
-  a.n_rows = (uint32_t)ix->n_rows;
   a.nq = nq;
   a.k = k;
   a.ef = (uint32_t)ef;
   a.cap = (uint32_t)cap;
   a.nbmax = nbmax;
-  a.vlog_cap = kVlogCap;
-  a.max_layer = ix->max_layer;
-  a.entry_point = (uint32_t)ix->entry_point;
-  a.metric = ix->metric;
-  a.n_cus = (uint32_t)ix->n_cus;
   a.list_slots = reg_list ? kSearchRegSlots : 0;
   a.vis_log2 = cap_mult == 1 ? 1u : 0u;  // "the LDS visited set is allowed" (a re-run after an overflow takes the bitmap)
   A.codes = CodeCtx{ix->codes.as<uint32_t>(), ix->codes_sq.as<uint32_t>(), ix->code_words};

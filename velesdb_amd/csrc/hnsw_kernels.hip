@@ -59,6 +59,8 @@ __global__ __launch_bounds__(LAT ? 1024 : 256, 4) void hnsw_search_kernel(HnswSe
 }
 
 // ---- host side -----------------------------------------------------------------------------
+// the dynamic LDS of a walk block: the arrays WalkLds (vdb_hnsw_device.hpp) carves out — the same offsets, change both together —
+// plus the query scratch of the distance phase
 size_t hnsw_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint32_t words, int metric) {
   size_t s = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
   if (metric == kHamming || metric == kJaccard)
@@ -259,6 +261,37 @@ int32_t ensure_traversal_scratch(vdb_hip_index* ix, hipStream_t st, int want_slo
   return VDB_OK;
 }
 
+// Index -> HnswSearchArgs, the one copy every walk launch fills its arguments from (the f32 and half walks below, hnsw_int8.hip,
+// hnsw_filtered.hip).  The graph: every layer's lists (at most kMaxLayers: the callers refuse or never see more); returns the
+// longest neighbour list, unrounded — the caller rounds it with whatever else shares its nb arrays ...
+uint32_t walk_args_graph(const vdb_hip_index* ix, HnswSearchArgs& a) {
+  uint32_t longest = 0;
+  for (size_t l = 0; l < ix->layers.size() && l < (size_t)kMaxLayers; l++) {
+    a.layers[l].nbr = ix->layers[l].nbr.as<uint32_t>();
+    a.layers[l].cnt = ix->layers[l].cnt.as<uint32_t>();
+    a.layers[l].stride = ix->layers[l].stride;
+    longest = std::max(longest, ix->layers[l].stride);
+  }
+  return longest;
+}
+// ... and the index fields (rows = the f32 rows).  Queries, outputs, list sizes, scratch and counters are the caller's.
+void walk_args_index(const vdb_hip_index* ix, HnswSearchArgs& a) {
+  a.rows = ix->rows.as<float>();
+  a.norms = ix->norms.as<float>();
+  a.bits = ix->bits.as<uint32_t>();
+  a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  a.ext_ids = ix->ext_ids.as<uint64_t>();
+  a.row_stride = ix->row_stride;
+  a.dim = ix->dim;
+  a.words = ix->words;
+  a.n_rows = (uint32_t)ix->n_rows;
+  a.vlog_cap = kVlogCap;
+  a.max_layer = ix->max_layer;
+  a.entry_point = (uint32_t)ix->entry_point;
+  a.metric = ix->metric;
+  a.n_cus = (uint32_t)ix->n_cus;
+}
+
 // What a walk launch needs, shared by the f32 walk below and the half-precision walk (hnsw_half.hip): the graph checks, list
 // capacity and LDS rule, the visited scratch, the zeroed counters and every HnswSearchArgs field (rows = the f32 rows).
 // *slots = the resident blocks to launch; 0: nothing to launch, the outputs are already what the call returns.
@@ -275,14 +308,7 @@ int32_t hnsw_search_prepare(vdb_hip_index* ix, const float* d_q, uint64_t q_stri
   if (ix->layers.size() > (size_t)kMaxLayers) return fail(VDB_ERR_UNSUPPORTED, "more than 16 graph layers");
   HnswSearchArgs& a = *out;
   a = HnswSearchArgs{};
-  uint32_t nbmax = 0;
-  for (size_t l = 0; l < ix->layers.size(); l++) {
-    a.layers[l].nbr = ix->layers[l].nbr.as<uint32_t>();
-    a.layers[l].cnt = ix->layers[l].cnt.as<uint32_t>();
-    a.layers[l].stride = ix->layers[l].stride;
-    nbmax = std::max(nbmax, ix->layers[l].stride);
-  }
-  nbmax = (std::max(nbmax, rerank_k) + 63) / 64 * 64;
+  const uint32_t nbmax = (std::max(walk_args_graph(ix, a), rerank_k) + 63) / 64 * 64;
   // list capacity: ef results + room for evicted candidates that tie with the furthest result
   uint64_t cap = (uint64_t)ef + std::max<uint64_t>(64, (uint64_t)ef * cap_mult / 2);
   cap = (cap + 63) / 64 * 64;
@@ -300,15 +326,9 @@ int32_t hnsw_search_prepare(vdb_hip_index* ix, const float* d_q, uint64_t q_stri
   int32_t rcs = ensure_traversal_scratch(ix, st, slots);
   if (rcs != VDB_OK) return rcs;
   const uint64_t vis_words = ix->vis_words;
-  const uint32_t vlog_cap = kVlogCap;
   VDB_HIP(hipMemsetAsync(ix->s_stats.p, 0, 24, st));
-  a.rows = ix->rows.as<float>();
-  a.norms = ix->norms.as<float>();
-  a.bits = ix->bits.as<uint32_t>();
-  a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
-  a.ext_ids = ix->ext_ids.as<uint64_t>();
+  walk_args_index(ix, a);
   a.queries = d_q;
-  a.row_stride = ix->row_stride;
   a.q_stride = q_stride;
   a.visited = ix->s_visited.as<uint32_t>();
   a.vlog = ix->s_vlog.as<uint32_t>();
@@ -317,24 +337,16 @@ int32_t hnsw_search_prepare(vdb_hip_index* ix, const float* d_q, uint64_t q_stri
   a.out_scores = d_scores;
   a.out_n = d_n;
   a.stats = ix->s_stats.as<unsigned long long>();
-  a.dim = ix->dim;
-  a.words = ix->words;
-  a.n_rows = (uint32_t)ix->n_rows;
   a.nq = nq;
   a.k = k;
   a.ef = ef;
   a.cap = (uint32_t)cap;
   a.nbmax = nbmax;
-  a.vlog_cap = vlog_cap;
-  a.max_layer = ix->max_layer;
-  a.entry_point = (uint32_t)ix->entry_point;
-  a.metric = ix->metric;
   a.rerank_k = rerank_k;
   a.extra_eps = d_extra_eps;
   a.raw_small_ef = raw_small ? 1u : 0u;
   a.list_slots = reg_list ? kSearchRegSlots : 0;
   a.vis_log2 = cap_mult == 1 ? 1u : 0u;  // "the LDS visited set is allowed" (a re-run after an overflow takes the bitmap)
-  a.n_cus = (uint32_t)ix->n_cus;
   *out_slots = slots;
   return VDB_OK;
 }

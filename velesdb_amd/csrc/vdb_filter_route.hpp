@@ -1,6 +1,7 @@
 // vdb_filter_route.hpp — which route a filtered exact call takes (vdb_hip_index_search_batch_filtered) and which a
 // filtered graph call takes (vdb_hip_index_search_graph_filtered), and which queries of a call with one filter per
-// query share a launch (vdb_hip_index_search_graph_filters).
+// query share a launch (vdb_hip_index_search_graph_filters) — the one-filter call is planned here too: it is a call
+// of the second kind with every query on the same filter.
 // Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_graph_route_model.cpp and
 // tests/filters_plan_model.cpp compile it alone and walk its boundaries.
 #pragma once
@@ -67,8 +68,9 @@ static inline FilterGraphPlan filter_graph_route(int route, uint32_t ef_eff, uin
 
 // ---- one filter per query (vdb_hip_index_search_graph_filters): which queries share a launch ----
 // Every query keeps the plan filter_graph_route gives ITS filter and climbs ITS OWN ladder — first list plan.cap, four times the
-// room while it overflows, cap_max last, then the exact pass: the sequence the single-filter host loop runs.  Only the grouping into
-// launches looks at the other queries, and a launch changes nothing a query computes: the kernel sizes the LDS layout by the
+// room while it overflows, cap_max last, then the exact pass.  When every query has the same plan a round is one launch at that
+// capacity: the loop the one-filter call ran while it had one of its own (tests/filters_plan_model.cpp keeps a transcription and
+// holds filters_walk_ladders to it).  Only the grouping into launches looks at the other queries, and a launch changes nothing a query computes: the kernel sizes the LDS layout by the
 // launch's PHYSICAL capacity and runs all list logic of a query on its own LOGICAL one.
 struct FiltersSlot {   // one launch slot (device layout, 16 bytes)
   uint32_t query, filter, cap, pad;  // cap: the query's logical list capacity in this attempt
@@ -79,7 +81,7 @@ struct FiltersLaunch {
   uint32_t per_cu;        // walks a CU holds at that footprint (1..4)
 };
 constexpr uint64_t kFgLdsBudget = 160 * 1024;
-// walks per CU at an LDS footprint: the rule of the single-filter loop
+// walks per CU at an LDS footprint: hnsw_search_prepare's rule
 static inline uint32_t fg_per_cu(uint64_t lds) {
   const uint64_t n = lds ? kFgLdsBudget / lds : 4;
   return (uint32_t)(n > 4 ? 4 : (n < 1 ? 1 : n));

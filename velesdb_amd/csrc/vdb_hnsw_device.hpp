@@ -84,6 +84,51 @@ __device__ __forceinline__ void list_insert(lds_vu64* keys, lds_vu8* flags, uint
   cnt = newcnt;
 }
 
+// The scan of a greedy step on the upper layers (graph.rs:413-421): sequential with strict `<` == the first index of nb_d[0..m)
+// attaining the minimum, if that is below best_d; 0xFFFFFFFF when no neighbour improves.  Wave-uniform result.
+__device__ __forceinline__ uint32_t greedy_scan(lds_vf32* nb_d, uint32_t m, float best_d, int lane) {
+  float mn = 0.0f;
+  uint32_t besti = 0xFFFFFFFFu;
+  for (uint32_t base = 0; base < m; base += 64) {
+    const uint32_t t = base + lane;
+    const float d = t < m ? nb_d[t] : 0.0f;
+    const bool ok = t < m && d < best_d;  // raw compare: NaN never improves
+    const uint64_t okm = __ballot(ok);
+    if (okm) {
+      float v = ok ? d : __uint_as_float(0x7F800000u);
+#pragma unroll
+      for (int s = 32; s >= 1; s >>= 1) v = fminf(v, shx(v, s));
+      v = rflf(v);
+      if (besti == 0xFFFFFFFFu || v < mn) {
+        const uint64_t eq = __ballot(ok && d == v);
+        besti = base + (uint32_t)__ffsll((long long)eq) - 1;
+        mn = v;
+      }
+    }
+  }
+  return besti;
+}
+
+// The dynamic LDS of a walk block: keys[cap] u64 | nb_id[nbmax] | nb_d[nbmax] | ctl[4] | flags[cap] u8 (padded to 16) | the query
+// scratch of the distance phase.  These are the offsets hnsw_lds_bytes (hnsw_kernels.hip) adds up: change both together.
+struct WalkLds {
+  lds_vu64* keys;
+  lds_vu32* nb_id;
+  lds_vf32* nb_d;
+  lds_vu32* ctl;
+  lds_vu8* flags;
+  unsigned char* query;
+  __device__ __forceinline__ WalkLds(unsigned char* smem, uint32_t cap, uint32_t nbmax) {
+    const size_t lists = (size_t)cap * 8 + (size_t)nbmax * 8;
+    keys = (lds_vu64*)(lds_void_p)(smem);
+    nb_id = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8);
+    nb_d = (lds_vf32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 4);
+    ctl = (lds_vu32*)(lds_void_p)(smem + lists);
+    flags = (lds_vu8*)(lds_void_p)(smem + lists + 16);
+    query = smem + lists + 16 + (((size_t)cap + 15) & ~(size_t)15);
+  }
+};
+
 // ---- exact visited set in LDS (round 3): open addressing over node id + 1 (0 = empty), linear probing, one LDS compare-
 // and-swap per probe.  The HBM bitmap costs a dependent memory round trip per expansion (atomicOr on a line that is rarely
 // in L2: 125 KB of bitmap per query in flight) between the neighbour ids and their rows; this costs ~100 cycles.  Exact: a
@@ -736,12 +781,7 @@ __device__ __forceinline__ void hnsw_walk_body(const HnswSearchArgs& a) {
   const uint32_t ef_launch = a.ef;
   uint32_t ef_query = a.ef;  // RAWEF only (wave-uniform)
 #define ef (RAWEF ? ef_query : ef_launch)
-  lds_vu64* keys = (lds_vu64*)(lds_void_p)(smem);
-  lds_vu32* nb_id = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8);
-  lds_vf32* nb_d = (lds_vf32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 4);
-  lds_vu32* ctl = (lds_vu32*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8);
-  lds_vu8* flags = (lds_vu8*)(lds_void_p)(smem + (size_t)cap * 8 + (size_t)nbmax * 8 + 16);
-  const size_t qoff = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+  const auto [keys, nb_id, nb_d, ctl, flags, qscratch] = WalkLds(smem, cap, nbmax);
 
   uint32_t* vis = a.visited + (size_t)blockIdx.x * a.vis_words;
   uint32_t* vlog = a.vlog + (size_t)blockIdx.x * a.vlog_cap;
@@ -753,7 +793,7 @@ __device__ __forceinline__ void hnsw_walk_body(const HnswSearchArgs& a) {
     __syncthreads();
   }
   DIST dist;
-  dist.init(a, smem + qoff);
+  dist.init(a, qscratch);
 
   for (uint32_t qi = blockIdx.x; qi < a.nq; qi += gridDim.x) {
     const float* qp = a.queries + (size_t)qi * a.q_stride;
@@ -826,26 +866,7 @@ __device__ __forceinline__ void hnsw_walk_body(const HnswSearchArgs& a) {
             }
           } else if (phase == P_G_SCAN) {
             n_dist += m_prev;
-            // sequential scan with strict `<` == first index attaining the minimum, if below best
-            float mn = 0.0f;
-            uint32_t besti = 0xFFFFFFFFu;
-            for (uint32_t base = 0; base < m_prev; base += 64) {
-              const uint32_t t = base + lane;
-              const float d = t < m_prev ? nb_d[t] : 0.0f;
-              const bool ok = t < m_prev && d < best_d;  // raw compare: NaN never improves
-              const uint64_t okm = __ballot(ok);
-              if (okm) {
-                float v = ok ? d : __uint_as_float(0x7F800000u);
-#pragma unroll
-                for (int s = 32; s >= 1; s >>= 1) v = fminf(v, shx(v, s));
-                v = rflf(v);
-                if (besti == 0xFFFFFFFFu || v < mn) {
-                  const uint64_t eq = __ballot(ok && d == v);
-                  besti = base + (uint32_t)__ffsll((long long)eq) - 1;
-                  mn = v;
-                }
-              }
-            }
+            const uint32_t besti = greedy_scan(nb_d, m_prev, best_d, lane);
             if (besti != 0xFFFFFFFFu) {
               cur = rfl(nb_id[besti]);
               best_d = rflf(nb_d[besti]);

@@ -413,6 +413,10 @@ int32_t hnsw_search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, 
                         uint32_t cap_mult, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st,
                         uint32_t rerank_k = 0, const uint32_t* d_extra_eps = nullptr);
 struct HnswSearchArgs;  // vdb_kernels.hpp
+// index -> HnswSearchArgs for every walk launch: the layers' lists (returns the longest neighbour list, unrounded) and the index
+// fields; queries, outputs, list sizes, scratch and counters are the caller's
+uint32_t walk_args_graph(const vdb_hip_index* ix, vdb::HnswSearchArgs& a);
+void walk_args_index(const vdb_hip_index* ix, vdb::HnswSearchArgs& a);
 // the launch-independent part of hnsw_search_dev (args, scratch, counters); *slots = 0: nothing to launch
 int32_t hnsw_search_prepare(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint32_t ef,
                             uint32_t cap_mult, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st,
