@@ -400,6 +400,36 @@ int32_t vdb_hip_index_search_graph_filters_half(vdb_hip_index* idx, int32_t mode
                                                 const uint32_t* filter_of_query, const float* queries_rowmajor, uint32_t nq,
                                                 uint32_t k, uint32_t ef, int32_t route, uint32_t max_list, uint64_t* out_ids,
                                                 float* out_scores, uint32_t* out_n, uint32_t* out_route);
+/* vdb_hip_index_search_graph_filters over the U8 CODES of the trained scalar quantiser (hnsw_filtered.hip): the walk of
+ * DualPrecisionHnsw::search_with_config(use_int8_traversal) (native/dual_precision.rs:223-441) with the allow-list consulted inside
+ * it.  For one query: ef_search' = ef_search, or the Balanced rule max(128, 4k) when 0; ratio = oversampling_ratio, or the handle's
+ * VDB_OPT_INT8_OVERSAMPLING / the process default when 0; cand_k = k * ratio; ef_w = max(ef_search', cand_k) (dual_precision.rs:334).
+ * Every distance of the walk is the INTEGER L2^2 between the quantised query and the row's codes, ordered as an integer, keys
+ * (distance, row); the greedy descent is unfiltered; layer 0 is the filtered search_layer of vdb_hip_index_search_graph_filters with
+ * ef_w for ef, unchanged in every rule (results take allowed rows only, the pivot is the ef_w-th allowed entry, the overflow
+ * report).  The first min(cand_k, results) allowed entries are re-scored with the exact f32 engine distance, stable-sorted by
+ * total_cmp (equal distances keep the coarse order, dual_precision.rs:267-281) and cut to k; out_n = min(k, results); there is no
+ * post-drop, allowed means alive.  The exact pass (route 2, the plan's whole-call cut, queries the largest list cannot hold) is the
+ * f32 one of vdb_hip_index_search_graph_filters: the top-k of the allowed live rows by f32 engine distance — a row has the same score
+ * bits on either route.  The route plan, ladders, max_list, out_route, padding, "no filter" = n_filters and a query's independence
+ * from its companions and its position are that call's, with ef_w where the plan takes ef; the largest list follows the int8 walk's
+ * LDS layout (the query's code words and the re-score output lie behind the lists).
+ * Two corollaries:
+ *   - with no query filtered (n_filters = 0, or "no filter" everywhere) on a handle without dead rows the call IS
+ *     vdb_hip_index_search_batch(VDB_SEARCH_HNSW_INT8) at the same ef_search and ratio: ids, score bits, out_n, n_dist and n_expand;
+ *   - for every id both routes return, route 1 and route 2 report identical score bits.
+ * vdb_hip_index_last_search_stats: n_dist counts the int8 evaluations of a query's last walk attempt (re-scored rows are not
+ * counted, as in mode 4) plus the rows its exact pass evaluated.
+ * Errors, all checked before anything runs, the outputs untouched: oversampling_ratio > 64: VDB_ERR_INVALID_ARG; quantiser not
+ * trained (vdb_hip_index_train_quantizer): VDB_ERR_STATE, as mode 4; Hamming / Jaccard handles, multi-device handles and
+ * process-group members: VDB_ERR_UNSUPPORTED; a NULL table entry, a filter of another handle, a filter_of_query value > n_filters,
+ * route outside 0..2: VDB_ERR_INVALID_ARG; a stale filter or no graph: VDB_ERR_STATE.  vdb_hip_index_last_kernels:
+ * VDB_KERNEL_HNSW_FILTERED | VDB_KERNEL_HNSW_INT8 and / or VDB_KERNEL_FILTER_RANK.  The three calls above keep refusing mode 4. */
+int32_t vdb_hip_index_search_graph_filters_int8(vdb_hip_index* idx, void** filters, uint32_t n_filters,
+                                                const uint32_t* filter_of_query, const float* queries_rowmajor, uint32_t nq,
+                                                uint32_t k, uint32_t ef_search, uint32_t oversampling_ratio, int32_t route,
+                                                uint32_t max_list, uint64_t* out_ids, float* out_scores, uint32_t* out_n,
+                                                uint32_t* out_route);
 
 /* ---- multi-query search with result fusion: Collection::multi_query_search / multi_query_search_ids (collection/search/batch.rs:
  * 206-403) and FusionStrategy::fuse (fusion/strategy.rs:138-300) on the device (fusion.hip, vdb_fusion.hpp) ----

@@ -24,6 +24,11 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
   up to 8 elements, and `admitted` (one bitmap word per admitted neighbour, not visible from outside) bounded by n_dist.
   Beside every route the f32 filtered call on the same handle (`f32_<route>_*`), its timing blocks alternating with the image's.
   One run of it is recorded: profiles/filter_probe_half_f16_100k.json (100 K x 768, densities 0.5 and 0.1).
+  --graph --precision int8 [--ratio R]: the three filtered routes go through vdb_hip_index_search_graph_filters_int8
+  over the u8 codes (train_quantizer on the same handle) at oversampling ratio R.  Algorithmic bytes per walked query:
+  n_dist * (dim + 4) + n_expand * M0 * 4 + admitted * 4 + k * R * dim * 4 for the re-score; the exact route is the f32 exact pass
+  and is counted as such.  The f32 filtered call runs beside it as above, and both get recall@k against the f32 exact answer.
+  One run of it is recorded: profiles/filter_probe_int8_100k.json (same shape and protocol).
   --graph --per-query F: the PER-QUERY leg instead (vdb_hip_index_search_graph_filters): at each density F distinct
   random filters of that density, the --graph-nq queries dealt round-robin over them; one call of search_batch_with_filters against
   the same queries as F calls of search_batch_filtered_graph, one per filter — what a caller does today with the same library, timed
@@ -58,7 +63,8 @@ p.add_argument("--rider", action="store_true")
 p.add_argument("--graph", action="store_true", help="the filtered graph search leg instead of the exact one")
 p.add_argument("--graph-nq", type=int, default=1024)
 p.add_argument("--per-query", type=int, default=0, help="with --graph: F distinct filters per density in one call against F single-filter calls")
-p.add_argument("--precision", default="f32", choices=["f32", "f16", "bf16"], help="with --graph: the rows the filtered walk reads")
+p.add_argument("--precision", default="f32", choices=["f32", "f16", "bf16", "int8"], help="with --graph: the rows the filtered walk reads")
+p.add_argument("--ratio", type=int, default=4, help="with --precision int8: the oversampling ratio")
 p.add_argument("--ef", type=int, default=128)
 p.add_argument("--densities", default="1,0.5,0.25,0.125,0.0625,0.03125,0.015625,0.0078125,0.00390625,0.001953125,0.0009765625")
 p.add_argument("--out", default="")
@@ -130,8 +136,14 @@ def graph_leg():
         if half_mode is not None:
             ix.enable_half_precision(va.VectorPrecision.F16 if a.precision == "f16" else va.VectorPrecision.BF16)
         row_bytes = 4 * stride if half_mode is None else 2 * stride + (4 if mname == "cosine" else 0)
+        int8 = a.precision == "int8"
+        if int8:
+            ix.train_quantizer()
+            row_bytes = a.dim + 4  # the codes and the row's sum of squared codes
 
         def filtered(Q, flt, route):
+            if int8:
+                return ix.search_batch_filtered_graph_int8(Q, a.k, flt, ef=a.ef, oversampling=a.ratio, route=route)
             if half_mode is None:
                 return ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route)
             return ix.search_batch_filtered_graph_half(Q, a.k, flt, half_mode, ef=a.ef, route=route)
@@ -165,11 +177,17 @@ def graph_leg():
                     row[name + "_algo_bytes"] = (n_dist * row_bytes + n_expand * m0 * 4 + n_dist * 4) / a.graph_nq
                     row[name + "_walked"] = float(np.mean(routes == 1))
                     row[name + "_recall"] = recall(ids.tolist(), cnt.tolist())
-                    if half_mode is None:
+                    if int8:  # the exact pass reads f32 rows; a walked query re-scores k * ratio of them
+                        if route == va.ROUTE_EXACT:
+                            row[name + "_algo_bytes"] = (n_dist * 4 * stride + n_dist * 4) / a.graph_nq
+                        else:
+                            row[name + "_algo_bytes"] += row[name + "_walked"] * a.k * a.ratio * a.dim * 4
+                    if half_mode is None and not int8:
                         ms, sp = measure(lambda: filtered(Q, flt, route))
                     else:  # the f32 filtered walk of the same build on the same handle, blocks alternating
-                        ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route)
+                        (fids, _, fcnt), _ = ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route)
                         fd, fe = ix.last_search_stats()[:2]
+                        row["f32_" + name + "_recall"] = recall(fids.tolist(), fcnt.tolist())
                         row["f32_" + name + "_n_dist"] = fd / a.graph_nq
                         row["f32_" + name + "_algo_bytes"] = (fd * 4 * stride + fe * m0 * 4 + fd * 4) / a.graph_nq
                         (ms, sp), (fms, fsp) = measure_pair(lambda: filtered(Q, flt, route),

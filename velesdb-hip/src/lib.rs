@@ -1081,7 +1081,7 @@ impl HipHnswIndex {
         route: i32,
         max_list: u32,
     ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
-        self.filters_call(queries, k, quality, filters, VectorPrecision::F32, route, max_list)
+        self.filters_call(queries, k, quality, filters, VectorPrecision::F32, None, route, max_list)
     }
 
     /// [`Self::search_batch_with_filters`] over the half-precision image of the rows (`vdb_hip_index_search_graph_filters_half`;
@@ -1103,10 +1103,35 @@ impl HipHnswIndex {
         route: i32,
         max_list: u32,
     ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
-        self.filters_call(queries, k, quality, filters, precision, route, max_list)
+        self.filters_call(queries, k, quality, filters, precision, None, route, max_list)
     }
 
-    // one filter per query over the f32 rows or a half image: the table, the buffers and the call
+    /// [`Self::search_batch_with_filters`] over the u8 codes of the trained quantiser (`vdb_hip_index_search_graph_filters_int8`;
+    /// on the index under a [`HipDualPrecisionHnsw`] whose quantiser is trained, [`HipDualPrecisionHnsw::inner`]): the walk of `DualPrecisionHnsw::search_with_config(use_int8_traversal)`
+    /// (native/dual_precision.rs:223-441) with the filter consulted inside it at `ef = max(ef_search, k * oversampling_ratio)`, the
+    /// `k * oversampling_ratio` best allowed candidates re-scored with the exact f32 distance and cut to `k`.  The exact pass is the
+    /// f32 one: a row has the same score on either route.  `oversampling_ratio` 0 = the handle's option; more than 64 is refused.
+    /// With no query filtered the call is the plain int8 traversal at the same `ef_search` and ratio.
+    ///
+    /// # Panics
+    /// When `filters.len() != queries.len()`.
+    #[must_use]
+    #[allow(clippy::too_many_arguments)]
+    pub fn search_batch_with_filters_int8(
+        &self,
+        queries: &[&[f32]],
+        k: usize,
+        quality: SearchQuality,
+        filters: &[Option<&HipFilter>],
+        oversampling_ratio: u32,
+        route: i32,
+        max_list: u32,
+    ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
+        self.filters_call(queries, k, quality, filters, VectorPrecision::F32, Some(oversampling_ratio), route, max_list)
+    }
+
+    // one filter per query over the f32 rows, a half image or (int8 = the oversampling ratio) the u8 codes: the table, the buffers
+    // and the call
     #[allow(clippy::too_many_arguments)]
     fn filters_call(
         &self,
@@ -1115,6 +1140,7 @@ impl HipHnswIndex {
         quality: SearchQuality,
         filters: &[Option<&HipFilter>],
         precision: VectorPrecision,
+        int8: Option<u32>,
         route: i32,
         max_list: u32,
     ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
@@ -1162,8 +1188,25 @@ impl HipHnswIndex {
         let table_p = if table.is_empty() { std::ptr::null_mut() } else { table.as_mut_ptr() };
         let ef = quality.ef_search(k) as u32;
         check(unsafe {
-            match precision {
-                VectorPrecision::F32 => sys::vdb_hip_index_search_graph_filters(
+            match (int8, precision) {
+                (Some(ratio), _) => sys::vdb_hip_index_search_graph_filters_int8(
+                    self.h,
+                    table_p,
+                    none,
+                    fq.as_ptr(),
+                    flat.as_ptr(),
+                    nq as u32,
+                    k as u32,
+                    ef,
+                    ratio,
+                    route,
+                    max_list,
+                    ids.as_mut_ptr(),
+                    scores.as_mut_ptr(),
+                    counts.as_mut_ptr(),
+                    routes.as_mut_ptr(),
+                ),
+                (None, VectorPrecision::F32) => sys::vdb_hip_index_search_graph_filters(
                     self.h,
                     table_p,
                     none,
@@ -1180,7 +1223,7 @@ impl HipHnswIndex {
                     counts.as_mut_ptr(),
                     routes.as_mut_ptr(),
                 ),
-                half => sys::vdb_hip_index_search_graph_filters_half(
+                (None, half) => sys::vdb_hip_index_search_graph_filters_half(
                     self.h,
                     if half == VectorPrecision::F16 { sys::VDB_SEARCH_HNSW_F16 } else { sys::VDB_SEARCH_HNSW_BF16 },
                     table_p,

@@ -89,6 +89,7 @@ SIGNATURES = {
     "vdb_hip_index_search_graph_filtered": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filters": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filters_half": (_i32, [_vp, _i32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
+    "vdb_hip_index_search_graph_filters_int8": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_fuse_results": (_i32, [_i32, _i32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "vdb_hip_index_multi_query_search": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_batch_distance": (_i32, [_i32, _i32, _i32, _vp, _vp, _u64, _u32, _vp]),

@@ -28,6 +28,11 @@
 // filters_rank_half_kernel are the same two bodies with the half walk's distance phase (WalkDistHalf,
 // hnsw_half.hip) — the query rounded to the precision against the row's f16 / bf16 image, n_dist * (2 * stride [+ 4 Cosine]) row bytes.
 //
+// Over the u8 codes of the trained scalar quantiser (vdb_hip_index_search_graph_filters_int8):
+// hnsw_search_filters_int8_kernel is the walk body with WalkDistInt8 — integer distances, ordered as integers (DIST::UD), ef widened
+// over k * oversampling — and, behind the walk, the re-score of the k * oversampling best allowed candidates by the exact f32 engine
+// distance (DIST::RESCORE), as hnsw_search_int8_kernel (hnsw_int8.hip) ends; its exact pass is filters_rank_kernel itself.
+//
 // Algorithmic HBM bytes per query: walk n_dist * dim * 4 + n_expand * M0 * 4 + (admitted neighbours) * 4 for the bitmap words;
 // exact pass matched * (dim * 4 + 4).  Measured once, at one shape, f16 beside f32: tools/filter_probe.py has the graph leg.
 #include <algorithm>
@@ -145,14 +150,15 @@ __device__ __forceinline__ uint32_t find_pivot(lds_vu8* flags, uint32_t cnt, uin
   return kNoIndex;
 }
 
-// entries behind the pivot stay only up to the last one whose distance is not greater than the pivot's
+// entries behind the pivot stay only up to the last one whose distance is not greater than the pivot's (UD: key_dist_gt's domain)
+template <bool UD>
 __device__ __forceinline__ void pivot_truncate(lds_vu64* keys, uint32_t& cnt, uint32_t pivot, int lane) {
   if (pivot == kNoIndex || cnt <= pivot + 1) return;
   const uint64_t wk = keys[pivot];
   uint32_t last = pivot;
   for (uint32_t c = pivot + 1; c < cnt; c += 64) {
     const uint32_t e = c + lane;
-    const bool stay = e < cnt && !(key_dist(keys[e]) > key_dist(wk));  // negation of graph.rs:474's raw compare
+    const bool stay = e < cnt && !key_dist_gt<UD>(keys[e], wk);  // negation of graph.rs:474's raw compare
     const uint64_t mask = __ballot(stay);
     if (mask) last = c + 63u - (uint32_t)__clzll((long long)mask);
   }
@@ -178,10 +184,18 @@ template <int METRIC, int CPL>
 constexpr int kFiltHalfRows = (CPL == 4 ? 4 : 8);
 template <int METRIC, int CPL, bool F16>
 using FiltDistHalf = WalkDistHalf<METRIC, CPL, 4, kFiltHalfRows<METRIC, CPL>, F16>;
+// ... and over the u8 codes (vdb_hip_index_search_graph_filters_int8): dist_phase_int8 for the walk; the re-score is
+// one FiltDist phase, so a row has the score bits the f32 exact pass gives it
+template <int METRIC, int CPL>
+using FiltDistInt8 = WalkDistInt8<METRIC, CPL, 4, ((CPL == 4 || (CPL == 3 && METRIC == kEuclidean)) ? 4 : 8)>;
 
-// The walk of the kernel families below (LDS: WalkLds, vdb_hnsw_device.hpp); DIST says which rows the distances are taken over
-template <int METRIC, int CPL, class DIST = FiltDist<METRIC, CPL>>
-__device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa) {
+// The walk of the kernel families below (LDS: WalkLds, vdb_hnsw_device.hpp); DIST says which rows the distances are taken over, in
+// which domain they are ordered (DIST::UD: f32 raw compares, or the int8 walk's integers — walk_key / key_bound / dist_lt /
+// key_dist_gt / greedy_scan, vdb_hnsw_device.hpp) and whether the best candidates are re-scored behind the walk (DIST::RESCORE).
+// `dist` arrives with whatever its init cannot take from HnswSearchArgs already set.
+template <int METRIC, int CPL, class DIST>
+__device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa, DIST& dist) {
+  constexpr bool UD = DIST::UD;
   const HnswSearchArgs& a = fa.s;
   unsigned long long* qstats = fa.qstats;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -191,7 +205,6 @@ __device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa) {
   const auto [keys, nb_id, nb_d, ctl, flags, qscratch] = WalkLds(smem, cap, nbmax);
   uint32_t* vis = a.visited + (size_t)blockIdx.x * a.vis_words;
   uint32_t* vlog = a.vlog + (size_t)blockIdx.x * a.vlog_cap;
-  DIST dist;
   dist.init(a, qscratch);
 
   for (uint32_t slot = blockIdx.x; slot < a.nq; slot += gridDim.x) {
@@ -212,10 +225,10 @@ __device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa) {
     // (keys = keys: a structured binding cannot be captured in C++17)
     auto admit = [&, keys = keys, flags = flags](float d, uint32_t node) {
       uint32_t lost, lost_flag;
-      flist_insert(keys, flags, cnt, f.cap, make_key<false>(d, node), row_allowed(f, a.alive, node), lane, lost, lost_flag);
+      flist_insert(keys, flags, cnt, f.cap, walk_key<UD>(d, node), row_allowed(f, a.alive, node), lane, lost, lost_flag);
       pivot = find_pivot(flags, cnt, ef, lane);
       if (lost && ((lost_flag & kFlagExpanded) == 0 || ((lost_flag & kFlagAllowed) != 0 && pivot == kNoIndex))) overflow = 1;
-      pivot_truncate(keys, cnt, pivot, lane);
+      pivot_truncate<UD>(keys, cnt, pivot, lane);
     };
 
     for (;;) {
@@ -249,7 +262,7 @@ __device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa) {
             }
           } else if (phase == P_G_SCAN) {
             n_dist += m_prev;
-            const uint32_t besti = greedy_scan(nb_d, m_prev, best_d, lane);
+            const uint32_t besti = greedy_scan<UD>(nb_d, m_prev, best_d, lane);
             if (besti != 0xFFFFFFFFu) {
               cur = rfl(nb_id[besti]);
               best_d = rflf(nb_d[besti]);
@@ -287,7 +300,7 @@ __device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa) {
             } else {
               const uint64_t ckey = keys[idx];
               // graph.rs:474 with furthest = the pivot's distance and results.len() >= ef = "there is a pivot"
-              if (pivot != kNoIndex && key_dist(ckey) > key_dist(keys[pivot])) {
+              if (pivot != kNoIndex && key_dist_gt<UD>(ckey, keys[pivot])) {
                 phase = P_FINISH;
               } else {
                 if (lane == 0) flags[idx] = (uint8_t)(flags[idx] | kFlagExpanded);
@@ -329,13 +342,13 @@ __device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa) {
               const float d = t < m_prev ? nb_d[t] : 0.0f;
               // pre-filter against the bound at chunk start: it only falls while the result set is full (there is a pivot), so a
               // neighbour rejected now would be rejected at its turn too
-              const float far0 = pivot != kNoIndex ? key_dist(keys[pivot]) : 0.0f;
-              uint64_t mask = __ballot(t < m_prev && (pivot == kNoIndex || d < far0));
+              const float far0 = pivot != kNoIndex ? key_bound<UD>(keys[pivot]) : 0.0f;
+              uint64_t mask = __ballot(t < m_prev && (pivot == kNoIndex || dist_lt<UD>(d, far0)));
               while (mask) {
                 const int src = __ffsll((long long)mask) - 1;
                 mask &= mask - 1;
                 const float dj = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(d), src));
-                if (pivot == kNoIndex || dj < key_dist(keys[pivot])) admit(dj, nb_id[base + src]);  // graph.rs:503
+                if (pivot == kNoIndex || dist_lt<UD>(dj, key_bound<UD>(keys[pivot]))) admit(dj, nb_id[base + src]);  // graph.rs:503
               }
             }
             phase = P_Z_POP;
@@ -358,6 +371,56 @@ __device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa) {
       __syncthreads();
     }
 
+    if constexpr (DIST::RESCORE) {
+      // ---- re-score (dual_precision.rs:377-383, 267-281): the coarse candidates = the first min(cand_k, allowed) allowed entries in
+      // list order; their exact f32 engine distances in one phase (the f32 query is loaded only now); a stable sort by total_cmp —
+      // sort key = (total-order(dist) << 32 | coarse position), unique, rank = the smaller keys — and the cut to k.  No alive test:
+      // allowed means alive.  n_dist does not count these rows (hnsw_search_int8_kernel does not either). ----
+      if (wib == 0) {
+        const uint32_t want = min(dist.cand_k, nbmax);  // (the host rounds nbmax over cand_k)
+        uint32_t rr = 0;
+        for (uint32_t base = 0; base < cnt && rr < want; base += 64) {
+          const uint32_t e = base + lane;
+          const bool al = e < cnt && (flags[e] & kFlagAllowed) != 0;
+          const uint64_t mask = __ballot(al);
+          const uint32_t p = rr + (uint32_t)__popcll(mask & lt_mask(lane));
+          if (al && p < want) nb_id[p] = (uint32_t)keys[e];
+          rr = min(want, rr + (uint32_t)__popcll(mask));
+        }
+        if (lane == 0) ctl[3] = rr;
+      }
+      dist.load_exact(a.queries + (size_t)qi * a.q_stride, lane);
+      __syncthreads();
+      const uint32_t m = ctl[3];
+      dist.eval_exact(m, nb_id, nb_d, lane, wib);
+      __syncthreads();
+      if (wib == 0) {
+        lds_vu64* outp = dist.outp;
+        for (uint32_t i = lane; i < m; i += 64) keys[i] = make_key<false>(nb_d[i], i);  // (m <= cnt: the list has the room)
+        for (uint32_t i = lane; i < m; i += 64) {
+          const uint64_t mine = keys[i];
+          uint32_t rank = 0;
+          for (uint32_t j = 0; j < m; j++) rank += keys[j] < mine ? 1u : 0u;
+          outp[rank] = ((uint64_t)nb_id[i] << 32) | (uint64_t)__float_as_uint(nb_d[i]);  // (rank < m <= nbmax)
+        }
+        const uint32_t outn = m < a.k ? m : a.k;
+        for (uint32_t e = lane; e < outn; e += 64) {
+          const uint64_t pk = outp[e];
+          const uint32_t node = (uint32_t)(pk >> 32);
+          a.out_ids[(size_t)qi * a.k + e] = a.ext_ids ? a.ext_ids[node] : (uint64_t)node;
+          a.out_scores[(size_t)qi * a.k + e] = transform_score_dev(METRIC, __uint_as_float((uint32_t)pk));
+        }
+        for (uint32_t e = outn + lane; e < a.k; e += 64) {
+          a.out_ids[(size_t)qi * a.k + e] = ~0ull;
+          a.out_scores[(size_t)qi * a.k + e] = __uint_as_float(0x7FC00000u);
+        }
+        if (lane == 0) {
+          a.out_n[qi] = overflow ? 0xFFFFFFFFu : outn;
+          qstats[(size_t)qi * 2] = n_dist;
+          qstats[(size_t)qi * 2 + 1] = n_expand;
+        }
+      }
+    } else
     // ---- results: the first k allowed entries in list order (all of them are alive: the flag says so), scores through
     // transform_score; NaN / ~0 padding and out_n as the unfiltered walk ----
     if (wib == 0) {
@@ -398,13 +461,34 @@ __device__ __forceinline__ void filtered_walk_body(const HnswFiltersArgs& fa) {
 
 template <int METRIC, int CPL>
 __global__ __launch_bounds__(256, 4) void hnsw_search_filters_kernel(HnswFiltersArgs fa) {
-  filtered_walk_body<METRIC, CPL>(fa);
+  FiltDist<METRIC, CPL> dist;
+  filtered_walk_body<METRIC, CPL>(fa, dist);
 }
 // ... over the half image: a.rows = the image, a.row_stride in half elements, a.norms of the rounded rows; the queries stay f32 and
 // are rounded at load
 template <int METRIC, int CPL, bool F16>
 __global__ __launch_bounds__(256, 4) void hnsw_search_filters_half_kernel(HnswFiltersArgs fa) {
-  filtered_walk_body<METRIC, CPL, FiltDistHalf<METRIC, CPL, F16>>(fa);
+  FiltDistHalf<METRIC, CPL, F16> dist;
+  filtered_walk_body<METRIC, CPL>(fa, dist);
+}
+// ... over the u8 codes of DualPrecisionHnsw (vdb_hip_index_search_graph_filters_int8): the same body with the int8
+// walk's integer distances (WalkDistInt8: ordered as integers) and the re-score of the k * oversampling best allowed candidates by the
+// exact f32 engine distance behind it.  a.rows / a.norms stay the f32 rows (the re-score); a.ef = max(ef_search, k * oversampling).
+struct HnswFiltersInt8Args {
+  HnswFiltersArgs f;
+  CodeCtx codes;
+  const float* min_vals;  // [dim]
+  const float* scales;    // [dim]
+  uint32_t cand_k;        // k * oversampling (<= f.s.nbmax)
+};
+template <int METRIC, int CPL>
+__global__ __launch_bounds__(256, 4) void hnsw_search_filters_int8_kernel(HnswFiltersInt8Args A) {
+  FiltDistInt8<METRIC, CPL> dist;
+  dist.codes = A.codes;
+  dist.min_vals = A.min_vals;
+  dist.scales = A.scales;
+  dist.cand_k = A.cand_k;
+  filtered_walk_body<METRIC, CPL>(A.f, dist);
 }
 
 // The exact pass: one block per query over the filter's ascending row list in chunks of nbmax — dead rows skipped, distances by
@@ -517,9 +601,9 @@ static auto kernel_of() {
     return RANK ? filters_rank_half_kernel<METRIC, CPL, ROWS == kFiltersF16> : hnsw_search_filters_half_kernel<METRIC, CPL, ROWS == kFiltersF16>;
 }
 
-template <bool RANK, int METRIC, int CPL, int ROWS>
-static hipError_t launch_fk(const HnswFiltersArgs& fa, int slots, size_t lds, hipStream_t st) {
-  auto kern = kernel_of<RANK, METRIC, CPL, ROWS>();
+// one launch of a family's kernel (ARGS: HnswFiltersArgs, or HnswFiltersInt8Args around it)
+template <class KERN, class ARGS>
+static hipError_t launch_walk_blocks(KERN kern, const ARGS& fa, uint32_t n_cus, int slots, size_t lds, hipStream_t st) {
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -530,9 +614,13 @@ static hipError_t launch_fk(const HnswFiltersArgs& fa, int slots, size_t lds, hi
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, lds);
   if (e != hipSuccess) return e;
   occ = std::max(1, std::min(occ, 4));
-  const int grid = (int)std::min<int64_t>((int64_t)slots, (int64_t)fa.s.n_cus * occ);
+  const int grid = (int)std::min<int64_t>((int64_t)slots, (int64_t)n_cus * occ);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, fa);
   return hipGetLastError();
+}
+template <bool RANK, int METRIC, int CPL, int ROWS>
+static hipError_t launch_fk(const HnswFiltersArgs& fa, int slots, size_t lds, hipStream_t st) {
+  return launch_walk_blocks(kernel_of<RANK, METRIC, CPL, ROWS>(), fa, fa.s.n_cus, slots, lds, st);
 }
 template <bool RANK, int METRIC, int ROWS>
 static hipError_t launch_fk_cpl(const HnswFiltersArgs& fa, int slots, size_t lds, hipStream_t st) {
@@ -567,10 +655,33 @@ static hipError_t launch_filters_rows(const HnswFiltersArgs& fa, int rows, int s
   return launch_filtered<RANK>(fa, slots, lds, st);
 }
 
+// ... the walk over the u8 codes (three metrics: refused in front of the call otherwise)
+template <int METRIC>
+static hipError_t launch_int8_cpl(const HnswFiltersInt8Args& A, int slots, size_t lds, hipStream_t st) {
+  const uint32_t n_cus = A.f.s.n_cus;
+  switch (sweep_cpl_for_dim(A.f.s.dim)) {
+    case 1: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 1>, A, n_cus, slots, lds, st);
+    case 2: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 2>, A, n_cus, slots, lds, st);
+    case 3: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 3>, A, n_cus, slots, lds, st);
+    case 4: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 4>, A, n_cus, slots, lds, st);
+    default: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 0>, A, n_cus, slots, lds, st);
+  }
+}
+static hipError_t launch_filters_int8(const HnswFiltersInt8Args& A, int slots, size_t lds, hipStream_t st) {
+  switch (A.f.s.metric) {
+    case kCosine: return launch_int8_cpl<kCosine>(A, slots, lds, st);
+    case kEuclidean: return launch_int8_cpl<kEuclidean>(A, slots, lds, st);
+    case kDot: return launch_int8_cpl<kDot>(A, slots, lds, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // the largest list (entries) whose launch stays inside 160 KB of LDS at this nbmax: hnsw_search_prepare's limit
-static uint32_t largest_list(uint32_t nbmax, uint32_t dim, uint32_t words, int metric) {
+// (lds_of: the call's layout — hnsw_lds_bytes, or hnsw_int8_lds_bytes for the walk over the codes)
+template <class LdsOf>
+static uint32_t largest_list(LdsOf&& lds_of) {
   uint64_t cap = kFgLdsBudget / 9 / 64 * 64;
-  while (cap && hnsw_lds_bytes((uint32_t)cap, nbmax, dim, words, metric) > kFgLdsBudget) cap -= 64;
+  while (cap && lds_of((uint32_t)cap) > kFgLdsBudget) cap -= 64;
   return (uint32_t)cap;
 }
 
@@ -582,16 +693,23 @@ static uint32_t largest_list(uint32_t nbmax, uint32_t dim, uint32_t words, int m
 // filters: [n_filters] handles, non-null; fq: [nq] values in 0..n_filters, n_filters = no filter; routes: host, [nq].
 int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                        const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
-                                       uint32_t* routes, int half) {
+                                       uint32_t* routes, int half, uint32_t ratio) {
   int32_t rc;
+  const bool int8 = half == kFiltersInt8;
+  // (the statuses of the plain int8 walk, hnsw_search_int8_dev)
+  if (int8 && !ix->quantizer_trained) return fail(VDB_ERR_STATE, "int8 filtered graph search: call vdb_hip_index_train_quantizer first");
+  if (int8 && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, "int8 filtered graph search: Cosine, DotProduct and Euclidean only");
+  if (int8 && (ratio == 0 || ratio > 64)) return fail(VDB_ERR_INVALID_ARG, "int8 filtered graph search: oversampling ratio 1..64");
   // (the statuses of the plain half walk, hnsw_search_half_dev)
   if (half == kFiltersF16 && !ix->f16_enabled)
     return fail(VDB_ERR_STATE, "f16 filtered graph search: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
   if (half == kFiltersBF16 && !ix->bf16_enabled)
     return fail(VDB_ERR_STATE, "bf16 filtered graph search: call vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16) first");
-  if (half != kFiltersF32 && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+  if ((half == kFiltersF16 || half == kFiltersBF16) && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
     return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search: Cosine, DotProduct and Euclidean only");
-  const uint32_t half_kernels = half == kFiltersF32 ? 0u : (VDB_KERNEL_HNSW_HALF | (half == kFiltersF16 ? VDB_KERNEL_F16 : 0u));
+  const bool half_rows = half == kFiltersF16 || half == kFiltersBF16;
+  const uint32_t half_kernels = half_rows ? (VDB_KERNEL_HNSW_HALF | (half == kFiltersF16 ? VDB_KERNEL_F16 : 0u)) : 0u;
   for (uint32_t j = 0; j < n_filters; j++)
     if ((rc = filter_check(ix, filters[j])) != VDB_OK) return rc;
   if (!ix->graph_valid) return fail(VDB_ERR_STATE, "HNSW graph not built for all rows (use the exact filtered search or build it)");
@@ -634,14 +752,25 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   if (ix->layers.size() > (size_t)kMaxLayers) return fail(VDB_ERR_UNSUPPORTED, "more than 16 graph layers");
   if (ef == 0) ef = std::max<uint32_t>(128, k * 4);  // Balanced, params.rs:313
   ef = std::max(ef, k);                               // SearchQuality::Custom(ef) = max(ef, k), params.rs:317
+  // the walk over the codes: cand_k = k * ratio coarse candidates, ef widened over them (dual_precision.rs:334) — the plans take it
+  const uint64_t cand_k = int8 ? (uint64_t)k * ratio : 0;
+  if (int8) ef = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ef, cand_k), 0xFFFFFFFFull);
 
-  HnswFiltersArgs fa{};
+  HnswFiltersInt8Args fa8{};
+  HnswFiltersArgs& fa = fa8.f;
   HnswSearchArgs& a = fa.s;
-  const uint32_t nbmax = (walk_args_graph(ix, a) + 63) / 64 * 64;
-  uint32_t cap_max = largest_list(nbmax, ix->dim, ix->words, ix->metric);
+  // (the re-score gathers its cand_k candidates into the nb arrays: rounded over both, as hnsw_search_int8_dev)
+  const uint32_t longest = walk_args_graph(ix, a);
+  const uint32_t nbmax = (uint32_t)std::min<uint64_t>((std::max<uint64_t>(longest, cand_k) + 63) / 64 * 64, 0xFFFFFFC0ull);
+  const uint32_t nbmax_exact = (longest + 63) / 64 * 64;  // (the exact pass has no candidates to gather: the f32 call's chunks)
+  // the walk's layout and the exact pass's (always the f32 one)
+  auto lds_of = [&](uint32_t cap) -> uint64_t {
+    return int8 ? hnsw_int8_lds_bytes(cap, nbmax, ix->dim, ix->code_words) : hnsw_lds_bytes(cap, nbmax, ix->dim, ix->words, ix->metric);
+  };
+  auto lds_of_exact = [&](uint32_t cap) -> uint64_t { return hnsw_lds_bytes(cap, nbmax_exact, ix->dim, ix->words, ix->metric); };
+  uint32_t cap_max = largest_list(lds_of);
   if (max_list) cap_max = std::min(cap_max, max_list);
   const std::string limits = " (route " + std::to_string(route) + ", max_list " + std::to_string(max_list) + ", ef " + std::to_string(ef) + ")";
-  auto lds_of = [&](uint32_t cap) -> uint64_t { return hnsw_lds_bytes(cap, nbmax, ix->dim, ix->words, ix->metric); };
 
   // the descriptor table (the last entry: no filter) and every query's own plan
   std::vector<FilterDesc> descs(n_filters + 1);
@@ -698,7 +827,14 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   a.k = k;
   a.ef = ef;
   a.nbmax = nbmax;
-  if (half != kFiltersF32) {  // the image instead of the f32 rows, as hnsw_search_half_dev: same fields, the stride in half elements
+  if (int8) {  // the codes beside the f32 rows, which the re-score and the exact pass read
+    a.bits = nullptr;
+    fa8.codes = CodeCtx{ix->codes.as<uint32_t>(), ix->codes_sq.as<uint32_t>(), ix->code_words};
+    fa8.min_vals = ix->sq_min.as<float>();
+    fa8.scales = ix->sq_scale.as<float>();
+    fa8.cand_k = (uint32_t)cand_k;  // (<= nbmax <= 2^32 - 64, or the lists did not fit and no walk is planned)
+  }
+  if (half_rows) {  // the image instead of the f32 rows, as hnsw_search_half_dev: same fields, the stride in half elements
     const bool f16 = half == kFiltersF16;
     a.rows = reinterpret_cast<const float*>(f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>());
     a.norms = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
@@ -733,10 +869,10 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
       const size_t lds = lds_of(a.cap);
       if (lds > kFgLdsBudget) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: candidate list beyond the LDS" + limits);
       const int slots_l = (int)std::min<int64_t>((int64_t)L.count, (int64_t)ix->n_cus * (int64_t)L.per_cu);
-      const hipError_t e = launch_filters_rows<false>(fa, half, slots_l, lds, st);
+      const hipError_t e = int8 ? launch_filters_int8(fa8, slots_l, lds, st) : launch_filters_rows<false>(fa, half, slots_l, lds, st);
       if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filtered hnsw_search launch: ") + hipGetErrorString(e));
     }
-    ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED | half_kernels;
+    ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED | half_kernels | (int8 ? (uint32_t)VDB_KERNEL_HNSW_INT8 : 0u);
     r = fetch();
     if (r != VDB_OK) return r;
     for (uint32_t i = 0; i < n; i++) over[i] = h_n[slots[i].query] == 0xFFFFFFFFu;
@@ -754,15 +890,16 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   }
   if (!exact.empty()) {  // every exact pass of the call in one launch: the whole-route ones and what the largest list could not hold
     a.cap = (uint32_t)fg_round64(k);
+    a.nbmax = nbmax_exact;
     for (FiltersSlot& s : exact) s.cap = a.cap;
-    const size_t lds = lds_of(a.cap);
+    const size_t lds = lds_of_exact(a.cap);
     if (lds > kFgLdsBudget) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: k too large for the LDS-resident result list");
     rc = slots_up(exact.data(), exact.size());
     if (rc != VDB_OK) return rc;
     a.nq = (uint32_t)exact.size();
     fa.slots = d_slots;
     const int slots_l = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * 4);
-    const hipError_t e = launch_filters_rows<true>(fa, half, slots_l, lds, st);
+    const hipError_t e = launch_filters_rows<true>(fa, int8 ? (int)kFiltersF32 : half, slots_l, lds, st);  // (int8: scored in f32 anyway)
     if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filters_rank launch: ") + hipGetErrorString(e));
     ix->last_kernels |= VDB_KERNEL_FILTER_RANK | half_kernels;
     rc = fetch();

@@ -535,13 +535,8 @@ int32_t hnsw_search_int8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_str
   const bool reg_list = cap_mult == 1 && ef + 64 <= (uint64_t)kSearchRegSlots * 64 && ix->n_rows < (1ull << 31);
   if (reg_list) cap = (uint64_t)kSearchRegSlots * 64;
   cap = std::max<uint64_t>(cap, cand_k);
-  const int cpl = sweep_cpl_for_dim(ix->dim);
-  size_t lds = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
-  if (cpl == 0) lds += (size_t)((ix->dim + 3) / 4) * 16;
-  lds += (size_t)ix->code_words * 4;
-  lds = (lds + 15) & ~(size_t)15;
-  lds += (size_t)nbmax * 8;
-  if (cap > 0xFFFFFFFFull || lds > 160 * 1024)
+  const size_t lds = cap > 0xFFFFFFFFull ? ~(size_t)0 : hnsw_int8_lds_bytes((uint32_t)cap, nbmax, ix->dim, ix->code_words);
+  if (lds > 160 * 1024)
     return fail(VDB_ERR_UNSUPPORTED, "ef too large for the LDS-resident candidate list");
   int32_t rcs = ensure_traversal_scratch(ix, st);
   if (rcs != VDB_OK) return rcs;

@@ -69,6 +69,15 @@ size_t hnsw_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint32_t words
     s += (size_t)((dim + 3) / 4) * 16;
   return (s + 15) & ~(size_t)15;
 }
+// ... of an int8 walk block (hnsw_search_int8_kernel, hnsw_int8.hip; hnsw_search_filters_int8_kernel, hnsw_filtered.hip): WalkLds |
+// f32 query scratch (generic dims: the re-score) | the query's code words [code_words] | (pad 16) | re-score output [nbmax] u64
+size_t hnsw_int8_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint32_t code_words) {
+  size_t s = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+  if (sweep_cpl_for_dim(dim) == 0) s += (size_t)((dim + 3) / 4) * 16;
+  s += (size_t)code_words * 4;
+  s = (s + 15) & ~(size_t)15;
+  return s + (size_t)nbmax * 8;
+}
 
 // latency mode: one 1 024-thread block per query (at most one query per CU per call)
 template <int METRIC, int CPL, bool VIS>

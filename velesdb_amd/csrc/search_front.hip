@@ -109,11 +109,12 @@ static int32_t search_graph_filtered_direct(vdb_hip_index* handle, const RowFilt
 // half: the rows of the walk (FiltersRows; vdb_hip_index_search_graph_filters_half)
 static int32_t search_graph_filters_direct(vdb_hip_index* handle, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                            const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
-                                           uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route, int half = kFiltersF32) {
+                                           uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route, int half = kFiltersF32,
+                                           uint32_t ratio = 0) {
   std::vector<uint32_t> routes(nq, 0u);
   return run_search(
       handle, nq, k, ef, VDB_SEARCH_HNSW, 0,
-      [&](vdb_hip_index* ix) { return search_graph_filters_to_device(ix, filters, n_filters, fq, queries, nq, k, ef, route, max_list, routes.data(), half); },
+      [&](vdb_hip_index* ix) { return search_graph_filters_to_device(ix, filters, n_filters, fq, queries, nq, k, ef, route, max_list, routes.data(), half, ratio); },
       [&](vdb_hip_index* ix) {
         deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n);
         if (out_route) std::memcpy(out_route, routes.data(), (size_t)nq * 4);
@@ -375,6 +376,36 @@ int32_t vdb_hip_index_search_graph_filters_half(vdb_hip_index* ix, int32_t mode,
   return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k, ef,
                                      route, max_list, out_ids, out_scores, out_n, out_route,
                                      mode == VDB_SEARCH_HNSW_F16 ? kFiltersF16 : kFiltersBF16);
+  });
+}
+
+// the same call over the u8 codes of DualPrecisionHnsw: the int8 walk with the allow-list inside it, the re-score of the
+// k * oversampling_ratio best allowed candidates in f32, the f32 exact pass.  A symbol of its own — the three calls above keep
+// refusing mode 4, which is their documented contract
+int32_t vdb_hip_index_search_graph_filters_int8(vdb_hip_index* ix, void** filters, uint32_t n_filters, const uint32_t* filter_of_query,
+                                                const float* queries, uint32_t nq, uint32_t k, uint32_t ef_search,
+                                                uint32_t oversampling_ratio, int32_t route, uint32_t max_list, uint64_t* out_ids,
+                                                float* out_scores, uint32_t* out_n, uint32_t* out_route) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || (n_filters && !filters) || (nq && (!queries || !out_n || !filter_of_query)) || (nq && k && (!out_ids || !out_scores)))
+    return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filtered graph search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, "int8 filtered graph search: Cosine, DotProduct and Euclidean only");
+  // the bound vdb_hip_set_int8_oversampling holds the handle's option to: k * ratio sizes nbmax, ef and the LDS list of the walk
+  if (oversampling_ratio > 64) return fail(VDB_ERR_INVALID_ARG, "int8 filtered graph search: oversampling_ratio 0 (the handle's option) or 1..64");
+  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
+  for (uint32_t j = 0; j < n_filters; j++)
+    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: filter " + std::to_string(j) + " of the table is null");
+  for (uint32_t i = 0; i < nq; i++)
+    if (filter_of_query[i] > n_filters)
+      return fail(VDB_ERR_INVALID_ARG, "filtered graph search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
+                                           " of a table of " + std::to_string(n_filters));
+  if (nq == 0) return VDB_OK;
+  const uint32_t ratio = oversampling_ratio ? oversampling_ratio : (uint32_t)opt_value(ix, VDB_OPT_INT8_OVERSAMPLING);
+  return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k,
+                                     ef_search, route, max_list, out_ids, out_scores, out_n, out_route, kFiltersInt8, ratio);
   });
 }
 

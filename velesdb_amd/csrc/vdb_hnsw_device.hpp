@@ -86,7 +86,31 @@ __device__ __forceinline__ void list_insert(lds_vu64* keys, lds_vu8* flags, uint
 
 // The scan of a greedy step on the upper layers (graph.rs:413-421): sequential with strict `<` == the first index of nb_d[0..m)
 // attaining the minimum, if that is below best_d; 0xFFFFFFFF when no neighbour improves.  Wave-uniform result.
+// UD: nb_d and best_d carry u32 bit patterns (the int8 walk's integer distances, dual_precision.rs:422-433) and are ordered as such.
+template <bool UD = false>
 __device__ __forceinline__ uint32_t greedy_scan(lds_vf32* nb_d, uint32_t m, float best_d, int lane) {
+  if constexpr (UD) {
+    const uint32_t best_u = __float_as_uint(best_d);
+    uint32_t mn = 0, besti = 0xFFFFFFFFu;
+    for (uint32_t base = 0; base < m; base += 64) {
+      const uint32_t t = base + lane;
+      const uint32_t d = t < m ? __float_as_uint(nb_d[t]) : 0xFFFFFFFFu;
+      const bool ok = t < m && d < best_u;
+      const uint64_t okm = __ballot(ok);
+      if (okm) {
+        uint32_t v = ok ? d : 0xFFFFFFFFu;
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, s, 64));
+        v = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+        if (besti == 0xFFFFFFFFu || v < mn) {
+          const uint64_t eq = __ballot(ok && d == v);
+          besti = base + (uint32_t)__ffsll((long long)eq) - 1;
+          mn = v;
+        }
+      }
+    }
+    return besti;
+  }
   float mn = 0.0f;
   uint32_t besti = 0xFFFFFFFFu;
   for (uint32_t base = 0; base < m; base += 64) {
@@ -160,6 +184,26 @@ template <bool UD>
 __device__ __forceinline__ bool key_dist_gt(uint64_t a, uint64_t b) {
   if (UD) return (uint32_t)(a >> 32) > (uint32_t)(b >> 32);
   return key_dist(a) > key_dist(b);
+}
+
+// ... and what a walk whose distance phase says which domain it works in (DIST::UD) builds and asks with it: the key of
+// (distance, node), a key's distance as the bound of an admission test, and "distance d is below the bound" — the raw compare of
+// graph.rs:503 / dual_precision.rs:359.  With UD a float is only the carrier of the u32 bit pattern nb_d holds: never compared or
+// converted as a number.
+template <bool UD>
+__device__ __forceinline__ uint64_t walk_key(float d, uint32_t node) {
+  if (UD) return ((uint64_t)__float_as_uint(d) << 32) | (uint64_t)node;
+  return make_key<false>(d, node);
+}
+template <bool UD>
+__device__ __forceinline__ float key_bound(uint64_t key) {
+  if (UD) return __uint_as_float((uint32_t)(key >> 32));
+  return key_dist(key);
+}
+template <bool UD>
+__device__ __forceinline__ bool dist_lt(float d, float bound) {
+  if (UD) return __float_as_uint(d) < __float_as_uint(bound);
+  return d < bound;
 }
 
 // entries past ef stay only up to the last one the termination test could still expand
@@ -671,6 +715,8 @@ enum WalkPhase : int {
 // the f32 rows (Cosine / Euclidean / DotProduct, canonical arithmetic) and the packed bits (Hamming / Jaccard)
 template <int METRIC, int CPL, int WAVES, int R>
 struct WalkDistF32 {
+  static constexpr bool UD = false;       // f32 distances, ordered as the reference's raw compares order them
+  static constexpr bool RESCORE = false;  // the walk's own distances are the answer's
   static constexpr bool BITS = (METRIC == kHamming || METRIC == kJaccard);
   static constexpr int TPB = WAVES * 64;
   DistCtx dc;
@@ -731,6 +777,7 @@ struct WalkDistF32 {
 // over the ROUNDED query
 template <int METRIC, int CPL, int WAVES, int R, bool F16>
 struct WalkDistHalf {
+  static constexpr bool UD = false, RESCORE = false;
   static constexpr int TPB = WAVES * 64;
   DistCtx dc;  // rows = the image, row_stride in half elements, norms of the rounded rows
   float* qgen;
@@ -768,6 +815,67 @@ struct WalkDistHalf {
   }
   __device__ __forceinline__ void eval(uint32_t m, lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib, bool) const {
     dist_phase_half<METRIC, CPL, WAVES, R, F16>(dc, q, qnorm, qgen, m, nb_id, nb_d, lane, wib);
+  }
+};
+
+// the u8 codes of DualPrecisionHnsw (hnsw_int8.hip; the filtered walk of hnsw_filtered.hip): the query quantised once
+// per query (quantizer.quantize(query), dual_precision.rs:235), every distance the integer L2^2 of dist_phase_int8 — a u32 bit
+// pattern in nb_d, ordered as an integer (UD).  The walk ends with a re-score of its best candidates by the exact f32 engine
+// distance (RESCORE): `exact` is the f32 phase, its query loaded only then (load_exact), so no f32 query register lives through the
+// walk.  Query scratch: f32 query (generic dims) | code words [code_words] | re-score output [nbmax] u64 — hnsw_int8_lds_bytes.
+// codes / min_vals / scales / cand_k are set by the kernel before init.
+template <int METRIC, int CPL, int WAVES, int R>
+struct WalkDistInt8 {
+  static constexpr bool UD = true, RESCORE = true;
+  static constexpr int TPB = WAVES * 64;
+  static constexpr int QW = 4;  // code words per lane: dims up to 1024
+  WalkDistF32<METRIC, CPL, WAVES, R> exact;
+  CodeCtx codes;
+  const float* min_vals;  // [dim]
+  const float* scales;    // [dim]
+  uint32_t cand_k;        // k * oversampling
+  uint32_t* qcw;
+  lds_vu64* outp;
+  uint32_t qw[QW];
+  uint32_t qsq;
+  __device__ __forceinline__ void init(const HnswSearchArgs& a, unsigned char* qscratch) {
+    exact.init(a, qscratch);
+    const size_t qgen_bytes = CPL > 0 ? 0 : (size_t)((a.dim + 3) / 4) * 16;
+    qcw = reinterpret_cast<uint32_t*>(qscratch + qgen_bytes);
+    outp = (lds_vu64*)(lds_void_p)(qscratch + ((qgen_bytes + (size_t)codes.code_words * 4 + 15) & ~(size_t)15));
+  }
+  // every thread of the block; the caller's barrier follows
+  __device__ __forceinline__ void load_query(const float* qp, int lane) {
+    const uint32_t CW = codes.code_words, dim = exact.dc.dim;
+    for (uint32_t w = threadIdx.x; w < CW; w += TPB) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const uint32_t i = w * 4 + e;
+        if (i < dim) {
+          float v = roundf((qp[i] - min_vals[i]) * scales[i]);
+          v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
+          word |= ((v != v) ? 0u : (uint32_t)v) << (8 * e);
+        }
+      }
+      qcw[w] = word;
+    }
+    __syncthreads();
+    qsq = 0;
+#pragma unroll
+    for (int t = 0; t < QW; t++) {
+      qw[t] = ((uint32_t)lane + 64u * t < CW) ? qcw[lane + 64 * t] : 0u;
+      qsq = __builtin_amdgcn_udot4(qw[t], qw[t], qsq, false);
+    }
+    qsq = wave_sum_u32(qsq);
+  }
+  __device__ __forceinline__ void eval(uint32_t m, lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib, bool) const {
+    dist_phase_int8<QW, WAVES>(codes, qw, qsq, m, nb_id, nb_d, lane, wib);
+  }
+  // the re-score: the f32 query (every thread of the block; the caller's barrier follows) and the exact engine distances
+  __device__ __forceinline__ void load_exact(const float* qp, int lane) { exact.load_query(qp, lane); }
+  __device__ __forceinline__ void eval_exact(uint32_t m, lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib) const {
+    exact.eval(m, nb_id, nb_d, lane, wib, false);
   }
 };
 

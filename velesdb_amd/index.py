@@ -604,11 +604,9 @@ class HnswIndex:
                                                         max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
         return (ids, sc, cnt), routes
 
-    def search_batch_with_filters(self, queries, k: int, filters, ef: int = 0, route: int = ROUTE_AUTO, max_list: int = 0):
-        """search_batch_filtered_graph with one optional filter PER QUERY in one call (vdb_hip_index_search_graph_filters; the
-        collection layer's search_batch_with_filters).  filters: a sequence of Optional[Filter], one per query; None = no filter
-        (every row present now).  Query i gets bit for bit what search_batch_filtered_graph returns for it alone with its filter,
-        whatever its companions are.  Returns ((ids, scores, counts), routes)."""
+    def _filters_call_buffers(self, queries, k: int, filters):
+        """what the calls with one optional filter per query share: the validated queries, the table of distinct filters (by object
+        identity; index len(table) = no filter), every query's index into it and the output arrays"""
         qs = _f32(queries)
         if qs.ndim == 1:
             qs = qs.reshape(1, -1)
@@ -628,6 +626,14 @@ class HnswIndex:
         sc = np.empty((nq, kk), dtype=np.float32)
         cnt = np.zeros(nq, dtype=np.uint32)
         routes = np.zeros(nq, dtype=np.uint32)
+        return qs, nq, table, handles, fq, ids, sc, cnt, routes
+
+    def search_batch_with_filters(self, queries, k: int, filters, ef: int = 0, route: int = ROUTE_AUTO, max_list: int = 0):
+        """search_batch_filtered_graph with one optional filter PER QUERY in one call (vdb_hip_index_search_graph_filters; the
+        collection layer's search_batch_with_filters).  filters: a sequence of Optional[Filter], one per query; None = no filter
+        (every row present now).  Query i gets bit for bit what search_batch_filtered_graph returns for it alone with its filter,
+        whatever its companions are.  Returns ((ids, scores, counts), routes)."""
+        qs, nq, table, handles, fq, ids, sc, cnt, routes = self._filters_call_buffers(queries, k, filters)
         check(lib().vdb_hip_index_search_graph_filters(self._h, handles if table else None, len(table), _ptr(fq), _ptr(qs), nq, k, ef,
                                                        MODE_HNSW, route, max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
         return (ids, sc, cnt), routes
@@ -638,28 +644,30 @@ class HnswIndex:
         MODE_HNSW_F16 or MODE_HNSW_BF16 (enable_half_precision first).  Same filters, routes, lists and outputs; every distance of
         the walk and of the exact pass is the one search_batch(mode) takes — the query rounded to the precision against the row's
         image.  With no query filtered the call is search_batch(mode).  Returns ((ids, scores, counts), routes)."""
-        qs = _f32(queries)
-        if qs.ndim == 1:
-            qs = qs.reshape(1, -1)
-        self._validate(qs)
-        filters = list(filters)
-        nq, kk = qs.shape[0], max(k, 1)
-        if len(filters) != nq:
-            raise ValueError(f"Queries count ({nq}) does not match filters count ({len(filters)})")
-        table, slot_of = [], {}  # distinct filters by object identity; index len(table) = no filter
-        for f in filters:
-            if f is not None and id(f) not in slot_of:
-                slot_of[id(f)] = len(table)
-                table.append(f)
-        fq = np.array([len(table) if f is None else slot_of[id(f)] for f in filters], dtype=np.uint32)
-        handles = (C.c_void_p * max(len(table), 1))(*[f._h for f in table])
-        ids = np.empty((nq, kk), dtype=np.uint64)
-        sc = np.empty((nq, kk), dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        routes = np.zeros(nq, dtype=np.uint32)
+        qs, nq, table, handles, fq, ids, sc, cnt, routes = self._filters_call_buffers(queries, k, filters)
         check(lib().vdb_hip_index_search_graph_filters_half(self._h, mode, handles if table else None, len(table), _ptr(fq), _ptr(qs), nq,
                                                             k, ef, route, max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
         return (ids, sc, cnt), routes
+
+    def search_batch_with_filters_int8(self, queries, k: int, filters, ef: int = 0, oversampling: int = 0, route: int = ROUTE_AUTO,
+                                       max_list: int = 0):
+        """search_batch_with_filters over the u8 codes of the trained quantiser (vdb_hip_index_search_graph_filters_int8;
+        train_quantizer first): the int8 walk of search_batch(MODE_HNSW_INT8) with the filter consulted inside it at
+        ef = max(ef, k * oversampling), the k * oversampling best allowed candidates re-scored in f32 and cut to k; the exact pass is
+        the f32 one, so a row has the same score on either route.  oversampling 0 = the handle's option.  With no query filtered
+        the call is search_batch(MODE_HNSW_INT8) at the same ef and ratio.  Returns ((ids, scores, counts), routes)."""
+        qs, nq, table, handles, fq, ids, sc, cnt, routes = self._filters_call_buffers(queries, k, filters)
+        check(lib().vdb_hip_index_search_graph_filters_int8(self._h, handles if table else None, len(table), _ptr(fq), _ptr(qs), nq, k, ef,
+                                                            oversampling, route, max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
+        return (ids, sc, cnt), routes
+
+    def search_batch_filtered_graph_int8(self, queries, k: int, flt: Filter, ef: int = 0, oversampling: int = 0, route: int = ROUTE_AUTO,
+                                         max_list: int = 0):
+        """search_batch_filtered_graph over the u8 codes: search_batch_with_filters_int8 with `flt` for every query (a table of
+        one)."""
+        qs = _f32(queries)
+        nq = 1 if qs.ndim == 1 else qs.shape[0]
+        return self.search_batch_with_filters_int8(qs, k, [flt] * nq, ef=ef, oversampling=oversampling, route=route, max_list=max_list)
 
     def search_batch_filtered_graph_half(self, queries, k: int, flt: Filter, mode: int, ef: int = 0, route: int = ROUTE_AUTO,
                                          max_list: int = 0):
