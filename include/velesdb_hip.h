@@ -96,7 +96,9 @@ enum vdb_search_mode {
                            vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) (VDB_ERR_STATE otherwise, as
                            VDB_SEARCH_BRUTE_F16) and a graph (VDB_ERR_STATE).  Served by vdb_hip_index_search / _search_batch /
                            _search_batch_dev and by REPLICA device groups; RANGE groups answer VDB_ERR_UNSUPPORTED.  The
-                           rerank / multi-entry / with_config entry points and VDB_SEARCH_AUTO never take this walk.      */
+                           rerank / multi-entry / with_config entry points and VDB_SEARCH_AUTO never take this walk; the form
+                           that re-scores the walk's candidates with the exact f32 distance is a call of its own,
+                           vdb_hip_index_search_graph_filters_half_rescore (with or without filters).                  */
   VDB_SEARCH_HNSW_BF16 = 9  /* the same over the bf16 copy (VDB_PRECISION_BF16)                                                 */
 };
 
@@ -430,6 +432,38 @@ int32_t vdb_hip_index_search_graph_filters_int8(vdb_hip_index* idx, void** filte
                                                 uint32_t k, uint32_t ef_search, uint32_t oversampling_ratio, int32_t route,
                                                 uint32_t max_list, uint64_t* out_ids, float* out_scores, uint32_t* out_n,
                                                 uint32_t* out_route);
+/* vdb_hip_index_search_graph_filters_half with EXACT F32 ANSWERS (hnsw_filtered.hip): the walk over the f16 / bf16 image,
+ * the re-score of its best candidates over the f32 rows.  mode is VDB_SEARCH_HNSW_F16 or VDB_SEARCH_HNSW_BF16.  The contract is that of
+ * vdb_hip_index_search_graph_filters_int8 with the half image in place of the u8 codes.  For one query: ef_s = ef_search, or the
+ * Balanced rule max(128, 4k) when 0; ratio = oversampling_ratio, or 4 (DualPrecisionConfig::default) when 0 — the handle's
+ * VDB_OPT_INT8_OVERSAMPLING is NOT read; cand_k = k * ratio; ef_w = max(ef_s, cand_k).  The walk is exactly that of
+ * vdb_hip_index_search_graph_filters_half at ef = ef_w: the query rounded to the precision, every distance between the rounded query
+ * and the row's image in mode C order with the Cosine EPSILON rule, the descent unfiltered, layer 0 the filtered search_layer
+ * unchanged in every rule (the pivot, truncation, the overflow report, keys (distance, row)).  The first min(cand_k, results) allowed
+ * entries are re-scored with the exact f32 engine distance between the UNROUNDED query and the f32 row — the distance the exact pass
+ * gives that row —, stable-sorted by total_cmp (equal exact distances keep the coarse order) and cut to k; scores go through
+ * transform_score; out_n = min(k, results); there is no post-drop, allowed means alive.  The exact pass (route 2, the plan's
+ * whole-call cut, queries the largest list cannot hold) is the f32 one of vdb_hip_index_search_graph_filters, so a row has the same
+ * score bits on either route.  The route plan, ladders, max_list, out_route, padding, "no filter" = n_filters and a query's
+ * independence from its companions and its position are that call's, with ef_w where the plan takes ef.  The largest list follows
+ * THIS launch's LDS layout, because the re-score output lies behind the lists: list keys [cap] u64 | neighbour ids [nbmax] u32 |
+ * neighbour distances [nbmax] f32 | 16 control bytes | flags [cap rounded to 16] u8 | f32 query scratch (4 * dim rounded to 16 bytes,
+ * only when dim is not 256 / 512 / 768 / 1024) | pad to 16 | re-score output [nbmax] u64, where nbmax = max(longest neighbour list,
+ * cand_k) rounded up to 64; the largest list is the largest multiple of 64 entries for which this stays within 160 KB.
+ * With n_filters = 0 the call is the plain dual-precision half search; there is no separate unfiltered kernel.
+ * vdb_hip_index_last_search_stats: n_dist counts the half evaluations of a query's last walk attempt (re-scored rows are not
+ * counted, as in mode 4) plus the rows its exact pass evaluated.
+ * Errors, all checked before anything runs, the outputs untouched: mode other than VDB_SEARCH_HNSW_F16 / _BF16, Hamming / Jaccard
+ * handles, multi-device handles and process-group members: VDB_ERR_UNSUPPORTED; oversampling_ratio > 64: VDB_ERR_INVALID_ARG; no
+ * image of that precision (vdb_hip_index_enable_half_precision): VDB_ERR_STATE; a NULL table entry, a filter of another handle, a
+ * filter_of_query value > n_filters, route outside 0..2: VDB_ERR_INVALID_ARG; a stale filter or no graph: VDB_ERR_STATE.  The k and
+ * list limits are the int8 call's.  vdb_hip_index_last_kernels: VDB_KERNEL_HNSW_FILTERED | VDB_KERNEL_HNSW_HALF |
+ * VDB_KERNEL_HALF_RESCORE (plus VDB_KERNEL_F16 for f16) and / or VDB_KERNEL_FILTER_RANK. */
+int32_t vdb_hip_index_search_graph_filters_half_rescore(vdb_hip_index* idx, int32_t mode, void** filters, uint32_t n_filters,
+                                                        const uint32_t* filter_of_query, const float* queries_rowmajor, uint32_t nq,
+                                                        uint32_t k, uint32_t ef_search, uint32_t oversampling_ratio, int32_t route,
+                                                        uint32_t max_list, uint64_t* out_ids, float* out_scores, uint32_t* out_n,
+                                                        uint32_t* out_route);
 
 /* ---- multi-query search with result fusion: Collection::multi_query_search / multi_query_search_ids (collection/search/batch.rs:
  * 206-403) and FusionStrategy::fuse (fusion/strategy.rs:138-300) on the device (fusion.hip, vdb_fusion.hpp) ----
@@ -659,6 +693,9 @@ enum vdb_kernel_bit {
 /* one more bit of the same mask: fuse_lists_kernel ran (vdb_hip_index_multi_query_search sets it next to the walk's bits).  A macro
  * beside the enum, not an enumerator: tests/test_filters_graph_cpu.py pins VDB_KERNEL_FILTER_RANK as the enum's last member. */
 #define VDB_KERNEL_FUSE 524288
+/* ... and one more, for the same reason a macro: hnsw_search_filters_half_rescore_kernel ran (vdb_hip_index_search_graph_filters_half_rescore,
+ * the walk; next to VDB_KERNEL_HNSW_FILTERED | VDB_KERNEL_HNSW_HALF) */
+#define VDB_KERNEL_HALF_RESCORE 1048576
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same
  * context a moment later does not change it. */

@@ -29,6 +29,13 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
   n_dist * (dim + 4) + n_expand * M0 * 4 + admitted * 4 + k * R * dim * 4 for the re-score; the exact route is the f32 exact pass
   and is counted as such.  The f32 filtered call runs beside it as above, and both get recall@k against the f32 exact answer.
   One run of it is recorded: profiles/filter_probe_int8_100k.json (same shape and protocol).
+  --graph --precision f16|bf16 --rescore [--ratio R]: the three filtered routes go through
+  vdb_hip_index_search_graph_filters_half_rescore: the half walk at ef_w = max(ef, k * R) with the k * R best allowed
+  candidates re-scored over the f32 rows.  Beside every route, on the same handle with alternating timing blocks: the f32 filtered
+  call at ef = ef_w (`f32_<route>_*`) and the half filtered call without re-score at ef = ef_w (`half_<route>_*`); all three get
+  recall@k against the f32 exact answer.  Algorithmic bytes per walked query: n_dist * (2 * stride [+ 4]) + k * R * (4 * stride
+  [+ 4]) + n_expand * M0 * 4 + admitted * 4; the exact route is the f32 exact pass and is counted as such.
+  One run of it per precision is recorded: profiles/filter_probe_half_rescore_100k.json (100 K x 768, densities 1.0, 0.5 and 0.1).
   --graph --per-query F: the PER-QUERY leg instead (vdb_hip_index_search_graph_filters): at each density F distinct
   random filters of that density, the --graph-nq queries dealt round-robin over them; one call of search_batch_with_filters against
   the same queries as F calls of search_batch_filtered_graph, one per filter — what a caller does today with the same library, timed
@@ -64,7 +71,8 @@ p.add_argument("--graph", action="store_true", help="the filtered graph search l
 p.add_argument("--graph-nq", type=int, default=1024)
 p.add_argument("--per-query", type=int, default=0, help="with --graph: F distinct filters per density in one call against F single-filter calls")
 p.add_argument("--precision", default="f32", choices=["f32", "f16", "bf16", "int8"], help="with --graph: the rows the filtered walk reads")
-p.add_argument("--ratio", type=int, default=4, help="with --precision int8: the oversampling ratio")
+p.add_argument("--ratio", type=int, default=4, help="with --precision int8, or with --rescore: the oversampling ratio")
+p.add_argument("--rescore", action="store_true", help="with --graph --precision f16|bf16: the half walk with the f32 re-score")
 p.add_argument("--ef", type=int, default=128)
 p.add_argument("--densities", default="1,0.5,0.25,0.125,0.0625,0.03125,0.015625,0.0078125,0.00390625,0.001953125,0.0009765625")
 p.add_argument("--out", default="")
@@ -126,6 +134,26 @@ def measure_pair(fa, fb):
     return tuple((statistics.median(b), (max(b) - min(b)) / statistics.median(b)) for b in blocks)
 
 
+def measure_many(fns):
+    """measure_pair for any number of calls: the blocks go round (a, b, c, a, b, c, ...)"""
+    for _ in range(3):
+        for fn in fns:
+            fn()
+    t0 = time.perf_counter()
+    for fn in fns:
+        fn()
+    one = max((time.perf_counter() - t0) / len(fns), 1e-6)
+    iters = int(min(200, max(3, a.block_ms * 1e-3 / one)))
+    blocks = [[] for _ in fns]
+    for _ in range(a.repeats):
+        for which, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            blocks[which].append((time.perf_counter() - t0) / iters * 1e3)
+    return [(statistics.median(b), (max(b) - min(b)) / statistics.median(b)) for b in blocks]
+
+
 def graph_leg():
     rows_out = []
     half_mode = {"f16": va.MODE_HNSW_F16, "bf16": va.MODE_HNSW_BF16}.get(a.precision)
@@ -137,6 +165,9 @@ def graph_leg():
             ix.enable_half_precision(va.VectorPrecision.F16 if a.precision == "f16" else va.VectorPrecision.BF16)
         row_bytes = 4 * stride if half_mode is None else 2 * stride + (4 if mname == "cosine" else 0)
         int8 = a.precision == "int8"
+        rescore = a.rescore and half_mode is not None
+        ef_w = max(a.ef if a.ef else max(128, 4 * a.k), a.k * a.ratio) if rescore else a.ef  # what the comparison calls get as ef
+        norm_bytes = 4 if mname == "cosine" else 0
         if int8:
             ix.train_quantizer()
             row_bytes = a.dim + 4  # the codes and the row's sum of squared codes
@@ -146,6 +177,8 @@ def graph_leg():
                 return ix.search_batch_filtered_graph_int8(Q, a.k, flt, ef=a.ef, oversampling=a.ratio, route=route)
             if half_mode is None:
                 return ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route)
+            if rescore:
+                return ix.search_batch_filtered_graph_half_rescore(Q, a.k, flt, half_mode, ef=a.ef, oversampling=a.ratio, route=route)
             return ix.search_batch_filtered_graph_half(Q, a.k, flt, half_mode, ef=a.ef, route=route)
         t0 = time.perf_counter()
         ix.build_graph(0)
@@ -161,6 +194,8 @@ def graph_leg():
             with ix.create_filter(allowed) as flt:
                 row = dict(leg="graph", metric=mname, precision=a.precision, rows=a.rows, dim=a.dim, k=a.k, ef=a.ef, nq=a.graph_nq,
                            density=dens, count=count)
+                if rescore:
+                    row.update(rescore=True, ratio=a.ratio, ef_w=ef_w)
                 (eid, _, ecnt), _ = ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=va.ROUTE_EXACT)
                 truth = [set(eid[i, :ecnt[i]].tolist()) for i in range(a.graph_nq)]
 
@@ -182,7 +217,24 @@ def graph_leg():
                             row[name + "_algo_bytes"] = (n_dist * 4 * stride + n_dist * 4) / a.graph_nq
                         else:
                             row[name + "_algo_bytes"] += row[name + "_walked"] * a.k * a.ratio * a.dim * 4
-                    if half_mode is None and not int8:
+                    if rescore:  # the exact pass reads f32 rows; a walked query re-scores k * ratio of them
+                        if route == va.ROUTE_EXACT:
+                            row[name + "_algo_bytes"] = (n_dist * 4 * stride + n_dist * 4) / a.graph_nq
+                        else:
+                            row[name + "_algo_bytes"] += row[name + "_walked"] * a.k * a.ratio * (4 * stride + norm_bytes)
+                        # beside it: the f32 filtered walk and the half filtered walk without re-score, both at ef = ef_w
+                        f32_call = lambda: ix.search_batch_filtered_graph(Q, a.k, flt, ef=ef_w, route=route)  # noqa: E731
+                        half_call = lambda: ix.search_batch_filtered_graph_half(Q, a.k, flt, half_mode, ef=ef_w, route=route)  # noqa: E731
+                        for tag, call, rb in (("f32_", f32_call, 4 * stride), ("half_", half_call, row_bytes)):
+                            (oids, _, ocnt), _ = call()
+                            od, oe = ix.last_search_stats()[:2]
+                            row[tag + name + "_recall"] = recall(oids.tolist(), ocnt.tolist())
+                            row[tag + name + "_n_dist"] = od / a.graph_nq
+                            row[tag + name + "_algo_bytes"] = (od * rb + oe * m0 * 4 + od * 4) / a.graph_nq
+                        (ms, sp), (fms, fsp), (hms, hsp) = measure_many([lambda: filtered(Q, flt, route), f32_call, half_call])
+                        row["f32_" + name + "_qps"], row["f32_" + name + "_spread"] = a.graph_nq / (fms * 1e-3), fsp
+                        row["half_" + name + "_qps"], row["half_" + name + "_spread"] = a.graph_nq / (hms * 1e-3), hsp
+                    elif half_mode is None and not int8:
                         ms, sp = measure(lambda: filtered(Q, flt, route))
                     else:  # the f32 filtered walk of the same build on the same handle, blocks alternating
                         (fids, _, fcnt), _ = ix.search_batch_filtered_graph(Q, a.k, flt, ef=a.ef, route=route)

@@ -1130,8 +1130,34 @@ impl HipHnswIndex {
         self.filters_call(queries, k, quality, filters, VectorPrecision::F32, Some(oversampling_ratio), route, max_list)
     }
 
-    // one filter per query over the f32 rows, a half image or (int8 = the oversampling ratio) the u8 codes: the table, the buffers
-    // and the call
+    /// [`Self::search_batch_with_filters_half`] with exact f32 answers (`vdb_hip_index_search_graph_filters_half_rescore`;
+    /// [`Self::enable_half_precision`] first; `precision` is `F16` or `BF16`): the half walk with the filter consulted inside it at
+    /// `ef = max(ef_search, k * oversampling_ratio)`, the `k * oversampling_ratio` best allowed candidates re-scored with the exact
+    /// f32 distance between the unrounded query and the f32 row, stable-sorted and cut to `k`.  The exact pass is the f32 one: a row
+    /// has the same score on either route.  `oversampling_ratio` 0 = 4 (`DualPrecisionConfig::default`); more than 64 is refused.
+    /// With every filter `None` the call is the plain dual-precision half search.
+    ///
+    /// # Panics
+    /// When `filters.len() != queries.len()`, or when `precision` is `F32`.
+    #[must_use]
+    #[allow(clippy::too_many_arguments)]
+    pub fn search_batch_with_filters_half_rescore(
+        &self,
+        queries: &[&[f32]],
+        k: usize,
+        quality: SearchQuality,
+        filters: &[Option<&HipFilter>],
+        precision: VectorPrecision,
+        oversampling_ratio: u32,
+        route: i32,
+        max_list: u32,
+    ) -> (Vec<Vec<(u64, f32)>>, Vec<u32>) {
+        assert!(precision != VectorPrecision::F32, "the half walk with re-score needs F16 or BF16");
+        self.filters_call(queries, k, quality, filters, precision, Some(oversampling_ratio), route, max_list)
+    }
+
+    // one filter per query over the f32 rows, a half image or — `int8` = the oversampling ratio of a re-scoring call — the u8 codes
+    // (precision F32) or a half image with the f32 re-score (F16 / BF16): the table, the buffers and the call
     #[allow(clippy::too_many_arguments)]
     fn filters_call(
         &self,
@@ -1189,8 +1215,26 @@ impl HipHnswIndex {
         let ef = quality.ef_search(k) as u32;
         check(unsafe {
             match (int8, precision) {
-                (Some(ratio), _) => sys::vdb_hip_index_search_graph_filters_int8(
+                (Some(ratio), VectorPrecision::F32) => sys::vdb_hip_index_search_graph_filters_int8(
                     self.h,
+                    table_p,
+                    none,
+                    fq.as_ptr(),
+                    flat.as_ptr(),
+                    nq as u32,
+                    k as u32,
+                    ef,
+                    ratio,
+                    route,
+                    max_list,
+                    ids.as_mut_ptr(),
+                    scores.as_mut_ptr(),
+                    counts.as_mut_ptr(),
+                    routes.as_mut_ptr(),
+                ),
+                (Some(ratio), half) => sys::vdb_hip_index_search_graph_filters_half_rescore(
+                    self.h,
+                    if half == VectorPrecision::F16 { sys::VDB_SEARCH_HNSW_F16 } else { sys::VDB_SEARCH_HNSW_BF16 },
                     table_p,
                     none,
                     fq.as_ptr(),

@@ -97,6 +97,8 @@ pub const VDB_KERNEL_HNSW_FILTERED: i32 = 131072;
 pub const VDB_KERNEL_FILTER_RANK: i32 = 262144;
 // #define VDB_KERNEL_FUSE (one more bit of the same mask)
 pub const VDB_KERNEL_FUSE: i32 = 524288;
+// #define VDB_KERNEL_HALF_RESCORE (likewise)
+pub const VDB_KERNEL_HALF_RESCORE: i32 = 1048576;
 
 // enum vdb_fusion_strategy (FusionStrategy, fusion/strategy.rs:46-79)
 pub const VDB_FUSION_AVERAGE: i32 = 0;
@@ -149,6 +151,7 @@ extern "C" {
     pub fn vdb_hip_index_search_graph_filters(idx: *mut VdbHipIndex, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, mode: i32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filters_half(idx: *mut VdbHipIndex, mode: i32, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filters_int8(idx: *mut VdbHipIndex, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef_search: u32, oversampling_ratio: u32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
+    pub fn vdb_hip_index_search_graph_filters_half_rescore(idx: *mut VdbHipIndex, mode: i32, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef_search: u32, oversampling_ratio: u32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
     pub fn vdb_hip_fuse_results(device: i32, strategy: i32, rrf_k: u32, weights: *const f32, ids: *const u64, scores: *const f32, list_n: *const u32, n_lists: u32, list_stride: u32, group_sizes: *const u32, n_groups: u32, top_k: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_index_multi_query_search(idx: *mut VdbHipIndex, filter: *const c_void, queries_rowmajor: *const f32, group_sizes: *const u32, n_groups: u32, top_k: u32, strategy: i32, rrf_k: u32, weights: *const f32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_batch_distance(device: i32, metric: i32, kind: i32, query: *const f32, vecs_rowmajor: *const f32, n: u64, dim: u32, out: *mut f32) -> i32;

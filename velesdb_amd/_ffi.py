@@ -34,6 +34,8 @@ VDB_KERNEL_HNSW_FILTERED = 131072
 VDB_KERNEL_FILTER_RANK = 262144
 # ... and of the multi-query search with result fusion (vdb_hip_index_multi_query_search / vdb_hip_fuse_results)
 VDB_KERNEL_FUSE = 524288
+# ... and of the half walk with the f32 re-score (vdb_hip_index_search_graph_filters_half_rescore)
+VDB_KERNEL_HALF_RESCORE = 1048576
 VDB_FUSION_AVERAGE, VDB_FUSION_MAXIMUM, VDB_FUSION_RRF, VDB_FUSION_WEIGHTED = 0, 1, 2, 3
 
 # every function include/velesdb_hip.h declares: name -> (restype, argtypes)
@@ -90,6 +92,7 @@ SIGNATURES = {
     "vdb_hip_index_search_graph_filters": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filters_half": (_i32, [_vp, _i32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filters_int8": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
+    "vdb_hip_index_search_graph_filters_half_rescore": (_i32, [_vp, _i32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_fuse_results": (_i32, [_i32, _i32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "vdb_hip_index_multi_query_search": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_batch_distance": (_i32, [_i32, _i32, _i32, _vp, _vp, _u64, _u32, _vp]),

@@ -33,6 +33,11 @@
 // over k * oversampling — and, behind the walk, the re-score of the k * oversampling best allowed candidates by the exact f32 engine
 // distance (DIST::RESCORE), as hnsw_search_int8_kernel (hnsw_int8.hip) ends; its exact pass is filters_rank_kernel itself.
 //
+// Over a half image with exact answers (vdb_hip_index_search_graph_filters_half_rescore):
+// hnsw_search_filters_half_rescore_kernel is the walk body with WalkDistHalfRescore — the half walk's distances over the image at ef
+// widened over k * oversampling, then the same re-score over the f32 rows with the unrounded query; its exact pass is
+// filters_rank_kernel itself, so a row has the same score bits on either route.
+//
 // Algorithmic HBM bytes per query: walk n_dist * dim * 4 + n_expand * M0 * 4 + (admitted neighbours) * 4 for the bitmap words;
 // exact pass matched * (dim * 4 + 4).  Measured once, at one shape, f16 beside f32: tools/filter_probe.py has the graph leg.
 #include <algorithm>
@@ -188,6 +193,12 @@ using FiltDistHalf = WalkDistHalf<METRIC, CPL, 4, kFiltHalfRows<METRIC, CPL>, F1
 // one FiltDist phase, so a row has the score bits the f32 exact pass gives it
 template <int METRIC, int CPL>
 using FiltDistInt8 = WalkDistInt8<METRIC, CPL, 4, ((CPL == 4 || (CPL == 3 && METRIC == kEuclidean)) ? 4 : 8)>;
+// ... and over the f16 / bf16 image with the re-score over the f32 rows (vdb_hip_index_search_graph_filters_half_rescore):
+// FiltDistHalf's phase for the walk with its rows per group, and one f32 phase (FiltDist's arithmetic) for the re-score at 4 rows
+// per group: the re-score is one phase per query, and with 8 rows the bf16 Cosine 768-dimension instance spilled 13 vector registers
+// and the generic Euclidean / DotProduct ones reserved 36 bytes of scratch per lane (the group size does not change a bit)
+template <int METRIC, int CPL, bool F16>
+using FiltDistHalfRescore = WalkDistHalfRescore<METRIC, CPL, 4, kFiltHalfRows<METRIC, CPL>, F16, 4>;
 
 // The walk of the kernel families below (LDS: WalkLds, vdb_hnsw_device.hpp); DIST says which rows the distances are taken over, in
 // which domain they are ordered (DIST::UD: f32 raw compares, or the int8 walk's integers — walk_key / key_bound / dist_lt /
@@ -490,6 +501,25 @@ __global__ __launch_bounds__(256, 4) void hnsw_search_filters_int8_kernel(HnswFi
   dist.cand_k = A.cand_k;
   filtered_walk_body<METRIC, CPL>(A.f, dist);
 }
+// ... over the f16 / bf16 image with exact f32 answers (vdb_hip_index_search_graph_filters_half_rescore): the same body
+// with the half walk's distances over the image and the re-score of the k * oversampling best allowed candidates over the f32 rows
+// behind it.  a.rows / a.norms / a.row_stride stay the f32 rows (the re-score); a.ef = max(ef_search, k * oversampling).
+struct HnswFiltersHalfRescoreArgs {
+  HnswFiltersArgs f;
+  const float* image;        // the f16 / bf16 image of the rows, [n][image_stride] half elements
+  const float* image_norms;  // [n], of the rounded rows
+  uint32_t image_stride;     // in half elements
+  uint32_t cand_k;           // k * oversampling (<= f.s.nbmax)
+};
+template <int METRIC, int CPL, bool F16>
+__global__ __launch_bounds__(256, 4) void hnsw_search_filters_half_rescore_kernel(HnswFiltersHalfRescoreArgs A) {
+  FiltDistHalfRescore<METRIC, CPL, F16> dist;
+  dist.image = A.image;
+  dist.image_norms = A.image_norms;
+  dist.image_stride = A.image_stride;
+  dist.cand_k = A.cand_k;
+  filtered_walk_body<METRIC, CPL>(A.f, dist);
+}
 
 // The exact pass: one block per query over the filter's ascending row list in chunks of nbmax — dead rows skipped, distances by
 // the walk's DIST::eval, the k best by (total-order(distance), row) in the same LDS list (a.cap >= k entries), results in the
@@ -676,6 +706,28 @@ static hipError_t launch_filters_int8(const HnswFiltersInt8Args& A, int slots, s
   }
 }
 
+// ... the walk over a half image with the re-score over the f32 rows (three metrics: refused in front of the call otherwise)
+template <int METRIC, bool F16>
+static hipError_t launch_half_rescore_cpl(const HnswFiltersHalfRescoreArgs& A, int slots, size_t lds, hipStream_t st) {
+  const uint32_t n_cus = A.f.s.n_cus;
+  switch (sweep_cpl_for_dim(A.f.s.dim)) {
+    case 1: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 1, F16>, A, n_cus, slots, lds, st);
+    case 2: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 2, F16>, A, n_cus, slots, lds, st);
+    case 3: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 3, F16>, A, n_cus, slots, lds, st);
+    case 4: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 4, F16>, A, n_cus, slots, lds, st);
+    default: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 0, F16>, A, n_cus, slots, lds, st);
+  }
+}
+template <bool F16>
+static hipError_t launch_filters_half_rescore(const HnswFiltersHalfRescoreArgs& A, int slots, size_t lds, hipStream_t st) {
+  switch (A.f.s.metric) {
+    case kCosine: return launch_half_rescore_cpl<kCosine, F16>(A, slots, lds, st);
+    case kEuclidean: return launch_half_rescore_cpl<kEuclidean, F16>(A, slots, lds, st);
+    case kDot: return launch_half_rescore_cpl<kDot, F16>(A, slots, lds, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // the largest list (entries) whose launch stays inside 160 KB of LDS at this nbmax: hnsw_search_prepare's limit
 // (lds_of: the call's layout — hnsw_lds_bytes, or hnsw_int8_lds_bytes for the walk over the codes)
 template <class LdsOf>
@@ -701,7 +753,17 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   if (int8 && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
     return fail(VDB_ERR_UNSUPPORTED, "int8 filtered graph search: Cosine, DotProduct and Euclidean only");
   if (int8 && (ratio == 0 || ratio > 64)) return fail(VDB_ERR_INVALID_ARG, "int8 filtered graph search: oversampling ratio 1..64");
+  // the half walk with the f32 re-score: the image's statuses below, the ratio's as above
+  const bool hresc = half == kFiltersF16Rescore || half == kFiltersBF16Rescore;
+  const bool rescore = int8 || hresc;
+  if (hresc && (ratio == 0 || ratio > 64)) return fail(VDB_ERR_INVALID_ARG, "half-precision filtered graph search with re-score: oversampling ratio 1..64");
   // (the statuses of the plain half walk, hnsw_search_half_dev)
+  if (half == kFiltersF16Rescore && !ix->f16_enabled)
+    return fail(VDB_ERR_STATE, "f16 filtered graph search with re-score: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
+  if (half == kFiltersBF16Rescore && !ix->bf16_enabled)
+    return fail(VDB_ERR_STATE, "bf16 filtered graph search with re-score: call vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16) first");
+  if (hresc && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search with re-score: Cosine, DotProduct and Euclidean only");
   if (half == kFiltersF16 && !ix->f16_enabled)
     return fail(VDB_ERR_STATE, "f16 filtered graph search: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
   if (half == kFiltersBF16 && !ix->bf16_enabled)
@@ -710,6 +772,10 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
     return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search: Cosine, DotProduct and Euclidean only");
   const bool half_rows = half == kFiltersF16 || half == kFiltersBF16;
   const uint32_t half_kernels = half_rows ? (VDB_KERNEL_HNSW_HALF | (half == kFiltersF16 ? VDB_KERNEL_F16 : 0u)) : 0u;
+  // (what the walk launches of the re-scoring calls add; their exact pass is the f32 one and adds nothing)
+  const uint32_t walk_kernels = int8    ? (uint32_t)VDB_KERNEL_HNSW_INT8
+                                : hresc ? (VDB_KERNEL_HNSW_HALF | VDB_KERNEL_HALF_RESCORE | (half == kFiltersF16Rescore ? VDB_KERNEL_F16 : 0u))
+                                        : 0u;
   for (uint32_t j = 0; j < n_filters; j++)
     if ((rc = filter_check(ix, filters[j])) != VDB_OK) return rc;
   if (!ix->graph_valid) return fail(VDB_ERR_STATE, "HNSW graph not built for all rows (use the exact filtered search or build it)");
@@ -752,9 +818,10 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   if (ix->layers.size() > (size_t)kMaxLayers) return fail(VDB_ERR_UNSUPPORTED, "more than 16 graph layers");
   if (ef == 0) ef = std::max<uint32_t>(128, k * 4);  // Balanced, params.rs:313
   ef = std::max(ef, k);                               // SearchQuality::Custom(ef) = max(ef, k), params.rs:317
-  // the walk over the codes: cand_k = k * ratio coarse candidates, ef widened over them (dual_precision.rs:334) — the plans take it
-  const uint64_t cand_k = int8 ? (uint64_t)k * ratio : 0;
-  if (int8) ef = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ef, cand_k), 0xFFFFFFFFull);
+  // the walk over the codes or a half image with the re-score: cand_k = k * ratio coarse candidates, ef widened over them
+  // (dual_precision.rs:334) — the plans take it
+  const uint64_t cand_k = rescore ? (uint64_t)k * ratio : 0;
+  if (rescore) ef = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ef, cand_k), 0xFFFFFFFFull);
 
   HnswFiltersInt8Args fa8{};
   HnswFiltersArgs& fa = fa8.f;
@@ -765,7 +832,9 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   const uint32_t nbmax_exact = (longest + 63) / 64 * 64;  // (the exact pass has no candidates to gather: the f32 call's chunks)
   // the walk's layout and the exact pass's (always the f32 one)
   auto lds_of = [&](uint32_t cap) -> uint64_t {
-    return int8 ? hnsw_int8_lds_bytes(cap, nbmax, ix->dim, ix->code_words) : hnsw_lds_bytes(cap, nbmax, ix->dim, ix->words, ix->metric);
+    if (int8) return hnsw_int8_lds_bytes(cap, nbmax, ix->dim, ix->code_words);
+    if (hresc) return hnsw_half_rescore_lds_bytes(cap, nbmax, ix->dim);
+    return hnsw_lds_bytes(cap, nbmax, ix->dim, ix->words, ix->metric);
   };
   auto lds_of_exact = [&](uint32_t cap) -> uint64_t { return hnsw_lds_bytes(cap, nbmax_exact, ix->dim, ix->words, ix->metric); };
   uint32_t cap_max = largest_list(lds_of);
@@ -841,6 +910,15 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
     a.row_stride = ix->bf16_stride;
     a.bits = nullptr;
   }
+  HnswFiltersHalfRescoreArgs hr{};  // (its .f is copied from fa at every launch)
+  if (hresc) {  // the image beside the f32 rows, which the re-score and the exact pass read
+    const bool f16 = half == kFiltersF16Rescore;
+    a.bits = nullptr;
+    hr.image = reinterpret_cast<const float*>(f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>());
+    hr.image_norms = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
+    hr.image_stride = (uint32_t)ix->bf16_stride;
+    hr.cand_k = (uint32_t)cand_k;  // (<= nbmax, as above)
+  }
   fa.descs = reinterpret_cast<const FilterDesc*>(d_up + q_bytes);
   fa.qstats = ix->s_fgraph.as<unsigned long long>();
 
@@ -869,10 +947,18 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
       const size_t lds = lds_of(a.cap);
       if (lds > kFgLdsBudget) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: candidate list beyond the LDS" + limits);
       const int slots_l = (int)std::min<int64_t>((int64_t)L.count, (int64_t)ix->n_cus * (int64_t)L.per_cu);
-      const hipError_t e = int8 ? launch_filters_int8(fa8, slots_l, lds, st) : launch_filters_rows<false>(fa, half, slots_l, lds, st);
+      hipError_t e;
+      if (int8) {
+        e = launch_filters_int8(fa8, slots_l, lds, st);
+      } else if (hresc) {
+        hr.f = fa;
+        e = half == kFiltersF16Rescore ? launch_filters_half_rescore<true>(hr, slots_l, lds, st) : launch_filters_half_rescore<false>(hr, slots_l, lds, st);
+      } else {
+        e = launch_filters_rows<false>(fa, half, slots_l, lds, st);
+      }
       if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filtered hnsw_search launch: ") + hipGetErrorString(e));
     }
-    ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED | half_kernels | (int8 ? (uint32_t)VDB_KERNEL_HNSW_INT8 : 0u);
+    ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED | half_kernels | walk_kernels;
     r = fetch();
     if (r != VDB_OK) return r;
     for (uint32_t i = 0; i < n; i++) over[i] = h_n[slots[i].query] == 0xFFFFFFFFu;
@@ -899,7 +985,7 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
     a.nq = (uint32_t)exact.size();
     fa.slots = d_slots;
     const int slots_l = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * 4);
-    const hipError_t e = launch_filters_rows<true>(fa, int8 ? (int)kFiltersF32 : half, slots_l, lds, st);  // (int8: scored in f32 anyway)
+    const hipError_t e = launch_filters_rows<true>(fa, rescore ? (int)kFiltersF32 : half, slots_l, lds, st);  // (re-scoring calls: scored in f32 anyway)
     if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filters_rank launch: ") + hipGetErrorString(e));
     ix->last_kernels |= VDB_KERNEL_FILTER_RANK | half_kernels;
     rc = fetch();

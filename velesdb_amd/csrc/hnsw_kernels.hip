@@ -78,6 +78,12 @@ size_t hnsw_int8_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint32_t 
   s = (s + 15) & ~(size_t)15;
   return s + (size_t)nbmax * 8;
 }
+// ... of a half walk block with the f32 re-score behind it (hnsw_search_filters_half_rescore_kernel, hnsw_filtered.hip): WalkLds |
+// f32 query scratch (generic dims: the rounded query of the walk, then the unrounded one of the re-score) | (pad 16) | re-score
+// output [nbmax] u64
+size_t hnsw_half_rescore_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim) {
+  return hnsw_lds_bytes(cap, nbmax, dim, 0, kCosine) + (size_t)nbmax * 8;
+}
 
 // latency mode: one 1 024-thread block per query (at most one query per CU per call)
 template <int METRIC, int CPL, bool VIS>

@@ -409,6 +409,40 @@ int32_t vdb_hip_index_search_graph_filters_int8(vdb_hip_index* ix, void** filter
   });
 }
 
+// the half call with exact f32 answers: the walk over the f16 / bf16 image with the allow-list inside it at
+// ef = max(ef_search, k * ratio), the re-score of the k * ratio best allowed candidates over the f32 rows, the f32 exact pass.
+// oversampling_ratio 0 = 4 (DualPrecisionConfig::default; the handle's int8 option is not read)
+int32_t vdb_hip_index_search_graph_filters_half_rescore(vdb_hip_index* ix, int32_t mode, void** filters, uint32_t n_filters,
+                                                        const uint32_t* filter_of_query, const float* queries, uint32_t nq, uint32_t k,
+                                                        uint32_t ef_search, uint32_t oversampling_ratio, int32_t route, uint32_t max_list,
+                                                        uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || (n_filters && !filters) || (nq && (!queries || !out_n || !filter_of_query)) || (nq && k && (!out_ids || !out_scores)))
+    return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filtered graph search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  if (mode != VDB_SEARCH_HNSW_F16 && mode != VDB_SEARCH_HNSW_BF16)
+    return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search with re-score: VDB_SEARCH_HNSW_F16 or VDB_SEARCH_HNSW_BF16");
+  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search with re-score: Cosine, DotProduct and Euclidean only");
+  // k * ratio sizes nbmax, ef and the LDS list of the walk: the int8 call's bound
+  if (oversampling_ratio > 64)
+    return fail(VDB_ERR_INVALID_ARG, "half-precision filtered graph search with re-score: oversampling_ratio 0 (= 4) or 1..64");
+  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
+  for (uint32_t j = 0; j < n_filters; j++)
+    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: filter " + std::to_string(j) + " of the table is null");
+  for (uint32_t i = 0; i < nq; i++)
+    if (filter_of_query[i] > n_filters)
+      return fail(VDB_ERR_INVALID_ARG, "filtered graph search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
+                                           " of a table of " + std::to_string(n_filters));
+  if (nq == 0) return VDB_OK;
+  return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k,
+                                     ef_search, route, max_list, out_ids, out_scores, out_n, out_route,
+                                     mode == VDB_SEARCH_HNSW_F16 ? kFiltersF16Rescore : kFiltersBF16Rescore,
+                                     oversampling_ratio ? oversampling_ratio : 4u);
+  });
+}
+
 // Collection::multi_query_search / multi_query_search_ids (collection/search/batch.rs:206-403) for n_groups user queries: the walks at
 // the over-fetched k and FusionStrategy::fuse (fusion/strategy.rs) on the device (include/velesdb_hip.h)
 int32_t vdb_hip_index_multi_query_search(vdb_hip_index* ix, const void* filter, const float* queries, const uint32_t* group_sizes,

@@ -879,6 +879,44 @@ struct WalkDistInt8 {
   }
 };
 
+// the f16 / bf16 image for the walk and the f32 rows behind it (the filtered walk of hnsw_filtered.hip): every distance
+// of the walk is WalkDistHalf's — the rounded query against the row's image, f32 values ordered by the raw compares — and the walk
+// ends with a re-score of its best candidates by the exact f32 engine distance between the UNROUNDED query and the f32 row
+// (RESCORE): `exact` is the f32 phase over a.rows / a.norms, its query loaded only then (load_exact), when the rounded one is dead —
+// the two query register sets are never live together.  Query scratch: the query (generic dims: the rounded one during the walk,
+// the unrounded one during the re-score) | re-score output [nbmax] u64 — hnsw_half_rescore_lds_bytes.
+// image / image_norms / image_stride / cand_k are set by the kernel before init.
+// R / RX: rows per group of the walk's phase and of the re-score's (neither changes a bit, reduce_rows).
+template <int METRIC, int CPL, int WAVES, int R, bool F16, int RX = R>
+struct WalkDistHalfRescore {
+  static constexpr bool UD = false, RESCORE = true;
+  WalkDistHalf<METRIC, CPL, WAVES, R, F16> walk;
+  WalkDistF32<METRIC, CPL, WAVES, RX> exact;
+  const float* image;        // [n][image_stride] half elements
+  const float* image_norms;  // of the rounded rows
+  uint32_t image_stride;     // in half elements
+  uint32_t cand_k;           // k * oversampling
+  lds_vu64* outp;
+  __device__ __forceinline__ void init(const HnswSearchArgs& a, unsigned char* qscratch) {
+    exact.init(a, qscratch);
+    walk.dc = DistCtx{image, image_norms, nullptr, image_stride, a.dim, 0};
+    walk.qgen = reinterpret_cast<float*>(qscratch);
+    const size_t qgen_bytes = CPL > 0 ? 0 : (size_t)((a.dim + 3) / 4) * 16;
+    outp = (lds_vu64*)(lds_void_p)(qscratch + qgen_bytes);
+  }
+  // every thread of the block; the caller's barrier follows
+  __device__ __forceinline__ void load_query(const float* qp, int lane) { walk.load_query(qp, lane); }
+  __device__ __forceinline__ void eval(uint32_t m, lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib, bool raw) const {
+    walk.eval(m, nb_id, nb_d, lane, wib, raw);
+  }
+  // the re-score: the unrounded f32 query (every thread of the block, behind the barrier that ends the walk's last phase: the
+  // generic-dimension scratch is rewritten; the caller's barrier follows) and the exact engine distances
+  __device__ __forceinline__ void load_exact(const float* qp, int lane) { exact.load_query(qp, lane); }
+  __device__ __forceinline__ void eval_exact(uint32_t m, lds_vu32* nb_id, lds_vf32* nb_d, int lane, int wib) const {
+    exact.eval(m, nb_id, nb_d, lane, wib, false);
+  }
+};
+
 template <int METRIC, int CPL, int NS, bool LAT, bool VIS, bool RAWEF, class DIST>
 __device__ __forceinline__ void hnsw_walk_body(const HnswSearchArgs& a) {
   constexpr int WAVES = LAT ? 16 : 4, TPB = WAVES * 64;

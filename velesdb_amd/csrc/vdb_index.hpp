@@ -333,8 +333,10 @@ int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, c
 // filter); same locking, result block and routes.  half: the rows the distances are taken over — kFiltersF32, or the f16 / bf16
 // image (vdb_hip_index_search_graph_filters_half), or kFiltersInt8: the walk over the u8 codes with the re-score of the
 // k * ratio best allowed candidates in f32 and the f32 exact pass (vdb_hip_index_search_graph_filters_int8) — ef is then
-// the caller's ef_search, ratio the oversampling ratio (1..64), unused otherwise
-enum FiltersRows : int { kFiltersF32 = 0, kFiltersF16 = 1, kFiltersBF16 = 2, kFiltersInt8 = 3 };
+// the caller's ef_search, ratio the oversampling ratio (1..64), unused otherwise; or kFiltersF16Rescore / kFiltersBF16Rescore: the walk
+// over that image with the same re-score and the f32 exact pass (vdb_hip_index_search_graph_filters_half_rescore), ef
+// and ratio as for kFiltersInt8
+enum FiltersRows : int { kFiltersF32 = 0, kFiltersF16 = 1, kFiltersBF16 = 2, kFiltersInt8 = 3, kFiltersF16Rescore = 4, kFiltersBF16Rescore = 5 };
 int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                        const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
                                        uint32_t* routes, int half = kFiltersF32, uint32_t ratio = 0);

@@ -151,6 +151,7 @@ struct HnswSearchArgs {
 };
 size_t hnsw_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint32_t words, int metric);  // without the visited set
 size_t hnsw_int8_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint32_t code_words);    // the int8 walks' layout, likewise
+size_t hnsw_half_rescore_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim);  // the half walk with the f32 re-score, likewise
 // returns hipSuccess or the launch error; grid = slots blocks of 256 threads
 hipError_t launch_hnsw_search(const HnswSearchArgs& a, int slots, hipStream_t st);
 

@@ -44,6 +44,8 @@ KERNEL_SWEEP_LISTED = _ffi.VDB_KERNEL_SWEEP_LISTED
 ROUTE_AUTO, ROUTE_WALK, ROUTE_EXACT = 0, 1, 2
 KERNEL_HNSW_FILTERED = _ffi.VDB_KERNEL_HNSW_FILTERED
 KERNEL_FILTER_RANK = _ffi.VDB_KERNEL_FILTER_RANK
+# ... and the half walk whose candidates are re-scored over the f32 rows (HnswIndex.search_batch_with_filters_half_rescore)
+KERNEL_HALF_RESCORE = _ffi.VDB_KERNEL_HALF_RESCORE
 # multi-query search with result fusion (HnswIndex.multi_query_search_ids / FusionStrategy.fuse): the fusion kernel's bit, the limits
 KERNEL_FUSE = _ffi.VDB_KERNEL_FUSE
 MAX_FUSED_VECTORS = 10      # MAX_VECTORS of multi_query_search (collection/search/batch.rs:238)
@@ -668,6 +670,35 @@ class HnswIndex:
         qs = _f32(queries)
         nq = 1 if qs.ndim == 1 else qs.shape[0]
         return self.search_batch_with_filters_int8(qs, k, [flt] * nq, ef=ef, oversampling=oversampling, route=route, max_list=max_list)
+
+    def search_batch_with_filters_half_rescore(self, queries, k: int, filters, mode: int, ef: int = 0, oversampling: int = 0,
+                                               route: int = ROUTE_AUTO, max_list: int = 0):
+        """search_batch_with_filters_half with exact f32 answers (vdb_hip_index_search_graph_filters_half_rescore; mode is
+        MODE_HNSW_F16 or MODE_HNSW_BF16, enable_half_precision first): the half walk with the filter consulted inside it at
+        ef = max(ef, k * oversampling), the k * oversampling best allowed candidates re-scored with the exact f32 distance between
+        the unrounded query and the f32 row, stable-sorted and cut to k; the exact pass is the f32 one, so a row has the same score
+        on either route.  oversampling 0 = 4; more than 64 is refused.  Returns ((ids, scores, counts), routes)."""
+        qs, nq, table, handles, fq, ids, sc, cnt, routes = self._filters_call_buffers(queries, k, filters)
+        check(lib().vdb_hip_index_search_graph_filters_half_rescore(self._h, mode, handles if table else None, len(table), _ptr(fq),
+                                                                    _ptr(qs), nq, k, ef, oversampling, route, max_list, _ptr(ids),
+                                                                    _ptr(sc), _ptr(cnt), _ptr(routes)))
+        return (ids, sc, cnt), routes
+
+    def search_batch_filtered_graph_half_rescore(self, queries, k: int, flt: Filter, mode: int, ef: int = 0, oversampling: int = 0,
+                                                 route: int = ROUTE_AUTO, max_list: int = 0):
+        """search_batch_filtered_graph over the half-precision image with exact f32 answers:
+        search_batch_with_filters_half_rescore with `flt` for every query (a table of one)."""
+        qs = _f32(queries)
+        nq = 1 if qs.ndim == 1 else qs.shape[0]
+        return self.search_batch_with_filters_half_rescore(qs, k, [flt] * nq, mode, ef=ef, oversampling=oversampling, route=route,
+                                                           max_list=max_list)
+
+    def search_batch_half_rescore(self, queries, k: int, mode: int, ef: int = 0, oversampling: int = 0):
+        """the plain dual-precision half search: search_batch_with_filters_half_rescore with no filter for any query (n_filters = 0).
+        Returns (ids, scores, counts)."""
+        qs = _f32(queries)
+        nq = 1 if qs.ndim == 1 else qs.shape[0]
+        return self.search_batch_with_filters_half_rescore(qs, k, [None] * nq, mode, ef=ef, oversampling=oversampling)[0]
 
     def search_batch_filtered_graph_half(self, queries, k: int, flt: Filter, mode: int, ef: int = 0, route: int = ROUTE_AUTO,
                                          max_list: int = 0):
