@@ -328,6 +328,34 @@ void vdb_hip_filter_destroy(void* f);
  * call (it does not go through the combining front) and leaves the handle's adaptive selection state as it found it. */
 int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* idx, const void* f, const float* queries_rowmajor, uint32_t nq,
                                             uint32_t k, int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+/* One filter PER QUERY on the exact sweep: the collection layer's search_batch_with_filters (collection/search/batch.rs:26-115;
+ * DESIGN 4.1n).  The table follows vdb_hip_index_search_graph_filters below: filters = n_filters distinct filter handles of this
+ * index; filter_of_query[i] in 0..n_filters-1 names query i's filter, filter_of_query[i] == n_filters = query i has NO filter;
+ * n_filters == 0 with filters == NULL is legal.
+ * THE CONTRACT: query i gets, bit for bit, what vdb_hip_index_search_batch_filtered returns for that query ALONE with its filter and
+ * the same k — ids, ranks, score bits, out_n, padding — and a query without a filter what vdb_hip_index_search_batch(VDB_SEARCH_BRUTE)
+ * returns for it alone.  A query's answer never depends on its companions, on its position in the batch, on VDB_OPT_FILTER_ROUTE or
+ * on how the call grouped its work; a query with an empty filter gets out_n = 0 while the others are answered.
+ * Queries are grouped by filter and every group takes the route vdb_hip_index_search_batch_filtered's rule gives it with ITS matched
+ * count and ITS number of queries (VDB_OPT_FILTER_ROUTE applies per group).  The groups on the listed route share one set of
+ * launches — sweep_topk_listed_groups / _groups_m, at most three launches (mode C: one per pass width 8 / 4 / 1) or one (mode M) and
+ * ONE merge, whatever n_filters and nq are: VDB_KERNEL_SWEEP_LISTED_GROUPS —; the groups on mask substitution run one after another
+ * through the exact path, and the unfiltered queries together as one such job.  A call whose queries all name ONE filter runs
+ * vdb_hip_index_search_batch_filtered itself: the same launches, the same vdb_hip_index_last_kernels.
+ * The call leaves the handle's adaptive selection state as it found it and posts no selection verdicts, for its unfiltered queries
+ * too.  It never goes through the combining front.  All five metrics (Hamming / Jaccard: mask substitution per group).  k limits
+ * and k errors as vdb_hip_index_search_batch_filtered.
+ * Errors, checked for every filter of the table before anything runs: a NULL table entry or a filter of another handle, a
+ * filter_of_query value > n_filters: VDB_ERR_INVALID_ARG; a stale filter: VDB_ERR_STATE; mode other than VDB_SEARCH_BRUTE,
+ * multi-device handles and process-group members: VDB_ERR_UNSUPPORTED.  The outputs are untouched on error.  Host pointers only. */
+int32_t vdb_hip_index_search_batch_filters(vdb_hip_index* idx, void** filters, uint32_t n_filters,
+                                           const uint32_t* filter_of_query, const float* queries_rowmajor, uint32_t nq,
+                                           uint32_t k, int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+/* diagnostic: the plan of THIS THREAD's last vdb_hip_index_search_batch_filters call on the handle (the rule of
+ * vdb_hip_index_last_kernels).  out holds six values: out[0] distinct filter groups, out[1] groups on the listed route, out[2] groups on mask
+ * substitution, out[3] unfiltered queries, out[4] grouped sweep launches, out[5] merge launches behind them (a call that ran the
+ * one-filter path itself has none of either: out[4] = out[5] = 0). */
+int32_t vdb_hip_index_last_filters_exact_plan(vdb_hip_index* idx, uint32_t* out);
 /* Filtered GRAPH search: VDB_SEARCH_HNSW with the allow-list consulted inside the walk (hnsw_filtered.hip).
  * allowed(r) = r < the filter's row count, its bit r set, row r alive at search time (the rules above).  The greedy descent over the
  * upper layers is unfiltered (rejected nodes navigate); layer 0 is search_layer (native/graph.rs:438-520) with ONE change: `results`
@@ -696,6 +724,9 @@ enum vdb_kernel_bit {
 /* ... and one more, for the same reason a macro: hnsw_search_filters_half_rescore_kernel ran (vdb_hip_index_search_graph_filters_half_rescore,
  * the walk; next to VDB_KERNEL_HNSW_FILTERED | VDB_KERNEL_HNSW_HALF) */
 #define VDB_KERNEL_HALF_RESCORE 1048576
+/* ... and one more: sweep_topk_listed_groups / sweep_topk_listed_groups_m ran (vdb_hip_index_search_batch_filters, the grouped
+ * launches of its groups on the listed route) */
+#define VDB_KERNEL_SWEEP_LISTED_GROUPS 2097152
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same
  * context a moment later does not change it. */

@@ -42,9 +42,18 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
   in the same run, the spread of the blocks beside each.  Also n_dist per query of both (they must agree: the same walks), and the
   launches each side needs AT LEAST (first attempts by LDS class plus one exact pass; re-runs are not visible from outside).
 
+  --exact-per-query F[,F...]: the PER-QUERY EXACT leg instead (vdb_hip_index_search_batch_filters): at each density F
+  distinct random filters of that density, --graph-nq queries (1 024) dealt round-robin over them, k = 10; one call of
+  search_batch_brute_force_with_filters beside the only way the library had before it — a loop of search_batch_brute_force_filtered
+  calls, one per filter, over the same queries —, the blocks of the two alternating (--repeats rounds, at least five), median and
+  min / max of the blocks of each; once under the auto route rule and once with mask substitution forced.  The answers are held
+  to agree bit for bit first.  Asserted: at F = 1 the new call's median lies inside the loop's own min-max spread (it is the same
+  code path); everything else is recorded.  Defaults of this leg: --rows 100000, --densities 0.001,0.01,0.1.
+
 Every figure is the median of --repeats blocks, each block the mean over enough calls to last ~--block-ms; the spread is
 (max - min) / median over the blocks.  Not part of the product or the test-suite."""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -70,6 +79,7 @@ p.add_argument("--rider", action="store_true")
 p.add_argument("--graph", action="store_true", help="the filtered graph search leg instead of the exact one")
 p.add_argument("--graph-nq", type=int, default=1024)
 p.add_argument("--per-query", type=int, default=0, help="with --graph: F distinct filters per density in one call against F single-filter calls")
+p.add_argument("--exact-per-query", default="", help="F[,F...]: distinct filters per call of the exact per-query-filters leg")
 p.add_argument("--precision", default="f32", choices=["f32", "f16", "bf16", "int8"], help="with --graph: the rows the filtered walk reads")
 p.add_argument("--ratio", type=int, default=4, help="with --precision int8, or with --rescore: the oversampling ratio")
 p.add_argument("--rescore", action="store_true", help="with --graph --precision f16|bf16: the half walk with the f32 re-score")
@@ -314,8 +324,97 @@ def per_query_leg():
     return rows_out
 
 
+def measure_alternating(fa, fb):
+    """blocks of the two calls alternate (a, b, a, b, ...); per call the median, min and max ms of its blocks"""
+    for _ in range(2):
+        fa()
+        fb()
+    t0 = time.perf_counter()
+    fa()
+    fb()
+    one = max((time.perf_counter() - t0) / 2, 1e-6)
+    iters = int(min(200, max(1, a.block_ms * 1e-3 / one)))
+    blocks = ([], [])
+    for _ in range(max(a.repeats, 5)):
+        for which, fn in enumerate((fa, fb)):
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                fn()
+            blocks[which].append((time.perf_counter() - t0) / iters * 1e3)
+    return tuple(dict(median=statistics.median(b), min=min(b), max=max(b)) for b in blocks)
+
+
+def exact_per_query_leg():
+    rows_out = []
+    nq = a.graph_nq
+    for mname in a.metrics.split(","):
+        ix = build(METRICS[mname])
+        ix.set_option(va.OPT_COMBINE_MAX_BATCH, 0)
+        rng = np.random.default_rng(7)
+        Q = rng.standard_normal((nq, a.dim)).astype(np.float32)
+        for F in [int(x) for x in a.exact_per_query.split(",")]:
+            of = np.arange(nq) % F
+            parts = [np.flatnonzero(of == j) for j in range(F)]
+            Qs = [np.ascontiguousarray(Q[p]) for p in parts]
+            for dens in [float(x) for x in a.densities.split(",")]:
+                count = max(1, int(a.rows * dens))
+                flts = [ix.create_filter(np.sort(rng.choice(a.rows, size=count, replace=False)).astype(np.uint64)) for _ in range(F)]
+                per_q = [flts[j] for j in of]
+
+                # both sides are timed AT THE C ENTRY POINTS with their tables and output arrays prepared once: building a
+                # 1 024-entry filter table in Python costs ~0.1 ms per call, which is the binding's, not the library's
+                L, vp = va._ffi.lib(), (lambda x: x.ctypes.data_as(C.c_void_p))
+                handles = (C.c_void_p * F)(*[f._h for f in flts])
+                fq = np.ascontiguousarray(of, dtype=np.uint32)
+                o_ids, o_sc, o_cnt = np.empty((nq, a.k), np.uint64), np.empty((nq, a.k), np.float32), np.zeros(nq, np.uint32)
+                outs = [(np.empty((len(p), a.k), np.uint64), np.empty((len(p), a.k), np.float32), np.zeros(len(p), np.uint32)) for p in parts]
+
+                new_args = (ix._h, handles, F, vp(fq), vp(Q), nq, a.k, va.MODE_BRUTE, vp(o_ids), vp(o_sc), vp(o_cnt))
+                loop_args = [(ix._h, flts[j]._h, vp(Qs[j]), len(parts[j]), a.k, va.MODE_BRUTE, vp(outs[j][0]), vp(outs[j][1]), vp(outs[j][2]))
+                             for j in range(F)]
+
+                def one_call():
+                    va._ffi.check(L.vdb_hip_index_search_batch_filters(*new_args))
+                    return o_ids, o_sc, o_cnt
+
+                def loop():
+                    for args in loop_args:
+                        va._ffi.check(L.vdb_hip_index_search_batch_filtered(*args))
+                    return outs
+                for rname, route in (("auto", va.FILTER_ROUTE_AUTO), ("mask", va.FILTER_ROUTE_MASK)):
+                    ix.set_option(va.OPT_FILTER_ROUTE, route)
+                    row = dict(leg="exact_per_query", metric=mname, arith=ix.sweep_arith_mode(a.k), rows=a.rows, dim=a.dim, k=a.k, nq=nq, filters=F,
+                               density=dens, count=count, route=rname)
+                    ids, sc, cnt = one_call()
+                    row["plan"] = list(ix.last_filters_exact_plan())
+                    for j, (i1, s1, c1) in enumerate(loop()):  # a probe that times different answers measures nothing
+                        pj = parts[j]
+                        assert len(pj) and np.array_equal(c1, cnt[pj]) and np.array_equal(i1, ids[pj]), (mname, F, dens, rname, j)
+                        assert np.array_equal(s1.view(np.uint32), sc[pj].view(np.uint32)), (mname, F, dens, rname, j)
+                    new, old = measure_alternating(one_call, loop)
+                    row["one_call_ms"], row["loop_ms"] = new, old
+                    row["loop_over_one_call"] = old["median"] / new["median"]
+                    if F == 1:  # the same code path
+                        row["f1_inside_loop_spread"] = bool(old["min"] <= new["median"] <= old["max"])
+                    rows_out.append(row)
+                    print(json.dumps(row), flush=True)
+                for f in flts:
+                    f.close()
+        ix.close()
+    bad = [r for r in rows_out if r["filters"] == 1 and not r["f1_inside_loop_spread"]]
+    return rows_out, bad
+
+
 table = []
-if a.graph:
+f1_outside = []
+if a.exact_per_query:
+    if a.rows == 1_000_000:
+        a.rows = 100_000
+    if a.densities.startswith("1,0.5"):
+        a.densities = "0.001,0.01,0.1"
+    table, f1_outside = exact_per_query_leg()
+    a.metrics = ""
+elif a.graph:
     table = per_query_leg() if a.per_query > 0 else graph_leg()
     a.metrics = ""
 for mname in [m for m in a.metrics.split(",") if m]:
@@ -363,3 +462,5 @@ if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(dict(device=va.device_name(0), table=table), f, indent=1)
+# (after the table is written: the one gate of the per-query exact leg)
+assert not f1_outside, ("F = 1: the new call's median lies outside the loop's min-max spread", f1_outside)

@@ -998,6 +998,88 @@ impl HipHnswIndex {
             .collect()
     }
 
+    /// `search_batch_brute_force_filtered` with one optional filter PER QUERY in one call (`vdb_hip_index_search_batch_filters`; the
+    /// collection layer's `search_batch_with_filters`, `collection/search/batch.rs:26-115`, on the exact sweep).  `None` = no
+    /// filter.  Query `i` gets bit for bit what [`Self::search_batch_brute_force_filtered`] returns for it alone with its filter
+    /// (without one: what `search_batch_brute_force` returns for it alone), whatever its companions are; the queries of the
+    /// selective filters share a constant number of launches.
+    #[must_use]
+    pub fn search_batch_brute_force_with_filters(&self, queries: &[&[f32]], k: usize, filters: &[Option<&HipFilter>]) -> Vec<Vec<(u64, f32)>> {
+        assert!(
+            queries.len() == filters.len(),
+            "Queries count ({}) does not match filters count ({})",
+            queries.len(),
+            filters.len()
+        );
+        for q in queries {
+            self.validate_dimension(q, "Query");
+        }
+        if queries.is_empty() {
+            return Vec::new();
+        }
+        let nq = queries.len();
+        if k == 0 {
+            return vec![Vec::new(); nq];
+        }
+        // the table of distinct handles; `None` is numbered behind it once its length is known
+        let mut table: Vec<*mut c_void> = Vec::new();
+        let slots: Vec<Option<usize>> = filters
+            .iter()
+            .map(|f| {
+                f.map(|f| {
+                    table.iter().position(|t| *t == f.h).unwrap_or_else(|| {
+                        table.push(f.h);
+                        table.len() - 1
+                    })
+                })
+            })
+            .collect();
+        let none = table.len() as u32;
+        let fq: Vec<u32> = slots.iter().map(|s| s.map_or(none, |at| at as u32)).collect();
+        let mut flat = Vec::with_capacity(nq * self.dimension);
+        for q in queries {
+            flat.extend_from_slice(q);
+        }
+        let mut ids = vec![0u64; nq * k];
+        let mut scores = vec![0f32; nq * k];
+        let mut counts = vec![0u32; nq];
+        let table_p = if table.is_empty() { std::ptr::null_mut() } else { table.as_mut_ptr() };
+        // SAFETY: buffer sizes are n_filters / nq / nq*dim / nq*k / nq as the ABI requires; every handle of the table is live
+        // (borrowed from `filters`); the library does not write through the table.
+        check(unsafe {
+            sys::vdb_hip_index_search_batch_filters(
+                self.h,
+                table_p,
+                none,
+                fq.as_ptr(),
+                flat.as_ptr(),
+                nq as u32,
+                k as u32,
+                sys::VDB_SEARCH_BRUTE,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                counts.as_mut_ptr(),
+            )
+        });
+        (0..nq)
+            .map(|i| {
+                let c = counts[i] as usize;
+                (0..c).map(|j| (ids[i * k + j], scores[i * k + j])).collect()
+            })
+            .collect()
+    }
+
+    /// The plan of this thread's last [`Self::search_batch_brute_force_with_filters`] call
+    /// (`vdb_hip_index_last_filters_exact_plan`): `[filter groups, groups on the listed route, groups on mask substitution,
+    /// unfiltered queries, grouped sweep launches, merge launches behind them]`.
+    #[must_use]
+    pub fn last_filters_exact_plan(&self) -> [u32; 6] {
+        let mut out = [0u32; 6];
+        // SAFETY: `out` holds the six values the ABI writes.
+        check(unsafe { sys::vdb_hip_index_last_filters_exact_plan(self.h, out.as_mut_ptr()) });
+        out
+    }
+
     /// `search_brute_force` among the filter's rows only (one query).
     #[must_use]
     pub fn search_brute_force_filtered(&self, query: &[f32], k: usize, filter: &HipFilter) -> Vec<(u64, f32)> {

@@ -99,6 +99,8 @@ pub const VDB_KERNEL_FILTER_RANK: i32 = 262144;
 pub const VDB_KERNEL_FUSE: i32 = 524288;
 // #define VDB_KERNEL_HALF_RESCORE (likewise)
 pub const VDB_KERNEL_HALF_RESCORE: i32 = 1048576;
+// #define VDB_KERNEL_SWEEP_LISTED_GROUPS (likewise)
+pub const VDB_KERNEL_SWEEP_LISTED_GROUPS: i32 = 2097152;
 
 // enum vdb_fusion_strategy (FusionStrategy, fusion/strategy.rs:46-79)
 pub const VDB_FUSION_AVERAGE: i32 = 0;
@@ -148,6 +150,8 @@ extern "C" {
     pub fn vdb_hip_filter_destroy(f: *mut c_void);
     pub fn vdb_hip_index_search_batch_filtered(idx: *mut VdbHipIndex, f: *const c_void, queries_rowmajor: *const f32, nq: u32, k: u32, mode: i32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filtered(idx: *mut VdbHipIndex, f: *const c_void, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, mode: i32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
+    pub fn vdb_hip_index_search_batch_filters(idx: *mut VdbHipIndex, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, mode: i32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
+    pub fn vdb_hip_index_last_filters_exact_plan(idx: *mut VdbHipIndex, out: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filters(idx: *mut VdbHipIndex, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, mode: i32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filters_half(idx: *mut VdbHipIndex, mode: i32, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filters_int8(idx: *mut VdbHipIndex, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef_search: u32, oversampling_ratio: u32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;

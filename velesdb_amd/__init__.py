@@ -15,6 +15,7 @@ from .index import (KERNEL_BITS, KERNEL_BITS_GEMM, KERNEL_GEMM_BF16, KERNEL_GEMM
 from .index import KERNEL_F16, KERNEL_SWEEP_HALF_L2, MODE_BRUTE_F16, VectorPrecision  # noqa: F401
 from .index import KERNEL_HNSW_HALF, MODE_HNSW_BF16, MODE_HNSW_F16  # noqa: F401
 from .index import KERNEL_FILTER_RANK, KERNEL_HALF_RESCORE, KERNEL_HNSW_FILTERED, ROUTE_AUTO, ROUTE_EXACT, ROUTE_WALK  # noqa: F401
+from .index import KERNEL_SWEEP_LISTED_GROUPS  # noqa: F401
 from .index import (FILTER_ROUTE_AUTO, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK, KERNEL_SWEEP_LISTED, OPT_FILTER_ROUTE, Filter)  # noqa: F401
 from .index import FUSE_MAX_RECORDS, FusionError, FusionStrategy, KERNEL_FUSE, MAX_FUSED_VECTORS, fuse_arrays, fuse_groups  # noqa: F401
 from .params import DistanceMetric, DualPrecisionConfig, HnswParams, SearchQuality, StorageMode  # noqa: F401

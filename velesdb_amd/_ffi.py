@@ -36,6 +36,7 @@ VDB_KERNEL_FILTER_RANK = 262144
 VDB_KERNEL_FUSE = 524288
 # ... and of the half walk with the f32 re-score (vdb_hip_index_search_graph_filters_half_rescore)
 VDB_KERNEL_HALF_RESCORE = 1048576
+VDB_KERNEL_SWEEP_LISTED_GROUPS = 2097152
 VDB_FUSION_AVERAGE, VDB_FUSION_MAXIMUM, VDB_FUSION_RRF, VDB_FUSION_WEIGHTED = 0, 1, 2, 3
 
 # every function include/velesdb_hip.h declares: name -> (restype, argtypes)
@@ -89,6 +90,8 @@ SIGNATURES = {
     "vdb_hip_filter_destroy": (None, [_vp]),
     "vdb_hip_index_search_batch_filtered": (_i32, [_vp, _vp, _vp, _u32, _u32, _i32, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filtered": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
+    "vdb_hip_index_search_batch_filters": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _i32, _vp, _vp, _vp]),
+    "vdb_hip_index_last_filters_exact_plan": (_i32, [_vp, _pu32]),
     "vdb_hip_index_search_graph_filters": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filters_half": (_i32, [_vp, _i32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filters_int8": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),

@@ -241,6 +241,7 @@ vdb_hip_index* last_context(vdb_hip_index* ix) {
 // ::test_concurrent_searches_on_one_handle_overlap saw the mask of a neighbour's sweep, once, in round 5)
 static thread_local bool tl_kernels_valid = false;
 static thread_local uint32_t tl_kernels = 0;
+static thread_local uint32_t tl_fx_plan[6] = {0, 0, 0, 0, 0, 0};  // (vdb_hip_index_last_filters_exact_plan: the same rule)
 uint32_t last_kernels_of_this_thread(vdb_hip_index* ix) {
   if (tl_kernels_valid && tl_ctx_owner == ix && tl_ctx_gen == ix->generation) return tl_kernels;
   return last_context(ix)->last_kernels;
@@ -251,6 +252,11 @@ uint32_t last_kernels_of_this_thread(vdb_hip_index* ix) {
 static thread_local bool tl_stats_valid = false;
 static thread_local uint64_t tl_n_dist = 0, tl_n_expand = 0, tl_pf_hits = 0;
 static bool stats_of_this_thread(const vdb_hip_index* ix) { return tl_stats_valid && tl_ctx_owner == ix && tl_ctx_gen == ix->generation; }
+void last_fx_plan_of_this_thread(vdb_hip_index* ix, uint32_t out[6]) {
+  const bool own = tl_kernels_valid && tl_ctx_owner == ix && tl_ctx_gen == ix->generation;
+  const uint32_t* src = own ? tl_fx_plan : last_context(ix)->last_fx_plan;
+  std::copy(src, src + 6, out);
+}
 void note_last_kernels(uint32_t mask) {  // (behind note_last_context: a search the combining front had another thread run)
   tl_kernels = mask;
   tl_kernels_valid = true;
@@ -315,6 +321,7 @@ CtxLease::~CtxLease() {
   if (!ctx) return;
   if (tl_ctx == ctx) {
     tl_kernels = ctx->last_kernels;
+    std::copy(ctx->last_fx_plan, ctx->last_fx_plan + 6, tl_fx_plan);
     tl_kernels_valid = true;
     tl_stats_valid = !ctx->stats_pending;
     if (tl_stats_valid) {
@@ -942,6 +949,8 @@ static bool sweep_mode_m(const vdb_hip_index* ix, uint32_t k) {
   return opt_engine(ix) == 1 && (ix->metric == VDB_COSINE || ix->metric == VDB_DOT) && sweep_mfma_lds_bytes(1, k, ix->dim) <= 160 * 1024;
 }
 
+static int32_t brute_masked_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
+                                float* d_scores, uint32_t* d_n, hipStream_t st);
 // vdb_hip_index_search_batch_filtered: exact top-k among the rows of ix->flt that are alive now.  Two routes, same bits.
 static int32_t brute_filtered_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
                                   float* d_scores, uint32_t* d_n, hipStream_t st) {
@@ -991,8 +1000,13 @@ static int32_t brute_filtered_dev(vdb_hip_index* ix, const float* d_q, uint64_t 
     VDB_HIP(hipGetLastError());
     return VDB_OK;
   }
-  // mask substitution: mask = filter AND alive, n_rows bytes written per call into this context's scratch (nothing is cached between
-  // calls or shared between contexts); rows past the filter's row count (inserted since) get 0
+  return brute_masked_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+}
+// mask substitution for ix->flt: mask = filter AND alive, n_rows bytes written per call into this context's scratch (nothing is
+// cached between calls or shared between contexts); rows past the filter's row count (inserted since) get 0
+static int32_t brute_masked_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
+                                float* d_scores, uint32_t* d_n, hipStream_t st) {
+  const RowFilter* f = ix->flt;
   const size_t mask_cap = (size_t)ix->capacity + kRowSlack;  // (what the row arrays hold: a tile kernel may look past n_rows)
   if (ix->s_flt_mask.cap < mask_cap) {
     if (ix->s_flt_mask.reserve(mask_cap, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "filter mask scratch");
@@ -1145,7 +1159,7 @@ std::vector<DevBuf*> index_buffers(vdb_hip_index* ix) {
       &ix->sq8_img, &ix->sq8_nrm, &ix->sq8_seed, &ix->sq8_rho,              // SQ8 selection images
       &ix->bits_img, &ix->bits_cnt,                                         // four-bit image of the bit rows (Hamming / Jaccard GEMM)
       &ix->s_queries, &ix->s_part_keys, &ix->s_part_cnt, &ix->s_out, &ix->s_qbits, &ix->s_tickets, &ix->s_flt_mask,
-      &ix->s_misc, &ix->s_fgraph, &ix->s_fuse, &ix->s_fb_keys, &ix->s_seed, &ix->s_visited, &ix->s_vlog, &ix->s_stats, &ix->s_build_stats, &ix->s_levels, &ix->s_req_keys,
+      &ix->s_misc, &ix->s_fx, &ix->s_fgraph, &ix->s_fuse, &ix->s_fb_keys, &ix->s_seed, &ix->s_visited, &ix->s_vlog, &ix->s_stats, &ix->s_build_stats, &ix->s_levels, &ix->s_req_keys,
       &ix->s_req_vals, &ix->s_sort_tmp};
   for (auto& L : ix->layers) {
     v.push_back(&L.nbr);
@@ -1318,6 +1332,205 @@ int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const f
   const int32_t rc = search_to_device(ix, queries, nq, k, 0, VDB_SEARCH_BRUTE, 0, nullptr);
   ix->flt = nullptr;
   return rc;
+}
+
+// vdb_hip_index_search_batch_filters: one optional filter per query on the exact sweep.  Queries are grouped by
+// filter (vdb_filter_route.hpp); the groups on the listed route share ONE set of grouped launches and one merge, the groups on mask
+// substitution and the unfiltered queries run one after another through the existing exact path.  Device rows of the call: rows
+// [0, nq) hold the queries at their positions in the call (the grouped kernels and their merge address a query by that position),
+// the rows behind them hold the gathered queries of the other jobs, one job after another; row_of[i] says where query i's answer
+// lands in the result block (h_out, `*rows_total` rows; row_of empty = row i).  One upload, one copy back, one synchronisation.
+int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
+                                       const float* queries, uint32_t nq, uint32_t k, std::vector<uint32_t>* row_of, uint32_t* rows_total) {
+  for (uint32_t j = 0; j < n_filters; j++) {
+    const int32_t rcf = filter_check(ix, filters[j]);
+    if (rcf != VDB_OK) return rcf;
+  }
+  row_of->clear();  // (empty = row i holds query i: the one-job calls below)
+  *rows_total = nq;
+  uint32_t* diag = ix->last_fx_plan;
+  std::fill(diag, diag + 6, 0u);
+  bool one = true;
+  for (uint32_t i = 1; i < nq; i++) one &= fq[i] == fq[0];
+  if (one && fq[0] < n_filters) {  // every query on the same filter: the one-filter call itself
+    const int32_t rc = search_filtered_to_device(ix, filters[fq[0]], queries, nq, k);
+    diag[0] = 1;
+    diag[1] = (ix->last_kernels & VDB_KERNEL_SWEEP_LISTED) ? 1u : 0u;
+    diag[2] = 1u - diag[1];
+    return rc;
+  }
+  const uint32_t seen = ix->sel_seq_seen, h16 = ix->sel16_hold, hw = ix->wide_hold, hl2 = ix->l2_hold;
+  struct Quiet {  // the call posts no verdicts and leaves the adaptive selection state as it found it, whatever path ends it
+    vdb_hip_index* ix;
+    uint32_t seen, h16, hw, hl2;
+    ~Quiet() {
+      ix->quiet_verdicts = false;
+      ix->flt = nullptr;
+      ix->sel_seq_seen = seen;
+      ix->sel16_hold = h16;
+      ix->wide_hold = hw;
+      ix->l2_hold = hl2;
+    }
+  } quiet{ix, seen, h16, hw, hl2};
+  ix->quiet_verdicts = true;
+  if (k == 0 || ix->n_rows == 0) {  // nothing can answer: the plain call's empty result
+    diag[3] = nq;
+    return search_to_device(ix, queries, nq, k, 0, VDB_SEARCH_BRUTE, 0, nullptr);
+  }
+  const bool mode_m = sweep_mode_m(ix, k);
+  const bool listed_metric = !is_bits_metric(ix->metric);
+  auto plan_of = [&](uint32_t nq_left) {
+    ListedPlan lp;
+    if (listed_metric) sweep_listed_plan(mode_m, ix->dim, k, 1, nq_left, ix->n_cus, &lp);
+    return lp;
+  };
+  auto pass_of = [&](uint32_t nq_left) {
+    const ListedPlan lp = plan_of(nq_left);
+    return FxPass{mode_m ? 0 : lp.B, lp.blocks > 0 ? lp.nq_pass : 0u};
+  };
+  auto count_of = [&](uint32_t f) { return (uint64_t)filters[f]->count; };
+  auto list_of = [&](uint32_t f) { return (const uint32_t*)filters[f]->list.as<uint32_t>(); };
+  auto occ_of = [&](int B, uint32_t nq_max) { return (uint32_t)listed_occupancy(mode_m, B, mode_m ? plan_of(nq_max).lds : 0); };
+  const std::vector<FxGroup> groups = filters_exact_groups(fq, nq, n_filters, opt_value(ix, VDB_OPT_FILTER_ROUTE), ix->n_rows, count_of, pass_of);
+  // rows of the call
+  uint32_t n_listed = 0, extra = 0;
+  for (const FxGroup& g : groups) {
+    if (g.filter == n_filters) diag[3] = (uint32_t)g.queries.size(); else diag[0]++;
+    if (g.route == kFilterRouteListed) {
+      diag[1]++;
+      n_listed += (uint32_t)g.queries.size();
+    } else {
+      if (g.filter != n_filters) diag[2]++;
+      extra += (uint32_t)g.queries.size();
+    }
+  }
+  const uint32_t base = n_listed ? nq : 0;
+  const uint32_t rows = base + extra;
+  *rows_total = rows;
+  row_of->resize(nq);
+  for (uint32_t i = 0; i < nq; i++) (*row_of)[i] = i;
+  ListedGroupsPlan plan;
+  if (n_listed) {
+    // the partial lists are [nq][lists_per_query][k] keys: the chunks of a pass are held to what 256 MB of them allow
+    const uint64_t per_list = (uint64_t)nq * k * 8;
+    listed_groups_plan(groups, mode_m, ix->n_cus, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, ((uint64_t)256 << 20) / per_list)), list_of,
+                       count_of, pass_of, occ_of, &plan);
+  }
+  const size_t q_bytes = (size_t)rows * ix->row_stride * 4, items_bytes = plan.items.size() * sizeof(ListedGroupItem), gate_bytes = n_listed ? (size_t)nq * 4 : 0;
+  hipStream_t st = ix->stream;
+  hipError_t e;
+  if ((e = ix->h_in.reserve(q_bytes + items_bytes + gate_bytes)) != hipSuccess)
+    return fail(VDB_ERR_OOM, std::string("pinned query staging: ") + hipGetErrorString(e));
+  if (n_listed) {
+    const int32_t rs = stage_queries(ix, queries, 0, nq, rows);
+    if (rs != VDB_OK) return rs;
+  }
+  uint32_t at = base;
+  for (const FxGroup& g : groups) {
+    if (g.route == kFilterRouteListed) continue;
+    for (uint32_t i : g.queries) {
+      const int32_t rs = stage_queries(ix, queries + (size_t)i * ix->dim, at, 1, rows);
+      if (rs != VDB_OK) return rs;
+      (*row_of)[i] = at++;
+    }
+  }
+  unsigned char* h_tab = ix->h_in.as<unsigned char>() + q_bytes;
+  if (n_listed) {
+    std::memcpy(h_tab, plan.items.data(), items_bytes);
+    uint32_t* gate = reinterpret_cast<uint32_t*>(h_tab + items_bytes);
+    std::fill(gate, gate + nq, 0u);
+    for (const FxGroup& g : groups)
+      if (g.route == kFilterRouteListed)
+        for (uint32_t i : g.queries) gate[i] = 1u;
+  }
+  if ((e = ix->s_queries.reserve(q_bytes, false, st)) != hipSuccess || (e = ix->s_fx.reserve(items_bytes + gate_bytes + 16, false, st)) != hipSuccess)
+    return fail(VDB_ERR_OOM, std::string("search scratch: ") + hipGetErrorString(e));
+  int32_t rc = reserve_out(ix, rows, k, st);
+  if (rc != VDB_OK) return rc;
+  if ((e = ix->h_out.reserve(ix->s_out_bytes)) != hipSuccess)
+    return fail(VDB_ERR_OOM, std::string("pinned result staging: ") + hipGetErrorString(e));
+  float* dq = ix->s_queries.as<float>();
+  uint64_t* d_ids = ix->s_out_ids.as<uint64_t>();
+  float* d_scores = ix->s_out_scores.as<float>();
+  uint32_t* d_n = ix->s_out_n.as<uint32_t>();
+  VDB_HIP(hipMemcpyAsync(dq, ix->h_in.p, q_bytes, hipMemcpyHostToDevice, st));
+  ix->ev_used = 0;
+  ix->sel_ev_used = 0;
+  ix->last_select_level = 0;
+  ix->split_flags_n = 0;
+  ix->last_kernels = 0;
+  auto run = [&]() -> int32_t {
+    if (n_listed) {
+      const uint32_t L = plan.lists_per_query;
+      const size_t keys_bytes = (size_t)nq * L * k * 8;
+      if (ix->s_part_keys.reserve(keys_bytes, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+      VDB_HIP(hipMemsetAsync(ix->s_part_keys.p, 0xFF, keys_bytes, st));  // (kKeyInvalid: the lists past a pass's chunk count)
+      VDB_HIP(hipMemcpyAsync(ix->s_fx.p, h_tab, items_bytes + gate_bytes, hipMemcpyHostToDevice, st));
+      const ListedGroupItem* d_items = ix->s_fx.as<ListedGroupItem>();
+      ListedArgs a{};
+      a.rows = ix->rows.as<float>();
+      a.norms = ix->norms.as<float>();
+      a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+      a.queries = dq;
+      a.part_keys = ix->s_part_keys.as<uint64_t>();
+      a.row_stride = ix->row_stride;
+      a.q_stride = ix->row_stride;
+      a.dim = ix->dim;
+      a.k = k;
+      ix->last_kernels |= VDB_KERNEL_SWEEP_LISTED_GROUPS;
+      for (uint32_t li = 0; li < plan.n_launches; li++) {
+        const ListedGroupsLaunch& l = plan.launches[li];
+        EventPair* ev = next_events(ix);
+        if (ev) (void)hipEventRecord(ev->a, st);
+        const hipError_t le = launch_sweep_listed_groups(ix->metric, mode_m, l.B, a, d_items + l.begin, l.count, l.nq_max, L, st);
+        if (le != hipSuccess) return fail(VDB_ERR_HIP, std::string("grouped listed sweep launch: ") + hipGetErrorString(le));
+        if (ev) (void)hipEventRecord(ev->b, st);
+        diag[4]++;
+      }
+      MergeArgs m{};
+      m.part_keys = a.part_keys;
+      m.ext_ids = ix->ext_ids.as<uint64_t>();
+      m.out_ids = d_ids;
+      m.out_scores = d_scores;
+      m.out_n = d_n;
+      m.n_lists = L;
+      m.k = k;
+      m.gate = reinterpret_cast<const uint32_t*>(ix->s_fx.as<unsigned char>() + items_bytes);
+      launch_merge(higher_is_better_host(ix->metric), m, nq, st);
+      VDB_HIP(hipGetLastError());
+      diag[5]++;
+    }
+    uint32_t r0 = base;
+    for (const FxGroup& g : groups) {
+      if (g.route == kFilterRouteListed) continue;
+      const uint32_t nq_g = (uint32_t)g.queries.size();
+      const float* q_g = dq + (size_t)r0 * ix->row_stride;
+      int32_t rg;
+      if (g.filter == n_filters) {
+        rg = brute_dev(ix, q_g, ix->row_stride, nq_g, k, d_ids + (size_t)r0 * k, d_scores + (size_t)r0 * k, d_n + r0, st);
+      } else if (filters[g.filter]->count == 0) {  // the empty filter: no row can answer — out_n = 0 behind the merge's padding
+        rg = VDB_OK;
+        VDB_HIP(hipMemsetAsync(d_n + r0, 0, (size_t)nq_g * 4, st));
+        VDB_HIP(hipMemsetAsync(d_ids + (size_t)r0 * k, 0xFF, (size_t)nq_g * k * 8, st));
+        VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_scores + (size_t)r0 * k), 0x7FC00000, (size_t)nq_g * k, st));
+      } else {
+        ix->flt = filters[g.filter];
+        rg = brute_masked_dev(ix, q_g, ix->row_stride, nq_g, k, d_ids + (size_t)r0 * k, d_scores + (size_t)r0 * k, d_n + r0, st);
+        ix->flt = nullptr;
+      }
+      if (rg != VDB_OK) return rg;
+      r0 += nq_g;
+    }
+    return VDB_OK;
+  };
+  rc = run();
+  if (rc != VDB_OK) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  VDB_HIP(hipMemcpyAsync(ix->h_out.p, ix->s_out.p, ix->s_out_bytes, hipMemcpyDeviceToHost, st));
+  VDB_HIP(hipStreamSynchronize(st));
+  return VDB_OK;
 }
 
 }  // namespace vdb

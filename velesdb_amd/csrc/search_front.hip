@@ -95,6 +95,22 @@ static int32_t search_filtered_direct(vdb_hip_index* handle, const RowFilter* f,
       [&](vdb_hip_index* ix) { deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n); });
 }
 
+// vdb_hip_index_search_batch_filters: the same with one optional filter per query; query i's answer sits in row
+// row_of[i] of the context's result block
+static int32_t search_filters_exact_direct(vdb_hip_index* handle, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
+                                           const float* queries, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  std::vector<uint32_t> row_of;  // (stays empty when the call is one job whose rows are the call's: one copy out, as the calls above)
+  uint32_t rows = 0;
+  return run_search(
+      handle, nq, k, 0, VDB_SEARCH_BRUTE, 0,
+      [&](vdb_hip_index* ix) { return search_filters_exact_to_device(ix, filters, n_filters, fq, queries, nq, k, &row_of, &rows); },
+      [&](vdb_hip_index* ix) {
+        if (row_of.empty()) return deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n);
+        for (uint32_t i = 0; i < nq; i++)
+          deliver_slice(ix, row_of[i], 1, rows, k, out_ids + (size_t)i * k, out_scores + (size_t)i * k, out_n + i);
+      });
+}
+
 // vdb_hip_index_search_graph_filtered: a launch (or a few) of its own on a leased context, like the exact filtered call
 static int32_t search_graph_filtered_direct(vdb_hip_index* handle, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k,
                                             uint32_t ef, int32_t route, uint32_t max_list, uint64_t* out_ids, float* out_scores,
@@ -308,6 +324,41 @@ int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* ix, const void* filte
   if (mode != VDB_SEARCH_BRUTE) return fail(VDB_ERR_UNSUPPORTED, "filtered search: VDB_SEARCH_BRUTE only (the graph and quantised modes keep the over-fetch rule)");
   if (nq == 0) return VDB_OK;
   return search_filtered_direct(ix, f, queries, nq, k, out_ids, out_scores, out_n);
+  });
+}
+
+// search_batch_with_filters (collection/search/batch.rs:26-115) on the exact sweep: one optional filter per query.
+// The table's conventions are those of vdb_hip_index_search_graph_filters below.
+int32_t vdb_hip_index_search_batch_filters(vdb_hip_index* ix, void** filters, uint32_t n_filters, const uint32_t* filter_of_query,
+                                           const float* queries, uint32_t nq, uint32_t k, int32_t mode, uint64_t* out_ids, float* out_scores,
+                                           uint32_t* out_n) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || (n_filters && !filters) || (nq && (!queries || !out_n || !filter_of_query)) || (nq && k && (!out_ids || !out_scores)))
+    return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filtered search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered search: not available on a member of a process group");
+  if (mode != VDB_SEARCH_BRUTE) return fail(VDB_ERR_UNSUPPORTED, "filtered search: VDB_SEARCH_BRUTE only (the graph modes have vdb_hip_index_search_graph_filters)");
+  for (uint32_t j = 0; j < n_filters; j++)
+    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered search: filter " + std::to_string(j) + " of the table is null");
+  for (uint32_t i = 0; i < nq; i++)
+    if (filter_of_query[i] > n_filters)
+      return fail(VDB_ERR_INVALID_ARG, "filtered search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
+                                           " of a table of " + std::to_string(n_filters));
+  if (nq == 0) return VDB_OK;
+  return search_filters_exact_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k, out_ids,
+                                     out_scores, out_n);
+  });
+}
+
+// diagnostic: the plan of this thread's last vdb_hip_index_search_batch_filters call — {filter groups, groups on the listed route,
+// groups on mask substitution, unfiltered queries, grouped sweep launches, merge launches behind them}
+int32_t vdb_hip_index_last_filters_exact_plan(vdb_hip_index* ix, uint32_t* out) {
+  return vdb::guarded([&]() -> int32_t {
+    if (!ix || !out) return fail(VDB_ERR_INVALID_ARG, "null argument");
+    VDB_NO_GROUP(ix, "last_filters_exact_plan");
+    std::shared_lock<vdb::IndexMutex> g(ix->mu);
+    last_fx_plan_of_this_thread(ix, out);
+    return VDB_OK;
   });
 }
 

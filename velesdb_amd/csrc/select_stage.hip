@@ -798,7 +798,7 @@ int32_t brute_split_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, 
   fin.out_n = d_n;
   fin.nq = nqg;
   fin.k = k;
-  if (ix->sel_stats && !ix->alive_override) {  // (a filtered call's verdicts say nothing about the handle's data: not posted)
+  if (ix->sel_stats && !ix->alive_override && !ix->quiet_verdicts) {  // (a filtered call's verdicts say nothing about the handle's data: not posted)
     fin.stats_host = ix->sel_stats;
     fin.stats_seq = ++ix->sel_seq;
     fin.stats_level = sq8 ? 3u : (l2 ? 5u : (uint32_t)level);
@@ -1163,7 +1163,7 @@ int32_t brute_wide_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
     fq.out_n = d_n;
     fq.nq = nqg;
     fq.k = k;
-    if (ix->sel_stats && !ix->alive_override) {
+    if (ix->sel_stats && !ix->alive_override && !ix->quiet_verdicts) {
       fq.stats_host = ix->sel_stats;
       fq.stats_seq = ++ix->sel_seq;
       fq.stats_level = 4u;
@@ -1257,7 +1257,7 @@ int32_t brute_wide_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
   fin.out_n = d_n;
   fin.nq = nqg;
   fin.k = k;
-  if (ix->sel_stats && !ix->alive_override) {  // (a filtered call's verdicts say nothing about the handle's data: not posted)
+  if (ix->sel_stats && !ix->alive_override && !ix->quiet_verdicts) {  // (a filtered call's verdicts say nothing about the handle's data: not posted)
     fin.stats_host = ix->sel_stats;
     fin.stats_seq = ++ix->sel_seq;
     fin.stats_level = 4u;

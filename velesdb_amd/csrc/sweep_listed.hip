@@ -1,4 +1,5 @@
-// sweep_listed.hip — filtered exact search (vdb_hip_index_search_batch_filtered).
+// sweep_listed.hip — filtered exact search (vdb_hip_index_search_batch_filtered) and its form with one filter per
+// query (vdb_hip_index_search_batch_filters, DESIGN 4.1n: the GROUPED kernels share the arithmetic bodies below).
 //
 // The caller hands over the set of ids a predicate matched; the filter object holds them as a bitmap and as the ascending list of
 // internal rows.  Two routes give the same bits:
@@ -16,6 +17,7 @@
 #include <algorithm>
 
 #include "vdb_device.hpp"
+#include "vdb_filter_route.hpp"
 #include "vdb_kernels.hpp"
 
 namespace vdb {
@@ -24,8 +26,44 @@ namespace vdb {
 // B queries per pass (1, 4, 8), RPG = 64 / B listed rows per group, CPL = float4 chunks per lane (dim == CPL * 256) or 0 for any
 // dim.  Block b owns the groups [b * per_block, (b + 1) * per_block) of the list, its 4 waves take them in turn.
 // LDS as sweep_topk_f32: lists[B][k] u64 | cnt[B] | lock[B] | generic-dim query scratch.
-template <int METRIC, int B, int CPL>
-__global__ __launch_bounds__(256) void sweep_topk_listed(ListedArgs a, uint32_t per_block) {
+// The body is shared by the one-filter kernel and the grouped one: GROUPED says where a block finds its work — query
+// b of the pass is row it->q[b] of a.queries and of the partial-list area (else row b), the block sweeps the WHOLE of a.list —
+// the item's chunk of the filter's list, handed over as a list of its own — (else its per_block share), and its lists go to slot
+// it->slot of the lists_per_q a query owns (else to list blockIdx.x of gridDim.x).  (A sweep that starts at unit 0 keeps the
+// register counts of the one-filter kernels; one that started at a unit read from the item, or that derived its end from
+// a.count, cost mode M eight more VGPRs.)  What is
+// only needed at the end (slot, the query positions) is read there and does not stay live across the sweep.
+struct ListedWork {
+  const ListedGroupItem* it;
+  uint32_t lists_per_q;
+};
+// a field of the block's item: the same value in every lane, so it belongs in a scalar register
+__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ ListedWork listed_work_of(const ListedGroupItem* __restrict__ it, uint32_t lists_per_q, ListedArgs* a) {
+  const uint64_t lp = reinterpret_cast<uint64_t>(it->list);
+  // (a pointer read from memory is a generic one: rebuilt as a GLOBAL pointer, so that the list is read with global_load, not flat_load)
+  typedef const __attribute__((address_space(1))) uint32_t* glb_u32_p;
+  a->list = (const uint32_t*)(glb_u32_p)(((uint64_t)uniform_u32((uint32_t)(lp >> 32)) << 32) | uniform_u32((uint32_t)lp));
+  a->count = uniform_u32(it->count);
+  a->nq = uniform_u32(it->nq);
+  return ListedWork{it, lists_per_q};
+}
+// Rows a wave fetches together before it runs their chains (a matter of fetching only: every (row, query) chain is the same
+// whatever its companions).  The one-filter kernels take 4.  At 4 rows x CPL float4 next to the 64 accumulators and the B x CPL
+// query float4, six instances need more registers than the occupancy the plans size their launches by allows (4 / 3 / 2 blocks
+// per CU for B = 1 / 4 / 8): the grouped kernels take 2 rows there (1 in one case), fence the scheduler after each such group
+// and ask for the occupancy, and reach it without spilling; the one-filter instances stay as they were.
+constexpr bool listed_groups_tight(int metric, int b, int cpl) {
+  return (b == 1 && cpl == 4) || (metric == kEuclidean && ((b == 1 && cpl >= 2) || (b == 4 && cpl == 4)));
+}
+constexpr int listed_rows_in_flight(int metric, int b, int cpl, int rpg, bool grouped) {
+  if (!grouped || !listed_groups_tight(metric, b, cpl)) return rpg >= 4 ? 4 : rpg;
+  return b == 4 ? 1 : 2;  // (Euclidean, B = 4, CPL = 4: sixteen query float4 stay resident, two rows next to them spilled)
+}
+// ... and the compiler is told the occupancy there (waves per SIMD = 256-thread blocks per CU); 1 = no request
+constexpr int listed_groups_min_waves(int metric, int b, int cpl) { return listed_groups_tight(metric, b, cpl) ? (b == 1 ? 4 : 3) : 1; }
+template <int METRIC, int B, int CPL, bool GROUPED>
+__device__ __forceinline__ void listed_body_c(const ListedArgs& a, uint32_t per_block, const ListedWork& w) {
   constexpr int OP = (METRIC == kEuclidean) ? kOpL2 : kOpDot;
   constexpr int RPG = 64 / B;
   constexpr bool HIB = higher_is_better(METRIC);
@@ -53,7 +91,8 @@ __global__ __launch_bounds__(256) void sweep_topk_listed(ListedArgs a, uint32_t 
       float nacc = 0.0f;
 #pragma unroll
       for (int j = 0; j < CPL; j++) {
-        q[b][j] = (b < (int)nq_here) ? ld4(a.queries + (size_t)b * a.q_stride + (size_t)(j * 64 + lane) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        q[b][j] = (b < (int)nq_here) ? ld4(a.queries + (GROUPED ? (size_t)w.it->q[b] : (size_t)b) * a.q_stride + (size_t)(j * 64 + lane) * 4)
+                                     : make_float4(0.f, 0.f, 0.f, 0.f);
         nacc = chain4<kOpDot>(nacc, q[b][j], q[b][j]);
       }
       if (METRIC == kCosine) {
@@ -65,7 +104,7 @@ __global__ __launch_bounds__(256) void sweep_topk_listed(ListedArgs a, uint32_t 
     const int qlen = d4 * 4;
     for (int i = threadIdx.x; i < B * qlen; i += 256) {
       int b = i / qlen, e = i % qlen;
-      qgen[i] = (b < (int)nq_here && e < (int)a.dim) ? a.queries[(size_t)b * a.q_stride + e] : 0.0f;
+      qgen[i] = (b < (int)nq_here && e < (int)a.dim) ? a.queries[(GROUPED ? (size_t)w.it->q[b] : (size_t)b) * a.q_stride + e] : 0.0f;
     }
     __syncthreads();
     if (METRIC == kCosine) {
@@ -83,14 +122,14 @@ __global__ __launch_bounds__(256) void sweep_topk_listed(ListedArgs a, uint32_t 
   }
 
   const uint32_t ngroups = (a.count + RPG - 1) / RPG;
-  const uint32_t g_end = min(ngroups, (blockIdx.x + 1) * per_block);
-  for (uint32_t g = blockIdx.x * per_block + (uint32_t)wib; g < g_end; g += 4) {
+  const uint32_t g_end = GROUPED ? uniform_u32(w.it->units) : min(ngroups, (blockIdx.x + 1) * per_block);
+  for (uint32_t g = (GROUPED ? 0u : blockIdx.x * per_block) + (uint32_t)wib; g < g_end; g += 4) {
     float acc[64];
 #pragma unroll
     for (int i = 0; i < 64; i++) acc[i] = 0.0f;
     const uint32_t pos0 = g * RPG;
     if (CPL > 0) {
-      constexpr int RB = (RPG >= 4) ? 4 : RPG;  // rows in flight together
+      constexpr int RB = listed_rows_in_flight(METRIC, B, CPL, RPG, GROUPED);  // rows in flight together
 #pragma unroll
       for (int r = 0; r < RPG; r += RB) {
         float4 v[RB][CPL > 0 ? CPL : 1];
@@ -111,6 +150,8 @@ __global__ __launch_bounds__(256) void sweep_topk_listed(ListedArgs a, uint32_t 
             for (int j = 0; j < CPL; j++) s = chain4<OP>(s, q[b][j], v[rr][j]);
             acc[(r + rr) * B + b] = s;
           }
+        // (the loops are unrolled into one block: without a fence the scheduler fetches far more rows ahead than RB)
+        if (GROUPED && listed_groups_tight(METRIC, B, CPL)) __builtin_amdgcn_sched_barrier(0);
       }
     } else {
       const int qlen = d4 * 4;
@@ -156,9 +197,21 @@ __global__ __launch_bounds__(256) void sweep_topk_listed(ListedArgs a, uint32_t 
   __syncthreads();
   for (int b = wib; b < (int)nq_here && b < B; b += 4) {
     const uint32_t c = cnts[b];
-    uint64_t* out = a.part_keys + ((size_t)b * gridDim.x + blockIdx.x) * k;
+    uint64_t* out = a.part_keys + (GROUPED ? (size_t)w.it->q[b] * w.lists_per_q + uniform_u32(w.it->slot) : (size_t)b * gridDim.x + blockIdx.x) * k;
     for (uint32_t e = lane; e < k; e += 64) out[e] = e < c ? lists[(size_t)b * k + e] : kKeyInvalid;
   }
+}
+template <int METRIC, int B, int CPL>
+__global__ __launch_bounds__(256) void sweep_topk_listed(ListedArgs a, uint32_t per_block) {
+  listed_body_c<METRIC, B, CPL, false>(a, per_block, ListedWork{});
+}
+// One filter per query (vdb_hip_index_search_batch_filters): block b does work item b — one chunk of one pass of one
+// filter's list (listed_groups_plan, vdb_filter_route.hpp).  The item is read with uniform loads; a.list / count / nq come from it.
+template <int METRIC, int B, int CPL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(listed_groups_min_waves(METRIC, B, CPL))))
+void sweep_topk_listed_groups(ListedArgs a, const ListedGroupItem* __restrict__ items, uint32_t lists_per_q) {
+  const ListedWork w = listed_work_of(items + blockIdx.x, lists_per_q, &a);
+  listed_body_c<METRIC, B, CPL, true>(a, 0, w);
 }
 
 // ---- mode M -------------------------------------------------------------------------------------------------------------
@@ -171,8 +224,8 @@ static size_t listed_m_lds_bytes(uint32_t nq, uint32_t k, uint32_t dim) {
   return (size_t)nq * dim_pad * 4 + 2 * (size_t)kListedMTile * kListedMStride * 4 + (size_t)nq * k * 8 + 3 * (size_t)kListedMQueries * 4 +
          (size_t)kListedMTile * 4;
 }
-template <int METRIC>
-__global__ __launch_bounds__(256) void sweep_topk_listed_m(ListedArgs a, uint32_t dim_pad, uint32_t per_block) {
+template <int METRIC, bool GROUPED>
+__device__ __forceinline__ void listed_body_m(const ListedArgs& a, uint32_t dim_pad, uint32_t per_block, const ListedWork& w) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t tid = threadIdx.x, k = a.k, nq = a.nq;
   const int lane = lane_id();
@@ -191,7 +244,7 @@ __global__ __launch_bounds__(256) void sweep_topk_listed_m(ListedArgs a, uint32_
   }
   for (uint32_t i = tid; i < nq * dim_pad; i += 256) {
     const uint32_t b = i / dim_pad, e = i % dim_pad;
-    qs[i] = e < a.dim ? a.queries[(size_t)b * a.q_stride + e] : 0.0f;
+    qs[i] = e < a.dim ? a.queries[(GROUPED ? (size_t)w.it->q[b] : (size_t)b) * a.q_stride + e] : 0.0f;
   }
   __syncthreads();
   if (METRIC == kCosine) {  // the query norms are the canonical ones (mode C), as in sweep_topk_mfma_f32
@@ -209,7 +262,9 @@ __global__ __launch_bounds__(256) void sweep_topk_listed_m(ListedArgs a, uint32_
     __syncthreads();
   }
   const uint32_t ntiles = (a.count + kListedMTile - 1) / kListedMTile;
-  const uint32_t t_end = min(ntiles, (blockIdx.x + 1) * per_block);
+  // (GROUPED: an item holds at least one tile — listed_groups_plan emits no empty chunk; saying so keeps the Dot instance at the
+  // one-filter kernel's 98 VGPRs, it took 108 without)
+  const uint32_t t_end = GROUPED ? max(1u, uniform_u32(w.it->units)) : min(ntiles, (blockIdx.x + 1) * per_block);
   const uint32_t r = tid & 63u;
   float4 v[4];  // 64 rows x 16 float4 per step: 4 per thread, 16 consecutive threads read one row's 256 bytes
   auto fetch = [&](uint32_t U) {
@@ -237,7 +292,7 @@ __global__ __launch_bounds__(256) void sweep_topk_listed_m(ListedArgs a, uint32_
       *reinterpret_cast<float4*>(stage + ((size_t)buf * kListedMTile + fr) * kListedMStride + 4 * c4) = v[i];
     }
   };
-  for (uint32_t t = blockIdx.x * per_block; t < t_end; t++) {
+  for (uint32_t t = GROUPED ? 0u : blockIdx.x * per_block; t < t_end; t++) {
     if (tid < kListedMTile) {
       const uint32_t pos = t * kListedMTile + tid;
       crow[tid] = a.list[pos < a.count ? pos : a.count - 1];  // tail of the list: its last row again, masked below
@@ -299,9 +354,20 @@ __global__ __launch_bounds__(256) void sweep_topk_listed_m(ListedArgs a, uint32_
   __syncthreads();
   for (uint32_t b = wib; b < nq; b += 4) {
     const uint32_t c = cnts[b];
-    uint64_t* out = a.part_keys + ((size_t)b * gridDim.x + blockIdx.x) * k;
+    uint64_t* out = a.part_keys + (GROUPED ? (size_t)w.it->q[b] * w.lists_per_q + uniform_u32(w.it->slot) : (size_t)b * gridDim.x + blockIdx.x) * k;
     for (uint32_t e = (uint32_t)lane; e < k; e += 64) out[e] = e < c ? lists[(size_t)b * k + e] : kKeyInvalid;
   }
+}
+template <int METRIC>
+__global__ __launch_bounds__(256) void sweep_topk_listed_m(ListedArgs a, uint32_t dim_pad, uint32_t per_block) {
+  listed_body_m<METRIC, false>(a, dim_pad, per_block, ListedWork{});
+}
+// the grouped form: as sweep_topk_listed_groups, the chunk counted in 64-row tiles; the LDS layout follows the item's nq
+template <int METRIC>
+__global__ __launch_bounds__(256) void sweep_topk_listed_groups_m(ListedArgs a, uint32_t dim_pad, const ListedGroupItem* __restrict__ items,
+                                                                  uint32_t lists_per_q) {
+  const ListedWork w = listed_work_of(items + blockIdx.x, lists_per_q, &a);
+  listed_body_m<METRIC, true>(a, dim_pad, 0, w);
 }
 
 // ---- the row mask of the mask-substitution route: 4 rows per thread, one 32-bit store -----------------------------------------
@@ -334,7 +400,7 @@ void sweep_listed_plan(bool mode_m, uint32_t dim, uint32_t k, uint32_t count, ui
     const size_t lds = listed_m_lds_bytes(nqp, k, dim);
     if (lds > 160 * 1024) return;
     const uint32_t ntiles = (count + kListedMTile - 1) / kListedMTile;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 4));
+    const int per_cu = listed_occupancy(true, 0, lds);
     const uint32_t want = (uint32_t)std::min<uint64_t>(ntiles, (uint64_t)n_cus * per_cu);
     p->per_block = (ntiles + want - 1) / want;
     p->blocks = (int)((ntiles + p->per_block - 1) / p->per_block);
@@ -348,7 +414,7 @@ void sweep_listed_plan(bool mode_m, uint32_t dim, uint32_t k, uint32_t count, ui
   if (sweep_lds_bytes(B, k, dim, cpl) > 60 * 1024) return;
   const uint32_t rpg = 64u / (uint32_t)B;
   const uint32_t ngroups = (count + rpg - 1) / rpg;
-  const int occ = (B == 1) ? 4 : (B == 8 ? 2 : 3);  // resident 256-thread blocks per CU (VGPR-limited, as sweep_topk_f32)
+  const int occ = listed_occupancy(false, B, 0);
   const uint32_t want = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)ngroups + 3) / 4, (uint64_t)n_cus * occ));
   p->per_block = (ngroups + want - 1) / want;
   p->blocks = (int)((ngroups + p->per_block - 1) / p->per_block);
@@ -399,6 +465,64 @@ hipError_t launch_sweep_listed(int metric, bool mode_m, const ListedPlan& p, con
     case kCosine: return launch_listed_b<kCosine>(p, a, st);
     case kEuclidean: return launch_listed_b<kEuclidean>(p, a, st);
     default: return launch_listed_b<kDot>(p, a, st);
+  }
+}
+
+// ---- the grouped launches: one block per work item, the same dispatch by metric, B and CPL ----
+int listed_occupancy(bool mode_m, int B, size_t lds) {
+  if (mode_m) return (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / std::max<size_t>(lds, 1), 4));
+  return (B == 1) ? 4 : (B == 8 ? 2 : 3);  // resident 256-thread blocks per CU (VGPR-limited, as sweep_topk_f32)
+}
+template <int METRIC, int B, int CPL>
+static hipError_t launch_groups_t(const ListedArgs& a, const ListedGroupItem* items, uint32_t n_items, uint32_t lists_per_q, hipStream_t st) {
+  const size_t lds = sweep_lds_bytes(B, a.k, a.dim, CPL);
+  hipLaunchKernelGGL((sweep_topk_listed_groups<METRIC, B, CPL>), dim3(n_items), dim3(256), lds, st, a, items, lists_per_q);
+  return hipGetLastError();
+}
+template <int METRIC, int B>
+static hipError_t launch_groups_cpl(const ListedArgs& a, const ListedGroupItem* items, uint32_t n_items, uint32_t lists_per_q, hipStream_t st) {
+  switch (sweep_cpl_for_dim(a.dim)) {
+    case 1: return launch_groups_t<METRIC, B, 1>(a, items, n_items, lists_per_q, st);
+    case 2: return launch_groups_t<METRIC, B, 2>(a, items, n_items, lists_per_q, st);
+    case 3: return launch_groups_t<METRIC, B, 3>(a, items, n_items, lists_per_q, st);
+    case 4: return launch_groups_t<METRIC, B, 4>(a, items, n_items, lists_per_q, st);
+    default: return launch_groups_t<METRIC, B, 0>(a, items, n_items, lists_per_q, st);
+  }
+}
+template <int METRIC>
+static hipError_t launch_groups_b(int B, const ListedArgs& a, const ListedGroupItem* items, uint32_t n_items, uint32_t lists_per_q, hipStream_t st) {
+  switch (B) {
+    case 1: return launch_groups_cpl<METRIC, 1>(a, items, n_items, lists_per_q, st);
+    case 4: return launch_groups_cpl<METRIC, 4>(a, items, n_items, lists_per_q, st);
+    default: return launch_groups_cpl<METRIC, 8>(a, items, n_items, lists_per_q, st);
+  }
+}
+template <int METRIC>
+static hipError_t launch_groups_m(const ListedArgs& a, const ListedGroupItem* items, uint32_t n_items, uint32_t nq_max, uint32_t lists_per_q,
+                                  hipStream_t st) {
+  const size_t lds = listed_m_lds_bytes(nq_max, a.k, a.dim);
+  static bool done = false;
+  if (lds > 64 * 1024 && !done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_listed_groups_m<METRIC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    done = true;
+  }
+  const uint32_t dim_pad = (a.dim + 127) / 128 * 128;
+  hipLaunchKernelGGL((sweep_topk_listed_groups_m<METRIC>), dim3(n_items), dim3(256), lds, st, a, dim_pad, items, lists_per_q);
+  return hipGetLastError();
+}
+// a: rows / norms / alive / queries / part_keys / strides / dim / k (list, count and nq travel in the items); B: the launch's class
+// (mode C), nq_max: the largest pass of the launch (mode M: it sizes the LDS)
+hipError_t launch_sweep_listed_groups(int metric, bool mode_m, int B, const ListedArgs& a, const ListedGroupItem* items, uint32_t n_items,
+                                      uint32_t nq_max, uint32_t lists_per_q, hipStream_t st) {
+  if (n_items == 0) return hipSuccess;
+  if (mode_m)
+    return metric == kCosine ? launch_groups_m<kCosine>(a, items, n_items, nq_max, lists_per_q, st)
+                             : launch_groups_m<kDot>(a, items, n_items, nq_max, lists_per_q, st);
+  switch (metric) {
+    case kCosine: return launch_groups_b<kCosine>(B, a, items, n_items, lists_per_q, st);
+    case kEuclidean: return launch_groups_b<kEuclidean>(B, a, items, n_items, lists_per_q, st);
+    default: return launch_groups_b<kDot>(B, a, items, n_items, lists_per_q, st);
   }
 }
 

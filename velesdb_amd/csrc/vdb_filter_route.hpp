@@ -1,9 +1,10 @@
 // vdb_filter_route.hpp — which route a filtered exact call takes (vdb_hip_index_search_batch_filtered) and which a
 // filtered graph call takes (vdb_hip_index_search_graph_filtered), and which queries of a call with one filter per
 // query share a launch (vdb_hip_index_search_graph_filters) — the one-filter call is planned here too: it is a call
-// of the second kind with every query on the same filter.
-// Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_graph_route_model.cpp and
-// tests/filters_plan_model.cpp compile it alone and walk its boundaries.
+// of the second kind with every query on the same filter — and how an EXACT call with one filter per query groups its queries and
+// cuts its listed groups into the work items of the grouped launches (vdb_hip_index_search_batch_filters).
+// Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_graph_route_model.cpp,
+// tests/filters_plan_model.cpp and tests/listed_groups_plan_model.cpp compile it alone and walk its boundaries.
 #pragma once
 #include <stdint.h>
 
@@ -140,6 +141,139 @@ static inline int filters_walk_ladders(std::vector<FiltersSlot> round, uint32_t 
     round.swap(next);
   }
   return 0;
+}
+
+// ---- one filter per query on the exact sweep (vdb_hip_index_search_batch_filters) ----
+// Queries are grouped by filter; every group takes the route filter_route gives it with ITS count and ITS number of queries.  The
+// groups on the listed route share one set of grouped launches (below); the groups on mask substitution and the unfiltered queries
+// run one after another through the existing exact path.
+struct FxPass {        // what sweep_listed_plan gives a group with nq_left queries still to serve
+  int B;               // mode C: 8, 4 or 1 queries per wave pass; mode M: 0
+  uint32_t nq_pass;    // queries of the next pass; 0 = the listed kernels cannot take the shape (k-lists / queries do not fit the LDS)
+};
+struct FxGroup {
+  uint32_t filter;                 // index into the call's table; n_filters = the unfiltered queries
+  int route;                       // kFilterRouteListed or kFilterRouteDense (mask substitution; the unfiltered queries: the plain path)
+  std::vector<uint32_t> queries;   // positions in the call, ascending
+};
+// groups in the order their first query appears.  count_of(f) = rows of filter f; pass_of(nq_left) -> FxPass
+template <class CountOf, class PassOf>
+static inline std::vector<FxGroup> filters_exact_groups(const uint32_t* fq, uint32_t nq, uint32_t n_filters, int64_t opt, uint64_t n_rows,
+                                                        CountOf&& count_of, PassOf&& pass_of) {
+  std::vector<uint32_t> at(n_filters + 1u, ~0u);
+  std::vector<FxGroup> g;
+  for (uint32_t i = 0; i < nq; i++) {
+    const uint32_t f = fq[i];
+    if (at[f] == ~0u) {
+      at[f] = (uint32_t)g.size();
+      g.push_back(FxGroup{f, kFilterRouteDense, {}});
+    }
+    g[at[f]].queries.push_back(i);
+  }
+  for (FxGroup& x : g) {
+    if (x.filter == n_filters) continue;
+    const uint32_t nq_g = (uint32_t)x.queries.size();
+    x.route = filter_route(opt, pass_of(nq_g).nq_pass > 0, count_of(x.filter), n_rows, nq_g);
+  }
+  return g;
+}
+
+// The grouped launches.  Every listed group is cut into PASSES of pass_of(nq_left).nq_pass queries (the loop of the one-filter
+// call), every pass into CHUNKS of per_block units of its list — a unit is a row group of 64 / B rows (mode C) or a 64-row tile
+// (mode M).  One chunk = one work item = one block.  Passes of one class (B) share a launch and its per_block:
+//   units  = sum over the launch's passes of ceil(count / rows per unit)
+//   want   = mode C: max(1, min(ceil(units / 4), n_cus * occ))     (four waves, a unit each: sweep_listed_plan's rule)
+//            mode M: min(units, n_cus * occ)
+//   per_block = ceil(units / want), raised until no pass has more than max_lists chunks
+// so a launch has at most want + (its passes) blocks — a pass's last chunk may be short, none is empty — and a table of one
+// pass is sweep_listed_plan's plan.  A query owns lists_per_query partial lists (the largest chunk count of any pass of the call);
+// chunk c of a pass writes list c of each of its queries, the lists past a pass's chunk count stay invalid.
+constexpr uint32_t kLgPassQueries = 16;
+struct ListedGroupItem {    // device layout, 96 bytes
+  const uint32_t* list;     // the chunk: where it starts in the filter's ascending rows ...
+  uint32_t count;           // ... and its rows (per_block units; the last chunk of a pass may hold fewer)
+  uint32_t nq;              // queries of the pass
+  uint32_t slot;            // the partial list of each of its queries this block writes (the chunk's number in its pass)
+  uint32_t units;           // ceil(count / rows per unit): where the block's sweep ends
+  uint32_t q[kLgPassQueries];  // the pass's queries: positions in the call (unused entries 0)
+  uint32_t pad2[2];
+};
+static_assert(sizeof(ListedGroupItem) == 96, "device layout");
+struct ListedGroupsLaunch {
+  int B;                    // class (mode M: 0)
+  uint32_t begin, count;    // items [begin, begin + count)
+  uint32_t per_block, want, passes;
+  uint32_t nq_max;          // the largest pass (mode M sizes its LDS by it)
+};
+struct ListedGroupsPlan {
+  std::vector<ListedGroupItem> items;
+  ListedGroupsLaunch launches[3];
+  uint32_t n_launches = 0;
+  uint32_t lists_per_query = 0;
+};
+// list_of(f) -> const uint32_t*; count_of(f) -> rows; pass_of(nq_left) -> FxPass; occ_of(B, nq_max) -> resident blocks per CU
+template <class ListOf, class CountOf, class PassOf, class OccOf>
+static inline void listed_groups_plan(const std::vector<FxGroup>& groups, bool mode_m, int n_cus, uint32_t max_lists, ListOf&& list_of,
+                                      CountOf&& count_of, PassOf&& pass_of, OccOf&& occ_of, ListedGroupsPlan* out) {
+  struct Pass {
+    uint32_t group, q0, nq, units;
+    int B;
+  };
+  std::vector<Pass> passes;
+  for (uint32_t gi = 0; gi < (uint32_t)groups.size(); gi++) {
+    const FxGroup& g = groups[gi];
+    if (g.route != kFilterRouteListed) continue;
+    const uint64_t count = count_of(g.filter);
+    for (uint32_t q0 = 0, nq_g = (uint32_t)g.queries.size(); q0 < nq_g;) {
+      const FxPass p = pass_of(nq_g - q0);
+      if (p.nq_pass == 0) break;  // (cannot happen for a group filters_exact_groups put on this route)
+      const uint32_t rpu = mode_m ? 64u : 64u / (uint32_t)p.B;
+      passes.push_back(Pass{gi, q0, p.nq_pass, (uint32_t)((count + rpu - 1) / rpu), mode_m ? 0 : p.B});
+      q0 += p.nq_pass;
+    }
+  }
+  *out = ListedGroupsPlan{};
+  if (max_lists == 0) max_lists = 1;
+  static const int kClasses[3] = {8, 4, 1};
+  for (int ci = 0; ci < (mode_m ? 1 : 3); ci++) {
+    const int B = mode_m ? 0 : kClasses[ci];
+    uint64_t units = 0;
+    uint32_t n_pass = 0, nq_max = 0, units_max = 0;
+    for (const Pass& p : passes) {
+      if (p.B != B) continue;
+      units += p.units;
+      n_pass++;
+      if (p.nq > nq_max) nq_max = p.nq;
+      if (p.units > units_max) units_max = p.units;
+    }
+    if (!n_pass) continue;
+    const uint64_t room = (uint64_t)(n_cus > 0 ? n_cus : 1) * (uint64_t)occ_of(B, nq_max);
+    uint64_t want = mode_m ? (units < room ? units : room) : ((units + 3) / 4 < room ? (units + 3) / 4 : room);
+    if (want < 1) want = 1;
+    uint32_t per_block = (uint32_t)((units + want - 1) / want);
+    if ((units_max + per_block - 1) / per_block > max_lists) per_block = (units_max + max_lists - 1) / max_lists;
+    ListedGroupsLaunch l{B, (uint32_t)out->items.size(), 0, per_block, (uint32_t)want, n_pass, nq_max};
+    for (const Pass& p : passes) {
+      if (p.B != B) continue;
+      const FxGroup& g = groups[p.group];
+      const uint32_t rpu = mode_m ? 64u : 64u / (uint32_t)B;
+      uint32_t slot = 0;
+      for (uint32_t u = 0; u < p.units; u += per_block, slot++) {
+        ListedGroupItem it{};
+        const uint64_t first = (uint64_t)u * rpu, left = count_of(g.filter) - first, room = (uint64_t)per_block * rpu;
+        it.list = list_of(g.filter) + first;
+        it.count = (uint32_t)(left < room ? left : room);
+        it.units = (it.count + rpu - 1) / rpu;
+        it.nq = p.nq;
+        it.slot = slot;
+        for (uint32_t j = 0; j < p.nq; j++) it.q[j] = g.queries[p.q0 + j];
+        out->items.push_back(it);
+      }
+      if (slot > out->lists_per_query) out->lists_per_query = slot;
+    }
+    l.count = (uint32_t)out->items.size() - l.begin;
+    out->launches[out->n_launches++] = l;
+  }
 }
 
 }  // namespace vdb

@@ -245,11 +245,17 @@ struct vdb_hip_index {
   // substitution — the row mask `filter AND alive` that stands in for `alive` on every tier (search_alive below); s_flt_mask owns it
   const vdb::RowFilter* flt = nullptr;
   const uint8_t* alive_override = nullptr;
+  // one filter per query on the exact sweep (vdb_hip_index_search_batch_filters), per search context and per call:
+  // no job of the call posts a selection verdict — its unfiltered queries neither (select_stage.hip) —, and the plan of the
+  // context's last such call (vdb_hip_index_last_filters_exact_plan)
+  bool quiet_verdicts = false;
+  uint32_t last_fx_plan[6] = {0, 0, 0, 0, 0, 0};
   bool raw_ef = false;  // transient, under the exclusive lock: the running call is NativeHnsw-level (search_multi_entry) — its ef is used as given
 
   // scratch
   vdb::DevBuf s_queries, s_part_keys, s_part_cnt, s_qbits, s_misc;
   vdb::DevBuf s_flt_mask;  // [capacity + slack] u8: the row mask of a filtered call on the mask-substitution route (n_rows bytes written per call)
+  vdb::DevBuf s_fx;        // per-query filters on the exact sweep (index.hip): [work items of the grouped launches | [nq] u32 merge gate]
   vdb::DevBuf s_fgraph;    // filtered graph search (hnsw_filtered.hip): [nq][2] u64 per-query counters | [nq] u32 launch slot -> query (per-query filters: | descriptors | slots)
   // multi-query search (search_front.hip, fusion.hip): [lists | groups | fused ids | fused scores | fused n] of the call on the device,
   // and the same block in pinned host memory (the tables go up from it, the fused results come back into it)
@@ -325,6 +331,12 @@ static inline const uint8_t* search_alive(const vdb_hip_index* ix) {
 int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k);
 // the filter belongs to this handle (generation) and to its present row numbering (row_epoch): anything else is an error
 int32_t filter_check(vdb_hip_index* ix, const RowFilter* f);
+// one optional filter per query on the exact sweep (index.hip): filters[n_filters] handles (checked inside, all of them
+// before anything runs), fq[nq] in 0..n_filters (n_filters = no filter); same locking.  The result block ends in ix->h_out with
+// *rows_total rows, query i's answer in row (*row_of)[i]
+int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
+                                       const float* queries, uint32_t nq, uint32_t k, std::vector<uint32_t>* row_of, uint32_t* rows_total);
+void last_fx_plan_of_this_thread(vdb_hip_index* ix, uint32_t out[6]);
 // filtered graph search (hnsw_filtered.hip): same locking; the result block ends in ix->h_out, routes[nq] (host, nullable) says per
 // query 1 = walk, 2 = exact pass, 0 = nothing was launched
 int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k, uint32_t ef,

@@ -286,6 +286,14 @@ struct ListedPlan {
 // mode_m: one k-ordered fmaf chain per (row, query) (oracle mode M) — else the canonical lane chains + butterfly (mode C)
 void sweep_listed_plan(bool mode_m, uint32_t dim, uint32_t k, uint32_t count, uint32_t nq_left, int n_cus, ListedPlan* p);
 hipError_t launch_sweep_listed(int metric, bool mode_m, const ListedPlan& p, const ListedArgs& a, hipStream_t st);
+// resident blocks per CU the listed plans assume: mode C by B (VGPR-limited), mode M by the LDS footprint
+int listed_occupancy(bool mode_m, int B, size_t lds);
+// one filter per query (vdb_hip_index_search_batch_filters): block b of the launch does items[b] (device memory; the
+// table is planned by listed_groups_plan, vdb_filter_route.hpp).  `a` carries what every item shares — list, count and nq travel in
+// the items; part_keys is [call's queries][lists_per_q][k]; B: the launch's class (mode C), nq_max: its largest pass (mode M LDS)
+struct ListedGroupItem;
+hipError_t launch_sweep_listed_groups(int metric, bool mode_m, int B, const ListedArgs& a, const ListedGroupItem* items, uint32_t n_items,
+                                      uint32_t nq_max, uint32_t lists_per_q, hipStream_t st);
 // mask[r] = bit r of `bitmap` (r < f_rows) && (alive ? alive[r] : 1), r < n_rows
 void launch_filter_mask(const uint32_t* bitmap, uint32_t f_rows, const uint8_t* alive, uint8_t* mask, uint32_t n_rows, hipStream_t st);
 void launch_max_norm(const float* norms, uint32_t n_rows, uint32_t* out_bits, hipStream_t st);  // bits of max |v| (NaN propagates)

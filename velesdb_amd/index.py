@@ -46,6 +46,7 @@ KERNEL_HNSW_FILTERED = _ffi.VDB_KERNEL_HNSW_FILTERED
 KERNEL_FILTER_RANK = _ffi.VDB_KERNEL_FILTER_RANK
 # ... and the half walk whose candidates are re-scored over the f32 rows (HnswIndex.search_batch_with_filters_half_rescore)
 KERNEL_HALF_RESCORE = _ffi.VDB_KERNEL_HALF_RESCORE
+KERNEL_SWEEP_LISTED_GROUPS = _ffi.VDB_KERNEL_SWEEP_LISTED_GROUPS
 # multi-query search with result fusion (HnswIndex.multi_query_search_ids / FusionStrategy.fuse): the fusion kernel's bit, the limits
 KERNEL_FUSE = _ffi.VDB_KERNEL_FUSE
 MAX_FUSED_VECTORS = 10      # MAX_VECTORS of multi_query_search (collection/search/batch.rs:238)
@@ -639,6 +640,23 @@ class HnswIndex:
         check(lib().vdb_hip_index_search_graph_filters(self._h, handles if table else None, len(table), _ptr(fq), _ptr(qs), nq, k, ef,
                                                        MODE_HNSW, route, max_list, _ptr(ids), _ptr(sc), _ptr(cnt), _ptr(routes)))
         return (ids, sc, cnt), routes
+
+    def search_batch_brute_force_with_filters(self, queries, k: int, filters):
+        """search_batch_brute_force_filtered with one optional filter PER QUERY in one call (vdb_hip_index_search_batch_filters; the
+        collection layer's search_batch_with_filters on the exact sweep).  filters: a sequence of Optional[Filter], one per query;
+        None = no filter.  Query i gets bit for bit what search_batch_brute_force_filtered returns for it alone with its filter
+        (without one: what search_batch_brute_force returns for it alone), whatever its companions are.  numpy outputs."""
+        qs, nq, table, handles, fq, ids, sc, cnt, _ = self._filters_call_buffers(queries, k, filters)
+        check(lib().vdb_hip_index_search_batch_filters(self._h, handles if table else None, len(table), _ptr(fq), _ptr(qs), nq, k,
+                                                       MODE_BRUTE, _ptr(ids), _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
+
+    def last_filters_exact_plan(self):
+        """the plan of this thread's last search_batch_brute_force_with_filters call: (filter groups, groups on the listed route,
+        groups on mask substitution, unfiltered queries, grouped sweep launches, merge launches behind them)"""
+        out = (C.c_uint32 * 6)()
+        check(lib().vdb_hip_index_last_filters_exact_plan(self._h, out))
+        return tuple(int(v) for v in out)
 
     def search_batch_with_filters_half(self, queries, k: int, filters, mode: int, ef: int = 0, route: int = ROUTE_AUTO,
                                        max_list: int = 0):
