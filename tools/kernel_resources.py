@@ -11,6 +11,7 @@
     python tools/kernel_resources.py            # one line per kernel family (ranges over the template instances)
     python tools/kernel_resources.py --all      # one line per kernel
     python tools/kernel_resources.py --loops sweep_topk_gemm_bf16_pp   # the innermost loops of the matching kernels (those with MFMAs, if any)
+    python tools/kernel_resources.py --diff OTHER_LIB   # against another build: the kernel set, every metadata record, every kernel's instructions
 
 tests/test_kernel_resources_cpu.py pins the properties the measured numbers of DESIGN.md rest on (a register budget IS an occupancy;
 scratch in a sweep kernel or a spill in a matrix-core main loop would be a silent slowdown that no parity test sees)."""
@@ -90,7 +91,7 @@ def kernels(lib=LIB):
                 rows.append({"symbol": k[".name"], "obj": oi, "vgpr": v, "agpr": k[".agpr_count"], "sgpr": k[".sgpr_count"],
                              "sgpr_spill": k[".sgpr_spill_count"], "vgpr_spill": k[".vgpr_spill_count"],
                              "scratch": k[".private_segment_fixed_size"], "lds": k[".group_segment_fixed_size"],
-                             "block": k[".max_flat_workgroup_size"], "dynamic_stack": bool(k.get(".uses_dynamic_stack", False)),
+                             "block": k[".max_flat_workgroup_size"], "kernarg": k[".kernarg_segment_size"], "dynamic_stack": bool(k.get(".uses_dynamic_stack", False)),
                              "waves_per_simd": min(8, REGS_PER_LANE // max(8, (v + 7) // 8 * 8))})
     for r, n in zip(rows, demangle([r["symbol"] for r in rows])):
         r["name"] = n
@@ -167,7 +168,37 @@ def count(ins, *prefixes):
     return sum(1 for x in ins if x.startswith(prefixes))
 
 
+def instructions(lib=LIB):
+    """{symbol: the kernel's instruction text, one per line, branch labels renumbered from the kernel's own first one}"""
+    out = {}
+    for elf in code_objects(lib):
+        for sym, blocks in disassemble(elf).items():
+            # ("...": the zero padding behind the object's last function, whichever that is)
+            text = "\n".join(f"{lab}:\n" + "\n".join(x for x in ins if x != "...") for lab, ins in blocks)
+            labels = {}
+            out[sym] = re.sub(r"\bL\d+\b", lambda m: labels.setdefault(m.group(0), f"L{len(labels)}"), text)
+    return out
+
+
+def diff(other, lib=LIB):
+    """(kernels only in lib, only in other, with another metadata record, with other instructions): symbols; all empty = the same kernels"""
+    a, b = {r["symbol"]: r for r in kernels(lib)}, {r["symbol"]: r for r in kernels(other)}
+    both = sorted(set(a) & set(b))
+    ia, ib = instructions(lib), instructions(other)
+    meta = [s_ for s_ in both if {k: v for k, v in a[s_].items() if k != "obj"} != {k: v for k, v in b[s_].items() if k != "obj"}]
+    return sorted(set(a) - set(b)), sorted(set(b) - set(a)), meta, [s_ for s_ in both if ia[s_] != ib[s_]]
+
+
 def main():
+    if "--diff" in sys.argv:
+        other = sys.argv[sys.argv.index("--diff") + 1]
+        only_a, only_b, meta, code = diff(other)
+        print(f"{len(kernels())} kernels here, {len(kernels(other))} in {other}: {len(only_a)} only here, {len(only_b)} only there, "
+              f"{len(meta)} with another metadata record, {len(code)} with other instructions")
+        for what, syms in (("only here", only_a), ("only there", only_b), ("metadata differs", meta), ("instructions differ", code)):
+            for n in demangle(syms) if syms else []:
+                print(f"  {what}: {n}")
+        sys.exit(1 if only_a or only_b or meta or code else 0)
     rows = kernels()
     cols = ("vgpr", "agpr", "sgpr", "sgpr_spill", "vgpr_spill", "scratch", "lds", "block", "waves_per_simd")
     if "--loops" in sys.argv:

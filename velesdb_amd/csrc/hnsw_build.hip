@@ -40,6 +40,7 @@
 
 #include "vdb_hnsw_device.hpp"
 #include "vdb_index.hpp"
+#include "vdb_walk_launch.hpp"
 
 namespace vdb {
 
@@ -646,96 +647,6 @@ static size_t insert_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint3
   return (s + 15) & ~(size_t)15;
 }
 
-template <int METRIC, int CPL>
-static hipError_t launch_insert_t(const HnswInsertArgs& a, int slots, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hnsw_insert_kernel<METRIC, CPL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((hnsw_insert_kernel<METRIC, CPL>), dim3(slots), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-template <int METRIC, int CPL>
-static hipError_t launch_ndist_t(const HnswNdistArgs& a, int blocks, size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL((hnsw_ndist_kernel<METRIC, CPL>), dim3(blocks), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-
-template <int METRIC, int CPL, bool F16>
-static hipError_t launch_insert_half_t(const HnswInsertArgs& a, int slots, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hnsw_insert_half_kernel<METRIC, CPL, F16>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((hnsw_insert_half_kernel<METRIC, CPL, F16>), dim3(slots), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-template <int METRIC, int CPL, bool F16>
-static hipError_t launch_ndist_half_t(const HnswNdistArgs& a, int blocks, size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL((hnsw_ndist_half_kernel<METRIC, CPL, F16>), dim3(blocks), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-
-// the half families: Cosine / Euclidean / DotProduct x CPL 0-4 x f16 / bf16 (FN<METRIC, CPL, F16>)
-#define VDB_DISPATCH_HALF_CPL_(FN, M_, F16_, cpl_, ...)          \
-  switch (cpl_) {                                                \
-    case 1: return FN<M_, 1, F16_>(__VA_ARGS__);                 \
-    case 2: return FN<M_, 2, F16_>(__VA_ARGS__);                 \
-    case 3: return FN<M_, 3, F16_>(__VA_ARGS__);                 \
-    case 4: return FN<M_, 4, F16_>(__VA_ARGS__);                 \
-    default: return FN<M_, 0, F16_>(__VA_ARGS__);                \
-  }
-#define VDB_DISPATCH_HALF_METRIC_(FN, metric, F16_, cpl_, ...)                          \
-  switch (metric) {                                                                     \
-    case kCosine: VDB_DISPATCH_HALF_CPL_(FN, kCosine, F16_, cpl_, __VA_ARGS__)          \
-    case kEuclidean: VDB_DISPATCH_HALF_CPL_(FN, kEuclidean, F16_, cpl_, __VA_ARGS__)    \
-    default: VDB_DISPATCH_HALF_CPL_(FN, kDot, F16_, cpl_, __VA_ARGS__)                  \
-  }
-#define VDB_DISPATCH_HALF(FN, metric, dim, f16, ...)                                    \
-  [&]() -> hipError_t {                                                                 \
-    const int cpl_ = sweep_cpl_for_dim(dim);                                            \
-    if (f16) {                                                                          \
-      VDB_DISPATCH_HALF_METRIC_(FN, metric, true, cpl_, __VA_ARGS__)                    \
-    } else {                                                                            \
-      VDB_DISPATCH_HALF_METRIC_(FN, metric, false, cpl_, __VA_ARGS__)                   \
-    }                                                                                   \
-  }()
-
-#define VDB_DISPATCH_METRIC_CPL(FN, metric, dim, ...)                                 \
-  [&]() -> hipError_t {                                                                 \
-    const int cpl_ = sweep_cpl_for_dim(dim);                                            \
-    switch (metric) {                                                                   \
-      case kCosine:                                                                     \
-        switch (cpl_) {                                                                 \
-          case 1: return FN<kCosine, 1>(__VA_ARGS__);                                   \
-          case 2: return FN<kCosine, 2>(__VA_ARGS__);                                   \
-          case 3: return FN<kCosine, 3>(__VA_ARGS__);                                   \
-          case 4: return FN<kCosine, 4>(__VA_ARGS__);                                   \
-          default: return FN<kCosine, 0>(__VA_ARGS__);                                  \
-        }                                                                               \
-      case kEuclidean:                                                                  \
-        switch (cpl_) {                                                                 \
-          case 1: return FN<kEuclidean, 1>(__VA_ARGS__);                                \
-          case 2: return FN<kEuclidean, 2>(__VA_ARGS__);                                \
-          case 3: return FN<kEuclidean, 3>(__VA_ARGS__);                                \
-          case 4: return FN<kEuclidean, 4>(__VA_ARGS__);                                \
-          default: return FN<kEuclidean, 0>(__VA_ARGS__);                               \
-        }                                                                               \
-      case kDot:                                                                        \
-        switch (cpl_) {                                                                 \
-          case 1: return FN<kDot, 1>(__VA_ARGS__);                                      \
-          case 2: return FN<kDot, 2>(__VA_ARGS__);                                      \
-          case 3: return FN<kDot, 3>(__VA_ARGS__);                                      \
-          case 4: return FN<kDot, 4>(__VA_ARGS__);                                      \
-          default: return FN<kDot, 0>(__VA_ARGS__);                                     \
-        }                                                                               \
-      case kHamming: return FN<kHamming, 0>(__VA_ARGS__);                               \
-      default: return FN<kJaccard, 0>(__VA_ARGS__);                                     \
-    }                                                                                   \
-  }()
-
 static void fill_layers(vdb_hip_index* ix, HnswLayerMut* out, uint32_t* max_stride) {
   uint32_t ms = 0;
   for (size_t l = 0; l < ix->layers.size() && l < (size_t)kMaxLayers; l++) {
@@ -814,10 +725,18 @@ int32_t graph_fill_ndist(vdb_hip_index* ix) {
       else if (sweep_cpl_for_dim(ix->dim) == 0)
         lds += (size_t)((ix->dim + 3) / 4) * 16;
       const int blocks = (int)std::min<uint64_t>(ix->graph_nodes, (uint64_t)ix->n_cus * 8);
-      hipError_t e = ix->graph_precision == VDB_PRECISION_F32
-                         ? VDB_DISPATCH_METRIC_CPL(launch_ndist_t, ix->metric, ix->dim, a, blocks, lds, st)
-                         : VDB_DISPATCH_HALF(launch_ndist_half_t, ix->metric, ix->dim, ix->graph_precision == VDB_PRECISION_F16, a, blocks,
-                                             lds, st);
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, st, a);
+        return hipGetLastError();
+      };
+      const hipError_t e =
+          ix->graph_precision == VDB_PRECISION_F32
+              ? walk_dispatch<BitMetrics::kTaken>(ix->metric, ix->dim, [&](auto M, auto C) { return launch(hnsw_ndist_kernel<M(), C()>); })
+              : dispatch_bool(ix->graph_precision == VDB_PRECISION_F16, [&](auto F16) {
+                  constexpr bool kF16 = F16();
+                  return walk_dispatch<BitMetrics::kFallToDot>(ix->metric, ix->dim,
+                                                               [&](auto M, auto C) { return launch(hnsw_ndist_half_kernel<M(), C(), kF16>); });
+                });
       if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("ndist launch: ") + hipGetErrorString(e));
     }
   }
@@ -924,8 +843,18 @@ static int32_t graph_insert_rows_impl(vdb_hip_index* ix, uint64_t first, uint64_
         VDB_HIP(hipMemsetAsync(d_req_n, 0, 8, st));  // request counter + overflow flags
         VDB_HIP(hipMemsetAsync(keys_in, 0xFF, (size_t)nreq * 8, st));
         const int slots = (int)std::min<uint64_t>(b, (uint64_t)ix->n_cus * per_cu);
-        e = half ? VDB_DISPATCH_HALF(launch_insert_half_t, ix->metric, ix->dim, half_f16, a, slots, lds, st)
-                 : VDB_DISPATCH_METRIC_CPL(launch_insert_t, ix->metric, ix->dim, a, slots, lds, st);
+        if (half) {  // (Cosine, Euclidean and DotProduct: vdb_hip_index_set_graph_precision refuses the others)
+          e = dispatch_bool(half_f16, [&](auto F16) {
+            constexpr bool kF16 = F16();
+            return walk_dispatch<BitMetrics::kFallToDot>(ix->metric, ix->dim, [&](auto M, auto C) {
+              return launch_walk_grid(hnsw_insert_half_kernel<M(), C(), kF16>, a, slots, lds, st);
+            });
+          });
+        } else {
+          e = walk_dispatch<BitMetrics::kTaken>(ix->metric, ix->dim, [&](auto M, auto C) {
+            return launch_walk_grid(hnsw_insert_kernel<M(), C()>, a, slots, lds, st);
+          });
+        }
         if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("insert launch: ") + hipGetErrorString(e));
         // The insert kernel only writes the NEW nodes' own lists and the request buffer (back-links are applied by the
         // link kernel below), so a batch can be repeated.  Candidates tied with the worst result stay in the list

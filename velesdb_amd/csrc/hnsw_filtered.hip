@@ -47,6 +47,7 @@
 #include "vdb_filter_route.hpp"
 #include "vdb_hnsw_device.hpp"
 #include "vdb_index.hpp"
+#include "vdb_walk_launch.hpp"
 
 namespace vdb {
 
@@ -631,51 +632,13 @@ static auto kernel_of() {
     return RANK ? filters_rank_half_kernel<METRIC, CPL, ROWS == kFiltersF16> : hnsw_search_filters_half_kernel<METRIC, CPL, ROWS == kFiltersF16>;
 }
 
-// one launch of a family's kernel (ARGS: HnswFiltersArgs, or HnswFiltersInt8Args around it)
-template <class KERN, class ARGS>
-static hipError_t launch_walk_blocks(KERN kern, const ARGS& fa, uint32_t n_cus, int slots, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  // resident blocks per CU of THIS instantiation: a larger grid would queue whole blocks behind the persistent ones — and the
-  // walk's visited bitmaps are sized for `slots` blocks
-  int occ = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, lds);
-  if (e != hipSuccess) return e;
-  occ = std::max(1, std::min(occ, 4));
-  const int grid = (int)std::min<int64_t>((int64_t)slots, (int64_t)n_cus * occ);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, fa);
-  return hipGetLastError();
-}
-template <bool RANK, int METRIC, int CPL, int ROWS>
-static hipError_t launch_fk(const HnswFiltersArgs& fa, int slots, size_t lds, hipStream_t st) {
-  return launch_walk_blocks(kernel_of<RANK, METRIC, CPL, ROWS>(), fa, fa.s.n_cus, slots, lds, st);
-}
-template <bool RANK, int METRIC, int ROWS>
-static hipError_t launch_fk_cpl(const HnswFiltersArgs& fa, int slots, size_t lds, hipStream_t st) {
-  switch (sweep_cpl_for_dim(fa.s.dim)) {
-    case 1: return launch_fk<RANK, METRIC, 1, ROWS>(fa, slots, lds, st);
-    case 2: return launch_fk<RANK, METRIC, 2, ROWS>(fa, slots, lds, st);
-    case 3: return launch_fk<RANK, METRIC, 3, ROWS>(fa, slots, lds, st);
-    case 4: return launch_fk<RANK, METRIC, 4, ROWS>(fa, slots, lds, st);
-    default: return launch_fk<RANK, METRIC, 0, ROWS>(fa, slots, lds, st);
-  }
-}
+// one launch of the walk (RANK = false) or the exact pass over the f32 rows and packed bits, or over a half image (Cosine, Euclidean
+// and DotProduct: there is no image of packed bits — refused in front of the call)
 template <bool RANK, int ROWS = kFiltersF32>
 static hipError_t launch_filtered(const HnswFiltersArgs& fa, int slots, size_t lds, hipStream_t st) {
-  switch (fa.s.metric) {
-    case kCosine: return launch_fk_cpl<RANK, kCosine, ROWS>(fa, slots, lds, st);
-    case kEuclidean: return launch_fk_cpl<RANK, kEuclidean, ROWS>(fa, slots, lds, st);
-    case kDot: return launch_fk_cpl<RANK, kDot, ROWS>(fa, slots, lds, st);
-    default: break;
-  }
-  if constexpr (ROWS == kFiltersF32) {
-    if (fa.s.metric == kHamming) return launch_fk<RANK, kHamming, 0, ROWS>(fa, slots, lds, st);
-    return launch_fk<RANK, kJaccard, 0, ROWS>(fa, slots, lds, st);
-  } else {
-    return hipErrorInvalidValue;  // (no image of packed bits: refused in front of the call)
-  }
+  return walk_dispatch<ROWS == kFiltersF32 ? BitMetrics::kTaken : BitMetrics::kRefused>(fa.s.metric, fa.s.dim, [&](auto M, auto C) {
+    return launch_walk_blocks(kernel_of<RANK, M(), C(), ROWS>(), fa, fa.s.n_cus, slots, lds, st);
+  });
 }
 // ... over the rows the call names
 template <bool RANK>
@@ -684,48 +647,18 @@ static hipError_t launch_filters_rows(const HnswFiltersArgs& fa, int rows, int s
   if (rows == kFiltersBF16) return launch_filtered<RANK, kFiltersBF16>(fa, slots, lds, st);
   return launch_filtered<RANK>(fa, slots, lds, st);
 }
-
 // ... the walk over the u8 codes (three metrics: refused in front of the call otherwise)
-template <int METRIC>
-static hipError_t launch_int8_cpl(const HnswFiltersInt8Args& A, int slots, size_t lds, hipStream_t st) {
-  const uint32_t n_cus = A.f.s.n_cus;
-  switch (sweep_cpl_for_dim(A.f.s.dim)) {
-    case 1: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 1>, A, n_cus, slots, lds, st);
-    case 2: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 2>, A, n_cus, slots, lds, st);
-    case 3: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 3>, A, n_cus, slots, lds, st);
-    case 4: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 4>, A, n_cus, slots, lds, st);
-    default: return launch_walk_blocks(hnsw_search_filters_int8_kernel<METRIC, 0>, A, n_cus, slots, lds, st);
-  }
-}
 static hipError_t launch_filters_int8(const HnswFiltersInt8Args& A, int slots, size_t lds, hipStream_t st) {
-  switch (A.f.s.metric) {
-    case kCosine: return launch_int8_cpl<kCosine>(A, slots, lds, st);
-    case kEuclidean: return launch_int8_cpl<kEuclidean>(A, slots, lds, st);
-    case kDot: return launch_int8_cpl<kDot>(A, slots, lds, st);
-    default: return hipErrorInvalidValue;
-  }
+  return walk_dispatch<BitMetrics::kRefused>(A.f.s.metric, A.f.s.dim, [&](auto M, auto C) {
+    return launch_walk_blocks(hnsw_search_filters_int8_kernel<M(), C()>, A, A.f.s.n_cus, slots, lds, st);
+  });
 }
-
 // ... the walk over a half image with the re-score over the f32 rows (three metrics: refused in front of the call otherwise)
-template <int METRIC, bool F16>
-static hipError_t launch_half_rescore_cpl(const HnswFiltersHalfRescoreArgs& A, int slots, size_t lds, hipStream_t st) {
-  const uint32_t n_cus = A.f.s.n_cus;
-  switch (sweep_cpl_for_dim(A.f.s.dim)) {
-    case 1: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 1, F16>, A, n_cus, slots, lds, st);
-    case 2: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 2, F16>, A, n_cus, slots, lds, st);
-    case 3: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 3, F16>, A, n_cus, slots, lds, st);
-    case 4: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 4, F16>, A, n_cus, slots, lds, st);
-    default: return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<METRIC, 0, F16>, A, n_cus, slots, lds, st);
-  }
-}
 template <bool F16>
 static hipError_t launch_filters_half_rescore(const HnswFiltersHalfRescoreArgs& A, int slots, size_t lds, hipStream_t st) {
-  switch (A.f.s.metric) {
-    case kCosine: return launch_half_rescore_cpl<kCosine, F16>(A, slots, lds, st);
-    case kEuclidean: return launch_half_rescore_cpl<kEuclidean, F16>(A, slots, lds, st);
-    case kDot: return launch_half_rescore_cpl<kDot, F16>(A, slots, lds, st);
-    default: return hipErrorInvalidValue;
-  }
+  return walk_dispatch<BitMetrics::kRefused>(A.f.s.metric, A.f.s.dim, [&](auto M, auto C) {
+    return launch_walk_blocks(hnsw_search_filters_half_rescore_kernel<M(), C(), F16>, A, A.f.s.n_cus, slots, lds, st);
+  });
 }
 
 // the largest list (entries) whose launch stays inside 160 KB of LDS at this nbmax: hnsw_search_prepare's limit
@@ -737,6 +670,44 @@ static uint32_t largest_list(LdsOf&& lds_of) {
   return (uint32_t)cap;
 }
 
+// What a filtered call does with the rows it names (FiltersRows, vdb_index.hpp): filled once, read by everything below.
+enum WalkRows : int { kWalkF32, kWalkF16, kWalkBF16, kWalkCodes };
+enum WalkLdsRule : int { kLdsWalk, kLdsInt8, kLdsHalfRescore };  // hnsw_lds_bytes / hnsw_int8_lds_bytes / hnsw_half_rescore_lds_bytes
+struct FiltersMode {
+  WalkRows walk;                  // the rows the walk's distances are taken over
+  bool rescore;                   // behind the walk, the k * ratio best allowed candidates are re-scored over the f32 rows
+  bool vdb_hip_index::*enabled;   // what the index must have been given for it (null: nothing) ...
+  const char* enable_first;       // ... and the status that says so (those of the plain walks: hnsw_search_half_dev, hnsw_search_int8_dev)
+  const char* what;               // the text the metric and ratio statuses start with
+  uint32_t walk_kernels;          // VDB_KERNEL_* bits of a round of walk launches ...
+  uint32_t exact_kernels;         // ... and of the exact pass
+  WalkLdsRule lds;                // the layout of a walk launch
+  int exact_rows;                 // the rows of the exact pass (FiltersRows): the walk's own, or f32 behind a re-score — scored in f32 anyway
+};
+static FiltersMode filters_mode(int rows) {
+  constexpr uint32_t W = VDB_KERNEL_HNSW_FILTERED, X = VDB_KERNEL_FILTER_RANK, H = VDB_KERNEL_HNSW_HALF, F = VDB_KERNEL_F16;
+  switch (rows) {
+    case kFiltersF16:
+      return {kWalkF16, false, &vdb_hip_index::f16_enabled, "f16 filtered graph search: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first",
+              "half-precision filtered graph search", W | H | F, X | H | F, kLdsWalk, kFiltersF16};
+    case kFiltersBF16:
+      return {kWalkBF16, false, &vdb_hip_index::bf16_enabled, "bf16 filtered graph search: call vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16) first",
+              "half-precision filtered graph search", W | H, X | H, kLdsWalk, kFiltersBF16};
+    case kFiltersInt8:
+      return {kWalkCodes, true, &vdb_hip_index::quantizer_trained, "int8 filtered graph search: call vdb_hip_index_train_quantizer first",
+              "int8 filtered graph search", W | VDB_KERNEL_HNSW_INT8, X, kLdsInt8, kFiltersF32};
+    case kFiltersF16Rescore:
+      return {kWalkF16, true, &vdb_hip_index::f16_enabled,
+              "f16 filtered graph search with re-score: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first",
+              "half-precision filtered graph search with re-score", W | H | VDB_KERNEL_HALF_RESCORE | F, X, kLdsHalfRescore, kFiltersF32};
+    case kFiltersBF16Rescore:
+      return {kWalkBF16, true, &vdb_hip_index::bf16_enabled,
+              "bf16 filtered graph search with re-score: call vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16) first",
+              "half-precision filtered graph search with re-score", W | H | VDB_KERNEL_HALF_RESCORE, X, kLdsHalfRescore, kFiltersF32};
+    default: return {kWalkF32, false, nullptr, nullptr, "filtered graph search", W, X, kLdsWalk, kFiltersF32};
+  }
+}
+
 // vdb_hip_index_search_graph_filters on a leased context (ix->mu shared, by the caller): one filter per query.  The
 // queries go up, every query gets its own plan (filter_graph_route on ITS filter), climbs its own ladder of capacities and takes the
 // exact pass behind it if the largest list could not hold it; the result block comes back in ix->h_out (reserve_out's layout).
@@ -745,37 +716,17 @@ static uint32_t largest_list(LdsOf&& lds_of) {
 // filters: [n_filters] handles, non-null; fq: [nq] values in 0..n_filters, n_filters = no filter; routes: host, [nq].
 int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                        const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
-                                       uint32_t* routes, int half, uint32_t ratio) {
+                                       uint32_t* routes, int rows, uint32_t ratio) {
   int32_t rc;
-  const bool int8 = half == kFiltersInt8;
-  // (the statuses of the plain int8 walk, hnsw_search_int8_dev)
-  if (int8 && !ix->quantizer_trained) return fail(VDB_ERR_STATE, "int8 filtered graph search: call vdb_hip_index_train_quantizer first");
-  if (int8 && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
-    return fail(VDB_ERR_UNSUPPORTED, "int8 filtered graph search: Cosine, DotProduct and Euclidean only");
-  if (int8 && (ratio == 0 || ratio > 64)) return fail(VDB_ERR_INVALID_ARG, "int8 filtered graph search: oversampling ratio 1..64");
-  // the half walk with the f32 re-score: the image's statuses below, the ratio's as above
-  const bool hresc = half == kFiltersF16Rescore || half == kFiltersBF16Rescore;
-  const bool rescore = int8 || hresc;
-  if (hresc && (ratio == 0 || ratio > 64)) return fail(VDB_ERR_INVALID_ARG, "half-precision filtered graph search with re-score: oversampling ratio 1..64");
-  // (the statuses of the plain half walk, hnsw_search_half_dev)
-  if (half == kFiltersF16Rescore && !ix->f16_enabled)
-    return fail(VDB_ERR_STATE, "f16 filtered graph search with re-score: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
-  if (half == kFiltersBF16Rescore && !ix->bf16_enabled)
-    return fail(VDB_ERR_STATE, "bf16 filtered graph search with re-score: call vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16) first");
-  if (hresc && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
-    return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search with re-score: Cosine, DotProduct and Euclidean only");
-  if (half == kFiltersF16 && !ix->f16_enabled)
-    return fail(VDB_ERR_STATE, "f16 filtered graph search: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
-  if (half == kFiltersBF16 && !ix->bf16_enabled)
-    return fail(VDB_ERR_STATE, "bf16 filtered graph search: call vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16) first");
-  if ((half == kFiltersF16 || half == kFiltersBF16) && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
-    return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search: Cosine, DotProduct and Euclidean only");
-  const bool half_rows = half == kFiltersF16 || half == kFiltersBF16;
-  const uint32_t half_kernels = half_rows ? (VDB_KERNEL_HNSW_HALF | (half == kFiltersF16 ? VDB_KERNEL_F16 : 0u)) : 0u;
-  // (what the walk launches of the re-scoring calls add; their exact pass is the f32 one and adds nothing)
-  const uint32_t walk_kernels = int8    ? (uint32_t)VDB_KERNEL_HNSW_INT8
-                                : hresc ? (VDB_KERNEL_HNSW_HALF | VDB_KERNEL_HALF_RESCORE | (half == kFiltersF16Rescore ? VDB_KERNEL_F16 : 0u))
-                                        : 0u;
+  const FiltersMode m = filters_mode(rows);
+  const bool int8 = m.walk == kWalkCodes, f16 = m.walk == kWalkF16;
+  // the ratio's status comes last for the walk over the codes and first for a half image with the re-score
+  const bool bad_ratio = m.rescore && (ratio == 0 || ratio > 64);
+  if (bad_ratio && !int8) return fail(VDB_ERR_INVALID_ARG, std::string(m.what) + ": oversampling ratio 1..64");
+  if (m.enabled && !(ix->*m.enabled)) return fail(VDB_ERR_STATE, m.enable_first);
+  if (m.walk != kWalkF32 && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, std::string(m.what) + ": Cosine, DotProduct and Euclidean only");
+  if (bad_ratio) return fail(VDB_ERR_INVALID_ARG, std::string(m.what) + ": oversampling ratio 1..64");
   for (uint32_t j = 0; j < n_filters; j++)
     if ((rc = filter_check(ix, filters[j])) != VDB_OK) return rc;
   if (!ix->graph_valid) return fail(VDB_ERR_STATE, "HNSW graph not built for all rows (use the exact filtered search or build it)");
@@ -820,8 +771,8 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   ef = std::max(ef, k);                               // SearchQuality::Custom(ef) = max(ef, k), params.rs:317
   // the walk over the codes or a half image with the re-score: cand_k = k * ratio coarse candidates, ef widened over them
   // (dual_precision.rs:334) — the plans take it
-  const uint64_t cand_k = rescore ? (uint64_t)k * ratio : 0;
-  if (rescore) ef = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ef, cand_k), 0xFFFFFFFFull);
+  const uint64_t cand_k = m.rescore ? (uint64_t)k * ratio : 0;
+  if (m.rescore) ef = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(ef, cand_k), 0xFFFFFFFFull);
 
   HnswFiltersInt8Args fa8{};
   HnswFiltersArgs& fa = fa8.f;
@@ -832,8 +783,8 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   const uint32_t nbmax_exact = (longest + 63) / 64 * 64;  // (the exact pass has no candidates to gather: the f32 call's chunks)
   // the walk's layout and the exact pass's (always the f32 one)
   auto lds_of = [&](uint32_t cap) -> uint64_t {
-    if (int8) return hnsw_int8_lds_bytes(cap, nbmax, ix->dim, ix->code_words);
-    if (hresc) return hnsw_half_rescore_lds_bytes(cap, nbmax, ix->dim);
+    if (m.lds == kLdsInt8) return hnsw_int8_lds_bytes(cap, nbmax, ix->dim, ix->code_words);
+    if (m.lds == kLdsHalfRescore) return hnsw_half_rescore_lds_bytes(cap, nbmax, ix->dim);
     return hnsw_lds_bytes(cap, nbmax, ix->dim, ix->words, ix->metric);
   };
   auto lds_of_exact = [&](uint32_t cap) -> uint64_t { return hnsw_lds_bytes(cap, nbmax_exact, ix->dim, ix->words, ix->metric); };
@@ -896,29 +847,35 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
   a.k = k;
   a.ef = ef;
   a.nbmax = nbmax;
+  if (m.walk != kWalkF32) a.bits = nullptr;
   if (int8) {  // the codes beside the f32 rows, which the re-score and the exact pass read
-    a.bits = nullptr;
     fa8.codes = CodeCtx{ix->codes.as<uint32_t>(), ix->codes_sq.as<uint32_t>(), ix->code_words};
     fa8.min_vals = ix->sq_min.as<float>();
     fa8.scales = ix->sq_scale.as<float>();
     fa8.cand_k = (uint32_t)cand_k;  // (<= nbmax <= 2^32 - 64, or the lists did not fit and no walk is planned)
   }
-  if (half_rows) {  // the image instead of the f32 rows, as hnsw_search_half_dev: same fields, the stride in half elements
-    const bool f16 = half == kFiltersF16;
-    a.rows = reinterpret_cast<const float*>(f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>());
-    a.norms = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
-    a.row_stride = ix->bf16_stride;
-    a.bits = nullptr;
-  }
   HnswFiltersHalfRescoreArgs hr{};  // (its .f is copied from fa at every launch)
-  if (hresc) {  // the image beside the f32 rows, which the re-score and the exact pass read
-    const bool f16 = half == kFiltersF16Rescore;
-    a.bits = nullptr;
-    hr.image = reinterpret_cast<const float*>(f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>());
-    hr.image_norms = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
-    hr.image_stride = (uint32_t)ix->bf16_stride;
-    hr.cand_k = (uint32_t)cand_k;  // (<= nbmax, as above)
+  if (m.walk == kWalkF16 || m.walk == kWalkBF16) {
+    const float* image = reinterpret_cast<const float*>(f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>());
+    const float* image_norms = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
+    if (m.rescore) {  // the image beside the f32 rows, which the re-score and the exact pass read
+      hr.image = image;
+      hr.image_norms = image_norms;
+      hr.image_stride = (uint32_t)ix->bf16_stride;
+      hr.cand_k = (uint32_t)cand_k;  // (<= nbmax, as above)
+    } else {  // the image instead of the f32 rows, as hnsw_search_half_dev: same fields, the stride in half elements
+      a.rows = image;
+      a.norms = image_norms;
+      a.row_stride = ix->bf16_stride;
+    }
   }
+  // one walk launch of the call's mode
+  auto launch_walk = [&](int slots_l, size_t lds) -> hipError_t {
+    if (int8) return launch_filters_int8(fa8, slots_l, lds, st);
+    if (!m.rescore) return launch_filters_rows<false>(fa, rows, slots_l, lds, st);
+    hr.f = fa;
+    return f16 ? launch_filters_half_rescore<true>(hr, slots_l, lds, st) : launch_filters_half_rescore<false>(hr, slots_l, lds, st);
+  };
   fa.descs = reinterpret_cast<const FilterDesc*>(d_up + q_bytes);
   fa.qstats = ix->s_fgraph.as<unsigned long long>();
 
@@ -947,18 +904,10 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
       const size_t lds = lds_of(a.cap);
       if (lds > kFgLdsBudget) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: candidate list beyond the LDS" + limits);
       const int slots_l = (int)std::min<int64_t>((int64_t)L.count, (int64_t)ix->n_cus * (int64_t)L.per_cu);
-      hipError_t e;
-      if (int8) {
-        e = launch_filters_int8(fa8, slots_l, lds, st);
-      } else if (hresc) {
-        hr.f = fa;
-        e = half == kFiltersF16Rescore ? launch_filters_half_rescore<true>(hr, slots_l, lds, st) : launch_filters_half_rescore<false>(hr, slots_l, lds, st);
-      } else {
-        e = launch_filters_rows<false>(fa, half, slots_l, lds, st);
-      }
+      const hipError_t e = launch_walk(slots_l, lds);
       if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filtered hnsw_search launch: ") + hipGetErrorString(e));
     }
-    ix->last_kernels |= VDB_KERNEL_HNSW_FILTERED | half_kernels | walk_kernels;
+    ix->last_kernels |= m.walk_kernels;
     r = fetch();
     if (r != VDB_OK) return r;
     for (uint32_t i = 0; i < n; i++) over[i] = h_n[slots[i].query] == 0xFFFFFFFFu;
@@ -985,9 +934,9 @@ int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const
     a.nq = (uint32_t)exact.size();
     fa.slots = d_slots;
     const int slots_l = (int)std::min<int64_t>((int64_t)a.nq, (int64_t)ix->n_cus * 4);
-    const hipError_t e = launch_filters_rows<true>(fa, rescore ? (int)kFiltersF32 : half, slots_l, lds, st);  // (re-scoring calls: scored in f32 anyway)
+    const hipError_t e = launch_filters_rows<true>(fa, m.exact_rows, slots_l, lds, st);
     if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("filters_rank launch: ") + hipGetErrorString(e));
-    ix->last_kernels |= VDB_KERNEL_FILTER_RANK | half_kernels;
+    ix->last_kernels |= m.exact_kernels;
     rc = fetch();
     if (rc != VDB_OK) return rc;
     for (const FiltersSlot& s : exact) routes[s.query] = kFgExact;

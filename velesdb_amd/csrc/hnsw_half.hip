@@ -15,6 +15,7 @@
 
 #include "vdb_hnsw_device.hpp"
 #include "vdb_index.hpp"
+#include "vdb_walk_launch.hpp"
 
 namespace vdb {
 
@@ -26,44 +27,17 @@ __global__ __launch_bounds__(256, 4) void hnsw_search_half_kernel(HnswSearchArgs
   hnsw_walk_body<METRIC, CPL, NS, false, false, false, WalkDistHalf<METRIC, CPL, 4, (CPL == 4 ? 4 : 8), F16>>(a);
 }
 
-template <int METRIC, int CPL, int NS, bool F16>
-static hipError_t launch_half_ns(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hnsw_search_half_kernel<METRIC, CPL, NS, F16>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  // resident blocks per CU of THIS instantiation: a larger grid would queue whole blocks behind the persistent ones
-  int occ = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, hnsw_search_half_kernel<METRIC, CPL, NS, F16>, 256, lds);
-  if (e != hipSuccess) return e;
-  occ = std::max(1, std::min(occ, 4));
-  const int grid = (int)std::min<int64_t>((int64_t)slots, (int64_t)a.n_cus * occ);
-  hipLaunchKernelGGL((hnsw_search_half_kernel<METRIC, CPL, NS, F16>), dim3(grid), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
+// list_slots: 0 = LDS list (any ef), kSearchRegSlots = register list, as the f32 walk
 template <int METRIC, int CPL, bool F16>
 static hipError_t launch_half_t(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  if (a.list_slots == kSearchRegSlots) return launch_half_ns<METRIC, CPL, kSearchRegSlots, F16>(a, slots, lds, st);
-  return launch_half_ns<METRIC, CPL, 0, F16>(a, slots, lds, st);
+  if (a.list_slots == kSearchRegSlots)
+    return launch_walk_blocks(hnsw_search_half_kernel<METRIC, CPL, kSearchRegSlots, F16>, a, a.n_cus, slots, lds, st);
+  return launch_walk_blocks(hnsw_search_half_kernel<METRIC, CPL, 0, F16>, a, a.n_cus, slots, lds, st);
 }
-template <int METRIC, bool F16>
-static hipError_t launch_half_cpl(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  switch (sweep_cpl_for_dim(a.dim)) {
-    case 1: return launch_half_t<METRIC, 1, F16>(a, slots, lds, st);
-    case 2: return launch_half_t<METRIC, 2, F16>(a, slots, lds, st);
-    case 3: return launch_half_t<METRIC, 3, F16>(a, slots, lds, st);
-    case 4: return launch_half_t<METRIC, 4, F16>(a, slots, lds, st);
-    default: return launch_half_t<METRIC, 0, F16>(a, slots, lds, st);
-  }
-}
+// (Cosine, Euclidean and DotProduct: refused in front of the call otherwise)
 template <bool F16>
 static hipError_t launch_half(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  switch (a.metric) {
-    case kCosine: return launch_half_cpl<kCosine, F16>(a, slots, lds, st);
-    case kEuclidean: return launch_half_cpl<kEuclidean, F16>(a, slots, lds, st);
-    default: return launch_half_cpl<kDot, F16>(a, slots, lds, st);
-  }
+  return walk_dispatch<BitMetrics::kFallToDot>(a.metric, a.dim, [&](auto M, auto C) { return launch_half_t<M(), C(), F16>(a, slots, lds, st); });
 }
 
 // NativeHnsw::search over the f16 (f16 = true) or bf16 image for nq device-resident f32 queries + result mapping.  Enqueues on

@@ -19,6 +19,7 @@
 #include "vdb_probe_env.hpp"
 #include "vdb_hnsw_device.hpp"
 #include "vdb_index.hpp"
+#include "vdb_walk_launch.hpp"
 
 namespace vdb {
 
@@ -424,20 +425,10 @@ __global__ __launch_bounds__(WAVES * 64, 4) void hnsw_search_int8_kernel(HnswInt
 }
 
 // ---- host side -----------------------------------------------------------------------------
+// (up to kTraversalSlotsPerCu blocks per CU: the two-wave walks)
 template <int METRIC, int CPL, int NS, int WAVES, bool VIS>
 static hipError_t launch_i8_wv(const HnswInt8Args& A, int slots, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hnsw_search_int8_kernel<METRIC, CPL, NS, WAVES, VIS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  int occ = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, hnsw_search_int8_kernel<METRIC, CPL, NS, WAVES, VIS>, WAVES * 64, lds);
-  if (e != hipSuccess) return e;
-  occ = std::max(1, std::min(occ, kTraversalSlotsPerCu));
-  const int grid = (int)std::min<int64_t>((int64_t)slots, (int64_t)A.s.n_cus * occ);
-  hipLaunchKernelGGL((hnsw_search_int8_kernel<METRIC, CPL, NS, WAVES, VIS>), dim3(grid), dim3(WAVES * 64), lds, st, A);
-  return hipGetLastError();
+  return launch_walk_blocks(hnsw_search_int8_kernel<METRIC, CPL, NS, WAVES, VIS>, A, A.s.n_cus, slots, lds, st, WAVES * 64, kTraversalSlotsPerCu);
 }
 // VELESDB_INT8_VIS_LDS: 0 = HBM bitmaps, 1 = the exact LDS visited set (2^14 entries = 64 KiB: two queries in flight per CU);
 // unset = the measured default
@@ -467,16 +458,6 @@ template <int METRIC, int CPL>
 static hipError_t launch_i8_t(const HnswInt8Args& A, int slots, size_t lds, hipStream_t st) {
   if (A.s.list_slots == kSearchRegSlots) return launch_i8_ns<METRIC, CPL, kSearchRegSlots>(A, slots, lds, st);
   return launch_i8_ns<METRIC, CPL, 0>(A, slots, lds, st);
-}
-template <int METRIC>
-static hipError_t launch_i8_cpl(const HnswInt8Args& A, int slots, size_t lds, hipStream_t st) {
-  switch (sweep_cpl_for_dim(A.s.dim)) {
-    case 1: return launch_i8_t<METRIC, 1>(A, slots, lds, st);
-    case 2: return launch_i8_t<METRIC, 2>(A, slots, lds, st);
-    case 3: return launch_i8_t<METRIC, 3>(A, slots, lds, st);
-    case 4: return launch_i8_t<METRIC, 4>(A, slots, lds, st);
-    default: return launch_i8_t<METRIC, 0>(A, slots, lds, st);
-  }
 }
 
 // ScalarQuantizer::train on the first sample_rows rows (0 = min(1000, n_rows), dual_precision.rs:95,134-157) and
@@ -566,12 +547,8 @@ int32_t hnsw_search_int8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_str
   const int slots = (int)std::min<int64_t>((int64_t)nq, (int64_t)ix->n_cus * kTraversalSlotsPerCu);
   EventPair* ev = next_events(ix);
   if (ev) (void)hipEventRecord(ev->a, st);
-  hipError_t e;
-  switch (ix->metric) {
-    case kCosine: e = launch_i8_cpl<kCosine>(A, slots, lds, st); break;
-    case kEuclidean: e = launch_i8_cpl<kEuclidean>(A, slots, lds, st); break;
-    default: e = launch_i8_cpl<kDot>(A, slots, lds, st); break;
-  }
+  const hipError_t e =
+      walk_dispatch<BitMetrics::kFallToDot>(ix->metric, a.dim, [&](auto M, auto C) { return launch_i8_t<M(), C()>(A, slots, lds, st); });
   if (ev) (void)hipEventRecord(ev->b, st);
   if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("int8 search launch: ") + hipGetErrorString(e));
   ix->stats_pending = true;

@@ -29,6 +29,7 @@
 #include "vdb_probe_env.hpp"
 #include "vdb_hnsw_device.hpp"
 #include "vdb_index.hpp"
+#include "vdb_walk_launch.hpp"
 
 namespace vdb {
 
@@ -59,10 +60,13 @@ __global__ __launch_bounds__(LAT ? 1024 : 256, 4) void hnsw_search_kernel(HnswSe
 }
 
 // ---- host side -----------------------------------------------------------------------------
-// the dynamic LDS of a walk block: the arrays WalkLds (vdb_hnsw_device.hpp) carves out — the same offsets, change both together —
-// plus the query scratch of the distance phase
+// the arrays WalkLds (vdb_hnsw_device.hpp) carves out of a walk block's dynamic LDS — the same offsets, change both together
+static size_t walk_lds_base(uint32_t cap, uint32_t nbmax) {
+  return (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+}
+// the dynamic LDS of a walk block: WalkLds plus the query scratch of the distance phase
 size_t hnsw_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint32_t words, int metric) {
-  size_t s = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+  size_t s = walk_lds_base(cap, nbmax);
   if (metric == kHamming || metric == kJaccard)
     s += (size_t)words * 4;
   else if (sweep_cpl_for_dim(dim) == 0)
@@ -72,7 +76,7 @@ size_t hnsw_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint32_t words
 // ... of an int8 walk block (hnsw_search_int8_kernel, hnsw_int8.hip; hnsw_search_filters_int8_kernel, hnsw_filtered.hip): WalkLds |
 // f32 query scratch (generic dims: the re-score) | the query's code words [code_words] | (pad 16) | re-score output [nbmax] u64
 size_t hnsw_int8_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim, uint32_t code_words) {
-  size_t s = (size_t)cap * 8 + (size_t)nbmax * 8 + 16 + (((size_t)cap + 15) & ~(size_t)15);
+  size_t s = walk_lds_base(cap, nbmax);
   if (sweep_cpl_for_dim(dim) == 0) s += (size_t)((dim + 3) / 4) * 16;
   s += (size_t)code_words * 4;
   s = (s + 15) & ~(size_t)15;
@@ -85,68 +89,22 @@ size_t hnsw_half_rescore_lds_bytes(uint32_t cap, uint32_t nbmax, uint32_t dim) {
   return hnsw_lds_bytes(cap, nbmax, dim, 0, kCosine) + (size_t)nbmax * 8;
 }
 
-// latency mode: one 1 024-thread block per query (at most one query per CU per call)
-template <int METRIC, int CPL, bool VIS>
-static hipError_t launch_lat_v(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hnsw_search_kernel<METRIC, CPL, kSearchRegSlots, true, VIS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((hnsw_search_kernel<METRIC, CPL, kSearchRegSlots, true, VIS>), dim3(slots), dim3(1024), lds, st, a);
-  return hipGetLastError();
-}
+// latency mode: one 1 024-thread block per query (at most one query per CU per call); vis_log2: the LDS visited set or the HBM bitmaps
 template <int METRIC, int CPL>
 static hipError_t launch_lat(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  return a.vis_log2 ? launch_lat_v<METRIC, CPL, true>(a, slots, lds, st) : launch_lat_v<METRIC, CPL, false>(a, slots, lds, st);
+  return dispatch_bool(a.vis_log2 != 0, [&](auto VIS) {
+    return launch_walk_grid(hnsw_search_kernel<METRIC, CPL, kSearchRegSlots, true, VIS()>, a, slots, lds, st, 1024);
+  });
 }
-template <int METRIC, int CPL, int NS, bool VIS>
-static hipError_t launch_ns_v(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hnsw_search_kernel<METRIC, CPL, NS, false, VIS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  // resident blocks per CU of THIS instantiation (registers / LDS): a grid larger than what is resident would
-  // queue whole blocks behind the persistent ones
-  int occ = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, hnsw_search_kernel<METRIC, CPL, NS, false, VIS>, 256, lds);
-  if (e != hipSuccess) return e;
-  occ = std::max(1, std::min(occ, 4));
-  const int grid = (int)std::min<int64_t>((int64_t)slots, (int64_t)a.n_cus * occ);
-  hipLaunchKernelGGL((hnsw_search_kernel<METRIC, CPL, NS, false, VIS>), dim3(grid), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-template <int METRIC, int CPL, int NS>
-static hipError_t launch_ns(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  return a.vis_log2 ? launch_ns_v<METRIC, CPL, NS, true>(a, slots, lds, st) : launch_ns_v<METRIC, CPL, NS, false>(a, slots, lds, st);
-}
-// list_slots: 0 = LDS list (any ef), kSearchRegSlots = register list (ef + 64 <= kSearchRegSlots * 64)
+// the throughput kernel.  list_slots: 0 = LDS list (any ef), kSearchRegSlots = register list (ef + 64 <= kSearchRegSlots * 64)
 template <int METRIC, int CPL>
 static hipError_t launch_t(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  if (a.list_slots == kSearchRegSlots) return launch_ns<METRIC, CPL, kSearchRegSlots>(a, slots, lds, st);
-  return launch_ns<METRIC, CPL, 0>(a, slots, lds, st);
-}
-template <int METRIC>
-static hipError_t launch_cpl(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  switch (sweep_cpl_for_dim(a.dim)) {
-    case 1: return launch_t<METRIC, 1>(a, slots, lds, st);
-    case 2: return launch_t<METRIC, 2>(a, slots, lds, st);
-    case 3: return launch_t<METRIC, 3>(a, slots, lds, st);
-    case 4: return launch_t<METRIC, 4>(a, slots, lds, st);
-    default: return launch_t<METRIC, 0>(a, slots, lds, st);
-  }
-}
-
-template <int METRIC>
-static hipError_t launch_lat_cpl(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  switch (sweep_cpl_for_dim(a.dim)) {
-    case 1: return launch_lat<METRIC, 1>(a, slots, lds, st);
-    case 2: return launch_lat<METRIC, 2>(a, slots, lds, st);
-    case 3: return launch_lat<METRIC, 3>(a, slots, lds, st);
-    case 4: return launch_lat<METRIC, 4>(a, slots, lds, st);
-    default: return launch_lat<METRIC, 0>(a, slots, lds, st);
-  }
+  return dispatch_bool(a.list_slots == kSearchRegSlots, [&](auto REG) {
+    constexpr int NS = REG() ? kSearchRegSlots : 0;
+    return dispatch_bool(a.vis_log2 != 0, [&](auto VIS) {
+      return launch_walk_blocks(hnsw_search_kernel<METRIC, CPL, NS, false, VIS()>, a, a.n_cus, slots, lds, st);
+    });
+  });
 }
 // VELESDB_HNSW_LATENCY_MODE=0 keeps the throughput kernel for every call (A / B measurements), =2 takes the latency-mode kernel
 // whatever the corpus size (fuzzing it over small graphs: tools/fuzz_hnsw.py)
@@ -185,35 +143,15 @@ static uint32_t pick_vis(const HnswSearchArgs& a, size_t lds, bool lat) {
   return 0;
 }
 
-template <int METRIC>
-static hipError_t launch_raw_ef(const HnswSearchArgs& a, int slots, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hnsw_search_kernel<METRIC, 0, 0, false, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  int occ = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, hnsw_search_kernel<METRIC, 0, 0, false, false, true>, 256, lds);
-  if (e != hipSuccess) return e;
-  occ = std::max(1, std::min(occ, 4));
-  const int grid = (int)std::min<int64_t>((int64_t)slots, (int64_t)a.n_cus * occ);
-  hipLaunchKernelGGL((hnsw_search_kernel<METRIC, 0, 0, false, false, true>), dim3(grid), dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_hnsw_search(const HnswSearchArgs& a0, int slots, hipStream_t st) {
   HnswSearchArgs a = a0;
   size_t lds = hnsw_lds_bytes(a.cap, a.nbmax, a.dim, a.words, a.metric);
   if (a.raw_small_ef) {  // NativeHnsw-level call with ef_search < 4: the generic instance that raises ef to the entry points per query
     a.vis_log2 = 0;      // (HBM bitmaps)
     a.pf_ids = 0;
-    switch (a.metric) {
-      case kCosine: return launch_raw_ef<kCosine>(a, slots, lds, st);
-      case kEuclidean: return launch_raw_ef<kEuclidean>(a, slots, lds, st);
-      case kDot: return launch_raw_ef<kDot>(a, slots, lds, st);
-      case kHamming: return launch_raw_ef<kHamming>(a, slots, lds, st);
-      default: return launch_raw_ef<kJaccard>(a, slots, lds, st);
-    }
+    return walk_dispatch_metric<BitMetrics::kTaken>(a.metric, [&](auto M) {
+      return launch_walk_blocks(hnsw_search_kernel<M(), 0, 0, false, false, true>, a, a.n_cus, slots, lds, st);
+    });
   }
   // at most one query per CU (measured at 1 M x 768, ef 128: 64 queries 1.57 ms against 2.68 ms on the throughput kernel, 256
   // queries 2.12 against 3.21 ms — a 1 024-thread block per CU is all the chip holds of this kernel) over a corpus that does not
@@ -237,22 +175,12 @@ hipError_t launch_hnsw_search(const HnswSearchArgs& a0, int slots, hipStream_t s
     a.vis_log2 = pick_vis(a0, lds, true);
     a.vis_off = (uint32_t)lds;
     if (a.vis_log2) lds += (size_t)4 << a.vis_log2;
-    switch (a.metric) {
-      case kCosine: return launch_lat_cpl<kCosine>(a, (int)a.nq, lds, st);
-      case kEuclidean: return launch_lat_cpl<kEuclidean>(a, (int)a.nq, lds, st);
-      default: return launch_lat_cpl<kDot>(a, (int)a.nq, lds, st);
-    }
+    return walk_dispatch<BitMetrics::kFallToDot>(a.metric, a.dim, [&](auto M, auto C) { return launch_lat<M(), C()>(a, (int)a.nq, lds, st); });
   }
   a.vis_log2 = pick_vis(a0, lds, false);
   a.vis_off = (uint32_t)lds;
   if (a.vis_log2) lds += (size_t)4 << a.vis_log2;
-  switch (a.metric) {
-    case kCosine: return launch_cpl<kCosine>(a, slots, lds, st);
-    case kEuclidean: return launch_cpl<kEuclidean>(a, slots, lds, st);
-    case kDot: return launch_cpl<kDot>(a, slots, lds, st);
-    case kHamming: return launch_t<kHamming, 0>(a, slots, lds, st);
-    default: return launch_t<kJaccard, 0>(a, slots, lds, st);
-  }
+  return walk_dispatch<BitMetrics::kTaken>(a.metric, a.dim, [&](auto M, auto C) { return launch_t<M(), C()>(a, slots, lds, st); });
 }
 
 // one visited bitmap (capacity bits) + one id log per resident block, zero between launches.  want_slots = the blocks the

@@ -122,15 +122,15 @@ static int32_t search_graph_filtered_direct(vdb_hip_index* handle, const RowFilt
 }
 
 // vdb_hip_index_search_graph_filters: the same, one filter per query; the routes travel with the results (nothing is written on error).
-// half: the rows of the walk (FiltersRows; vdb_hip_index_search_graph_filters_half)
+// rows: the rows of the walk (FiltersRows, vdb_index.hpp)
 static int32_t search_graph_filters_direct(vdb_hip_index* handle, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                            const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
-                                           uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route, int half = kFiltersF32,
+                                           uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route, int rows = kFiltersF32,
                                            uint32_t ratio = 0) {
   std::vector<uint32_t> routes(nq, 0u);
   return run_search(
       handle, nq, k, ef, VDB_SEARCH_HNSW, 0,
-      [&](vdb_hip_index* ix) { return search_graph_filters_to_device(ix, filters, n_filters, fq, queries, nq, k, ef, route, max_list, routes.data(), half, ratio); },
+      [&](vdb_hip_index* ix) { return search_graph_filters_to_device(ix, filters, n_filters, fq, queries, nq, k, ef, route, max_list, routes.data(), rows, ratio); },
       [&](vdb_hip_index* ix) {
         deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n);
         if (out_route) std::memcpy(out_route, routes.data(), (size_t)nq * 4);
@@ -362,18 +362,43 @@ int32_t vdb_hip_index_last_filters_exact_plan(vdb_hip_index* ix, uint32_t* out) 
   });
 }
 
+// The argument checks the five filtered graph entry points below share, in two parts around each entry point's own mode, metric and
+// ratio checks (their statuses come between these).  In front of them: the null arguments — table_ok: the call's filter, or its table and
+// filter_of_query — the multi-device handle and the process group ...
+static bool fg_table_ok(void** filters, uint32_t n_filters, const uint32_t* filter_of_query, uint32_t nq) {
+  return !(n_filters && !filters) && !(nq && !filter_of_query);
+}
+static int32_t fg_check_handle(vdb_hip_index* ix, bool table_ok, const float* queries, uint32_t nq, uint32_t k, const uint64_t* out_ids,
+                               const float* out_scores, const uint32_t* out_n) {
+  if (!ix || !table_ok || (nq && (!queries || !out_n)) || (nq && k && (!out_ids || !out_scores))) return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filtered graph search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  return VDB_OK;
+}
+// ... and behind them: the route, the table's entries and every query's index into the table (filter_of_query null: the one-filter
+// call, which has no table).  A call of no queries returns VDB_OK behind this.
+static int32_t fg_check_table(int32_t route, void** filters, uint32_t n_filters, const uint32_t* filter_of_query, uint32_t nq) {
+  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
+  for (uint32_t j = 0; j < n_filters; j++)
+    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: filter " + std::to_string(j) + " of the table is null");
+  for (uint32_t i = 0; filter_of_query && i < nq; i++)
+    if (filter_of_query[i] > n_filters)
+      return fail(VDB_ERR_INVALID_ARG, "filtered graph search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
+                                           " of a table of " + std::to_string(n_filters));
+  return VDB_OK;
+}
+
 // VDB_SEARCH_HNSW with the allow-list consulted inside the walk, and the exact pass behind it (hnsw_filtered.hip)
 int32_t vdb_hip_index_search_graph_filtered(vdb_hip_index* ix, const void* filter, const float* queries, uint32_t nq, uint32_t k,
                                             uint32_t ef, int32_t mode, int32_t route, uint32_t max_list, uint64_t* out_ids,
                                             float* out_scores, uint32_t* out_n, uint32_t* out_route) {
   return vdb::guarded([&]() -> int32_t {
   const RowFilter* f = static_cast<const RowFilter*>(filter);
-  if (!ix || !f || (nq && (!queries || !out_n)) || (nq && k && (!out_ids || !out_scores))) return fail(VDB_ERR_INVALID_ARG, "null argument");
-  VDB_NO_GROUP(ix, "filtered graph search");
-  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  int32_t rc = fg_check_handle(ix, f != nullptr, queries, nq, k, out_ids, out_scores, out_n);
+  if (rc != VDB_OK) return rc;
   if (mode != VDB_SEARCH_HNSW) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: VDB_SEARCH_HNSW only (no filtered walk over the half / int8 images)");
-  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
-  if (nq == 0) return VDB_OK;
+  rc = fg_check_table(route, nullptr, 0, nullptr, nq);  // (no table: the route alone)
+  if (rc != VDB_OK || nq == 0) return rc;
   return search_graph_filtered_direct(ix, f, queries, nq, k, ef, route, max_list, out_ids, out_scores, out_n, out_route);
   });
 }
@@ -383,19 +408,11 @@ int32_t vdb_hip_index_search_graph_filters(vdb_hip_index* ix, void** filters, ui
                                            const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t mode, int32_t route,
                                            uint32_t max_list, uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route) {
   return vdb::guarded([&]() -> int32_t {
-  if (!ix || (n_filters && !filters) || (nq && (!queries || !out_n || !filter_of_query)) || (nq && k && (!out_ids || !out_scores)))
-    return fail(VDB_ERR_INVALID_ARG, "null argument");
-  VDB_NO_GROUP(ix, "filtered graph search");
-  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  int32_t rc = fg_check_handle(ix, fg_table_ok(filters, n_filters, filter_of_query, nq), queries, nq, k, out_ids, out_scores, out_n);
+  if (rc != VDB_OK) return rc;
   if (mode != VDB_SEARCH_HNSW) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: VDB_SEARCH_HNSW only (no filtered walk over the half / int8 images)");
-  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
-  for (uint32_t j = 0; j < n_filters; j++)
-    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: filter " + std::to_string(j) + " of the table is null");
-  for (uint32_t i = 0; i < nq; i++)
-    if (filter_of_query[i] > n_filters)
-      return fail(VDB_ERR_INVALID_ARG, "filtered graph search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
-                                           " of a table of " + std::to_string(n_filters));
-  if (nq == 0) return VDB_OK;
+  rc = fg_check_table(route, filters, n_filters, filter_of_query, nq);
+  if (rc != VDB_OK || nq == 0) return rc;
   return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k, ef,
                                      route, max_list, out_ids, out_scores, out_n, out_route);
   });
@@ -408,22 +425,14 @@ int32_t vdb_hip_index_search_graph_filters_half(vdb_hip_index* ix, int32_t mode,
                                                 int32_t route, uint32_t max_list, uint64_t* out_ids, float* out_scores, uint32_t* out_n,
                                                 uint32_t* out_route) {
   return vdb::guarded([&]() -> int32_t {
-  if (!ix || (n_filters && !filters) || (nq && (!queries || !out_n || !filter_of_query)) || (nq && k && (!out_ids || !out_scores)))
-    return fail(VDB_ERR_INVALID_ARG, "null argument");
-  VDB_NO_GROUP(ix, "filtered graph search");
-  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  int32_t rc = fg_check_handle(ix, fg_table_ok(filters, n_filters, filter_of_query, nq), queries, nq, k, out_ids, out_scores, out_n);
+  if (rc != VDB_OK) return rc;
   if (mode != VDB_SEARCH_HNSW_F16 && mode != VDB_SEARCH_HNSW_BF16)
     return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search: VDB_SEARCH_HNSW_F16 or VDB_SEARCH_HNSW_BF16");
   if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
     return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search: Cosine, DotProduct and Euclidean only");
-  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
-  for (uint32_t j = 0; j < n_filters; j++)
-    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: filter " + std::to_string(j) + " of the table is null");
-  for (uint32_t i = 0; i < nq; i++)
-    if (filter_of_query[i] > n_filters)
-      return fail(VDB_ERR_INVALID_ARG, "filtered graph search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
-                                           " of a table of " + std::to_string(n_filters));
-  if (nq == 0) return VDB_OK;
+  rc = fg_check_table(route, filters, n_filters, filter_of_query, nq);
+  if (rc != VDB_OK || nq == 0) return rc;
   return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k, ef,
                                      route, max_list, out_ids, out_scores, out_n, out_route,
                                      mode == VDB_SEARCH_HNSW_F16 ? kFiltersF16 : kFiltersBF16);
@@ -438,22 +447,14 @@ int32_t vdb_hip_index_search_graph_filters_int8(vdb_hip_index* ix, void** filter
                                                 uint32_t oversampling_ratio, int32_t route, uint32_t max_list, uint64_t* out_ids,
                                                 float* out_scores, uint32_t* out_n, uint32_t* out_route) {
   return vdb::guarded([&]() -> int32_t {
-  if (!ix || (n_filters && !filters) || (nq && (!queries || !out_n || !filter_of_query)) || (nq && k && (!out_ids || !out_scores)))
-    return fail(VDB_ERR_INVALID_ARG, "null argument");
-  VDB_NO_GROUP(ix, "filtered graph search");
-  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  int32_t rc = fg_check_handle(ix, fg_table_ok(filters, n_filters, filter_of_query, nq), queries, nq, k, out_ids, out_scores, out_n);
+  if (rc != VDB_OK) return rc;
   if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
     return fail(VDB_ERR_UNSUPPORTED, "int8 filtered graph search: Cosine, DotProduct and Euclidean only");
   // the bound vdb_hip_set_int8_oversampling holds the handle's option to: k * ratio sizes nbmax, ef and the LDS list of the walk
   if (oversampling_ratio > 64) return fail(VDB_ERR_INVALID_ARG, "int8 filtered graph search: oversampling_ratio 0 (the handle's option) or 1..64");
-  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
-  for (uint32_t j = 0; j < n_filters; j++)
-    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: filter " + std::to_string(j) + " of the table is null");
-  for (uint32_t i = 0; i < nq; i++)
-    if (filter_of_query[i] > n_filters)
-      return fail(VDB_ERR_INVALID_ARG, "filtered graph search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
-                                           " of a table of " + std::to_string(n_filters));
-  if (nq == 0) return VDB_OK;
+  rc = fg_check_table(route, filters, n_filters, filter_of_query, nq);
+  if (rc != VDB_OK || nq == 0) return rc;
   const uint32_t ratio = oversampling_ratio ? oversampling_ratio : (uint32_t)opt_value(ix, VDB_OPT_INT8_OVERSAMPLING);
   return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k,
                                      ef_search, route, max_list, out_ids, out_scores, out_n, out_route, kFiltersInt8, ratio);
@@ -468,10 +469,8 @@ int32_t vdb_hip_index_search_graph_filters_half_rescore(vdb_hip_index* ix, int32
                                                         uint32_t ef_search, uint32_t oversampling_ratio, int32_t route, uint32_t max_list,
                                                         uint64_t* out_ids, float* out_scores, uint32_t* out_n, uint32_t* out_route) {
   return vdb::guarded([&]() -> int32_t {
-  if (!ix || (n_filters && !filters) || (nq && (!queries || !out_n || !filter_of_query)) || (nq && k && (!out_ids || !out_scores)))
-    return fail(VDB_ERR_INVALID_ARG, "null argument");
-  VDB_NO_GROUP(ix, "filtered graph search");
-  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered graph search: not available on a member of a process group");
+  int32_t rc = fg_check_handle(ix, fg_table_ok(filters, n_filters, filter_of_query, nq), queries, nq, k, out_ids, out_scores, out_n);
+  if (rc != VDB_OK) return rc;
   if (mode != VDB_SEARCH_HNSW_F16 && mode != VDB_SEARCH_HNSW_BF16)
     return fail(VDB_ERR_UNSUPPORTED, "half-precision filtered graph search with re-score: VDB_SEARCH_HNSW_F16 or VDB_SEARCH_HNSW_BF16");
   if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
@@ -479,14 +478,8 @@ int32_t vdb_hip_index_search_graph_filters_half_rescore(vdb_hip_index* ix, int32
   // k * ratio sizes nbmax, ef and the LDS list of the walk: the int8 call's bound
   if (oversampling_ratio > 64)
     return fail(VDB_ERR_INVALID_ARG, "half-precision filtered graph search with re-score: oversampling_ratio 0 (= 4) or 1..64");
-  if (route < 0 || route > 2) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: route 0 (auto), 1 (walk) or 2 (exact pass)");
-  for (uint32_t j = 0; j < n_filters; j++)
-    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered graph search: filter " + std::to_string(j) + " of the table is null");
-  for (uint32_t i = 0; i < nq; i++)
-    if (filter_of_query[i] > n_filters)
-      return fail(VDB_ERR_INVALID_ARG, "filtered graph search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
-                                           " of a table of " + std::to_string(n_filters));
-  if (nq == 0) return VDB_OK;
+  rc = fg_check_table(route, filters, n_filters, filter_of_query, nq);
+  if (rc != VDB_OK || nq == 0) return rc;
   return search_graph_filters_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k,
                                      ef_search, route, max_list, out_ids, out_scores, out_n, out_route,
                                      mode == VDB_SEARCH_HNSW_F16 ? kFiltersF16Rescore : kFiltersBF16Rescore,

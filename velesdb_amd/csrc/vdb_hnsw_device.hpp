@@ -134,7 +134,7 @@ __device__ __forceinline__ uint32_t greedy_scan(lds_vf32* nb_d, uint32_t m, floa
 }
 
 // The dynamic LDS of a walk block: keys[cap] u64 | nb_id[nbmax] | nb_d[nbmax] | ctl[4] | flags[cap] u8 (padded to 16) | the query
-// scratch of the distance phase.  These are the offsets hnsw_lds_bytes (hnsw_kernels.hip) adds up: change both together.
+// scratch of the distance phase.  These are the offsets walk_lds_base (hnsw_kernels.hip) adds up: change both together.
 struct WalkLds {
   lds_vu64* keys;
   lds_vu32* nb_id;

@@ -342,7 +342,7 @@ void last_fx_plan_of_this_thread(vdb_hip_index* ix, uint32_t out[6]);
 int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k, uint32_t ef,
                                         int32_t route, uint32_t max_list, uint32_t* routes);
 // one filter per query (hnsw_filtered.hip): filters[n_filters] checked handles, fq[nq] in 0..n_filters (n_filters = no
-// filter); same locking, result block and routes.  half: the rows the distances are taken over — kFiltersF32, or the f16 / bf16
+// filter); same locking, result block and routes.  rows: the rows the distances are taken over — kFiltersF32, or the f16 / bf16
 // image (vdb_hip_index_search_graph_filters_half), or kFiltersInt8: the walk over the u8 codes with the re-score of the
 // k * ratio best allowed candidates in f32 and the f32 exact pass (vdb_hip_index_search_graph_filters_int8) — ef is then
 // the caller's ef_search, ratio the oversampling ratio (1..64), unused otherwise; or kFiltersF16Rescore / kFiltersBF16Rescore: the walk
@@ -351,7 +351,7 @@ int32_t search_graph_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, c
 enum FiltersRows : int { kFiltersF32 = 0, kFiltersF16 = 1, kFiltersBF16 = 2, kFiltersInt8 = 3, kFiltersF16Rescore = 4, kFiltersBF16Rescore = 5 };
 int32_t search_graph_filters_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                        const float* queries, uint32_t nq, uint32_t k, uint32_t ef, int32_t route, uint32_t max_list,
-                                       uint32_t* routes, int half = kFiltersF32, uint32_t ratio = 0);
+                                       uint32_t* routes, int rows = kFiltersF32, uint32_t ratio = 0);
 // rows per index: the tiled kernels count whole 256-row tiles of [0, n) in 32 bits — (n + 255) / 256 must not wrap
 // (tests/gemm_schedule_model.cpp walks the launch schedule up to this limit)
 constexpr uint64_t kMaxRowsPerIndex = 0xFFFFFE00ull;  // 2^32 - 512
