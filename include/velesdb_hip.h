@@ -328,6 +328,28 @@ void vdb_hip_filter_destroy(void* f);
  * call (it does not go through the combining front) and leaves the handle's adaptive selection state as it found it. */
 int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* idx, const void* f, const float* queries_rowmajor, uint32_t nq,
                                             uint32_t k, int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+/* The same over the SQ8 codes, the sign bits or a half image of the rows: the reference's search_with_filter works
+ * whatever the collection's storage mode.  mode is one of VDB_SEARCH_BRUTE_SQ8, VDB_SEARCH_BRUTE_BINARY, VDB_SEARCH_BRUTE_BF16,
+ * VDB_SEARCH_BRUTE_F16.
+ * THE CONTRACT: the call returns what vdb_hip_index_search_batch(mode) returns on an index that holds only the filter's live rows,
+ * inserted in the same order under the same ids, with the same storage mode / precision enabled — ids, ranks, score values, out_n and
+ * padding.  SQ8, Binary and Euclidean over a half image: bit for bit (their summation orders are declared).  Cosine / DotProduct over
+ * a half image: within the tolerance that mode carries, tie-aware (bit for bit on data whose partial sums are exact).
+ * The filter semantics are vdb_hip_index_search_batch_filtered's: a snapshot; negate; the empty filter answers out_n = 0; rows removed
+ * later are excluded, rows inserted later are not in it.
+ * Two routes (VDB_OPT_FILTER_ROUTE, the same three values): the LISTED kernels — sweep_topk_sq8_listed (SQ8, all three metrics) and
+ * sweep_topk_half_l2_listed (Euclidean over a half image) read only the filter's rows, gathered by index — and MASK SUBSTITUTION,
+ * the mode's own dispatch with every tier of it under the call's row mask (the only route of Binary and of Cosine / DotProduct over a
+ * half image).  Same bits on both where the bits are declared.  Auto (checked against one measurement): Euclidean over a
+ * half image takes the listed kernel iff matched <= 3/4 rows; SQ8 only for calls of at most three queries, with the same cut.  With
+ * fewer than 1/16 of the rows allowed the SQ8 selection stage is skipped, as the f32 one.
+ * vdb_hip_index_last_kernels: the mode's usual bits, plus VDB_KERNEL_SWEEP_LISTED when a listed kernel ran.
+ * Errors: null arguments and a filter of another handle VDB_ERR_INVALID_ARG; a stale filter VDB_ERR_STATE; a mode whose storage mode or
+ * image is not enabled VDB_ERR_STATE, as the plain call; any other mode (VDB_SEARCH_BRUTE has the call above), multi-device handles and
+ * process-group members VDB_ERR_UNSUPPORTED.  The outputs are untouched on error.  The call never goes through the combining front,
+ * leaves the handle's adaptive selection state as it found it and posts no selection verdicts.  Host pointers only. */
+int32_t vdb_hip_index_search_batch_filtered_mode(vdb_hip_index* idx, const void* f, int32_t mode, const float* queries_rowmajor,
+                                                 uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
 /* One filter PER QUERY on the exact sweep: the collection layer's search_batch_with_filters (collection/search/batch.rs:26-115;
  * DESIGN 4.1n).  The table follows vdb_hip_index_search_graph_filters below: filters = n_filters distinct filter handles of this
  * index; filter_of_query[i] in 0..n_filters-1 names query i's filter, filter_of_query[i] == n_filters = query i has NO filter;

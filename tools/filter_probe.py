@@ -50,6 +50,14 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
   to agree bit for bit first.  Asserted: at F = 1 the new call's median lies inside the loop's own min-max spread (it is the same
   code path); everything else is recorded.  Defaults of this leg: --rows 100000, --densities 0.001,0.01,0.1.
 
+  --exact --storage sq8|binary|f16|bf16: the exact leg over that image of the rows (vdb_hip_index_search_batch_filtered_mode, DESIGN
+  4.1o): per metric, batch size and selectivity the forced listed route, the forced mask route, the auto rule and — what an
+  over-fetching caller pays today, the parent has no filtered call in these modes — the UNFILTERED call in the same mode on the same
+  handle, the blocks of the four going round (unfiltered, listed, mask, auto, unfiltered, ...) in the same run.  Median and
+  (max - min) / median of the blocks of each; whether a listed kernel ran on the forced listed route (Binary and Cosine / DotProduct
+  over a half image have none: the column then repeats the mask route); which route auto took.  The routes are held to agree first:
+  bit for bit where the mode declares its summation order (SQ8, Binary, Euclidean over a half image), the same ids otherwise.
+
 Every figure is the median of --repeats blocks, each block the mean over enough calls to last ~--block-ms; the spread is
 (max - min) / median over the blocks.  Not part of the product or the test-suite."""
 import argparse
@@ -79,6 +87,8 @@ p.add_argument("--rider", action="store_true")
 p.add_argument("--graph", action="store_true", help="the filtered graph search leg instead of the exact one")
 p.add_argument("--graph-nq", type=int, default=1024)
 p.add_argument("--per-query", type=int, default=0, help="with --graph: F distinct filters per density in one call against F single-filter calls")
+p.add_argument("--exact", action="store_true", help="the exact leg (the default leg; names it next to --storage)")
+p.add_argument("--storage", default="", choices=["", "sq8", "binary", "f16", "bf16"], help="with --exact: the image of the rows the filtered exact call reads")
 p.add_argument("--exact-per-query", default="", help="F[,F...]: distinct filters per call of the exact per-query-filters leg")
 p.add_argument("--precision", default="f32", choices=["f32", "f16", "bf16", "int8"], help="with --graph: the rows the filtered walk reads")
 p.add_argument("--ratio", type=int, default=4, help="with --precision int8, or with --rescore: the oversampling ratio")
@@ -87,6 +97,10 @@ p.add_argument("--ef", type=int, default=128)
 p.add_argument("--densities", default="1,0.5,0.25,0.125,0.0625,0.03125,0.015625,0.0078125,0.00390625,0.001953125,0.0009765625")
 p.add_argument("--out", default="")
 a = p.parse_args()
+if a.exact and (a.graph or a.exact_per_query):
+    p.error("--exact names the exact leg: not with --graph / --exact-per-query")
+if a.storage and (not a.exact or a.graph or a.exact_per_query):
+    p.error("--storage goes with --exact (the exact leg over that image of the rows)")
 dev = torch.device("cuda", 0)
 st = torch.cuda.current_stream().cuda_stream
 METRICS = {"cosine": va.DistanceMetric.Cosine, "euclidean": va.DistanceMetric.Euclidean, "dot": va.DistanceMetric.DotProduct}
@@ -405,9 +419,69 @@ def exact_per_query_leg():
     return rows_out, bad
 
 
+def storage_leg():
+    rows_out = []
+    for mname in [m for m in a.metrics.split(",") if m]:
+        ix = build(METRICS[mname])
+        ix.set_option(va.OPT_COMBINE_MAX_BATCH, 0)  # the unfiltered yardstick launches alone too
+        if a.storage == "sq8":
+            ix.set_storage_mode(va.StorageMode.SQ8)
+            plain, filtered = ix.search_batch_sq8, ix.search_batch_filtered_sq8
+        elif a.storage == "binary":
+            ix.set_storage_mode(va.StorageMode.Binary)
+            plain, filtered = ix.search_batch_binary, ix.search_batch_filtered_binary
+        else:
+            prec = va.VectorPrecision.F16 if a.storage == "f16" else va.VectorPrecision.BF16
+            ix.enable_half_precision(prec)
+            plain, filtered = (lambda Q, k: ix.search_batch_brute_force_half(Q, k, prec)), (lambda Q, k, f: ix.search_batch_filtered_half(Q, k, f, prec))
+        declared = a.storage in ("sq8", "binary") or mname == "euclidean"  # the mode's summation order is declared: the routes agree bit for bit
+        rng = np.random.default_rng(7)
+        for nq in [int(x) for x in a.nq.split(",")]:
+            Q = rng.standard_normal((nq, a.dim)).astype(np.float32)
+            for sel in [float(x) for x in a.selectivities.split(",")]:
+                count = max(1, int(a.rows * sel))
+                allowed = np.sort(rng.choice(a.rows, size=count, replace=False)).astype(np.uint64)
+                with ix.create_filter(allowed) as flt:
+                    row = dict(storage=a.storage, metric=mname, rows=a.rows, dim=a.dim, k=a.k, nq=nq, selectivity=sel, count=count)
+                    ref = None
+                    for name, route in (("listed", va.FILTER_ROUTE_LISTED), ("mask", va.FILTER_ROUTE_MASK), ("auto", va.FILTER_ROUTE_AUTO)):
+                        ix.set_option(va.OPT_FILTER_ROUTE, route)
+                        got = filtered(Q, a.k, flt)
+                        ran = bool(ix.last_kernels() & va.KERNEL_SWEEP_LISTED)
+                        if name == "listed":
+                            row["listed_kernel_ran"] = ran
+                        if name == "auto":
+                            row["auto_took"] = "listed" if ran else "mask"
+                        if ref is None:
+                            ref = got
+                        else:  # (a probe that times wrong answers measures nothing)
+                            assert np.array_equal(ref[0], got[0]), (mname, nq, sel, name)
+                            assert not declared or np.array_equal(ref[1].view(np.uint32), got[1].view(np.uint32)), (mname, nq, sel, name)
+
+                    def call(route):
+                        def fn():
+                            ix.set_option(va.OPT_FILTER_ROUTE, route)
+                            filtered(Q, a.k, flt)
+                        return fn
+                    res = measure_many([lambda: plain(Q, a.k), call(va.FILTER_ROUTE_LISTED), call(va.FILTER_ROUTE_MASK), call(va.FILTER_ROUTE_AUTO)])
+                    for name, (ms, sp) in zip(("unfiltered", "listed", "mask", "auto"), res):
+                        row[name + "_ms"], row[name + "_spread"] = ms, sp
+                    best = min(("listed", "mask"), key=lambda r: row[r + "_ms"])
+                    row["better"] = best
+                    row["auto_over_better"] = row["auto_ms"] / row[best + "_ms"]
+                    row["listed_over_unfiltered"] = row["listed_ms"] / row["unfiltered_ms"]
+                    rows_out.append(row)
+                    print(json.dumps(row), flush=True)
+        ix.close()
+    return rows_out
+
+
 table = []
 f1_outside = []
-if a.exact_per_query:
+if a.storage:
+    table = storage_leg()
+    a.metrics = ""
+elif a.exact_per_query:
     if a.rows == 1_000_000:
         a.rows = 100_000
     if a.densities.startswith("1,0.5"):

@@ -998,6 +998,51 @@ impl HipHnswIndex {
             .collect()
     }
 
+    /// `search_batch_brute_force_filtered` over the SQ8 codes, the sign bits or a half image of the rows
+    /// (`vdb_hip_index_search_batch_filtered_mode`): `mode` is one of `sys::VDB_SEARCH_BRUTE_SQ8`, `_BINARY`, `_BF16`, `_F16`.  The
+    /// answer is what the plain search in that mode returns on an index that holds only the filter's live rows — the reference's
+    /// `search_with_filter` works whatever the collection's storage mode.
+    #[must_use]
+    pub fn search_batch_filtered_mode(&self, queries: &[&[f32]], k: usize, filter: &HipFilter, mode: i32) -> Vec<Vec<(u64, f32)>> {
+        for q in queries {
+            self.validate_dimension(q, "Query");
+        }
+        if queries.is_empty() {
+            return Vec::new();
+        }
+        if k == 0 {
+            return vec![Vec::new(); queries.len()];
+        }
+        let nq = queries.len();
+        let mut flat = Vec::with_capacity(nq * self.dimension);
+        for q in queries {
+            flat.extend_from_slice(q);
+        }
+        let mut ids = vec![0u64; nq * k];
+        let mut scores = vec![0f32; nq * k];
+        let mut counts = vec![0u32; nq];
+        // SAFETY: buffer sizes are nq*dim / nq*k / nq as the ABI requires; the filter handle is live (owned by `filter`).
+        check(unsafe {
+            sys::vdb_hip_index_search_batch_filtered_mode(
+                self.h,
+                filter.h,
+                mode,
+                flat.as_ptr(),
+                nq as u32,
+                k as u32,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                counts.as_mut_ptr(),
+            )
+        });
+        (0..nq)
+            .map(|i| {
+                let c = counts[i] as usize;
+                (0..c).map(|j| (ids[i * k + j], scores[i * k + j])).collect()
+            })
+            .collect()
+    }
+
     /// `search_batch_brute_force_filtered` with one optional filter PER QUERY in one call (`vdb_hip_index_search_batch_filters`; the
     /// collection layer's `search_batch_with_filters`, `collection/search/batch.rs:26-115`, on the exact sweep).  `None` = no
     /// filter.  Query `i` gets bit for bit what [`Self::search_batch_brute_force_filtered`] returns for it alone with its filter

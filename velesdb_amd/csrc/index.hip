@@ -950,7 +950,7 @@ static bool sweep_mode_m(const vdb_hip_index* ix, uint32_t k) {
 }
 
 static int32_t brute_masked_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                                float* d_scores, uint32_t* d_n, hipStream_t st);
+                                float* d_scores, uint32_t* d_n, hipStream_t st, int32_t mode = VDB_SEARCH_BRUTE);
 // vdb_hip_index_search_batch_filtered: exact top-k among the rows of ix->flt that are alive now.  Two routes, same bits.
 static int32_t brute_filtered_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
                                   float* d_scores, uint32_t* d_n, hipStream_t st) {
@@ -1004,8 +1004,11 @@ static int32_t brute_filtered_dev(vdb_hip_index* ix, const float* d_q, uint64_t 
 }
 // mask substitution for ix->flt: mask = filter AND alive, n_rows bytes written per call into this context's scratch (nothing is
 // cached between calls or shared between contexts); rows past the filter's row count (inserted since) get 0
+// (mode: VDB_SEARCH_BRUTE, or one of the SQ8 / Binary / half modes — the mode's own dispatch runs under the mask)
+static int32_t brute_mode_dev(vdb_hip_index* ix, int32_t mode, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
+                              float* d_scores, uint32_t* d_n, hipStream_t st);
 static int32_t brute_masked_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                                float* d_scores, uint32_t* d_n, hipStream_t st) {
+                                float* d_scores, uint32_t* d_n, hipStream_t st, int32_t mode) {
   const RowFilter* f = ix->flt;
   const size_t mask_cap = (size_t)ix->capacity + kRowSlack;  // (what the row arrays hold: a tile kernel may look past n_rows)
   if (ix->s_flt_mask.cap < mask_cap) {
@@ -1017,35 +1020,64 @@ static int32_t brute_masked_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_
   VDB_HIP(hipGetLastError());
   // the handle's adaptive selection state (park-after-failure counters, the verdict sequence it has seen) is for its unfiltered
   // batches: a filtered call reads it and leaves it as it was (its own verdicts are not posted: select_stage.hip)
-  const uint32_t seen = ix->sel_seq_seen, h16 = ix->sel16_hold, hw = ix->wide_hold, hl2 = ix->l2_hold;
+  const uint32_t seen = ix->sel_seq_seen, h16 = ix->sel16_hold, hw = ix->wide_hold, hl2 = ix->l2_hold, hsq = ix->sq8_hold;
   ix->alive_override = ix->s_flt_mask.as<uint8_t>();
-  const int32_t rc = brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  const int32_t rc = mode == VDB_SEARCH_BRUTE ? brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st)
+                                              : brute_mode_dev(ix, mode, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
   ix->alive_override = nullptr;
   ix->sel_seq_seen = seen;
   ix->sel16_hold = h16;
   ix->wide_hold = hw;
   ix->l2_hold = hl2;
+  ix->sq8_hold = hsq;
   return rc;
+}
+
+static_assert(kFmModeBf16 == VDB_SEARCH_BRUTE_BF16 && kFmModeSq8 == VDB_SEARCH_BRUTE_SQ8 && kFmModeBinary == VDB_SEARCH_BRUTE_BINARY &&
+                  kFmModeF16 == VDB_SEARCH_BRUTE_F16 && kFmMetricEuclidean == VDB_EUCLIDEAN,
+              "vdb_filter_route.hpp restates these values");
+// vdb_hip_index_search_batch_filtered_mode: exact top-k in one of the SQ8 / Binary / half modes among the rows of ix->flt
+// that are alive now.  What the plain call in that mode refuses is refused first, in its words.  Two routes: the listed kernels (SQ8;
+// Euclidean over a half image) read only the filter's rows; mask substitution runs the mode's own dispatch, every tier of it, under the
+// call's row mask.  Same bits either way where the mode declares its summation order.
+static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k,
+                                       uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
+  const RowFilter* f = ix->flt;
+  const bool half = mode == VDB_SEARCH_BRUTE_BF16 || mode == VDB_SEARCH_BRUTE_F16, f16 = mode == VDB_SEARCH_BRUTE_F16;
+  const bool metric3 = ix->metric == VDB_COSINE || ix->metric == VDB_EUCLIDEAN || ix->metric == VDB_DOT;
+  if (mode == VDB_SEARCH_BRUTE_SQ8) {
+    if (ix->storage_mode != VDB_STORAGE_SQ8) return fail(VDB_ERR_STATE, "SQ8 search: set the storage mode to SQ8 first");
+    if (!metric3) return fail(VDB_ERR_UNSUPPORTED, "SQ8 search: Cosine, Euclidean and DotProduct only");
+  } else if (mode == VDB_SEARCH_BRUTE_BINARY) {
+    if (ix->storage_mode != VDB_STORAGE_BINARY) return fail(VDB_ERR_STATE, "Binary search: set the storage mode to Binary first");
+  } else {
+    if (f16 && !ix->f16_enabled) return fail(VDB_ERR_STATE, "f16 sweep: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
+    if (!f16 && !ix->bf16_enabled) return fail(VDB_ERR_STATE, "bf16 sweep: call vdb_hip_index_enable_bf16 first");
+    if (!metric3) return fail(VDB_ERR_UNSUPPORTED, "half-precision sweep: Cosine, DotProduct and Euclidean only");
+  }
+  if (nq == 0) return VDB_OK;
+  if (f->count == 0 || k == 0) {  // the empty filter: no row can answer
+    VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
+    return VDB_OK;
+  }
+  bool listed_ok = false;
+  if (filter_mode_has_listed(mode, ix->metric)) listed_ok = mode_listed_plan(half, ix->dim, k, f->count, nq, ix->n_cus).blocks > 0;
+  if (filter_mode_route(opt_value(ix, VDB_OPT_FILTER_ROUTE), mode, ix->metric, f->count, ix->n_rows, nq, listed_ok) == kFilterRouteListed) {
+    if (half) return brute_half_l2_listed_dev(ix, f16, f->list.as<uint32_t>(), (uint32_t)f->count, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+    ix->last_kernels |= VDB_KERNEL_SQ8;
+    return brute_sq8_listed_dev(ix, f->list.as<uint32_t>(), (uint32_t)f->count, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  }
+  return brute_masked_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st, mode);
 }
 
 static uint32_t balanced_ef(uint32_t k) { return std::max<uint32_t>(128, k * 4); }  // params.rs:313
 
-// dispatch of search_with_quality (search.rs:59-94) for device-resident queries
-int32_t search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint32_t ef,
-                   int32_t mode, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st, uint32_t cap_mult,
-                   bool* used_hnsw, uint32_t rerank_k, const uint32_t* d_extra_eps) {
-  if (used_hnsw) *used_hnsw = false;
-  ix->ev_used = 0;
-  ix->sel_ev_used = 0;
-  // diagnostics describe THIS call: brute_split_dev / the sweep paths overwrite them when they run
-  ix->last_select_level = 0;
-  ix->split_flags_n = 0;
-  ix->last_kernels = 0;
-  if (ix->n_rows == 0) {  // empty index: no entry point => empty result (native/graph.rs:252-255)
-    if (nq) VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
-    return VDB_OK;
-  }
-  if (mode == VDB_SEARCH_BRUTE) return brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+// the exact sweeps over the SQ8 codes, the sign bits and the half images (VDB_SEARCH_BRUTE_SQ8 / _BINARY / _BF16 / _F16).  A filtered call
+// (vdb_hip_index_search_batch_filtered_mode) picks its route first; on the mask-substitution route it comes back here with the call's row
+// mask in place of the soft-delete flags
+static int32_t brute_mode_dev(vdb_hip_index* ix, int32_t mode, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
+                              float* d_scores, uint32_t* d_n, hipStream_t st) {
+  if (ix->flt && !ix->alive_override) return brute_filtered_mode_dev(ix, mode, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
   if (mode == VDB_SEARCH_BRUTE_BF16) return brute_bf16_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
   if (mode == VDB_SEARCH_BRUTE_F16) return brute_bf16_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st, /*f16=*/true);
   if (mode == VDB_SEARCH_BRUTE_SQ8) {
@@ -1053,7 +1085,9 @@ int32_t search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint3
     // proof (level 3); everything else, and what a handle's data defeats, on the exact SQ8 sweep
     if (ix->storage_mode != VDB_STORAGE_SQ8) return fail(VDB_ERR_STATE, "SQ8 search: set the storage mode to SQ8 first");
     uint32_t q0 = 0;
-    while (q0 < nq && k > 0 && ix->n_rows > 0) {
+    // (a filtered call keeps the selection stage — level 3 and WIDE — only while enough rows are allowed for its seed sample, as brute_dev)
+    const bool sel_ok = !ix->flt || filter_keeps_selection(ix->flt->count, ix->n_rows);
+    while (sel_ok && q0 < nq && k > 0 && ix->n_rows > 0) {
       if (select_level_wide(ix, nq - q0, k, /*sq8=*/true)) {  // 10 < k <= 128: the WIDE selection over the dequantised image (sweep_wide.hip)
         const uint32_t nqw = select_chunk(nq - q0, kSelectMinQueriesSq8);
         const int32_t rcw = brute_wide_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nqw, k, d_ids + (size_t)q0 * k, d_scores + (size_t)q0 * k, d_n + q0, st, true);
@@ -1073,8 +1107,27 @@ int32_t search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint3
     return brute_sq8_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nq - q0, k, d_ids + (size_t)q0 * k, d_scores + (size_t)q0 * k,
                          d_n + q0, st);
   }
-  if (mode == VDB_SEARCH_BRUTE_BINARY) ix->last_kernels |= VDB_KERNEL_BITS;
-  if (mode == VDB_SEARCH_BRUTE_BINARY) return brute_binary_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  ix->last_kernels |= VDB_KERNEL_BITS;
+  return brute_binary_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+}
+// dispatch of search_with_quality (search.rs:59-94) for device-resident queries
+int32_t search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint32_t ef,
+                   int32_t mode, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st, uint32_t cap_mult,
+                   bool* used_hnsw, uint32_t rerank_k, const uint32_t* d_extra_eps) {
+  if (used_hnsw) *used_hnsw = false;
+  ix->ev_used = 0;
+  ix->sel_ev_used = 0;
+  // diagnostics describe THIS call: brute_split_dev / the sweep paths overwrite them when they run
+  ix->last_select_level = 0;
+  ix->split_flags_n = 0;
+  ix->last_kernels = 0;
+  if (ix->n_rows == 0) {  // empty index: no entry point => empty result (native/graph.rs:252-255)
+    if (nq) VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
+    return VDB_OK;
+  }
+  if (mode == VDB_SEARCH_BRUTE) return brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  if (mode == VDB_SEARCH_BRUTE_BF16 || mode == VDB_SEARCH_BRUTE_F16 || mode == VDB_SEARCH_BRUTE_SQ8 || mode == VDB_SEARCH_BRUTE_BINARY)
+    return brute_mode_dev(ix, mode, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
   if (mode == VDB_SEARCH_AUTO && ix->live <= 100 && ix->n_rows > 0)  // search.rs:75-77
     return brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
   if (mode == VDB_SEARCH_HNSW_INT8) {
@@ -1326,10 +1379,14 @@ int32_t filter_check(vdb_hip_index* ix, const RowFilter* f) {
   return VDB_OK;
 }
 int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k) {
+  return search_filtered_mode_to_device(ix, f, VDB_SEARCH_BRUTE, queries, nq, k);
+}
+// (mode: VDB_SEARCH_BRUTE, or one of VDB_SEARCH_BRUTE_SQ8 / _BINARY / _BF16 / _F16 — DESIGN 4.1o; the entry points check which)
+int32_t search_filtered_mode_to_device(vdb_hip_index* ix, const RowFilter* f, int32_t mode, const float* queries, uint32_t nq, uint32_t k) {
   const int32_t rcf = filter_check(ix, f);
   if (rcf != VDB_OK) return rcf;
   ix->flt = f;
-  const int32_t rc = search_to_device(ix, queries, nq, k, 0, VDB_SEARCH_BRUTE, 0, nullptr);
+  const int32_t rc = search_to_device(ix, queries, nq, k, 0, mode, 0, nullptr);
   ix->flt = nullptr;
   return rc;
 }

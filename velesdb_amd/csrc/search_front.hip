@@ -95,6 +95,15 @@ static int32_t search_filtered_direct(vdb_hip_index* handle, const RowFilter* f,
       [&](vdb_hip_index* ix) { deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n); });
 }
 
+// vdb_hip_index_search_batch_filtered_mode: the same in one of the SQ8 / Binary / half modes
+static int32_t search_filtered_mode_direct(vdb_hip_index* handle, const RowFilter* f, int32_t mode, const float* queries, uint32_t nq, uint32_t k,
+                                           uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  return run_search(
+      handle, nq, k, 0, mode, 0,
+      [&](vdb_hip_index* ix) { return search_filtered_mode_to_device(ix, f, mode, queries, nq, k); },
+      [&](vdb_hip_index* ix) { deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n); });
+}
+
 // vdb_hip_index_search_batch_filters: the same with one optional filter per query; query i's answer sits in row
 // row_of[i] of the context's result block
 static int32_t search_filters_exact_direct(vdb_hip_index* handle, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
@@ -324,6 +333,23 @@ int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* ix, const void* filte
   if (mode != VDB_SEARCH_BRUTE) return fail(VDB_ERR_UNSUPPORTED, "filtered search: VDB_SEARCH_BRUTE only (the graph and quantised modes keep the over-fetch rule)");
   if (nq == 0) return VDB_OK;
   return search_filtered_direct(ix, f, queries, nq, k, out_ids, out_scores, out_n);
+  });
+}
+
+// search_with_filter on a collection whose rows live as SQ8 codes, sign bits or a half image (the reference's filtered search works
+// whatever the storage mode): exact top-k in that mode among exactly the filter's rows (include/velesdb_hip.h)
+int32_t vdb_hip_index_search_batch_filtered_mode(vdb_hip_index* ix, const void* filter, int32_t mode, const float* queries, uint32_t nq,
+                                                 uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  return vdb::guarded([&]() -> int32_t {
+  const RowFilter* f = static_cast<const RowFilter*>(filter);
+  if (!ix || !f || (nq && (!queries || !out_n)) || (nq && k && (!out_ids || !out_scores))) return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filtered search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered search: not available on a member of a process group");
+  if (mode != VDB_SEARCH_BRUTE_SQ8 && mode != VDB_SEARCH_BRUTE_BINARY && mode != VDB_SEARCH_BRUTE_BF16 && mode != VDB_SEARCH_BRUTE_F16)
+    return fail(VDB_ERR_UNSUPPORTED, "filtered search by mode: VDB_SEARCH_BRUTE_SQ8 / _BINARY / _BF16 / _F16 only (VDB_SEARCH_BRUTE has "
+                                     "vdb_hip_index_search_batch_filtered, the graph modes vdb_hip_index_search_graph_filtered)");
+  if (nq == 0) return VDB_OK;
+  return search_filtered_mode_direct(ix, f, mode, queries, nq, k, out_ids, out_scores, out_n);
   });
 }
 

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "vdb_filter_route.hpp"
 #include "vdb_probe_env.hpp"
 #include "vdb_select_stage.hpp"
 #include "vdb_wide.hpp"
@@ -74,6 +75,39 @@ static int32_t brute_half_l2_dev(vdb_hip_index* ix, const uint16_t* rows16, bool
     m.k = k;
     launch_merge(false, m, tile, st);
     q0 += tile;
+  }
+  VDB_HIP(hipGetLastError());
+  return VDB_OK;
+}
+
+// The listed route of a filtered Euclidean call over a half image (vdb_hip_index_search_batch_filtered_mode):
+// sweep_topk_half_l2_listed over the filter's ascending row list, pass by pass (mode_listed_plan, vdb_filter_route.hpp), merge_topk behind
+// every pass.  The caller has checked the image, the metric, k > 0 and count > 0.
+int32_t brute_half_l2_listed_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const float* d_q, uint64_t q_stride,
+                                 uint32_t nq, uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
+  const uint16_t* rows16 = f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>();
+  ix->last_kernels |= VDB_KERNEL_SWEEP_HALF_L2 | VDB_KERNEL_SWEEP_LISTED;
+  for (uint32_t q0 = 0; q0 < nq;) {
+    const ModeListedPlan lp = mode_listed_plan(true, ix->dim, k, count, nq - q0, ix->n_cus);
+    if (lp.blocks == 0) return fail(VDB_ERR_UNSUPPORTED, "half-precision Euclidean sweep: dim / k too large for the LDS query tile");
+    if (ix->s_part_keys.reserve((size_t)lp.B * lp.blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+    EventPair* ev = next_events(ix);
+    if (ev) (void)hipEventRecord(ev->a, st);
+    const hipError_t e = launch_sweep_half_l2_listed(f16, lp.B, rows16, ix->bf16_stride, ix->any_dead ? ix->alive.as<uint8_t>() : nullptr, list, count,
+                                                     lp.per_block, d_q + (size_t)q0 * q_stride, q_stride, ix->s_part_keys.as<uint64_t>(),
+                                                     (uint32_t)ix->n_rows, ix->dim, lp.nq_pass, k, lp.blocks, st);
+    if (ev) (void)hipEventRecord(ev->b, st);
+    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("listed half-precision Euclidean sweep launch: ") + hipGetErrorString(e));
+    MergeArgs m{};
+    m.part_keys = ix->s_part_keys.as<uint64_t>();
+    m.ext_ids = ix->ext_ids.as<uint64_t>();
+    m.out_ids = d_ids + (size_t)q0 * k;
+    m.out_scores = d_scores + (size_t)q0 * k;
+    m.out_n = d_n + q0;
+    m.n_lists = (uint32_t)lp.blocks;
+    m.k = k;
+    launch_merge(false, m, lp.nq_pass, st);
+    q0 += lp.nq_pass;
   }
   VDB_HIP(hipGetLastError());
   return VDB_OK;

@@ -23,6 +23,7 @@
 #include <memory>
 
 #include "vdb_device.hpp"
+#include "vdb_filter_route.hpp"
 #include "vdb_index.hpp"
 #include "vdb_kernels.hpp"
 
@@ -229,297 +230,39 @@ __device__ __forceinline__ void sq8_word_pair(float (&acc)[B], const uint32_t (&
   if constexpr (WI + 2 < 16) sq8_lds_wait(q0);
 }
 
+// The body (sq8_sweep_body.inc) is shared by the sweep over all rows and the LISTED one (filtered search over the codes):
+// there lane l of group g owns row list[g * 64 + l] — the staging loads gather their 16-byte pieces by that row, vmin / vmax / nsq are
+// read through the list, positions past `count` are clamped to count - 1 and masked, the key carries the real row — and block b takes
+// the groups [b * per_block, (b + 1) * per_block) of the list.  Every (row, query) chain is one lane's sequential chain over the row's
+// own codes: the bits do not depend on where the row sits or which rows share its group.
+// (Shared as TEXT, not as an inlined __device__ function: behind a function call — even an always-inlined one with nothing else
+// changed — the Euclidean instances of sweep_topk_sq8 came out with other registers, 150 -> 138 and 211 -> 213 VGPRs; included into the
+// kernel itself, every instance of sweep_topk_sq8 keeps the instructions it had.)
 template <int METRIC, int B>
 __global__ __launch_bounds__(256) void sweep_topk_sq8(Sq8Args a) {
-  constexpr bool HIB = METRIC != kEuclidean;  // cosine / dot similarity: larger is better; squared L2: smaller
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = (int)threadIdx.x, lane = tid & 63;
-  const int wib = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t k = a.k, dim = a.dim;
-  const uint32_t dpad = (dim + 3u) & ~3u;
-  // LDS: queries [dpad][B] f32 | per-wave tiles [4][64][80] | lists [B][k] | cnt[B] | lock[B] | qsum[B] | qnsq[B]
-  float* qs = reinterpret_cast<float*>(smem);
-  unsigned char* tiles = smem + (size_t)dpad * B * 4;
-  unsigned char* tile = tiles + (size_t)wib * 64 * kSq8TileStride;
-  unsigned char* tail = tiles + (size_t)4 * 64 * kSq8TileStride;
-  lds_vu64* lists = (lds_vu64*)(lds_void_p)(tail);
-  lds_vu32* cnts = (lds_vu32*)(lds_void_p)(tail + (size_t)B * k * 8);
-  uint32_t* locks = reinterpret_cast<uint32_t*>(tail + (size_t)B * k * 8 + B * 4);
-  float* qsum = reinterpret_cast<float*>(tail + (size_t)B * k * 8 + B * 8);
-  float* qnsq = reinterpret_cast<float*>(tail + (size_t)B * k * 8 + B * 12);
-
-  uint32_t nq_here = a.nq, slot0 = 0;
-  if (a.qmap) {
-    const uint32_t listed = *a.qcount;
-    slot0 = blockIdx.y * (uint32_t)B;
-    if (slot0 >= listed) return;  // (uniform per block)
-    nq_here = min((uint32_t)B, listed - slot0);
-  }
-  for (uint32_t i = tid; i < dpad * B; i += 256) {
-    const uint32_t d = i / B, b = i % B;
-    const uint32_t qrow = (a.qmap && b < nq_here) ? a.qmap[slot0 + b] : b;
-    qs[i] = (d < dim && b < nq_here) ? a.queries[(size_t)qrow * a.q_stride + d] : 0.0f;
-  }
-  if (tid < B) {
-    cnts[tid] = 0;
-    locks[tid] = 0;
-  }
-  __syncthreads();
-  if (tid < B) {  // per query: sum(q) (constant-vector branch, :332-334) and sum(q*q) (:528), left to right
-    float s = 0.0f, n2 = 0.0f;
-    for (uint32_t d = 0; d < dim; d++) {
-      const float x = qs[d * B + tid];
-      s = __fadd_rn(s, x);
-      n2 = __fadd_rn(n2, __fmul_rn(x, x));
-    }
-    qsum[tid] = s;
-    qnsq[tid] = n2;
-  }
-  __syncthreads();
-
-  const uint32_t ngroups = (a.n_rows + 63) / 64;
-  for (uint32_t g = blockIdx.x * 4 + wib; g < ngroups; g += gridDim.x * 4) {
-    const uint32_t row = g * 64 + lane;
-    const bool valid = row < a.n_rows;
-    const uint32_t rowc = valid ? row : a.n_rows - 1;
-    const float mn = a.vmin[rowc];
-    const float range = __fsub_rn(a.vmax[rowc], mn);
-    const bool flat = range < kF32Eps;
-    const float scale = __fdiv_rn(range, 255.0f);
-    float acc[B];
-#pragma unroll
-    for (int b = 0; b < B; b++) acc[b] = 0.0f;
-    // query elements: LDS, dimension-major [dim][B] — one broadcast ds_read_b128 brings element i of all 4 queries as two
-    // adjacent pairs, the operands of the packed multiplies below
-    // staging loads run one 64-byte column chunk ahead of the arithmetic (registers), so their latency hides
-    // behind the previous chunk's ~700 VALU instructions
-    // (the loads are RAW — clamped address, always in bounds — and the rows / columns past the end are zeroed where the staged value
-    // is USED, one chunk later: with the select beside the load, as rounds 1-4 had it, the compiler waited for the four loads
-    // (vmcnt) right where it had issued them, and every chunk paid the codes' trip from HBM in full — half of every wave's time,
-    // profiles/r05k_*: SQ_WAIT_ANY 0.51)
-    uint4 stg[4];
-    auto stage_load = [&](uint32_t c0) __attribute__((always_inline)) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint32_t rr = g * 64 + 16 * j + (lane >> 2);
-        const uint32_t off = c0 + (lane & 3) * 16;
-        const uint32_t rc = rr < a.n_rows ? rr : a.n_rows - 1;
-        const uint32_t oc = off < a.code_stride ? off : 0u;
-        stg[j] = *reinterpret_cast<const uint4*>(a.codes + (size_t)rc * a.code_stride + oc);
-      }
-    };
-    stage_load(0);
-    for (uint32_t c0 = 0; c0 < dim; c0 += 64) {
-      // stage 64 rows x 64 B: lane l moves 16 B of row 16 j + l/4, part l%4
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const bool ok = g * 64 + 16 * j + (lane >> 2) < a.n_rows && c0 + (lane & 3) * 16 < a.code_stride;
-        *reinterpret_cast<uint4*>(tile + (16 * j + (lane >> 2)) * kSq8TileStride + (lane & 3) * 16) =
-            make_uint4(ok ? stg[j].x : 0u, ok ? stg[j].y : 0u, ok ? stg[j].z : 0u, ok ? stg[j].w : 0u);
-      }
-      if (c0 + 64 < dim) stage_load(c0 + 64);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      uint4 w4[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) w4[j] = *reinterpret_cast<const uint4*>(tile + lane * kSq8TileStride + j * 16);
-      __builtin_amdgcn_wave_barrier();  // tile reads done before the next chunk overwrites it
-      const uint32_t wds[16] = {w4[0].x, w4[0].y, w4[0].z, w4[0].w, w4[1].x, w4[1].y, w4[1].z, w4[1].w,
-                                w4[2].x, w4[2].y, w4[2].z, w4[2].w, w4[3].x, w4[3].y, w4[3].z, w4[3].w};
-      if ((B == 4 || B == 8) && c0 + 64 <= dim) {  // full chunk, 4 or 8 queries: grouped query reads, one word ahead
-        if constexpr (B == 4 || B == 8) {
-          const uint32_t qaddr = (uint32_t)(size_t)(lds_void_p)smem + c0 * (uint32_t)B * 4u;  // (qs starts the dynamic LDS; uniform)
-          sq8_f32x4 qa[4][B / 4], qb[4][B / 4];
-          sq8_read_word<B, 0>(qa, qaddr);
-          sq8_lds_wait(qa);
-          sq8_word_pair<METRIC, B, 0>(acc, wds, scale, mn, qaddr, qa, qb);
-          sq8_word_pair<METRIC, B, 2>(acc, wds, scale, mn, qaddr, qa, qb);
-          sq8_word_pair<METRIC, B, 4>(acc, wds, scale, mn, qaddr, qa, qb);
-          sq8_word_pair<METRIC, B, 6>(acc, wds, scale, mn, qaddr, qa, qb);
-          sq8_word_pair<METRIC, B, 8>(acc, wds, scale, mn, qaddr, qa, qb);
-          sq8_word_pair<METRIC, B, 10>(acc, wds, scale, mn, qaddr, qa, qb);
-          sq8_word_pair<METRIC, B, 12>(acc, wds, scale, mn, qaddr, qa, qb);
-          sq8_word_pair<METRIC, B, 14>(acc, wds, scale, mn, qaddr, qa, qb);
-        }
-      } else if (c0 + 64 <= dim) {  // full chunk: no bounds tests => ONE basic block, the scheduler overlaps the LDS reads of
-                             // later groups with the arithmetic of earlier ones (per-group branches pinned them)
-  #pragma unroll
-        for (int wi = 0; wi < 16; wi++) {
-          const uint32_t i0 = c0 + wi * 4;
-          const uint32_t w = wds[wi];
-          float dq[4];
-  #pragma unroll
-          for (int e = 0; e < 4; e++) dq[e] = __fadd_rn(__fmul_rn((float)((w >> (8 * e)) & 0xFFu), scale), mn);
-          // Two queries per instruction where B is even (v_pk_mul_f32 / v_pk_add_f32: each half is the same IEEE
-          // operation as the scalar form, so the bits do not change; a plain f32 VALU op runs at half the packed rate).
-          constexpr int P = B / 2;  // query pairs
-          if (METRIC == kEuclidean) {
-            if (true) {  // a full group of four: sum += ((f0^2 + f1^2) + f2^2) + f3^2 (:495-507)
-  #pragma unroll
-              for (int p = 0; p < P; p++) {
-                f32x2 t = {0.f, 0.f};
-  #pragma unroll
-                for (int e = 0; e < 4; e++) {
-                  const f32x2 f = f32x2{qs[(size_t)(i0 + e) * B + (2 * p)], qs[(size_t)(i0 + e) * B + (2 * p + 1)]} - f32x2{dq[e], dq[e]};
-                  t = e == 0 ? f * f : t + f * f;
-                }
-                acc[2 * p] = __fadd_rn(acc[2 * p], t.x);
-                acc[2 * p + 1] = __fadd_rn(acc[2 * p + 1], t.y);
-              }
-              if (B & 1) {
-                const int b = B - 1;
-                const float f0 = __fsub_rn(qs[(size_t)(i0 + 0) * B + (b)], dq[0]), f1 = __fsub_rn(qs[(size_t)(i0 + 1) * B + (b)], dq[1]);
-                const float f2 = __fsub_rn(qs[(size_t)(i0 + 2) * B + (b)], dq[2]), f3 = __fsub_rn(qs[(size_t)(i0 + 3) * B + (b)], dq[3]);
-                const float t = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(f0, f0), __fmul_rn(f1, f1)), __fmul_rn(f2, f2)),
-                                          __fmul_rn(f3, f3));
-                acc[b] = __fadd_rn(acc[b], t);
-              }
-            } else {  // remainder: one element at a time (:510-515)
-  #pragma unroll
-              for (int e = 0; e < 4; e++) {
-                if (true) {
-  #pragma unroll
-                  for (int b = 0; b < B; b++) {
-                    const float f = __fsub_rn(qs[(size_t)(i0 + e) * B + (b)], dq[e]);
-                    acc[b] = __fadd_rn(acc[b], __fmul_rn(f, f));
-                  }
-                }
-              }
-            }
-          } else {  // dot chain (:452-466), also the numerator of the cosine
-  #pragma unroll
-            for (int e = 0; e < 4; e++) {
-              if (true) {
-  #pragma unroll
-                for (int p = 0; p < P; p++) {
-                  const f32x2 r = f32x2{acc[2 * p], acc[2 * p + 1]} +
-                                  f32x2{qs[(size_t)(i0 + e) * B + (2 * p)], qs[(size_t)(i0 + e) * B + (2 * p + 1)]} * f32x2{dq[e], dq[e]};
-                  acc[2 * p] = r.x;
-                  acc[2 * p + 1] = r.y;
-                }
-                if (B & 1) acc[B - 1] = __fadd_rn(acc[B - 1], __fmul_rn(qs[(size_t)(i0 + e) * B + (B - 1)], dq[e]));
-              }
-            }
-          }
-        }
-      } else {
-  #pragma unroll
-        for (int wi = 0; wi < 16; wi++) {
-          const uint32_t i0 = c0 + wi * 4;
-          if (i0 >= dim) break;  // uniform
-          const uint32_t w = wds[wi];
-          float dq[4];
-  #pragma unroll
-          for (int e = 0; e < 4; e++) dq[e] = __fadd_rn(__fmul_rn((float)((w >> (8 * e)) & 0xFFu), scale), mn);
-          // Two queries per instruction where B is even (v_pk_mul_f32 / v_pk_add_f32: each half is the same IEEE
-          // operation as the scalar form, so the bits do not change; a plain f32 VALU op runs at half the packed rate).
-          constexpr int P = B / 2;  // query pairs
-          if (METRIC == kEuclidean) {
-            if (i0 + 3 < dim) {  // a full group of four: sum += ((f0^2 + f1^2) + f2^2) + f3^2 (:495-507)
-  #pragma unroll
-              for (int p = 0; p < P; p++) {
-                f32x2 t = {0.f, 0.f};
-  #pragma unroll
-                for (int e = 0; e < 4; e++) {
-                  const f32x2 f = f32x2{qs[(size_t)(i0 + e) * B + (2 * p)], qs[(size_t)(i0 + e) * B + (2 * p + 1)]} - f32x2{dq[e], dq[e]};
-                  t = e == 0 ? f * f : t + f * f;
-                }
-                acc[2 * p] = __fadd_rn(acc[2 * p], t.x);
-                acc[2 * p + 1] = __fadd_rn(acc[2 * p + 1], t.y);
-              }
-              if (B & 1) {
-                const int b = B - 1;
-                const float f0 = __fsub_rn(qs[(size_t)(i0 + 0) * B + (b)], dq[0]), f1 = __fsub_rn(qs[(size_t)(i0 + 1) * B + (b)], dq[1]);
-                const float f2 = __fsub_rn(qs[(size_t)(i0 + 2) * B + (b)], dq[2]), f3 = __fsub_rn(qs[(size_t)(i0 + 3) * B + (b)], dq[3]);
-                const float t = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(f0, f0), __fmul_rn(f1, f1)), __fmul_rn(f2, f2)),
-                                          __fmul_rn(f3, f3));
-                acc[b] = __fadd_rn(acc[b], t);
-              }
-            } else {  // remainder: one element at a time (:510-515)
-  #pragma unroll
-              for (int e = 0; e < 4; e++) {
-                if (i0 + e < dim) {
-  #pragma unroll
-                  for (int b = 0; b < B; b++) {
-                    const float f = __fsub_rn(qs[(size_t)(i0 + e) * B + (b)], dq[e]);
-                    acc[b] = __fadd_rn(acc[b], __fmul_rn(f, f));
-                  }
-                }
-              }
-            }
-          } else {  // dot chain (:452-466), also the numerator of the cosine
-  #pragma unroll
-            for (int e = 0; e < 4; e++) {
-              if (i0 + e < dim) {
-  #pragma unroll
-                for (int p = 0; p < P; p++) {
-                  const f32x2 r = f32x2{acc[2 * p], acc[2 * p + 1]} +
-                                  f32x2{qs[(size_t)(i0 + e) * B + (2 * p)], qs[(size_t)(i0 + e) * B + (2 * p + 1)]} * f32x2{dq[e], dq[e]};
-                  acc[2 * p] = r.x;
-                  acc[2 * p + 1] = r.y;
-                }
-                if (B & 1) acc[B - 1] = __fadd_rn(acc[B - 1], __fmul_rn(qs[(size_t)(i0 + e) * B + (B - 1)], dq[e]));
-              }
-            }
-          }
-        }
-      }
-    }
-    // constant-vector rows (range < EPSILON) take the reference's other branch; rare, so a divergent redo
-    if (__ballot(valid && flat)) {
-      if (valid && flat) {
-#pragma unroll
-        for (int b = 0; b < B; b++) {
-          if (METRIC == kEuclidean) {  // sum((q - value)^2), left to right (:357-361)
-            float s = 0.0f;
-            for (uint32_t d = 0; d < dim; d++) {
-              const float f = __fsub_rn(qs[d * B + b], mn);
-              s = __fadd_rn(s, __fmul_rn(f, f));
-            }
-            acc[b] = s;
-          } else {
-            acc[b] = __fmul_rn(qsum[b], mn);  // sum(q) * value (:330-334)
-          }
-        }
-      }
-    }
-    const float vn2 = (METRIC == kCosine) ? a.nsq[rowc] : 0.0f;
-    uint64_t taus[B];  // the lists' bounds, read together (vdb_device.hpp list_tau_relaxed)
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int b = 0; b < B; b++) taus[b] = list_tau_relaxed(lists, cnts, (uint32_t)b, k);
-#pragma unroll
-    for (int b = 0; b < B; b++) {
-      float score = acc[b];
-      if (METRIC == kCosine) {  // :548-553
-        const float denom = sqrtf(__fmul_rn(qnsq[b], vn2));
-        score = denom < kF32Eps ? 0.0f : __fdiv_rn(acc[b], denom);
-      }
-      const bool ok = valid && (uint32_t)b < nq_here;
-      const uint64_t key = ok ? make_key<HIB>(score, row) : kKeyInvalid;
-      uint64_t mask = __ballot(key < taus[b]);
-      while (mask) {
-        const int src = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        const uint64_t kk = readlane64(key, src);
-        if (a.alive && a.alive[key_row(kk)] == 0) continue;
-        shared_list_offer(lists + (size_t)b * k, cnts + b, locks + b, k, kk, lane);
-      }
-    }
-  }
-  __syncthreads();
-  for (uint32_t b = wib; b < nq_here && b < (uint32_t)B; b += 4) {
-    const uint32_t c = cnts[b];
-    uint64_t* out = a.part_keys + ((size_t)(slot0 + b) * gridDim.x + blockIdx.x) * k;
-    for (uint32_t e = lane; e < k; e += 64) out[e] = e < c ? lists[(size_t)b * k + e] : kKeyInvalid;
-  }
+  constexpr bool LISTED = false;
+  const uint32_t* const list = nullptr;
+  const uint32_t count = 0u, per_block = 0u;
+#include "sq8_sweep_body.inc"
+}
+// the sweep over a filter's ascending row list; a.n_rows / qmap / qcount are not read
+struct Sq8ListedArgs {
+  Sq8Args a;
+  const uint32_t* list;   // [count] ascending internal rows (device memory)
+  uint32_t count;
+  uint32_t per_block;     // 64-row groups of the list per block
+};
+template <int METRIC, int B>
+__global__ __launch_bounds__(256) void sweep_topk_sq8_listed(Sq8ListedArgs la) {
+  constexpr bool LISTED = true;
+  const Sq8Args& a = la.a;
+  const uint32_t* const list = la.list;
+  const uint32_t count = la.count, per_block = la.per_block;
+#include "sq8_sweep_body.inc"
 }
 
-static size_t sq8_lds_bytes(int B, uint32_t k, uint32_t dim) {
-  const size_t dpad = (dim + 3u) & ~3u;
-  return (dpad * B * 4 + (size_t)4 * 64 * kSq8TileStride + (size_t)B * k * 8 + (size_t)B * 16 + 15) & ~(size_t)15;
-}
+static_assert(kSq8TileStride == 80, "fm_sq8_lds_bytes (vdb_filter_route.hpp) states the staging tile's stride");
+static size_t sq8_lds_bytes(int B, uint32_t k, uint32_t dim) { return (size_t)fm_sq8_lds_bytes(B, k, dim); }
 
 template <int METRIC, int B>
 static hipError_t launch_sq8_t(const Sq8Args& a, int blocks, size_t lds, hipStream_t st, int groups = 1) {
@@ -538,6 +281,25 @@ static hipError_t launch_sq8_m(int metric, const Sq8Args& a, int blocks, size_t 
   if (metric == kCosine) return launch_sq8_t<kCosine, B>(a, blocks, lds, st, groups);
   if (metric == kEuclidean) return launch_sq8_t<kEuclidean, B>(a, blocks, lds, st, groups);
   return launch_sq8_t<kDot, B>(a, blocks, lds, st, groups);
+}
+
+template <int METRIC, int B>
+static hipError_t launch_sq8_listed_t(const Sq8ListedArgs& la, int blocks, size_t lds, hipStream_t st) {
+  static bool done = false;
+  if (lds > 64 * 1024 && !done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_sq8_listed<METRIC, B>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    done = true;
+  }
+  hipLaunchKernelGGL((sweep_topk_sq8_listed<METRIC, B>), dim3(blocks), dim3(256), lds, st, la);
+  return hipGetLastError();
+}
+template <int B>
+static hipError_t launch_sq8_listed_m(int metric, const Sq8ListedArgs& la, int blocks, size_t lds, hipStream_t st) {
+  if (metric == kCosine) return launch_sq8_listed_t<kCosine, B>(la, blocks, lds, st);
+  if (metric == kEuclidean) return launch_sq8_listed_t<kEuclidean, B>(la, blocks, lds, st);
+  return launch_sq8_listed_t<kDot, B>(la, blocks, lds, st);
 }
 
 // ---- selection stage over the SQ8 storage mode (select_stage.hip brute_split_dev, level 3) -------------------------------------
@@ -693,7 +455,7 @@ int32_t sq8_fallback_flagged(vdb_hip_index* ix, const float* d_q, uint64_t q_str
                              const SelectFinishArgs& fin_in, hipStream_t st) {
   SelectFinishArgs fin = fin_in;
   const uint32_t* qcount = fin.qcount;
-  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  const uint8_t* alive = search_alive(ix);  // (a filtered call's row mask: the exact pass must not let disallowed rows back in)
   int B = 8;
   if (sq8_lds_bytes(8, k, ix->dim) > 160 * 1024) B = 4;
   if (B == 4 && sq8_lds_bytes(4, k, ix->dim) > 160 * 1024) B = 1;
@@ -761,7 +523,7 @@ int32_t brute_sq8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, ui
     VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
     return VDB_OK;
   }
-  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  const uint8_t* alive = search_alive(ix);
   for (uint32_t q0 = 0; q0 < nq;) {
     int B = nq - q0 >= 8 ? 8 : (nq - q0 >= 4 ? 4 : 1);
     if (B == 8 && sq8_lds_bytes(8, k, ix->dim) > 160 * 1024) B = 4;
@@ -805,6 +567,55 @@ int32_t brute_sq8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, ui
     m.k = k;
     launch_merge(ix->metric != VDB_EUCLIDEAN, m, tile, st);
     q0 += tile;
+  }
+  VDB_HIP(hipGetLastError());
+  return VDB_OK;
+}
+
+// The listed route of a filtered SQ8 call (vdb_hip_index_search_batch_filtered_mode): sweep_topk_sq8_listed over the
+// filter's ascending row list, pass by pass (mode_listed_plan, vdb_filter_route.hpp), merge_topk behind every pass.  The caller has
+// checked the storage mode, the metric, k > 0 and count > 0, and that the plan of the first pass fits.
+int32_t brute_sq8_listed_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const float* d_q, uint64_t q_stride, uint32_t nq,
+                             uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
+  for (uint32_t q0 = 0; q0 < nq;) {
+    const ModeListedPlan lp = mode_listed_plan(false, ix->dim, k, count, nq - q0, ix->n_cus);
+    if (lp.blocks == 0) return fail(VDB_ERR_UNSUPPORTED, "SQ8 search: dim / k too large for the LDS query tile");
+    if (ix->s_part_keys.reserve((size_t)lp.B * lp.blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+    Sq8ListedArgs la{};
+    la.a.codes = ix->sq8_codes.as<uint8_t>();
+    la.a.vmin = ix->sq8_min.as<float>();
+    la.a.vmax = ix->sq8_max.as<float>();
+    la.a.nsq = ix->sq8_nsq.as<float>();
+    la.a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;  // rows removed since the filter was made
+    la.a.queries = d_q + (size_t)q0 * q_stride;
+    la.a.part_keys = ix->s_part_keys.as<uint64_t>();
+    la.a.code_stride = ix->sq8_stride;
+    la.a.q_stride = q_stride;
+    la.a.n_rows = (uint32_t)ix->n_rows;
+    la.a.dim = ix->dim;
+    la.a.nq = lp.nq_pass;
+    la.a.k = k;
+    la.list = list;
+    la.count = count;
+    la.per_block = lp.per_block;
+    ix->last_kernels |= VDB_KERNEL_SWEEP_LISTED;
+    EventPair* ev = next_events(ix);
+    if (ev) (void)hipEventRecord(ev->a, st);
+    const hipError_t e = lp.B == 8 ? launch_sq8_listed_m<8>(ix->metric, la, lp.blocks, (size_t)lp.lds, st)
+                                   : (lp.B == 4 ? launch_sq8_listed_m<4>(ix->metric, la, lp.blocks, (size_t)lp.lds, st)
+                                                : launch_sq8_listed_m<1>(ix->metric, la, lp.blocks, (size_t)lp.lds, st));
+    if (ev) (void)hipEventRecord(ev->b, st);
+    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("listed SQ8 sweep launch: ") + hipGetErrorString(e));
+    MergeArgs m{};
+    m.part_keys = la.a.part_keys;
+    m.ext_ids = ix->ext_ids.as<uint64_t>();
+    m.out_ids = d_ids + (size_t)q0 * k;
+    m.out_scores = d_scores + (size_t)q0 * k;
+    m.out_n = d_n + q0;
+    m.n_lists = (uint32_t)lp.blocks;
+    m.k = k;
+    launch_merge(ix->metric != VDB_EUCLIDEAN, m, lp.nq_pass, st);
+    q0 += lp.nq_pass;
   }
   VDB_HIP(hipGetLastError());
   return VDB_OK;
@@ -858,7 +669,7 @@ int32_t brute_binary_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride,
     fa.bits = ix->sign_bits.as<uint32_t>();
     fa.q = d_q;
     fa.q_stride = q_stride;
-    fa.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+    fa.alive = search_alive(ix);
     fa.part_keys = ix->s_part_keys.as<uint64_t>();
     fa.tickets = ix->s_tickets.as<uint32_t>();
     fa.n_rows = (uint32_t)ix->n_rows;
@@ -908,7 +719,7 @@ int32_t brute_binary_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride,
   BitsArgs ba{};
   ba.bits = ix->sign_bits.as<uint32_t>();
   ba.qbits = qbits_rest;
-  ba.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  ba.alive = search_alive(ix);
   ba.part_keys = ix->s_part_keys.as<uint64_t>();
   ba.part_cnt = ix->s_part_cnt.as<uint32_t>();
   ba.n_rows = (uint32_t)ix->n_rows;

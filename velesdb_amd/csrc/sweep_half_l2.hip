@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "vdb_device.hpp"
+#include "vdb_filter_route.hpp"
 #include "vdb_kernels.hpp"
 
 namespace vdb {
@@ -58,8 +59,12 @@ __device__ __forceinline__ void unpack2(uint32_t w, float& lo, float& hi) {
   }
 }
 
-template <bool F16, int B>
-__global__ __launch_bounds__(256, 3) void sweep_topk_half_l2(HalfL2Args a) {
+// The body is shared by the sweep over all rows and the LISTED one (filtered search over a half image): there position p of
+// the filter's ascending row list stands where row p stood — the row pointer comes through the list, positions past `count` re-read the
+// list's last row and are masked, the key carries the real row — and block b takes the groups [b * per_block, (b + 1) * per_block) of
+// the list.  The declared summation order above is per (row, query): the same bits wherever the row sits.
+template <bool F16, int B, bool LISTED>
+__device__ __forceinline__ void half_l2_sweep_body(const HalfL2Args& a, const uint32_t* __restrict__ list, uint32_t count, uint32_t per_block) {
   constexpr int RPG = 64 / B;                // rows per group: 64 (row, query) pairs per lane
   constexpr int RB = RPG < 4 ? RPG : (B == 1 ? 8 : 4);  // rows in flight together
   constexpr bool HIB = false;                // a distance: smaller is better
@@ -86,8 +91,10 @@ __global__ __launch_bounds__(256, 3) void sweep_topk_half_l2(HalfL2Args a) {
   }
   __syncthreads();
 
-  const uint32_t ngroups = (a.n_rows + RPG - 1) / RPG;
-  for (uint32_t g = wave; g < ngroups; g += nwaves) {
+  const uint32_t n_here = LISTED ? count : a.n_rows;  // rows of the sweep: positions of the list, or rows of the index
+  const uint32_t ngroups = (n_here + RPG - 1) / RPG;
+  const uint32_t g_end = LISTED ? min(ngroups, (blockIdx.x + 1) * per_block) : ngroups;  // listed: the block's chunk of the list
+  for (uint32_t g = LISTED ? blockIdx.x * per_block + (uint32_t)wib : wave; g < g_end; g += LISTED ? 4u : nwaves) {
     float acc[64];
 #pragma unroll
     for (int i = 0; i < 64; i++) acc[i] = 0.0f;
@@ -98,7 +105,8 @@ __global__ __launch_bounds__(256, 3) void sweep_topk_half_l2(HalfL2Args a) {
 #pragma unroll
       for (int rr = 0; rr < RB; rr++) {
         uint32_t row = row0 + r0 + rr;
-        row = row < a.n_rows ? row : a.n_rows - 1;  // tail rows: re-read the last row, masked later
+        row = row < n_here ? row : n_here - 1;  // tail rows: re-read the last row, masked later
+        if constexpr (LISTED) row = list[row];
         rp[rr] = a.rows + (size_t)row * a.row_stride;
       }
       for (uint32_t c = lane; c < d8; c += 64) {
@@ -128,8 +136,9 @@ __global__ __launch_bounds__(256, 3) void sweep_topk_half_l2(HalfL2Args a) {
     treduce64(acc, lane);
     // lane l now owns pair idx = l: row r = l / B, query b = l % B
     const int b = lane % B;
-    const uint32_t row = row0 + lane / B;
-    const bool valid = row < a.n_rows && b < (int)a.nq;
+    const uint32_t pos = row0 + lane / B;
+    const bool valid = pos < n_here && b < (int)a.nq;
+    const uint32_t row = LISTED ? (valid ? list[pos] : 0u) : pos;
     const float score = finish_score<kEuclidean>(acc[0], 0.0f, 0.0f);
     const uint64_t key = valid ? make_key<HIB>(score, row) : kKeyInvalid;
     const uint32_t c_b = cnts[b];
@@ -151,11 +160,23 @@ __global__ __launch_bounds__(256, 3) void sweep_topk_half_l2(HalfL2Args a) {
     for (uint32_t e = lane; e < k; e += 64) out[e] = e < c ? lists[(size_t)b * k + e] : kKeyInvalid;
   }
 }
-
-size_t sweep_half_l2_lds_bytes(int B, uint32_t k, uint32_t dim) {
-  const size_t stride = ((size_t)dim + 7) / 8 * 8;
-  return (((size_t)B * stride * 4 + (size_t)B * k * 8 + (size_t)B * 8) + 15) & ~(size_t)15;
+template <bool F16, int B>
+__global__ __launch_bounds__(256, 3) void sweep_topk_half_l2(HalfL2Args a) {
+  half_l2_sweep_body<F16, B, false>(a, nullptr, 0u, 0u);
 }
+// the sweep over a filter's ascending row list; a.n_rows is not read
+struct HalfL2ListedArgs {
+  HalfL2Args a;
+  const uint32_t* list;   // [count] ascending internal rows (device memory)
+  uint32_t count;
+  uint32_t per_block;     // row groups (64 / B rows) of the list per block
+};
+template <bool F16, int B>
+__global__ __launch_bounds__(256, 3) void sweep_topk_half_l2_listed(HalfL2ListedArgs la) {
+  half_l2_sweep_body<F16, B, true>(la.a, la.list, la.count, la.per_block);
+}
+
+size_t sweep_half_l2_lds_bytes(int B, uint32_t k, uint32_t dim) { return (size_t)fm_half_l2_lds_bytes(B, k, dim); }
 
 template <bool F16, int B>
 static hipError_t launch_half_l2_t(const HalfL2Args& a, int blocks, size_t lds, hipStream_t st) {
@@ -186,6 +207,39 @@ hipError_t launch_sweep_half_l2(bool f16, int B, const uint16_t* rows, uint64_t 
   HalfL2Args a{rows, alive, queries, part_keys, row_stride, q_stride, n_rows, dim, nq, k};
   const size_t lds = sweep_half_l2_lds_bytes(B, k, dim);
   return f16 ? launch_half_l2_b<true>(B, a, blocks, lds, st) : launch_half_l2_b<false>(B, a, blocks, lds, st);
+}
+
+template <bool F16, int B>
+static hipError_t launch_half_l2_listed_t(const HalfL2ListedArgs& la, int blocks, size_t lds, hipStream_t st) {
+  static bool done = false;
+  if (lds > 64 * 1024 && !done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_half_l2_listed<F16, B>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    done = true;
+  }
+  hipLaunchKernelGGL((sweep_topk_half_l2_listed<F16, B>), dim3(blocks), dim3(256), lds, st, la);
+  return hipGetLastError();
+}
+template <bool F16>
+static hipError_t launch_half_l2_listed_b(int B, const HalfL2ListedArgs& la, int blocks, size_t lds, hipStream_t st) {
+  switch (B) {
+    case 16: return launch_half_l2_listed_t<F16, 16>(la, blocks, lds, st);
+    case 4: return launch_half_l2_listed_t<F16, 4>(la, blocks, lds, st);
+    case 1: return launch_half_l2_listed_t<F16, 1>(la, blocks, lds, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+// the same over `count` listed rows (ascending internal rows, device memory): blocks x per_block row groups cover the list
+// (mode_listed_plan, vdb_filter_route.hpp); part_keys: [nq][blocks][k]
+hipError_t launch_sweep_half_l2_listed(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const uint32_t* list,
+                                       uint32_t count, uint32_t per_block, const float* queries, uint64_t q_stride, uint64_t* part_keys,
+                                       uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks, hipStream_t st) {
+  if (row_stride % 8 != 0 || row_stride < dim || nq > (uint32_t)B || count == 0 || per_block == 0 || !list) return hipErrorInvalidValue;
+  if ((uint64_t)blocks * per_block * (64u / (uint32_t)B) < count) return hipErrorInvalidValue;  // (the chunks must cover the list)
+  HalfL2ListedArgs la{{rows, alive, queries, part_keys, row_stride, q_stride, n_rows, dim, nq, k}, list, count, per_block};
+  const size_t lds = sweep_half_l2_lds_bytes(B, k, dim);
+  return f16 ? launch_half_l2_listed_b<true>(B, la, blocks, lds, st) : launch_half_l2_listed_b<false>(B, la, blocks, lds, st);
 }
 
 }  // namespace vdb

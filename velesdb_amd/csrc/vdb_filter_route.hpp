@@ -2,9 +2,11 @@
 // filtered graph call takes (vdb_hip_index_search_graph_filtered), and which queries of a call with one filter per
 // query share a launch (vdb_hip_index_search_graph_filters) — the one-filter call is planned here too: it is a call
 // of the second kind with every query on the same filter — and how an EXACT call with one filter per query groups its queries and
-// cuts its listed groups into the work items of the grouped launches (vdb_hip_index_search_batch_filters).
-// Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_graph_route_model.cpp,
-// tests/filters_plan_model.cpp and tests/listed_groups_plan_model.cpp compile it alone and walk its boundaries.
+// cuts its listed groups into the work items of the grouped launches (vdb_hip_index_search_batch_filters), and the route
+// and the listed passes of a filtered exact call over the SQ8 / Binary / half images (vdb_hip_index_search_batch_filtered_mode).
+// Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_mode_route_model.cpp,
+// tests/filter_graph_route_model.cpp, tests/filters_plan_model.cpp and tests/listed_groups_plan_model.cpp compile it alone and walk
+// its boundaries.
 #pragma once
 #include <stdint.h>
 
@@ -31,6 +33,87 @@ static inline int filter_route(int64_t opt, bool listed_available, uint64_t coun
 // than 1/16 of the rows allowed the seed sample holds too few live rows to give k keys a bound (16 384 sample rows, one key per 64
 // rows: 256 keys, 16 of them live at 1/16), so those calls go straight to the exact kernels — which serve any mask.
 static inline bool filter_keeps_selection(uint64_t count, uint64_t n_rows) { return count * 16 >= n_rows; }
+
+// ---- filtered exact search over the SQ8 / Binary / half row images (vdb_hip_index_search_batch_filtered_mode) ----
+// (the values of enum vdb_search_mode / vdb_metric this header needs; index.hip holds them to include/velesdb_hip.h)
+constexpr int kFmModeBf16 = 3, kFmModeSq8 = 5, kFmModeBinary = 6, kFmModeF16 = 7;
+constexpr int kFmMetricEuclidean = 1;
+constexpr uint32_t kFmSq8ListedMaxQueries = 3;  // SQ8: the largest batch auto gives to the listed kernel (one-query passes only, below)
+// which of the four modes has a listed kernel for this metric at all: SQ8 (Cosine / Euclidean / DotProduct: the caller checks the
+// metric is one of the three), Euclidean over a half image.  Binary and Cosine / DotProduct over a half image run on mask substitution.
+static inline bool filter_mode_has_listed(int mode, int metric) {
+  if (mode == kFmModeSq8) return true;
+  if (mode == kFmModeBf16 || mode == kFmModeF16) return metric == kFmMetricEuclidean;
+  return false;
+}
+// The route of a filtered call in one of those modes.  Forced values behave as in filter_route; `listed_available`: the mode and
+// metric have a listed kernel (above) AND its plan fits the LDS (mode_listed_plan below).
+// Auto started as a stated guess and was then held against ONE measurement (100 K x 768, k = 10, 1 / 16 / 1 024 queries, densities
+// 0.01 - 1.0); what it is now:
+//   * Euclidean over a half image: the listed kernel does per listed row what the full sweep does per row, plus a gathered instead of
+//     a streamed read — listed iff count <= 3/4 n_rows.  Measured: listed ahead at 0.01 / 0.1 / 0.5 at all three batch sizes (0.24 -
+//     0.84 of the unfiltered call), 2 % behind at 1.0.
+//   * SQ8, all three metrics: listed iff the batch runs as one-query passes (nq <= kFmSq8ListedMaxQueries) and count <= 3/4 n_rows.
+//     Measured: at one query listed is ahead at 0.01 - 0.5 (0.65 - 0.77 of the unfiltered call); at 16 and 1 024 queries an 8-query
+//     listed pass costs ~0.23 ms whatever the list's length — more than a full 8-query pass over 100 K rows (0.16 ms) — and from six
+//     queries up mask substitution keeps the selection stage (Euclidean too: select_level_sq8), so mask substitution wins at every
+//     density.  The first guess (Euclidean: 3/4 at every batch size; Cosine / DotProduct: the f32 rule from six queries up) was wrong
+//     there.  NOT measured: batches of 2 - 15 queries (the 4-query pass), other corpus sizes; the fixed cost of the 4- and 8-query
+//     listed passes is not explained.
+static inline int filter_mode_route(int64_t opt, int mode, int metric, uint64_t count, uint64_t n_rows, uint32_t nq, bool listed_available) {
+  if (!listed_available || count == 0 || !filter_mode_has_listed(mode, metric)) return kFilterRouteDense;
+  if (opt == 1) return kFilterRouteListed;
+  if (opt >= 2) return kFilterRouteDense;
+  if (mode == kFmModeSq8 && nq > kFmSq8ListedMaxQueries) return kFilterRouteDense;
+  return count * 4 <= n_rows * 3 ? kFilterRouteListed : kFilterRouteDense;
+}
+
+// LDS footprints of the two streaming kernels (storage_modes.hip sweep_topk_sq8 / sweep_half_l2.hip sweep_topk_half_l2 and their listed
+// forms: the same layouts).  SQ8: queries [dpad][B] f32 | 4 staging tiles of 64 rows x 80 B | lists [B][k] | cnt, lock, qsum, qnsq [B]
+static inline uint64_t fm_sq8_lds_bytes(int B, uint32_t k, uint32_t dim) {
+  const uint64_t dpad = ((uint64_t)dim + 3u) & ~(uint64_t)3;
+  return (dpad * (uint64_t)B * 4 + (uint64_t)4 * 64 * 80 + (uint64_t)B * k * 8 + (uint64_t)B * 16 + 15) & ~(uint64_t)15;
+}
+// half Euclidean: q[B][stride] f32 | lists[B][k] | cnt[B] | lock[B], stride = dim rounded up to 8
+static inline uint64_t fm_half_l2_lds_bytes(int B, uint32_t k, uint32_t dim) {
+  const uint64_t stride = ((uint64_t)dim + 7) / 8 * 8;
+  return (((uint64_t)B * stride * 4 + (uint64_t)B * k * 8 + (uint64_t)B * 8) + 15) & ~(uint64_t)15;
+}
+// One pass of a listed sweep in these modes, next to sweep_listed_plan: the queries per pass follow the unlisted dispatch (SQ8: 8 from 8
+// queries left, 4 from 4, else 1; half Euclidean: 16 above 4 left, 4 above 1, else 1; a class whose LDS does not fit gives way to the
+// next), blocks take contiguous chunks of per_block row groups (a group = 64 listed rows for SQ8 — one per lane —, 64 / B for the half
+// kernel), four waves a block, at most n_cus x (resident blocks per CU) blocks.  blocks == 0: the route is "not available" (count,
+// k or nq zero, or not even one query fits 160 KiB).
+struct ModeListedPlan {
+  int blocks = 0;
+  int B = 0;
+  uint32_t nq_pass = 0, per_block = 0;
+  uint64_t lds = 0;
+};
+constexpr uint64_t kFmLdsBudget = 160 * 1024;
+static inline ModeListedPlan mode_listed_plan(bool half, uint32_t dim, uint32_t k, uint64_t count, uint32_t nq_left, int n_cus) {
+  ModeListedPlan p;
+  if (count == 0 || k == 0 || nq_left == 0 || count > 0xFFFFFFFFull) return p;
+  int B = half ? (nq_left > 4 ? 16 : (nq_left > 1 ? 4 : 1)) : (nq_left >= 8 ? 8 : (nq_left >= 4 ? 4 : 1));
+  auto lds_of = [&](int b) { return half ? fm_half_l2_lds_bytes(b, k, dim) : fm_sq8_lds_bytes(b, k, dim); };
+  while (B > 1 && lds_of(B) > kFmLdsBudget) B = half ? B / 4 : (B == 8 ? 4 : 1);
+  const uint64_t lds = lds_of(B);
+  if (lds > kFmLdsBudget) return p;
+  const uint64_t rpg = half ? 64u / (uint64_t)B : 64u;
+  const uint64_t ngroups = (count + rpg - 1) / rpg;
+  uint64_t per_cu = kFmLdsBudget / lds, cap = half ? 3 : 4;  // (the half kernel runs at 3 waves per SIMD)
+  if (per_cu > cap) per_cu = cap;
+  uint64_t want = (ngroups + 3) / 4;
+  const uint64_t room = (uint64_t)(n_cus > 0 ? n_cus : 1) * per_cu;
+  if (want > room) want = room;
+  if (want < 1) want = 1;
+  p.per_block = (uint32_t)((ngroups + want - 1) / want);
+  p.blocks = (int)((ngroups + p.per_block - 1) / p.per_block);
+  p.B = B;
+  p.nq_pass = nq_left < (uint32_t)B ? nq_left : (uint32_t)B;
+  p.lds = lds;
+  return p;
+}
 
 // ---- filtered graph search (vdb_hip_index_search_graph_filtered): walk or exact pass, and the walk's first list ----
 enum FilterGraphRoute : int { kFgRefuse = -1, kFgAuto = 0, kFgWalk = 1, kFgExact = 2 };

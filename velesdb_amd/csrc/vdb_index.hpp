@@ -329,6 +329,13 @@ static inline const uint8_t* search_alive(const vdb_hip_index* ix) {
 }
 // filtered exact search (index.hip): the caller holds ix->mu shared and leased the context `ix`
 int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k);
+// ... in one of the modes VDB_SEARCH_BRUTE_SQ8 / _BINARY / _BF16 / _F16 (vdb_hip_index_search_batch_filtered_mode)
+int32_t search_filtered_mode_to_device(vdb_hip_index* ix, const RowFilter* f, int32_t mode, const float* queries, uint32_t nq, uint32_t k);
+// the listed passes of that call (storage_modes.hip / select_stage.hip): `list` = the filter's ascending rows, count > 0, k > 0
+int32_t brute_sq8_listed_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const float* d_q, uint64_t q_stride, uint32_t nq,
+                             uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st);
+int32_t brute_half_l2_listed_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const float* d_q, uint64_t q_stride,
+                                 uint32_t nq, uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st);
 // the filter belongs to this handle (generation) and to its present row numbering (row_epoch): anything else is an error
 int32_t filter_check(vdb_hip_index* ix, const RowFilter* f);
 // one optional filter per query on the exact sweep (index.hip): filters[n_filters] handles (checked inside, all of them

@@ -264,6 +264,10 @@ size_t sweep_half_l2_lds_bytes(int B, uint32_t k, uint32_t dim);
 hipError_t launch_sweep_half_l2(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,
                                 uint64_t q_stride, uint64_t* part_keys, uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks,
                                 hipStream_t st);
+// ... and over a filter's ascending row list (sweep_topk_half_l2_listed; the plan: mode_listed_plan, vdb_filter_route.hpp)
+hipError_t launch_sweep_half_l2_listed(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const uint32_t* list,
+                                       uint32_t count, uint32_t per_block, const float* queries, uint64_t q_stride, uint64_t* part_keys,
+                                       uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks, hipStream_t st);
 void launch_merge(bool higher_is_better, const MergeArgs& m, uint32_t nq, hipStream_t st);
 // sweep_listed.hip — filtered exact search: the sweep over a LIST of rows, and the row mask of the other route
 struct ListedArgs {

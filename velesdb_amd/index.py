@@ -588,6 +588,44 @@ class HnswIndex:
                                                         _ptr(sc), _ptr(cnt)))
         return ids, sc, cnt
 
+    def _search_filtered_mode(self, queries, k: int, flt: Filter, mode: int):
+        """vdb_hip_index_search_batch_filtered_mode: the exact scan of `mode` (SQ8 codes, sign bits, a half image) among the filter's
+        rows only — what the plain call in that mode returns on an index that holds just the allowed live rows.  numpy outputs."""
+        if not isinstance(flt, Filter):
+            raise TypeError("filtered search: flt must be a Filter (create_filter)")
+        qs = _f32(queries)
+        if qs.ndim == 1:
+            qs = qs.reshape(1, -1)
+        if qs.ndim != 2:
+            raise ValueError(f"filtered search: queries must be one vector or a (nq, dim) array, got {qs.ndim} dimensions")
+        if int(k) < 0:
+            raise ValueError("filtered search: k must not be negative")
+        self._validate(qs)
+        nq, kk = qs.shape[0], max(int(k), 1)
+        ids = np.empty((nq, kk), dtype=np.uint64)
+        sc = np.empty((nq, kk), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        check(lib().vdb_hip_index_search_batch_filtered_mode(self._h, flt._h, mode, _ptr(qs), nq, int(k), _ptr(ids), _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
+
+    def search_batch_filtered_sq8(self, queries, k: int, flt: Filter):
+        """search_batch_sq8 among the filter's rows only (storage mode SQ8): ids, ranks and score bits of an SQ8 index that holds
+        just the allowed live rows.  OPT_FILTER_ROUTE picks the listed sweep over the codes or mask substitution (same bits)."""
+        return self._search_filtered_mode(queries, k, flt, MODE_BRUTE_SQ8)
+
+    def search_batch_filtered_binary(self, queries, k: int, flt: Filter):
+        """search_batch_binary among the filter's rows only (storage mode Binary): Hamming distances between sign-bit codes, ties by
+        row, of an index that holds just the allowed live rows."""
+        return self._search_filtered_mode(queries, k, flt, MODE_BRUTE_BINARY)
+
+    def search_batch_filtered_half(self, queries, k: int, flt: Filter, precision):
+        """search_batch_brute_force_half among the filter's rows only (enable_half_precision(precision) first).  Euclidean: bit
+        for bit on both routes; Cosine / DotProduct: mask substitution over the matrix-core tiers, within that mode's tolerance."""
+        precision = VectorPrecision(int(precision))
+        if precision == VectorPrecision.F32:
+            raise ValueError("half-precision search: F16 or BF16")
+        return self._search_filtered_mode(queries, k, flt, MODE_BRUTE_F16 if precision == VectorPrecision.F16 else MODE_BRUTE_BF16)
+
     def search_batch_filtered_graph(self, queries, k: int, flt: Filter, ef: int = 0, route: int = ROUTE_AUTO, max_list: int = 0,
                                     mode: int = MODE_HNSW):
         """Graph search with the filter consulted inside the walk (vdb_hip_index_search_graph_filtered): layer 0 keeps allowed live
