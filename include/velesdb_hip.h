@@ -564,6 +564,55 @@ int32_t vdb_hip_index_multi_query_search(vdb_hip_index* idx, const void* filter,
                                          const uint32_t* group_sizes, uint32_t n_groups, uint32_t top_k, int32_t strategy,
                                          uint32_t rrf_k, const float* weights, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
 
+/* ---- hybrid search: Collection::hybrid_search / hybrid_search_with_filter (collection/search/text.rs:113-299) — one vector query
+ * plus the hits of one BM25 text query, fused by a weighted Reciprocal Rank Fusion on the device (hybrid.hip, vdb_hybrid.hpp;
+ * DESIGN 4.1p).  The BM25 index stays the caller's, as payload predicates do: the caller runs its text search and hands over the ids,
+ * best first.  The rule uses ranks only, so no entry point takes scores.
+ * The rule, for one user query with a vector list V, a text list T (ids, best first) and a vector_weight:
+ *   w = clamp(vector_weight, 0, 1) in f32 (default 0.5f), tw = 1.0f - w;
+ *   score(id) = 0.0f, + w / ((float)r + 60.0f) for EVERY occurrence of the id at 0-based position r of V in ascending r, then
+ *               + tw / ((float)r + 60.0f) for every occurrence at position r of T in ascending r, every operation rounded on its own
+ *               (no in-list de-duplication: the reference has none here, unlike FusionStrategy::fuse);
+ *   one sort key: the fused score descending by the IEEE total order, EQUAL SCORES BY ID DESCENDING; the first k ids under it are the
+ *   result.  Membership at the cut is the reference's (its heap pops the smallest (score, id), text.rs:166-173); the order among
+ *   equal scores is unspecified there and fixed here.  This is NOT the tie rule of vdb_hip_fuse_results (id ascending), on purpose.
+ * Deviation: a NaN weight is VDB_ERR_INVALID_ARG (Rust's clamp lets NaN through and the reference then returns NaN scores).
+ *
+ * vdb_hip_hybrid_fuse: the rule alone over nq caller list pairs in ONE launch (one block per query), every id treated as live, no
+ * filter; host pointers.  vec_ids [nq][vec_stride] / text_ids [nq][text_stride], query i holds vec_n[i] <= vec_stride and
+ * text_n[i] <= text_stride ids; vector_weights [nq], NULL = 0.5 for all.  Outputs [nq][max(k, 1)] / out_n [nq]: the first
+ * min(k, distinct ids) fused records, padded as the search calls pad (id ~0, score NaN); k = 0: out_n = 0, nothing else written;
+ * nq = 0: VDB_OK.  A query with vec_n[i] + text_n[i] > 8192 (what one block's LDS takes, 128 of 160 KB) answers
+ * VDB_ERR_UNSUPPORTED before anything runs (the message names the query); a list longer than its stride, a null pointer, a NaN weight:
+ * VDB_ERR_INVALID_ARG.  The outputs are untouched on error. */
+int32_t vdb_hip_hybrid_fuse(int32_t device, const uint64_t* vec_ids, const uint32_t* vec_n, uint32_t vec_stride,
+                            const uint64_t* text_ids, const uint32_t* text_n, uint32_t text_stride, const float* vector_weights,
+                            uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+/* hybrid_search / hybrid_search_with_filter for nq user queries in one call: queries_rowmajor [nq][dim]; text_ids / text_n /
+ * text_stride / vector_weights / outputs as above.
+ * THE CONTRACT: query i gets, bit for bit, the rule above applied to its text ids and to
+ *   filter == NULL: the list vdb_hip_index_search_batch(mode = VDB_SEARCH_HNSW, ef = 0, k' = 2k) returns for it.  A text id the handle
+ *     does not know, or whose row is removed, takes its rank, its score and its place in the cut and is then dropped from the output
+ *     (the reference's filter_map over the vector storage BEHIND the cut, text.rs:186-200): out_n can be below min(k, distinct ids);
+ *   filter != NULL: the list vdb_hip_index_search_graph_filtered(filter, k' = max(4k, k + 10), ef = 0, route 0, max_list 0) returns
+ *     for it — the in-walk allow-list of DESIGN 4.1h — and text hits whose row is unknown, removed or outside the filter are dropped
+ *     BEFORE ranks are assigned (a stable compaction).  Deviation: the reference ranks, fuses, sorts, post-filters and takes k
+ *     (text.rs:244-296), so a selective filter leaves it short; this form does not come back short while allowed candidates exist.
+ * The text ids are mapped through the handle's id map under the handle's lock, as vdb_hip_index_filter_create maps ids; the live
+ * flags are read at search time.  A query's answer never depends on its companions or on its position in the call.
+ * k' + text_n[i] > 8192 answers VDB_ERR_UNSUPPORTED before anything runs (the message names the query); a NaN weight, a null
+ * pointer, text_n[i] > text_stride: VDB_ERR_INVALID_ARG; every other limit or error of the per-query call it stands on is passed
+ * through (no graph: VDB_ERR_STATE; a filter of another handle: VDB_ERR_INVALID_ARG; a stale filter: VDB_ERR_STATE).  Multi-device
+ * handles and process-group members: VDB_ERR_UNSUPPORTED.  The outputs are untouched on error.  Host pointers; launches of its own
+ * on one leased search context (no combining front): the walks — the per-query call's own code, which still brings its whole result
+ * block (nq x k' records and the counts) to pinned host memory and synchronises —, then hybrid_fuse_kernel over the context's DEVICE
+ * copy of the lists on the same stream, the nq x k fused records back and a second synchronisation.  What the call saves a caller is
+ * the copy of nq x k' records into its arrays and the hashing and sorting there, not that transfer.
+ * vdb_hip_index_last_kernels: VDB_KERNEL_HYBRID_FUSE next to the walk's bits. */
+int32_t vdb_hip_index_hybrid_search(vdb_hip_index* idx, const void* filter, const float* queries_rowmajor, uint32_t nq, uint32_t k,
+                                    const uint64_t* text_ids, const uint32_t* text_n, uint32_t text_stride,
+                                    const float* vector_weights, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+
 /* ---- DistanceEngine::batch_distance / GpuAccelerator::batch_{cosine_similarity,
  * euclidean_distance,dot_product} (native/distance.rs:21-24; gpu_backend.rs:157,355,397) ----
  * n rows of dim floats against one query; out has n floats, same order as the rows. */
@@ -749,6 +798,8 @@ enum vdb_kernel_bit {
 /* ... and one more: sweep_topk_listed_groups / sweep_topk_listed_groups_m ran (vdb_hip_index_search_batch_filters, the grouped
  * launches of its groups on the listed route) */
 #define VDB_KERNEL_SWEEP_LISTED_GROUPS 2097152
+/* ... and one more: hybrid_fuse_kernel ran (vdb_hip_index_hybrid_search sets it next to the walk's bits) */
+#define VDB_KERNEL_HYBRID_FUSE 4194304
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same
  * context a moment later does not change it. */

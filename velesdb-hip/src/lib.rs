@@ -1490,6 +1490,85 @@ impl HipHnswIndex {
         Ok((0..n as usize).map(|j| (ids[j], scores[j])).collect())
     }
 
+    /// `Collection::hybrid_search` (collection/search/text.rs:113-203) with the fusion on the device
+    /// (`vdb_hip_index_hybrid_search`): `text_hits` = the ids `text_index.search(text_query, 2 * k)` returned, best first.  The
+    /// query is walked at `2 * k` (`SearchQuality::Balanced`) and its list fused with the text hits by the weighted rank fusion —
+    /// `w = clamp(vector_weight.unwrap_or(0.5), 0, 1)`, every occurrence adds `w / (rank + 60)` resp. `(1 - w) / (rank + 60)` —
+    /// the first `k` by (fused score descending, id descending) come back.  Text ids the index does not hold take their place in
+    /// the cut and are then dropped, as the reference's `filter_map` drops them.
+    ///
+    /// # Errors
+    /// The reference's `Error::DimensionMismatch` message as `Err(String)`; a NaN weight (the reference lets it through).
+    ///
+    /// # Panics
+    /// On a status the library reports for the call itself (no graph, `2 * k` plus the text hits past what one block fuses).
+    pub fn hybrid_search(&self, vector_query: &[f32], text_hits: &[u64], k: usize, vector_weight: Option<f32>) -> Result<Vec<(u64, f32)>, String> {
+        self.hybrid_call(vector_query, text_hits, k, vector_weight, None)
+    }
+
+    /// `Collection::hybrid_search_with_filter` (text.rs:221-299): `text_hits` = the ids
+    /// `text_index.search(text_query, max(4 * k, k + 10))` returned.  The filter is consulted inside the walk (at that k) and in
+    /// front of the text ranks: text hits outside it take no rank — not the reference's post-filter, which a selective filter
+    /// leaves short of `k`.
+    ///
+    /// # Errors
+    /// As [`Self::hybrid_search`].
+    ///
+    /// # Panics
+    /// As [`Self::hybrid_search`]; a stale filter or one of another index.
+    pub fn hybrid_search_with_filter(
+        &self,
+        vector_query: &[f32],
+        text_hits: &[u64],
+        k: usize,
+        vector_weight: Option<f32>,
+        filter: &HipFilter,
+    ) -> Result<Vec<(u64, f32)>, String> {
+        self.hybrid_call(vector_query, text_hits, k, vector_weight, Some(filter))
+    }
+
+    fn hybrid_call(
+        &self,
+        vector_query: &[f32],
+        text_hits: &[u64],
+        k: usize,
+        vector_weight: Option<f32>,
+        filter: Option<&HipFilter>,
+    ) -> Result<Vec<(u64, f32)>, String> {
+        if vector_query.len() != self.dimension {
+            return Err(format!("Vector dimension mismatch: expected {}, got {}", self.dimension, vector_query.len()));
+        }
+        let weight = [vector_weight.unwrap_or(0.5)];
+        if weight[0].is_nan() {
+            return Err("vector_weight is NaN".into());
+        }
+        let kk = k.max(1);
+        let mut ids = vec![0u64; kk];
+        let mut scores = vec![0f32; kk];
+        let mut n = 0u32;
+        // (a list past u32 keeps a count past every limit: the library refuses it, it never wraps to a short one)
+        let text_n = [u32::try_from(text_hits.len()).unwrap_or(u32::MAX)];
+        // SAFETY: one query of `dimension` floats; one text list of text_n ids at stride text_n; one weight; outputs hold max(k, 1)
+        // records and one count; the filter handle is live (borrowed).
+        check(unsafe {
+            sys::vdb_hip_index_hybrid_search(
+                self.h,
+                filter.map_or(ptr::null(), |f| f.h.cast_const()),
+                vector_query.as_ptr(),
+                1,
+                u32::try_from(k).unwrap_or(u32::MAX),
+                text_hits.as_ptr(),
+                text_n.as_ptr(),
+                text_n[0],
+                weight.as_ptr(),
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                &mut n,
+            )
+        });
+        Ok((0..n as usize).map(|j| (ids[j], scores[j])).collect())
+    }
+
     /// Boxed as the trait object `Collection` holds: what a downstream crate's `hip` feature registers with the index factory
     /// hook of velesdb-core (see Cargo.toml: the dependency points from this crate to the core, never back).
     #[must_use]
@@ -1642,6 +1721,47 @@ impl FusionStrategy {
         });
         Ok((0..n as usize).map(|j| (out_ids[j], out_scores[j])).collect())
     }
+}
+
+/// The weighted rank fusion of `Collection::hybrid_search` (collection/search/text.rs:133-180) alone, on device 0
+/// (`vdb_hip_hybrid_fuse`): `vector_ids` and `text_ids` best first, every id treated as present.  The first `k` ids by (fused
+/// score descending, id descending) with their fused scores.
+///
+/// # Errors
+/// A NaN weight.
+///
+/// # Panics
+/// Without a device, or when the two lists hold more than 8192 ids together.
+pub fn hybrid_fuse(vector_ids: &[u64], text_ids: &[u64], k: usize, vector_weight: Option<f32>) -> Result<Vec<(u64, f32)>, String> {
+    let weight = [vector_weight.unwrap_or(0.5)];
+    if weight[0].is_nan() {
+        return Err("vector_weight is NaN".into());
+    }
+    let kk = k.max(1);
+    let mut ids = vec![0u64; kk];
+    let mut scores = vec![0f32; kk];
+    let mut n = 0u32;
+    // (a list past u32 keeps a count past every limit: the library refuses it, it never wraps to a short one)
+    let (vec_n, text_n) = ([u32::try_from(vector_ids.len()).unwrap_or(u32::MAX)], [u32::try_from(text_ids.len()).unwrap_or(u32::MAX)]);
+    // SAFETY: one query; each list holds as many ids as its count and its stride say; outputs hold max(k, 1) records and one count.
+    check(unsafe {
+        sys::vdb_hip_hybrid_fuse(
+            0,
+            vector_ids.as_ptr(),
+            vec_n.as_ptr(),
+            vec_n[0],
+            text_ids.as_ptr(),
+            text_n.as_ptr(),
+            text_n[0],
+            weight.as_ptr(),
+            1,
+            u32::try_from(k).unwrap_or(u32::MAX),
+            ids.as_mut_ptr(),
+            scores.as_mut_ptr(),
+            &mut n,
+        )
+    });
+    Ok((0..n as usize).map(|j| (ids[j], scores[j])).collect())
 }
 
 /// The reference's second `impl VectorIndex` (`index/hnsw/native_index.rs:403-427`) over the same graph.  What differs from

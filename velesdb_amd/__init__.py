@@ -18,7 +18,8 @@ from .index import KERNEL_FILTER_RANK, KERNEL_HALF_RESCORE, KERNEL_HNSW_FILTERED
 from .index import KERNEL_SWEEP_LISTED_GROUPS  # noqa: F401
 from .index import (FILTER_ROUTE_AUTO, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK, KERNEL_SWEEP_LISTED, OPT_FILTER_ROUTE, Filter)  # noqa: F401
 from .index import FUSE_MAX_RECORDS, FusionError, FusionStrategy, KERNEL_FUSE, MAX_FUSED_VECTORS, fuse_arrays, fuse_groups  # noqa: F401
+from .index import HYBRID_MAX_RECORDS, KERNEL_HYBRID_FUSE, hybrid_fuse_arrays  # noqa: F401
 from .params import DistanceMetric, DualPrecisionConfig, HnswParams, SearchQuality, StorageMode  # noqa: F401
 
-__all__ = ["HnswIndex", "Filter", "FusionStrategy", "FusionError", "NativeHnswIndex", "HipDistance", "GpuAccelerator", "DistanceMetric", "HnswParams", "SearchQuality", "StorageMode", "DualPrecisionConfig", "VectorPrecision",
+__all__ = ["HnswIndex", "Filter", "FusionStrategy", "FusionError", "hybrid_fuse_arrays", "NativeHnswIndex", "HipDistance", "GpuAccelerator", "DistanceMetric", "HnswParams", "SearchQuality", "StorageMode", "DualPrecisionConfig", "VectorPrecision",
            "device_count", "device_name", "comm_unique_id", "SHARD_RANGE", "SHARD_REPLICA", "set_kernel_timing", "set_max_query_tile", "set_sweep_engine", "set_split_selector", "lib", "VelesHipError"]

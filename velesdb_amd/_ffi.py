@@ -37,6 +37,8 @@ VDB_KERNEL_FUSE = 524288
 # ... and of the half walk with the f32 re-score (vdb_hip_index_search_graph_filters_half_rescore)
 VDB_KERNEL_HALF_RESCORE = 1048576
 VDB_KERNEL_SWEEP_LISTED_GROUPS = 2097152
+# ... and of the hybrid search (vdb_hip_index_hybrid_search / vdb_hip_hybrid_fuse)
+VDB_KERNEL_HYBRID_FUSE = 4194304
 VDB_FUSION_AVERAGE, VDB_FUSION_MAXIMUM, VDB_FUSION_RRF, VDB_FUSION_WEIGHTED = 0, 1, 2, 3
 
 # every function include/velesdb_hip.h declares: name -> (restype, argtypes)
@@ -99,6 +101,8 @@ SIGNATURES = {
     "vdb_hip_index_search_graph_filters_half_rescore": (_i32, [_vp, _i32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_fuse_results": (_i32, [_i32, _i32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "vdb_hip_index_multi_query_search": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
+    "vdb_hip_hybrid_fuse": (_i32, [_i32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "vdb_hip_index_hybrid_search": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_batch_distance": (_i32, [_i32, _i32, _i32, _vp, _vp, _u64, _u32, _vp]),
     "vdb_hip_batch_distance_dev": (_i32, [_i32, _i32, _vp, _vp, _u64, _u32, _vp, _vp]),
     "vdb_hip_index_load_reference_files": (_i32, [_vp, C.c_char_p, C.c_char_p]),

@@ -17,6 +17,7 @@
 #include "vdb_fusion.hpp"
 #include "vdb_index.hpp"
 #include "vdb_kernels.hpp"
+#include "vdb_lds_sort.hpp"
 
 namespace vdb {
 
@@ -24,29 +25,10 @@ using fusion::Rec;
 
 constexpr uint32_t kFuseItems = 8;  // LDS entries per thread in step 2
 
+// (the network and the scan: vdb_lds_sort.hpp, shared with hybrid.hip)
 template <bool BY_SCORE>
 __device__ __forceinline__ void fuse_bitonic(Rec* __restrict__ recs, uint32_t P, uint32_t tid, uint32_t nt) {
-  for (uint32_t k = 2; k <= P; k <<= 1) {
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t p = tid; p < (P >> 1); p += nt) {
-        const uint32_t i = ((p & ~(j - 1u)) << 1) | (p & (j - 1u));  // i < P - j, partner i | j < P
-        const uint32_t l = i | j;
-        const Rec a = recs[i], b = recs[l];
-        const bool swap = (i & k) == 0 ? fusion::rec_less<BY_SCORE>(b, a) : fusion::rec_less<BY_SCORE>(a, b);
-        if (swap) {
-          recs[i] = b;
-          recs[l] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-__device__ __forceinline__ uint32_t fuse_pow2(uint32_t n) {
-  uint32_t p = 1;
-  while (p < n) p <<= 1;
-  return p;
+  lds_bitonic(recs, P, tid, nt, [](const Rec& a, const Rec& b) { return fusion::rec_less<BY_SCORE>(a, b); });
 }
 
 __global__ void __launch_bounds__(1024) fuse_lists_kernel(const FuseArgs a) {
@@ -66,7 +48,7 @@ __global__ void __launch_bounds__(1024) fuse_lists_kernel(const FuseArgs a) {
     if (tid == 0) a.out_n[g] = 0;
     return;
   }
-  const uint32_t P = fuse_pow2(n);  // <= lds_records (a power of two >= the largest n)
+  const uint32_t P = lds_pow2(n);  // <= lds_records (a power of two >= the largest n)
 
   // the group's lists into LDS: one wave per list, lanes over its positions
   for (uint32_t l = tid >> 6; l < G.V; l += nt >> 6) {
@@ -107,20 +89,13 @@ __global__ void __launch_bounds__(1024) fuse_lists_kernel(const FuseArgs a) {
       }
     }
   }
-  scan[tid] = cnt;
-  __syncthreads();  // (every run has been read: the array may be overwritten from here on)
-  for (uint32_t off = 1; off < nt; off <<= 1) {
-    const uint32_t v = tid >= off ? scan[tid - off] : 0u;
-    __syncthreads();
-    scan[tid] += v;
-    __syncthreads();
-  }
+  lds_scan(scan, cnt, tid, nt);  // (behind its first barrier every run has been read: the array may be overwritten from here on)
   const uint32_t D = scan[nt - 1];  // distinct ids, 1 <= D <= n
   uint32_t d = scan[tid] - cnt;
 #pragma unroll
   for (uint32_t e = 0; e < kFuseItems; e++)
     if (heads & (1u << e)) recs[d++] = Rec{fusion::desc_key(fy[e]), fy[e], fz[e], fw[e]};  // d <= tid * 8 + e < n
-  const uint32_t P2 = fuse_pow2(D);
+  const uint32_t P2 = lds_pow2(D);
   for (uint32_t i = D + tid; i < P2; i += nt) recs[i] = Rec{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
   __syncthreads();
   fuse_bitonic<true>(recs, P2, tid, nt);

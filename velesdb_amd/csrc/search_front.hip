@@ -25,6 +25,7 @@
 
 #include "vdb_combiner.hpp"
 #include "vdb_fusion.hpp"
+#include "vdb_hybrid.hpp"
 #include "vdb_index.hpp"
 #include "vdb_kernels.hpp"
 
@@ -206,6 +207,102 @@ static int32_t multi_query_direct(vdb_hip_index* handle, const RowFilter* f, con
           std::memcpy(out_scores, h + o_os, (size_t)n_groups * top_k * 4);
         }
         std::memcpy(out_n, h + o_on, (size_t)n_groups * 4);
+      });
+}
+
+// text hits of a call from which their id-to-row mapping runs on a thread beside the walk
+constexpr size_t kHybridMapThreadCells = 4096;
+// vdb_hip_index_hybrid_search: ONE lease.  The walk of every query at the contract's k' is the per-query call's own
+// code: it brings its whole result block (nq x k' records and the counts) to the context's pinned h_out and synchronises — the host
+// needs the counts (a walk whose list overflowed is re-run).  Beside the walk a host thread maps the text ids to rows through the
+// handle's id map (the shared lock is held: as vdb_hip_index_filter_create maps ids).  Then hybrid_fuse_kernel runs over the
+// context's device lists (ix->s_out_ids at stride k': the fusion reads nothing of h_out but the counts) and the uploaded text ids on
+// the same stream, the nq x k fused records come back through pinned memory and a second synchronisation ends the call.  The live
+// flags and the filter's bitmap are read by the kernel.  `table` = hybrid_plan's (nv = the bound k'; set from the walk's counts here).
+static int32_t hybrid_direct(vdb_hip_index* handle, const RowFilter* f, const float* queries, uint32_t nq, uint32_t k, uint32_t kf,
+                             const uint64_t* text_ids, const uint32_t* text_n, uint32_t text_stride, std::vector<HybridQuery>& table,
+                             uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  const size_t kk = std::max<uint32_t>(k, 1);
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t tcells = (size_t)nq * text_stride;
+  const size_t o_tx = (size_t)nq * sizeof(HybridQuery), o_tr = o_tx + up16(tcells * 8), o_oi = o_tr + up16(tcells * 4),
+               o_os = o_oi + up16((size_t)nq * kk * 8), o_on = o_os + up16((size_t)nq * kk * 4), total = o_on + up16((size_t)nq * 4);
+  return run_search(
+      handle, nq, kf, 0, VDB_SEARCH_HNSW, 0,
+      [&](vdb_hip_index* ix) -> int32_t {
+        hipStream_t st = ix->stream;
+        if (ix->s_fuse.reserve(total, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "hybrid fusion scratch");
+        if (ix->h_fuse.reserve(total) != hipSuccess) return fail(VDB_ERR_OOM, "pinned hybrid fusion staging");
+        unsigned char* h = ix->h_fuse.as<unsigned char>();
+        unsigned char* d = ix->s_fuse.as<unsigned char>();
+        // text ids -> rows, into the pinned block (the id map lives on the handle, not on its search contexts; removed ids are not in it)
+        auto map_rows = [&, h]() {
+          uint32_t* h_rows = reinterpret_cast<uint32_t*>(h + o_tr);
+          const vdb_hip_index* own = primary_of(ix);
+          for (uint32_t i = 0; i < nq; i++)
+            for (uint32_t j = 0; j < text_stride; j++) {
+              uint32_t row = 0xFFFFFFFFu;
+              if (j < text_n[i]) {
+                auto it = own->id_to_idx.find(text_ids[(size_t)i * text_stride + j]);
+                if (it != own->id_to_idx.end() && it->second < ix->n_rows) row = (uint32_t)it->second;
+              }
+              h_rows[(size_t)i * text_stride + j] = row;
+            }
+        };
+        // a call with many text hits maps them on a thread of its own while the walk runs (it only reads: the caller's arrays and the
+        // id map, which the shared lock keeps as it is); a small one maps them in line (a thread costs more than a few hundred lookups)
+        struct Joined {
+          std::thread t;
+          ~Joined() {
+            if (t.joinable()) t.join();
+          }
+        } mapper;
+        if (tcells >= kHybridMapThreadCells) mapper.t = std::thread(map_rows); else map_rows();
+        int32_t rc = f ? search_graph_filtered_to_device(ix, f, queries, nq, kf, 0, 0, 0, nullptr)
+                       : search_to_device(ix, queries, nq, kf, 0, VDB_SEARCH_HNSW, 0, nullptr);
+        if (mapper.t.joinable()) mapper.t.join();
+        if (rc != VDB_OK) return rc;
+        const uint32_t* h_n = reinterpret_cast<const uint32_t*>(ix->h_out.as<unsigned char>() + ((unsigned char*)ix->s_out_n.p - (unsigned char*)ix->s_out.p));
+        uint32_t most = 0;
+        for (uint32_t i = 0; i < nq; i++) {
+          table[i].nv = std::min<uint32_t>(h_n[i], kf);  // (a walk returns at most k' records)
+          most = std::max(most, table[i].nv + table[i].nt);
+        }
+        std::memcpy(h, table.data(), o_tx);
+        if (tcells) std::memcpy(h + o_tx, text_ids, tcells * 8);
+        VDB_HIP(hipMemcpyAsync(d, h, o_oi, hipMemcpyHostToDevice, st));
+        HybridArgs a{};
+        a.vec_ids = ix->s_out_ids.as<uint64_t>();
+        a.vec_stride = std::max<uint32_t>(kf, 1);
+        a.text_ids = reinterpret_cast<const uint64_t*>(d + o_tx);
+        a.text_rows = reinterpret_cast<const uint32_t*>(d + o_tr);
+        a.text_stride = text_stride;
+        a.queries = reinterpret_cast<const HybridQuery*>(d);
+        a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+        a.n_rows = (uint32_t)ix->n_rows;
+        if (f) {
+          a.filtered = 1;
+          a.filter_bits = f->bitmap.as<uint32_t>();
+          a.filter_rows = (uint32_t)f->n_rows;  // (<= ix->n_rows: filter_check, inside the filtered search above)
+        }
+        a.k = k;
+        a.out_ids = reinterpret_cast<uint64_t*>(d + o_oi);
+        a.out_scores = reinterpret_cast<float*>(d + o_os);
+        a.out_n = reinterpret_cast<uint32_t*>(d + o_on);
+        rc = hybrid_launch(a, nq, most, st);
+        if (rc != VDB_OK) return rc;
+        ix->last_kernels |= VDB_KERNEL_HYBRID_FUSE;
+        VDB_HIP(hipMemcpyAsync(h + o_oi, d + o_oi, total - o_oi, hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipStreamSynchronize(st));
+        return VDB_OK;
+      },
+      [&](vdb_hip_index* ix) {
+        const unsigned char* h = ix->h_fuse.as<unsigned char>();
+        if (k) {
+          std::memcpy(out_ids, h + o_oi, (size_t)nq * k * 8);
+          std::memcpy(out_scores, h + o_os, (size_t)nq * k * 4);
+        }
+        std::memcpy(out_n, h + o_on, (size_t)nq * 4);
       });
 }
 
@@ -543,6 +640,29 @@ int32_t vdb_hip_index_multi_query_search(vdb_hip_index* ix, const void* filter, 
   if (nq > 0xFFFFFFFFull) return fail(VDB_ERR_INVALID_ARG, "multi_query_search: more than 2^32 - 1 vectors in one call");
   return multi_query_direct(ix, static_cast<const RowFilter*>(filter), queries, group_sizes, n_groups, (uint32_t)nq, top_k, (uint32_t)kf, strategy,
                             rrf_k, w, out_ids, out_scores, out_n);
+  });
+}
+
+// Collection::hybrid_search / hybrid_search_with_filter (collection/search/text.rs:113-299) for nq user queries with the text hits the
+// caller's BM25 index returned: the walks at k' = 2k (with a filter: max(4k, k + 10), inside the walk) and the weighted rank fusion
+// (vdb_hybrid.hpp) on the device (include/velesdb_hip.h)
+int32_t vdb_hip_index_hybrid_search(vdb_hip_index* ix, const void* filter, const float* queries, uint32_t nq, uint32_t k, const uint64_t* text_ids,
+                                    const uint32_t* text_n, uint32_t text_stride, const float* vector_weights, uint64_t* out_ids,
+                                    float* out_scores, uint32_t* out_n) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || (nq && (!queries || !text_n || !out_n)) || (nq && k && (!out_ids || !out_scores)) || (nq && text_stride && !text_ids))
+    return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "hybrid_search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "hybrid_search: not available on a member of a process group");
+  // text.rs:137 (k * 2) and 244 (k.saturating_mul(4).max(k + 10)); 64-bit, so that a product past u32 is seen and refused below
+  const uint64_t kf = filter ? std::max<uint64_t>((uint64_t)k * 4, (uint64_t)k + 10) : (uint64_t)k * 2;
+  // every argument and limit check in one place (hybrid.hip): the vector lists are planned at their bound k' until the walks are back
+  std::vector<HybridQuery> table;
+  uint32_t most = 0;
+  const int32_t rcp = hybrid_plan(nullptr, kf, text_n, text_stride, vector_weights, nq, &table, &most);
+  if (rcp != VDB_OK || nq == 0) return rcp;
+  return hybrid_direct(ix, static_cast<const RowFilter*>(filter), queries, nq, k, (uint32_t)kf, text_ids, text_n, text_stride, table, out_ids, out_scores,
+                       out_n);
   });
 }
 

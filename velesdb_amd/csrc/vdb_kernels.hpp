@@ -486,5 +486,33 @@ int32_t fuse_check_strategy(int32_t strategy, const float* weights, float* w);
 int32_t fuse_plan(const uint32_t* list_n, uint32_t n_lists, uint32_t list_stride, const uint32_t* group_sizes, uint32_t n_groups,
                   std::vector<FuseList>* lists, std::vector<FuseGroup>* groups, uint32_t* max_records);
 int32_t fuse_launch(FuseArgs a, uint32_t n_groups, uint32_t max_records, hipStream_t st);
+// hybrid.hip: hybrid_search's weighted rank fusion of a vector list and a text list, one block per user query (the rule: vdb_hybrid.hpp)
+struct HybridQuery {
+  uint32_t nv;  // ids in the query's vector list
+  uint32_t nt;  // ids in its text list
+  float w;      // the vector weight, clamped to [0, 1]
+  uint32_t pad;
+};
+struct HybridArgs {
+  const uint64_t* vec_ids;     // [nq][vec_stride]
+  uint32_t vec_stride;
+  const uint64_t* text_ids;    // [nq][text_stride]
+  const uint32_t* text_rows;   // [nq][text_stride] the handle's row of every text id, ~0u = unknown; null: caller lists, every id is live
+  uint32_t text_stride;
+  const HybridQuery* queries;  // [nq]
+  const uint8_t* alive;        // the handle's live flags (null: no row was ever removed); read only with text_rows
+  uint32_t n_rows;             // rows the handle holds
+  uint32_t filtered;           // 1 = the filtered form: text hits outside (filter AND live) take no rank
+  const uint32_t* filter_bits; // the filter's bitmap (read only for rows < filter_rows)
+  uint32_t filter_rows;        // rows the bitmap covers (rows at or past it are outside the filter)
+  uint32_t k;
+  uint32_t lds_records;        // entries of the launch's LDS array (a power of two >= every query's nv + nt; set by hybrid_launch)
+  uint64_t* out_ids;           // [nq][max(k, 1)]
+  float* out_scores;
+  uint32_t* out_n;             // [nq]
+};
+int32_t hybrid_plan(const uint32_t* vec_n, uint64_t vec_stride, const uint32_t* text_n, uint32_t text_stride, const float* weights, uint32_t nq,
+                    std::vector<HybridQuery>* queries, uint32_t* max_records);
+int32_t hybrid_launch(HybridArgs a, uint32_t nq, uint32_t max_records, hipStream_t st);
 
 }  // namespace vdb

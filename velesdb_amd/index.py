@@ -51,6 +51,9 @@ KERNEL_SWEEP_LISTED_GROUPS = _ffi.VDB_KERNEL_SWEEP_LISTED_GROUPS
 KERNEL_FUSE = _ffi.VDB_KERNEL_FUSE
 MAX_FUSED_VECTORS = 10      # MAX_VECTORS of multi_query_search (collection/search/batch.rs:238)
 FUSE_MAX_RECORDS = 8192     # records of one group the fusion kernel takes (VDB_FUSE_MAX_RECORDS)
+# hybrid search (HnswIndex.hybrid_search / hybrid_fuse_arrays): the kernel's bit, |V| + |T| of one query (VDB_HYBRID_MAX_RECORDS)
+KERNEL_HYBRID_FUSE = _ffi.VDB_KERNEL_HYBRID_FUSE
+HYBRID_MAX_RECORDS = 8192
 _PAD_ID = 0xFFFFFFFFFFFFFFFF  # what the library pads result ids with (the score beside it: NaN 0x7FC00000)
 SHARD_REPLICA, SHARD_RANGE = 0, 1
 COMM_ID_BYTES = 128
@@ -205,6 +208,54 @@ def fuse_arrays(fusion: FusionStrategy, ids, scores, list_n, group_sizes, top_k:
     check(lib().vdb_hip_fuse_results(device, fusion.code, fusion.rrf_k, wp, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None,
                                      _ptr(list_n) if n_lists else None, n_lists, stride, _ptr(group_sizes) if ng else None, ng, top_k,
                                      _ptr(out_ids), _ptr(out_sc), _ptr(out_n)))
+    return out_ids, out_sc, out_n
+
+
+def _id_lists(lists, nq: Optional[int] = None):
+    """a sequence of id sequences -> (ids [n][max(stride, 1)] u64, counts [n] u32, stride)"""
+    lists = [np.asarray(l, dtype=np.uint64).reshape(-1) for l in lists]
+    if nq is not None and len(lists) != nq:
+        raise ValueError(f"Queries count ({nq}) does not match id lists count ({len(lists)})")
+    stride = max([l.size for l in lists], default=0)
+    ids = np.zeros((len(lists), max(stride, 1)), dtype=np.uint64)
+    for j, l in enumerate(lists):
+        ids[j, :l.size] = l
+    return ids, np.array([l.size for l in lists], dtype=np.uint32), stride
+
+
+def _hybrid_weights(vector_weight, nq: int):
+    """None (0.5 for all), a scalar or a per-query array -> the [nq] f32 array the library takes, or None"""
+    if vector_weight is None:
+        return None
+    w = np.asarray(vector_weight, dtype=np.float32)
+    if w.ndim == 0:
+        return np.full(nq, w, dtype=np.float32)
+    if w.shape != (nq,):
+        raise ValueError(f"Queries count ({nq}) does not match vector_weight count ({w.size})")
+    return np.ascontiguousarray(w)
+
+
+def hybrid_fuse_arrays(vec_ids, vec_n, text_ids, text_n, k: int, vector_weights=None, device: int = 0):
+    """vdb_hip_hybrid_fuse over numpy arrays: the hybrid_search rule alone (collection/search/text.rs:113-203) for nq list pairs in
+    one launch, every id live, no filter.  vec_ids [nq][vec_stride] / text_ids [nq][text_stride] u64, best first; vec_n / text_n [nq];
+    vector_weights None (0.5), a scalar or [nq].  Returns (ids, fused scores, counts): [nq][max(k, 1)] padded with id 2^64 - 1 / NaN,
+    and [nq]; equal fused scores come back by id DESCENDING."""
+    vec_ids = np.ascontiguousarray(vec_ids, dtype=np.uint64)
+    text_ids = np.ascontiguousarray(text_ids, dtype=np.uint64)
+    vec_n = np.ascontiguousarray(vec_n, dtype=np.uint32)
+    text_n = np.ascontiguousarray(text_n, dtype=np.uint32)
+    nq, kk = vec_n.size, max(k, 1)
+    if text_n.size != nq:
+        raise ValueError(f"Queries count ({nq}) does not match id lists count ({text_n.size})")
+    vs = vec_ids.shape[1] if vec_ids.ndim == 2 else 0
+    ts = text_ids.shape[1] if text_ids.ndim == 2 else 0
+    w = _hybrid_weights(vector_weights, nq)
+    out_ids = np.full((nq, kk), _PAD_ID, dtype=np.uint64)      # (k = 0: the library writes counts only; the one slot stays padding)
+    out_sc = np.full((nq, kk), np.nan, dtype=np.float32)
+    out_n = np.zeros(nq, dtype=np.uint32)
+    check(lib().vdb_hip_hybrid_fuse(device, _ptr(vec_ids) if vec_ids.size else None, _ptr(vec_n) if nq else None, vs,
+                                    _ptr(text_ids) if text_ids.size else None, _ptr(text_n) if nq else None, ts,
+                                    _ptr(w) if w is not None and nq else None, nq, k, _ptr(out_ids), _ptr(out_sc), _ptr(out_n)))
     return out_ids, out_sc, out_n
 
 
@@ -796,6 +847,43 @@ class HnswIndex:
     def multi_query_search_ids(self, vectors, top_k: int, fusion: FusionStrategy, flt: Optional[Filter] = None) -> List[Tuple[int, float]]:
         """Collection::multi_query_search_ids for one user query: `vectors` = its 1..10 reformulations.  (id, fused score), best first."""
         ids, sc, cnt = self.multi_query_search_batch([list(vectors)], top_k, fusion, flt)
+        return self._tuples(ids[0], sc[0], cnt[0])
+
+    def hybrid_search_batch(self, queries, text_hits, k: int, vector_weight=None, flt: Optional[Filter] = None):
+        """Collection::hybrid_search / hybrid_search_with_filter (collection/search/text.rs:113-299) for MANY user queries in one call
+        (vdb_hip_index_hybrid_search).  `text_hits` = one id sequence per query: what the caller's BM25 index returned for the
+        query's text at 2k (with `flt`: max(4k, k + 10)), best first.  Every query is walked at that k (SearchQuality::Balanced; with
+        `flt` by the filtered graph search) and its list fused with its text hits on the device: w = clamp(vector_weight, 0, 1),
+        score = sum w / (rank + 60) over the vector list + sum (1 - w) / (rank + 60) over the text hits, the first k by (score
+        descending, id descending).  Without `flt`, text ids the index does not hold take their place in the cut and are then
+        dropped; with it, text hits outside (filter AND live) are dropped before ranks are assigned.  vector_weight: None (0.5), a
+        scalar or one per query; NaN is refused.  Returns (ids, fused scores, counts): [nq][max(k, 1)] padded with id 2^64 - 1 /
+        NaN, and [nq]."""
+        qs = _f32(queries)
+        if qs.ndim == 1:
+            qs = qs.reshape(1, -1)
+        self._validate(qs)
+        nq, kk = qs.shape[0], max(k, 1)
+        tids, tn, ts = _id_lists(text_hits, nq)
+        w = _hybrid_weights(vector_weight, nq)
+        ids = np.full((nq, kk), _PAD_ID, dtype=np.uint64)          # (k = 0: the library writes counts only)
+        sc = np.full((nq, kk), np.nan, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        check(lib().vdb_hip_index_hybrid_search(self._h, flt._h if flt is not None else None, _ptr(qs) if nq else None, nq, k,
+                                                _ptr(tids) if ts else None, _ptr(tn) if nq else None, ts,
+                                                _ptr(w) if w is not None and nq else None, _ptr(ids), _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
+
+    def hybrid_search(self, query, text_hits, k: int, vector_weight=None) -> List[Tuple[int, float]]:
+        """Collection::hybrid_search (text.rs:113-203) for one query: `text_hits` = the ids text_index.search(text, 2k) returned.
+        (id, fused score), best first."""
+        ids, sc, cnt = self.hybrid_search_batch(_f32(query).reshape(1, -1), [text_hits], k, vector_weight)
+        return self._tuples(ids[0], sc[0], cnt[0])
+
+    def hybrid_search_with_filter(self, query, text_hits, k: int, vector_weight, flt: Filter) -> List[Tuple[int, float]]:
+        """Collection::hybrid_search_with_filter (text.rs:221-299) for one query, `flt` consulted inside the walk and in front of
+        the text ranks: `text_hits` = the ids text_index.search(text, max(4k, k + 10)) returned."""
+        ids, sc, cnt = self.hybrid_search_batch(_f32(query).reshape(1, -1), [text_hits], k, vector_weight, flt)
         return self._tuples(ids[0], sc[0], cnt[0])
 
     def search_brute_force_filtered(self, query, k: int, flt: Filter) -> List[Tuple[int, float]]:
