@@ -22,6 +22,7 @@
 #include "vdb_device.hpp"
 #include "vdb_index.hpp"
 #include "vdb_kernels.hpp"
+#include "vdb_sweep_pass.hpp"
 
 namespace vdb {
 
@@ -167,11 +168,11 @@ uint32_t bits_gemm_chunk(const vdb_hip_index* ix, uint32_t nq_left, uint32_t k) 
   return nqg >= min_q ? nqg : 0;
 }
 
-// nqg packed queries (qbits [nqg][words]) against the index's four-bit image: exact top-k per query into d_ids / d_scores / d_n
+// s.nq packed queries (qbits [s.nq][words]) against the index's four-bit image: exact top-k per query into the slice's outputs
 // (metric, img, cnt: the index's own bit metric over bits_img / bits_cnt, or VDB_HAMMING over the sign-bit codes' image — the Binary
 // storage mode, storage_modes.hip)
-int32_t brute_bits_gemm_dev(vdb_hip_index* ix, int metric, const uint8_t* img, const float* cnt, const uint32_t* qbits, uint32_t nqg, uint32_t k,
-                            uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
+int32_t brute_bits_gemm_dev(vdb_hip_index* ix, int metric, const uint8_t* img, const float* cnt, const uint32_t* qbits, const QuerySlice& s, hipStream_t st) {
+  const uint32_t nqg = s.nq, k = s.k;
   const bool hib = metric == VDB_JACCARD;
   const uint8_t* alive = search_alive(ix);
   const uint32_t n = (uint32_t)ix->n_rows, stride = bits_image_stride(ix->dim), dim2 = stride / 2;  // the kernel's unit: two bytes
@@ -241,15 +242,7 @@ int32_t brute_bits_gemm_dev(vdb_hip_index* ix, int metric, const uint8_t* img, c
       });
   if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("bit-metric GEMM launch: ") + hipGetErrorString(e));
   if (evg) (void)hipEventRecord(evg->b, st);
-  MergeArgs mg{};
-  mg.part_keys = parts;
-  mg.ext_ids = ix->ext_ids.as<uint64_t>();
-  mg.out_ids = d_ids;
-  mg.out_scores = d_scores;
-  mg.out_n = d_n;
-  mg.n_lists = lists;
-  mg.k = k;
-  launch_merge(hib, mg, nqg, st);
+  merge_pass(ix, hib, parts, nullptr, lists, s, st);
   VDB_HIP(hipGetLastError());
   return VDB_OK;
 }

@@ -13,6 +13,7 @@
 #include "vdb_kernels.hpp"
 #include "vdb_select_stage.hpp"
 #include "vdb_filter_route.hpp"
+#include "vdb_sweep_pass.hpp"
 
 namespace vdb {
 
@@ -27,11 +28,9 @@ static std::atomic<int> g_split_selector{3};  // large exact Cosine / Dot batche
 static std::atomic<uint32_t> g_int8_oversampling{4};  // DualPrecisionConfig::default().oversampling_ratio (dual_precision.rs:57)
 
 // effective option values of a handle: its own (vdb_hip_index_set_option) or the process-wide default
-static inline uint32_t opt_max_tile(const vdb_hip_index* ix) { return ix->opt[VDB_OPT_MAX_QUERY_TILE] >= 0 ? (uint32_t)ix->opt[VDB_OPT_MAX_QUERY_TILE] : (uint32_t)g_max_tile.load(); }
 // one-launch packed-bit search for calls of one or two queries: the default engine's path (engine 0 keeps the three-launch form, so
 // both stay under the parity tests); probe builds: VELESDB_BITS_FUSED=0 turns it off for A/B runs
 bool opt_bits_fused(const vdb_hip_index* ix);
-static inline int opt_engine(const vdb_hip_index* ix) { return ix->opt[VDB_OPT_SWEEP_ENGINE] >= 0 ? ix->opt[VDB_OPT_SWEEP_ENGINE] : g_sweep_engine.load(); }
 bool opt_bits_fused(const vdb_hip_index* ix) {
   static const bool off = [] {
     const char* e = vdb::probe_env("VELESDB_BITS_FUSED");
@@ -46,8 +45,8 @@ static inline bool opt_timing(const vdb_hip_index* ix) { return (ix->opt[VDB_OPT
 static constexpr int32_t kOptDefaultCombineMaxBatch = 256, kOptDefaultCombineWindowUs = 100, kOptDefaultCombineInflight = 0;
 int64_t opt_value(const vdb_hip_index* ix, int32_t option) {
   switch (option) {
-    case VDB_OPT_MAX_QUERY_TILE: return opt_max_tile(ix);
-    case VDB_OPT_SWEEP_ENGINE: return opt_engine(ix);
+    case VDB_OPT_MAX_QUERY_TILE: return ix->opt[option] >= 0 ? ix->opt[option] : (int64_t)g_max_tile.load();
+    case VDB_OPT_SWEEP_ENGINE: return ix->opt[option] >= 0 ? ix->opt[option] : g_sweep_engine.load();
     case VDB_OPT_SELECTOR_LEVEL: return opt_selector(ix);
     case VDB_OPT_INT8_OVERSAMPLING: return opt_oversampling(ix);
     case VDB_OPT_KERNEL_TIMING: return opt_timing(ix) ? 1 : 0;
@@ -537,408 +536,320 @@ int blocks_for(const vdb_hip_index* ix, int B, uint32_t ngroups) {
   return (int)std::max<int64_t>(1, std::min(want, cap));
 }
 
-// HnswIndex::search_brute_force (search.rs:176-219) for nq device-resident queries.
-// Outputs are device buffers; nothing synchronises.
-static int32_t brute_filtered_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                                  float* d_scores, uint32_t* d_n, hipStream_t st);
-static int32_t brute_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k,
-                         uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
-  if (nq == 0) return VDB_OK;
-  if (k == 0 || ix->n_rows == 0) {
-    VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
-    return VDB_OK;
+// The exact dispatch, defined below in this order; a filtered call picks its route in brute_filtered(_mode)_dev and, on the
+// mask-substitution route, comes back to brute_dev / brute_mode_dev through brute_masked_dev
+static int32_t brute_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st);
+static int32_t brute_filtered_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st);
+static int32_t brute_masked_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st, int32_t mode = VDB_SEARCH_BRUTE);
+static int32_t brute_mode_dev(vdb_hip_index* ix, int32_t mode, const QuerySlice& s, hipStream_t st);
+
+// ---- packed bits: Hamming / Jaccard indexes and, from storage_modes.hip, the sign-bit codes of the Binary storage mode (BitsSource) ----
+// the queries of a Hamming / Jaccard index: packed by the same kernel that packs rows
+static void pack_queries_as_rows(const vdb_hip_index* ix, const QuerySlice& s, uint32_t* qbits, hipStream_t st) {
+  PrepArgs pa{};
+  pa.rows = s.d_q;
+  pa.bits = qbits;
+  pa.row_stride = s.q_stride;
+  pa.n_rows = s.nq;
+  pa.dim = ix->dim;
+  pa.words = ix->words;
+  launch_prep_rows(pa, st);
+}
+
+int32_t brute_bits_dev(vdb_hip_index* ix, const BitsSource& src, const QuerySlice& s, hipStream_t st) {
+  const uint32_t k = s.k;
+  if ((size_t)4 * k * 8 + (size_t)ix->words * 4 + 32 > 60 * 1024)
+    return fail(VDB_ERR_UNSUPPORTED, "k too large for the fused top-k path");
+  const uint8_t* alive = search_alive(ix);
+  // one or two queries: ONE launch — the blocks pack the query themselves, and the one that finishes last merges (sweep.hip)
+  if (opt_bits_fused(ix) && sweep_bits_fused_supported(ix->words, s.nq, k)) {
+    const int fblocks = sweep_bits_fused_blocks(ix->n_rows, ix->n_cus);
+    if (ix->s_tickets.cap == 0) {
+      if (ix->s_tickets.reserve(16, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "ticket scratch");
+      VDB_HIP(hipMemsetAsync(ix->s_tickets.p, 0, 16, st));
+    }
+    if (ix->s_part_keys.reserve((size_t)s.nq * fblocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+    BitsFusedArgs fa{};
+    fa.bits = src.bits;
+    fa.q = s.d_q;
+    fa.q_stride = s.q_stride;
+    fa.alive = alive;
+    fa.part_keys = ix->s_part_keys.as<uint64_t>();
+    fa.tickets = ix->s_tickets.as<uint32_t>();
+    fa.n_rows = (uint32_t)ix->n_rows;
+    fa.words = ix->words;
+    fa.dim = ix->dim;
+    fa.k = k;
+    fa.sign_rule = src.sign_rule;
+    fa.m.ext_ids = ix->ext_ids.as<uint64_t>();
+    fa.m.out_ids = s.d_ids;
+    fa.m.out_scores = s.d_scores;
+    fa.m.out_n = s.d_n;
+    return timed_launch(ix, VDB_KERNEL_BITS, st, src.what_fused, [&] { return launch_sweep_bits_fused(src.metric, fa, fblocks, s.nq, st); });
   }
+  if (ix->s_qbits.reserve((size_t)s.nq * ix->words * 4, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "qbits scratch");
+  src.pack_queries(ix, s, ix->s_qbits.as<uint32_t>(), st);
+  // large batches: the dot products as a four-bit GEMM on the matrix cores, exact (bits_gemm.hip); what is left of the batch
+  // (and every other shape) keeps the vector-ALU kernels below — the same keys either way
+  uint32_t qdone = 0;
+  while (opt_engine(ix) == 1 && opt_max_tile(ix) >= 128) {
+    const uint32_t nqg = bits_gemm_chunk(ix, s.nq - qdone, k);
+    if (!nqg) break;
+    int32_t rg = src.ensure_image(ix, st);
+    if (rg == VDB_OK)
+      rg = brute_bits_gemm_dev(ix, src.metric, (ix->*src.img).as<uint8_t>(), (ix->*src.cnt).as<float>(),
+                               ix->s_qbits.as<uint32_t>() + (size_t)qdone * ix->words, s.sub(qdone, nqg), st);
+    if (rg != VDB_OK) return rg;
+    qdone += nqg;
+  }
+  if (qdone == s.nq) return VDB_OK;
+  const QuerySlice rest = s.sub(qdone, s.nq - qdone);
+  const BitsPlan bp = plan_bits_sweep(ix->n_rows, ix->n_cus, ix->words, rest.nq, k);  // 8 / 32 queries per corpus pass
+  const uint32_t nw = (uint32_t)bp.blocks;  // one list per block
+  if (ix->s_part_keys.reserve((size_t)rest.nq * nw * k * 8, false, st) != hipSuccess ||
+      ix->s_part_cnt.reserve((size_t)rest.nq * nw * 4, false, st) != hipSuccess)
+    return fail(VDB_ERR_OOM, "top-k scratch");
+  BitsArgs ba{};
+  ba.bits = src.bits;
+  ba.qbits = ix->s_qbits.as<uint32_t>() + (size_t)qdone * ix->words;
+  ba.alive = alive;
+  ba.part_keys = ix->s_part_keys.as<uint64_t>();
+  ba.part_cnt = ix->s_part_cnt.as<uint32_t>();
+  ba.n_rows = (uint32_t)ix->n_rows;
+  ba.words = ix->words;
+  ba.k = k;
+  const int32_t rc = timed_launch(ix, VDB_KERNEL_BITS, st, src.what_sweep, [&] { return launch_bits_plan(src.metric, bp, ba, rest.nq, st); });
+  if (rc != VDB_OK) return rc;
+  merge_pass(ix, src.higher_is_better, ba.part_keys, ba.part_cnt, nw, rest, st);
+  VDB_HIP(hipGetLastError());
+  return VDB_OK;
+}
+
+// ---- f32 rows: the tiers of brute_dev's ladder.  Each is asked for the front of what is left of the batch (`rest`) ----
+// matrix-core engine (cosine / dot): one to three 16-query tiles per corpus pass; 0: does not fit the LDS (very large dim or k), or
+// another engine / metric — the VALU kernels
+static int mfma_query_tiles(const vdb_hip_index* ix, uint32_t nq_left, uint32_t k) {
+  if (opt_engine(ix) != 1 || (ix->metric != VDB_COSINE && ix->metric != VDB_DOT)) return 0;
+  int want = (nq_left > 32 && opt_max_tile(ix) >= 48) ? 3 : ((nq_left > 16 && opt_max_tile(ix) >= 32) ? 2 : 1);
+  for (; want >= 1; want--)
+    if (sweep_mfma_lds_bytes(want, k, ix->dim) <= 160 * 1024) break;
+  return want;
+}
+
+// a chunk through the selection stage (select_stage.hip: selection on the bf16 matrix pipe + exact re-scoring + proof, the same bits as
+// the exact kernels, which remain the fallback for unproven queries and every other shape).  level 4: the WIDE selection (sweep_wide.hip
+// — no block-local lists, every row above the bound is a candidate); 1 / 2: split / plain bf16 selection — Euclidean (2) over the
+// augmented form s = q.v - |v|^2 / 2, unproven queries gathered on the device.  The ladder has asked select_level_* first.
+static Took tier_select(vdb_hip_index* ix, const QuerySlice& rest, int level, hipStream_t st) {
+  const QuerySlice c = rest.sub(0, select_chunk(rest.nq));
+  const int32_t rc = level == 4 ? brute_wide_dev(ix, c.d_q, c.q_stride, c.nq, c.k, c.d_ids, c.d_scores, c.d_n, st)
+                                : brute_split_dev(ix, c.d_q, c.q_stride, c.nq, c.k, c.d_ids, c.d_scores, c.d_n, st, level);
+  return rc != VDB_OK ? Took(rc) : Took::queries(c.nq);
+}
+
+// Euclidean batches: approximate selection of k + slack candidates on the matrix cores, canonical re-scoring, proof of exactness per
+// query (read on the host: one synchronisation); the (rare) unproven queries go through the exact vector-ALU sweep one by one, a
+// chunk where more than one in eight lacks a proof is handed back whole
+static Took tier_euclid_gemm(vdb_hip_index* ix, const QuerySlice& rest, hipStream_t st) {
+  const uint32_t k = rest.k;
+  if (ix->metric != VDB_EUCLIDEAN || opt_engine(ix) != 1 || opt_max_tile(ix) < 128 || rest.nq < kGemmMinQueries || k + kEuclidSlack > kGemmMaxK)
+    return Took();
+  const QuerySlice c = rest.sub(0, std::min<uint32_t>(rest.nq, kGemmMaxQueries));
+  const uint32_t nqg = c.nq;
+  // k <= 10: 16 candidates — the 32-entry candidate buffers then leave room for two blocks per CU; the per-query
+  // verdict catches the (rare) query whose near-ties are wider than the slack
+  const uint32_t kp = k + 6 <= 16 ? 16 : k + kEuclidSlack;
+  GemmPlan gp;
+  sweep_gemm_plan(nqg, (uint32_t)ix->n_rows, ix->n_cus, kp, &gp);
+  if (gp.lds > 160 * 1024) return Took();
+  // scratch: norm max (16 B) | flags [nqg] | cand n [nqg] | cand approx [nqg][kp] | cand rows [nqg][kp] (8-B aligned)
+  const size_t off_flags = 16, off_n = off_flags + (size_t)nqg * 4, off_ap = off_n + (size_t)nqg * 4;
+  const size_t off_rows = (off_ap + (size_t)nqg * kp * 4 + 15) & ~(size_t)15;
+  if (ix->s_part_keys.reserve((size_t)nqg * gp.G * kp * 8, false, st) != hipSuccess ||
+      ix->s_misc.reserve(off_rows + (size_t)nqg * kp * 8, false, st) != hipSuccess)
+    return fail(VDB_ERR_OOM, "top-k scratch");
+  unsigned char* sc = ix->s_misc.as<unsigned char>();
+  SweepArgs ag = sweep_args(ix, c);
+  ag.part_keys = ix->s_part_keys.as<uint64_t>();
+  ag.nq = nqg;
+  ag.k = kp;
+  const int32_t rcl = timed_launch(ix, VDB_KERNEL_GEMM_F32, st, "gemm sweep launch", [&] { return launch_sweep_gemm(VDB_EUCLIDEAN, gp, ag, st); });
+  if (rcl != VDB_OK) return rcl;
+  // the kp candidates per query: internal rows and approximate values, in the scratch
+  const QuerySlice cand{nullptr, 0, nqg, kp, reinterpret_cast<uint64_t*>(sc + off_rows), reinterpret_cast<float*>(sc + off_ap),
+                        reinterpret_cast<uint32_t*>(sc + off_n)};
+  merge_pass(false, ag.part_keys, nullptr, gp.G, cand, st, /*ext_ids=*/nullptr);
+  EuclidRerankArgs ra{};
+  ra.rows = ag.rows;
+  ra.queries = ag.queries;
+  ra.cand_rows = cand.d_ids;
+  ra.cand_approx = cand.d_scores;
+  ra.cand_n = cand.d_n;
+  ra.ext_ids = ix->ext_ids.as<uint64_t>();
+  ra.norm_max_bits = reinterpret_cast<const uint32_t*>(sc);
+  ra.out_ids = c.d_ids;
+  ra.out_scores = c.d_scores;
+  ra.out_n = c.d_n;
+  ra.flags = reinterpret_cast<uint32_t*>(sc + off_flags);
+  ra.row_stride = ix->row_stride;
+  ra.q_stride = c.q_stride;
+  ra.dim = ix->dim;
+  ra.k = k;
+  ra.kp = kp;
+  launch_euclid_rerank(ra, ag.norms, ag.n_rows, nqg, st);
+  VDB_HIP(hipGetLastError());
+  std::vector<uint32_t> flags(nqg);
+  VDB_HIP(hipMemcpyAsync(flags.data(), ra.flags, (size_t)nqg * 4, hipMemcpyDeviceToHost, st));
+  VDB_HIP(hipStreamSynchronize(st));
+  uint32_t n_flagged = 0;
+  for (uint32_t i = 0; i < nqg; i++) n_flagged += flags[i] ? 1u : 0u;
+  if (n_flagged > nqg / 8) {
+    // tie-heavy data (duplicates, low-cardinality values): most queries lack a proof — the whole chunk goes through
+    // the exact vector-ALU tiles instead of one sweep per query
+    ix->euclid_fallbacks += nqg;
+    Took back;
+    back.handed_back = nqg;
+    return back;
+  }
+  for (uint32_t i = 0; i < nqg; i++) {
+    if (!flags[i]) continue;
+    const int32_t rc1 = brute_dev(ix, c.query(i), st);
+    if (rc1 != VDB_OK) return rc1;
+    ix->euclid_fallbacks++;
+  }
+  return Took::queries(nqg);
+}
+
+// large Cosine / DotProduct batches: GEMM-structured matrix-core kernel, up to 1 024 queries in one launch (sweep_gemm.hip)
+static Took tier_gemm_f32(vdb_hip_index* ix, const QuerySlice& rest, hipStream_t st) {
+  const uint32_t k = rest.k;
+  if (opt_max_tile(ix) < 128 || rest.nq < kGemmMinQueries || k > kGemmMaxK) return Took();
+  const QuerySlice c = rest.sub(0, std::min<uint32_t>(rest.nq, kGemmMaxQueries));
+  GemmPlan gp;
+  sweep_gemm_plan(c.nq, (uint32_t)ix->n_rows, ix->n_cus, k, &gp);
+  if (gp.lds > 160 * 1024) return Took();
+  if (ix->s_part_keys.reserve((size_t)c.nq * gp.G * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+  SweepArgs ag = sweep_args(ix, c);
+  ag.part_keys = ix->s_part_keys.as<uint64_t>();
+  ag.nq = c.nq;
+  ag.k = k;
+  const int32_t rc = timed_launch(ix, VDB_KERNEL_GEMM_F32, st, "gemm sweep launch", [&] { return launch_sweep_gemm(ix->metric, gp, ag, st); });
+  if (rc != VDB_OK) return rc;
+  merge_pass(ix, higher_is_better_host(ix->metric), ag.part_keys, nullptr, gp.G, c, st);
+  return Took::queries(c.nq);
+}
+
+// Cosine / DotProduct: the streaming matrix-core kernel, nqt 16-query tiles per corpus pass (mfma_query_tiles)
+static Took tier_mfma_f32(vdb_hip_index* ix, const QuerySlice& rest, int nqt, hipStream_t st) {
+  const uint32_t k = rest.k, Bm = (uint32_t)nqt * 16;
+  const QuerySlice c = rest.sub(0, std::min<uint32_t>(Bm, rest.nq));
+  const int waves = nqt >= 2 ? kMfmaWaves2 : kMfmaWaves1;
+  const size_t lds = sweep_mfma_lds_bytes(nqt, k, ix->dim);
+  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, (size_t)(16 / waves)));
+  const uint32_t ntiles = (uint32_t)((ix->n_rows + 15) / 16);
+  const int blocks_m = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)ntiles + waves - 1) / waves, (int64_t)ix->n_cus * per_cu));
+  if (ix->s_part_keys.reserve((size_t)Bm * blocks_m * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+  SweepArgs am = sweep_args(ix, c);
+  am.part_keys = ix->s_part_keys.as<uint64_t>();
+  am.nq = c.nq;
+  am.k = k;
+  const int32_t rc = timed_launch(ix, VDB_KERNEL_SWEEP_MFMA_F32, st, "mfma sweep launch", [&] { return launch_sweep_mfma(ix->metric, nqt, am, blocks_m, st); });
+  if (rc != VDB_OK) return rc;
+  merge_pass(ix, higher_is_better_host(ix->metric), am.part_keys, nullptr, (uint32_t)blocks_m, c, st);
+  return Took::queries(c.nq);
+}
+
+// every metric and shape: the vector-ALU tiles — queries in LDS, 16 or 32 per corpus pass (dims that are a multiple of 256, <= 1024),
+// else the generic tiles of 8 / 4 / 2 / 1 queries
+static Took tier_valu(vdb_hip_index* ix, const QuerySlice& rest, hipStream_t st) {
+  const uint32_t k = rest.k;
+  uint32_t B = pick_B(ix, rest.nq);
+  const int cpl = sweep_cpl_for_dim(ix->dim);
+  bool qlds = false;
+  const uint32_t max_tile = opt_max_tile(ix);
+  if (cpl > 0 && rest.nq >= 12 && max_tile >= 16) {
+    const uint32_t want = (rest.nq >= 24 && max_tile >= 32) ? 32 : 16;
+    for (uint32_t b = want; b >= 16; b /= 2) {
+      const int waves = b == 32 ? kQldsWaves32 : kQldsWaves16;
+      if (sweep_qlds_lds_bytes((int)b, k, ix->dim, waves) <= 160 * 1024) {
+        B = b;
+        qlds = true;
+        break;
+      }
+    }
+  }
+  // generic dims keep the query tile in LDS: shrink the tile until it fits the default 64 KiB window
+  while (!qlds && B > 1 && sweep_lds_bytes((int)B, k, ix->dim, cpl) > 60 * 1024) B /= 2;
+  if (!qlds && sweep_lds_bytes((int)B, k, ix->dim, cpl) > 60 * 1024)
+    return fail(VDB_ERR_UNSUPPORTED, "k (x dim) too large for the fused top-k path");
+  const QuerySlice c = rest.sub(0, std::min<uint32_t>(B, rest.nq));
+  const uint32_t rpg = 64 / B;
+  const uint32_t ngroups = (uint32_t)((ix->n_rows + rpg - 1) / rpg);
+  int blocks;
+  if (qlds) {
+    const int waves = B == 32 ? kQldsWaves32 : kQldsWaves16;
+    const size_t lds = sweep_qlds_lds_bytes((int)B, k, ix->dim, waves);
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, (size_t)(B == 32 ? 1 : 3)));
+    blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)ngroups + waves - 1) / waves, (int64_t)ix->n_cus * per_cu));
+  } else {
+    blocks = blocks_for(ix, (int)B, ngroups);
+  }
+  const uint32_t nw = (uint32_t)blocks;  // one list per block
+  if (ix->s_part_keys.reserve((size_t)B * nw * k * 8, false, st) != hipSuccess || ix->s_part_cnt.reserve((size_t)B * nw * 4, false, st) != hipSuccess)
+    return fail(VDB_ERR_OOM, "top-k scratch");
+  SweepArgs a = sweep_args(ix, c);
+  a.part_keys = ix->s_part_keys.as<uint64_t>();
+  a.part_cnt = ix->s_part_cnt.as<uint32_t>();
+  a.nq = c.nq;
+  a.k = k;
+  const int32_t rc = timed_launch(ix, VDB_KERNEL_SWEEP_VALU, st, "sweep launch", [&] {
+    return qlds ? launch_sweep_f32_qlds(ix->metric, (int)B, a, blocks, st) : launch_sweep_f32(ix->metric, (int)B, a, blocks, st);
+  });
+  if (rc != VDB_OK) return rc;
+  merge_pass(ix, higher_is_better_host(ix->metric), a.part_keys, a.part_cnt, nw, c, st);
+  return Took::queries(c.nq);
+}
+
+// HnswIndex::search_brute_force (search.rs:176-219) for the slice's device-resident queries: the ladder.  Every chunk of the batch goes
+// to the first tier that takes it.  Outputs are device buffers; nothing synchronises (but tier_euclid_gemm's verdicts).
+static int32_t brute_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st) {
+  if (s.nq == 0) return VDB_OK;
+  if (s.k == 0 || ix->n_rows == 0) return zero_results(s, st);
   // a filtered call (vdb_hip_index_search_batch_filtered) picks its route first; on the mask-substitution route it comes back here
   // with the call's row mask in place of the soft-delete flags
-  if (ix->flt && !ix->alive_override) return brute_filtered_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  if (ix->flt && !ix->alive_override) return brute_filtered_dev(ix, s, st);
   // ... and keeps the selection stage only while enough rows are allowed for its seed sample (vdb_filter_route.hpp)
   const bool sel_ok = !ix->flt || filter_keeps_selection(ix->flt->count, ix->n_rows);
-  const bool hib = higher_is_better_host(ix->metric);
-  const uint8_t* alive = search_alive(ix);
   if (is_bits_metric(ix->metric)) {
-    if ((size_t)4 * k * 8 + (size_t)ix->words * 4 + 32 > 60 * 1024)
-      return fail(VDB_ERR_UNSUPPORTED, "k too large for the fused top-k path");
-    hipError_t e;
-    // one or two queries: ONE launch — the blocks pack the query themselves, and the one that finishes last merges (sweep.hip)
-    if (opt_bits_fused(ix) && sweep_bits_fused_supported(ix->words, nq, k)) {
-      const int fblocks = sweep_bits_fused_blocks(ix->n_rows, ix->n_cus);
-      if (ix->s_tickets.cap == 0) {
-        if ((e = ix->s_tickets.reserve(16, false, st)) != hipSuccess) return fail(VDB_ERR_OOM, "ticket scratch");
-        VDB_HIP(hipMemsetAsync(ix->s_tickets.p, 0, 16, st));
-      }
-      if ((e = ix->s_part_keys.reserve((size_t)nq * fblocks * k * 8, false, st)) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
-      BitsFusedArgs fa{};
-      fa.bits = ix->bits.as<uint32_t>();
-      fa.q = d_q;
-      fa.q_stride = q_stride;
-      fa.alive = alive;
-      fa.part_keys = ix->s_part_keys.as<uint64_t>();
-      fa.tickets = ix->s_tickets.as<uint32_t>();
-      fa.n_rows = (uint32_t)ix->n_rows;
-      fa.words = ix->words;
-      fa.dim = ix->dim;
-      fa.k = k;
-      fa.m.ext_ids = ix->ext_ids.as<uint64_t>();
-      fa.m.out_ids = d_ids;
-      fa.m.out_scores = d_scores;
-      fa.m.out_n = d_n;
-      ix->last_kernels |= VDB_KERNEL_BITS;
-      EventPair* evf = next_events(ix);
-      if (evf) (void)hipEventRecord(evf->a, st);
-      const hipError_t ef = launch_sweep_bits_fused(ix->metric, fa, fblocks, nq, st);
-      if (ef != hipSuccess) return fail(VDB_ERR_HIP, std::string("one-launch packed-bit search: ") + hipGetErrorString(ef));
-      if (evf) (void)hipEventRecord(evf->b, st);
-      return VDB_OK;
-    }
-    // pack the queries with the same kernel that packs rows
-    e = ix->s_qbits.reserve((size_t)nq * ix->words * 4, false, st);
-    if (e != hipSuccess) return fail(VDB_ERR_OOM, "qbits scratch");
-    PrepArgs pa{};
-    pa.rows = d_q;
-    pa.bits = ix->s_qbits.as<uint32_t>();
-    pa.row_stride = q_stride;
-    pa.n_rows = nq;
-    pa.dim = ix->dim;
-    pa.words = ix->words;
-    launch_prep_rows(pa, st);
-    // large batches: the dot products as a four-bit GEMM on the matrix cores, exact (bits_gemm.hip); what is left of the batch
-    // (and every other shape) keeps the vector-ALU kernels below — the same keys either way
-    uint32_t qdone = 0;
-    while (opt_engine(ix) == 1 && opt_max_tile(ix) >= 128) {
-      const uint32_t nqg = bits_gemm_chunk(ix, nq - qdone, k);
-      if (!nqg) break;
-      int32_t rg = ensure_bits_image(ix, st);
-      if (rg == VDB_OK)
-        rg = brute_bits_gemm_dev(ix, ix->metric, ix->bits_img.as<uint8_t>(), ix->bits_cnt.as<float>(), ix->s_qbits.as<uint32_t>() + (size_t)qdone * ix->words,
-                                 nqg, k, d_ids + (size_t)qdone * k, d_scores + (size_t)qdone * k, d_n + qdone, st);
-      if (rg != VDB_OK) return rg;
-      qdone += nqg;
-    }
-    if (qdone == nq) return VDB_OK;
-    d_ids += (size_t)qdone * k;
-    d_scores += (size_t)qdone * k;
-    d_n += qdone;
-    nq -= qdone;
-    const uint32_t* qbits_rest = ix->s_qbits.as<uint32_t>() + (size_t)qdone * ix->words;
-    const BitsPlan bp = plan_bits_sweep(ix->n_rows, ix->n_cus, ix->words, nq, k);
-    const int blocks = bp.blocks;
-    const uint32_t nw = (uint32_t)blocks;  // one list per block
-    if ((e = ix->s_part_keys.reserve((size_t)nq * nw * k * 8, false, st)) != hipSuccess ||
-        (e = ix->s_part_cnt.reserve((size_t)nq * nw * 4, false, st)) != hipSuccess)
-      return fail(VDB_ERR_OOM, "top-k scratch");
-    BitsArgs ba{};
-    ba.bits = ix->bits.as<uint32_t>();
-    ba.qbits = qbits_rest;
-    ba.alive = alive;
-    ba.part_keys = ix->s_part_keys.as<uint64_t>();
-    ba.part_cnt = ix->s_part_cnt.as<uint32_t>();
-    ba.n_rows = (uint32_t)ix->n_rows;
-    ba.words = ix->words;
-    ba.k = k;
-    ix->last_kernels |= VDB_KERNEL_BITS;
-    EventPair* ev = next_events(ix);
-    if (ev) (void)hipEventRecord(ev->a, st);
-    {
-      hipError_t eb = launch_bits_plan(ix->metric, bp, ba, nq, st);
-      if (eb != hipSuccess) return fail(VDB_ERR_HIP, std::string("packed-bit sweep launch: ") + hipGetErrorString(eb));
-    }
-    if (ev) (void)hipEventRecord(ev->b, st);
-    MergeArgs m{};
-    m.part_keys = ba.part_keys;
-    m.part_cnt = ba.part_cnt;
-    m.ext_ids = ix->ext_ids.as<uint64_t>();
-    m.out_ids = d_ids;
-    m.out_scores = d_scores;
-    m.out_n = d_n;
-    m.n_lists = nw;
-    m.k = k;
-    launch_merge(hib, m, nq, st);
-    VDB_HIP(hipGetLastError());
-    return VDB_OK;
+    const BitsSource src{ix->bits.as<uint32_t>(), pack_queries_as_rows, ix->metric, ensure_bits_image, &vdb_hip_index::bits_img, &vdb_hip_index::bits_cnt,
+                         /*sign_rule=*/0u, higher_is_better_host(ix->metric), "one-launch packed-bit search", "packed-bit sweep launch"};
+    return brute_bits_dev(ix, src, s, st);
   }
+  const bool euclid = ix->metric == VDB_EUCLIDEAN;
   uint32_t euclid_skip_until = 0;  // Euclidean chunk without proofs: [q0, this) goes through the exact tiles
-  for (uint32_t q0 = 0; q0 < nq;) {
-    uint32_t B = pick_B(ix, nq - q0);
-    const int cpl = sweep_cpl_for_dim(ix->dim);
-    // matrix-core engine (cosine / dot): one or two 16-query tiles per corpus pass
-    int mfma_nqt = 0;
-    if (opt_engine(ix) == 1 && (ix->metric == VDB_COSINE || ix->metric == VDB_DOT)) {
-      int want = (nq - q0 > 32 && opt_max_tile(ix) >= 48) ? 3 : ((nq - q0 > 16 && opt_max_tile(ix) >= 32) ? 2 : 1);
-      for (; want >= 1; want--)
-        if (sweep_mfma_lds_bytes(want, k, ix->dim) <= 160 * 1024) break;
-      mfma_nqt = want;  // 0: does not fit the LDS (very large dim or k): VALU kernels
+  for (uint32_t q0 = 0; q0 < s.nq;) {
+    const QuerySlice rest = s.sub(q0, s.nq - q0);
+    const int mfma_nqt = mfma_query_tiles(ix, rest.nq, s.k);
+    const bool fresh = q0 >= euclid_skip_until;
+    // the select_level_* rules keep state (the verdicts they have seen, the hold counters): each is asked only when everything to its
+    // left holds, and in this order
+    Took t;
+    int level = 0;
+    if (sel_ok && (mfma_nqt || euclid) && fresh && select_level_wide(ix, rest.nq, s.k)) {
+      t = tier_select(ix, rest, 4, st);
+    } else if ((level = (sel_ok && mfma_nqt) ? select_level(ix, rest.nq, s.k) : 0) != 0) {
+      t = tier_select(ix, rest, level, st);
+    } else if (sel_ok && euclid && fresh && select_level_l2(ix, rest.nq, s.k)) {
+      t = tier_select(ix, rest, 2, st);
+    } else if (fresh) {
+      t = tier_euclid_gemm(ix, rest, st);
+      if (t.handed_back) euclid_skip_until = q0 + t.handed_back;
     }
-    // large Cosine / DotProduct batches over a large corpus: split-bf16 selection + exact re-scoring + proof (same bits
-    // as the exact matrix-core kernel below, which remains the fallback for unproven queries and every other shape)
-    // ... and with 10 < k <= 128: the WIDE selection (sweep_wide.hip) — no block-local lists, every row above the bound is a candidate
-    if (sel_ok && (mfma_nqt || ix->metric == VDB_EUCLIDEAN) && q0 >= euclid_skip_until && select_level_wide(ix, nq - q0, k)) {
-      const uint32_t nqg = select_chunk(nq - q0);
-      const int32_t rcw = brute_wide_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nqg, k, d_ids + (size_t)q0 * k, d_scores + (size_t)q0 * k, d_n + q0, st);
-      if (rcw != VDB_OK) return rcw;
-      q0 += nqg;
-      continue;
-    }
-    const int sel_level = (sel_ok && mfma_nqt) ? select_level(ix, nq - q0, k) : 0;
-    if (sel_level) {
-      const uint32_t nqg = select_chunk(nq - q0);
-      const int32_t rcs = brute_split_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nqg, k, d_ids + (size_t)q0 * k,
-                                          d_scores + (size_t)q0 * k, d_n + q0, st, sel_level);
-      if (rcs != VDB_OK) return rcs;
-      q0 += nqg;
-      continue;
-    }
-    // Euclidean batches, first choice: the selection stage of the Cosine / DotProduct batches over the augmented form
-    // s = q.v - |v|^2 / 2 (bf16 matrix pipe, canonical re-scoring, proof, unproven queries gathered on the device — no host
-    // synchronisation); the f32 matrix-core path below remains for the shapes it does not take and for handles it parks
-    if (sel_ok && ix->metric == VDB_EUCLIDEAN && q0 >= euclid_skip_until && select_level_l2(ix, nq - q0, k)) {
-      const uint32_t nqg = select_chunk(nq - q0);
-      const int32_t rcs = brute_split_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nqg, k, d_ids + (size_t)q0 * k,
-                                          d_scores + (size_t)q0 * k, d_n + q0, st, 2);
-      if (rcs != VDB_OK) return rcs;
-      q0 += nqg;
-      continue;
-    }
-    // Euclidean batches: approximate selection of k + slack candidates on the matrix cores, canonical re-scoring, proof
-    // of exactness per query; the (rare) unproven queries go through the exact vector-ALU sweep below
-    if (ix->metric == VDB_EUCLIDEAN && opt_engine(ix) == 1 && opt_max_tile(ix) >= 128 && nq - q0 >= kGemmMinQueries &&
-        k + kEuclidSlack <= kGemmMaxK && q0 >= euclid_skip_until) {
-      const uint32_t nqg = std::min<uint32_t>(nq - q0, kGemmMaxQueries);
-      // k <= 10: 16 candidates — the 32-entry candidate buffers then leave room for two blocks per CU; the per-query
-      // verdict catches the (rare) query whose near-ties are wider than the slack
-      const uint32_t kp = k + 6 <= 16 ? 16 : k + kEuclidSlack;
-      GemmPlan gp;
-      sweep_gemm_plan(nqg, (uint32_t)ix->n_rows, ix->n_cus, kp, &gp);
-      if (gp.lds <= 160 * 1024) {
-        hipError_t e3;
-        // scratch: norm max (16 B) | flags [nqg] | cand n [nqg] | cand approx [nqg][kp] | cand rows [nqg][kp] (8-B aligned)
-        const size_t off_flags = 16, off_n = off_flags + (size_t)nqg * 4, off_ap = off_n + (size_t)nqg * 4;
-        const size_t off_rows = (off_ap + (size_t)nqg * kp * 4 + 15) & ~(size_t)15;
-        if ((e3 = ix->s_part_keys.reserve((size_t)nqg * gp.G * kp * 8, false, st)) != hipSuccess ||
-            (e3 = ix->s_misc.reserve(off_rows + (size_t)nqg * kp * 8, false, st)) != hipSuccess)
-          return fail(VDB_ERR_OOM, "top-k scratch");
-        unsigned char* sc = ix->s_misc.as<unsigned char>();
-        SweepArgs ag{};
-        ag.rows = ix->rows.as<float>();
-        ag.norms = ix->norms.as<float>();
-        ag.alive = alive;
-        ag.queries = d_q + (size_t)q0 * q_stride;
-        ag.part_keys = ix->s_part_keys.as<uint64_t>();
-        ag.row_stride = ix->row_stride;
-        ag.q_stride = q_stride;
-        ag.n_rows = (uint32_t)ix->n_rows;
-        ag.dim = ix->dim;
-        ag.nq = nqg;
-        ag.k = kp;
-        EventPair* evg = next_events(ix);
-        if (evg) (void)hipEventRecord(evg->a, st);
-        ix->last_kernels |= VDB_KERNEL_GEMM_F32;
-        e3 = launch_sweep_gemm(VDB_EUCLIDEAN, gp, ag, st);
-        if (evg) (void)hipEventRecord(evg->b, st);
-        if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("gemm sweep launch: ") + hipGetErrorString(e3));
-        MergeArgs mg{};
-        mg.part_keys = ag.part_keys;
-        mg.ext_ids = nullptr;  // internal rows
-        mg.out_ids = reinterpret_cast<uint64_t*>(sc + off_rows);
-        mg.out_scores = reinterpret_cast<float*>(sc + off_ap);
-        mg.out_n = reinterpret_cast<uint32_t*>(sc + off_n);
-        mg.n_lists = gp.G;
-        mg.k = kp;
-        launch_merge(false, mg, nqg, st);
-        EuclidRerankArgs ra{};
-        ra.rows = ag.rows;
-        ra.queries = ag.queries;
-        ra.cand_rows = mg.out_ids;
-        ra.cand_approx = mg.out_scores;
-        ra.cand_n = mg.out_n;
-        ra.ext_ids = ix->ext_ids.as<uint64_t>();
-        ra.norm_max_bits = reinterpret_cast<const uint32_t*>(sc);
-        ra.out_ids = d_ids + (size_t)q0 * k;
-        ra.out_scores = d_scores + (size_t)q0 * k;
-        ra.out_n = d_n + q0;
-        ra.flags = reinterpret_cast<uint32_t*>(sc + off_flags);
-        ra.row_stride = ix->row_stride;
-        ra.q_stride = q_stride;
-        ra.dim = ix->dim;
-        ra.k = k;
-        ra.kp = kp;
-        launch_euclid_rerank(ra, ag.norms, ag.n_rows, nqg, st);
-        VDB_HIP(hipGetLastError());
-        std::vector<uint32_t> flags(nqg);
-        VDB_HIP(hipMemcpyAsync(flags.data(), ra.flags, (size_t)nqg * 4, hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipStreamSynchronize(st));
-        uint32_t n_flagged = 0;
-        for (uint32_t i = 0; i < nqg; i++) n_flagged += flags[i] ? 1u : 0u;
-        if (n_flagged > nqg / 8) {
-          // tie-heavy data (duplicates, low-cardinality values): most queries lack a proof — the whole chunk goes through
-          // the exact vector-ALU tiles below instead of one sweep per query
-          ix->euclid_fallbacks += nqg;
-          euclid_skip_until = q0 + nqg;
-          continue;
-        }
-        for (uint32_t i = 0; i < nqg; i++) {
-          if (!flags[i]) continue;
-          const int32_t rc1 = brute_dev(ix, d_q + (size_t)(q0 + i) * q_stride, q_stride, 1, k, d_ids + (size_t)(q0 + i) * k,
-                                        d_scores + (size_t)(q0 + i) * k, d_n + q0 + i, st);
-          if (rc1 != VDB_OK) return rc1;
-          ix->euclid_fallbacks++;
-        }
-        q0 += nqg;
-        continue;
-      }
-    }
-    // large batches: GEMM-structured matrix-core kernel, the whole batch in one launch (sweep_gemm.hip)
-    if (mfma_nqt && opt_max_tile(ix) >= 128 && nq - q0 >= kGemmMinQueries && k <= kGemmMaxK) {
-      const uint32_t nqg = std::min<uint32_t>(nq - q0, kGemmMaxQueries);
-      GemmPlan gp;
-      sweep_gemm_plan(nqg, (uint32_t)ix->n_rows, ix->n_cus, k, &gp);
-      if (gp.lds <= 160 * 1024) {
-        hipError_t e3;
-        if ((e3 = ix->s_part_keys.reserve((size_t)nqg * gp.G * k * 8, false, st)) != hipSuccess)
-          return fail(VDB_ERR_OOM, "top-k scratch");
-        SweepArgs ag{};
-        ag.rows = ix->rows.as<float>();
-        ag.norms = ix->norms.as<float>();
-        ag.alive = alive;
-        ag.queries = d_q + (size_t)q0 * q_stride;
-        ag.part_keys = ix->s_part_keys.as<uint64_t>();
-        ag.row_stride = ix->row_stride;
-        ag.q_stride = q_stride;
-        ag.n_rows = (uint32_t)ix->n_rows;
-        ag.dim = ix->dim;
-        ag.nq = nqg;
-        ag.k = k;
-        EventPair* evg = next_events(ix);
-        if (evg) (void)hipEventRecord(evg->a, st);
-        ix->last_kernels |= VDB_KERNEL_GEMM_F32;
-        e3 = launch_sweep_gemm(ix->metric, gp, ag, st);
-        if (evg) (void)hipEventRecord(evg->b, st);
-        if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("gemm sweep launch: ") + hipGetErrorString(e3));
-        MergeArgs mg{};
-        mg.part_keys = ag.part_keys;
-        mg.ext_ids = ix->ext_ids.as<uint64_t>();
-        mg.out_ids = d_ids + (size_t)q0 * k;
-        mg.out_scores = d_scores + (size_t)q0 * k;
-        mg.out_n = d_n + q0;
-        mg.n_lists = gp.G;
-        mg.k = k;
-        launch_merge(hib, mg, nqg, st);
-        q0 += nqg;
-        continue;
-      }
-    }
-    if (mfma_nqt) {
-      const uint32_t Bm = (uint32_t)mfma_nqt * 16;
-      const uint32_t tile_m = std::min<uint32_t>(Bm, nq - q0);
-      const int waves = mfma_nqt >= 2 ? kMfmaWaves2 : kMfmaWaves1;
-      const size_t lds = sweep_mfma_lds_bytes(mfma_nqt, k, ix->dim);
-      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, (size_t)(16 / waves)));
-      const uint32_t ntiles = (uint32_t)((ix->n_rows + 15) / 16);
-      const int blocks_m = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)ntiles + waves - 1) / waves,
-                                                                     (int64_t)ix->n_cus * per_cu));
-      hipError_t e2;
-      if ((e2 = ix->s_part_keys.reserve((size_t)Bm * blocks_m * k * 8, false, st)) != hipSuccess)
-        return fail(VDB_ERR_OOM, "top-k scratch");
-      SweepArgs am{};
-      am.rows = ix->rows.as<float>();
-      am.norms = ix->norms.as<float>();
-      am.alive = alive;
-      am.queries = d_q + (size_t)q0 * q_stride;
-      am.part_keys = ix->s_part_keys.as<uint64_t>();
-      am.row_stride = ix->row_stride;
-      am.q_stride = q_stride;
-      am.n_rows = (uint32_t)ix->n_rows;
-      am.dim = ix->dim;
-      am.nq = tile_m;
-      am.k = k;
-      EventPair* evm = next_events(ix);
-      if (evm) (void)hipEventRecord(evm->a, st);
-      ix->last_kernels |= VDB_KERNEL_SWEEP_MFMA_F32;
-      e2 = launch_sweep_mfma(ix->metric, mfma_nqt, am, blocks_m, st);
-      if (evm) (void)hipEventRecord(evm->b, st);
-      if (e2 != hipSuccess) return fail(VDB_ERR_HIP, std::string("mfma sweep launch: ") + hipGetErrorString(e2));
-      MergeArgs mm{};
-      mm.part_keys = am.part_keys;
-      mm.ext_ids = ix->ext_ids.as<uint64_t>();
-      mm.out_ids = d_ids + (size_t)q0 * k;
-      mm.out_scores = d_scores + (size_t)q0 * k;
-      mm.out_n = d_n + q0;
-      mm.n_lists = (uint32_t)blocks_m;
-      mm.k = k;
-      launch_merge(hib, mm, tile_m, st);
-      q0 += tile_m;
-      continue;
-    }
-    // large tiles: queries in LDS, 16 or 32 per corpus pass (dims that are a multiple of 256, <= 1024)
-    bool qlds = false;
-    const uint32_t max_tile = opt_max_tile(ix);
-    if (cpl > 0 && nq - q0 >= 12 && max_tile >= 16) {
-      const uint32_t want = (nq - q0 >= 24 && max_tile >= 32) ? 32 : 16;
-      for (uint32_t b = want; b >= 16; b /= 2) {
-        const int waves = b == 32 ? kQldsWaves32 : kQldsWaves16;
-        if (sweep_qlds_lds_bytes((int)b, k, ix->dim, waves) <= 160 * 1024) {
-          B = b;
-          qlds = true;
-          break;
-        }
-      }
-    }
-    // generic dims keep the query tile in LDS: shrink the tile until it fits the default 64 KiB window
-    while (!qlds && B > 1 && sweep_lds_bytes((int)B, k, ix->dim, cpl) > 60 * 1024) B /= 2;
-    const uint32_t tile = std::min<uint32_t>(B, nq - q0);
-    if (!qlds && sweep_lds_bytes((int)B, k, ix->dim, cpl) > 60 * 1024)
-      return fail(VDB_ERR_UNSUPPORTED, "k (x dim) too large for the fused top-k path");
-    const uint32_t rpg = 64 / B;
-    const uint32_t ngroups = (uint32_t)((ix->n_rows + rpg - 1) / rpg);
-    int blocks;
-    if (qlds) {
-      const int waves = B == 32 ? kQldsWaves32 : kQldsWaves16;
-      const size_t lds = sweep_qlds_lds_bytes((int)B, k, ix->dim, waves);
-      const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, (size_t)(B == 32 ? 1 : 3)));
-      blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)ngroups + waves - 1) / waves,
-                                                           (int64_t)ix->n_cus * per_cu));
-    } else {
-      blocks = blocks_for(ix, (int)B, ngroups);
-    }
-    const uint32_t nw = (uint32_t)blocks;  // one list per block
-    hipError_t e;
-    if ((e = ix->s_part_keys.reserve((size_t)B * nw * k * 8, false, st)) != hipSuccess ||
-        (e = ix->s_part_cnt.reserve((size_t)B * nw * 4, false, st)) != hipSuccess)
-      return fail(VDB_ERR_OOM, "top-k scratch");
-    SweepArgs a{};
-    a.rows = ix->rows.as<float>();
-    a.norms = ix->norms.as<float>();
-    a.alive = alive;
-    a.queries = d_q + (size_t)q0 * q_stride;
-    a.part_keys = ix->s_part_keys.as<uint64_t>();
-    a.part_cnt = ix->s_part_cnt.as<uint32_t>();
-    a.row_stride = ix->row_stride;
-    a.q_stride = q_stride;
-    a.n_rows = (uint32_t)ix->n_rows;
-    a.dim = ix->dim;
-    a.nq = tile;
-    a.k = k;
-    ix->last_kernels |= VDB_KERNEL_SWEEP_VALU;
-    EventPair* ev = next_events(ix);
-    if (ev) (void)hipEventRecord(ev->a, st);
-    if (qlds) {
-      hipError_t le = launch_sweep_f32_qlds(ix->metric, (int)B, a, blocks, st);
-      if (le != hipSuccess) return fail(VDB_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString(le));
-    } else {
-      hipError_t le = launch_sweep_f32(ix->metric, (int)B, a, blocks, st);
-      if (le != hipSuccess) return fail(VDB_ERR_HIP, std::string("sweep launch: ") + hipGetErrorString(le));
-    }
-    if (ev) (void)hipEventRecord(ev->b, st);
-    MergeArgs m{};
-    m.part_keys = a.part_keys;
-    m.part_cnt = a.part_cnt;
-    m.ext_ids = ix->ext_ids.as<uint64_t>();
-    m.out_ids = d_ids + (size_t)q0 * k;
-    m.out_scores = d_scores + (size_t)q0 * k;
-    m.out_n = d_n + q0;
-    m.n_lists = nw;
-    m.k = k;
-    launch_merge(hib, m, tile, st);
-    q0 += tile;
+    if (t.open() && mfma_nqt) t = tier_gemm_f32(ix, rest, st);
+    if (t.open() && mfma_nqt) t = tier_mfma_f32(ix, rest, mfma_nqt, st);
+    if (t.open()) t = tier_valu(ix, rest, st);
+    if (t.rc != VDB_OK) return t.rc;
+    q0 += t.n;
   }
   VDB_HIP(hipGetLastError());
   return VDB_OK;
@@ -949,66 +860,46 @@ static bool sweep_mode_m(const vdb_hip_index* ix, uint32_t k) {
   return opt_engine(ix) == 1 && (ix->metric == VDB_COSINE || ix->metric == VDB_DOT) && sweep_mfma_lds_bytes(1, k, ix->dim) <= 160 * 1024;
 }
 
-static int32_t brute_masked_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                                float* d_scores, uint32_t* d_n, hipStream_t st, int32_t mode = VDB_SEARCH_BRUTE);
 // vdb_hip_index_search_batch_filtered: exact top-k among the rows of ix->flt that are alive now.  Two routes, same bits.
-static int32_t brute_filtered_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                                  float* d_scores, uint32_t* d_n, hipStream_t st) {
+static int32_t brute_filtered_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st) {
   const RowFilter* f = ix->flt;
-  if (f->count == 0) {  // the empty filter: no row can answer
-    VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
-    return VDB_OK;
-  }
+  const uint32_t k = s.k;
+  if (f->count == 0) return zero_results(s, st);  // the empty filter: no row can answer
   const bool mode_m = sweep_mode_m(ix, k);
   ListedPlan lp;
-  if (!is_bits_metric(ix->metric)) sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, nq, ix->n_cus, &lp);
-  if (filter_route(opt_value(ix, VDB_OPT_FILTER_ROUTE), lp.blocks > 0, f->count, ix->n_rows, nq) == kFilterRouteListed) {
-    const bool hib = higher_is_better_host(ix->metric);
-    for (uint32_t q0 = 0; q0 < nq;) {
-      sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, nq - q0, ix->n_cus, &lp);
-      if (ix->s_part_keys.reserve((size_t)lp.nq_pass * lp.blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+  if (!is_bits_metric(ix->metric)) sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, s.nq, ix->n_cus, &lp);
+  if (filter_route(opt_value(ix, VDB_OPT_FILTER_ROUTE), lp.blocks > 0, f->count, ix->n_rows, s.nq) == kFilterRouteListed) {
+    for (uint32_t q0 = 0; q0 < s.nq;) {
+      sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, s.nq - q0, ix->n_cus, &lp);
+      const QuerySlice c = s.sub(q0, lp.nq_pass);
+      if (ix->s_part_keys.reserve((size_t)c.nq * lp.blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
       ListedArgs a{};
       a.rows = ix->rows.as<float>();
       a.norms = ix->norms.as<float>();
       a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
       a.list = f->list.as<uint32_t>();
-      a.queries = d_q + (size_t)q0 * q_stride;
+      a.queries = c.d_q;
       a.part_keys = ix->s_part_keys.as<uint64_t>();
       a.row_stride = ix->row_stride;
-      a.q_stride = q_stride;
+      a.q_stride = c.q_stride;
       a.count = (uint32_t)f->count;
       a.dim = ix->dim;
-      a.nq = lp.nq_pass;
+      a.nq = c.nq;
       a.k = k;
-      ix->last_kernels |= VDB_KERNEL_SWEEP_LISTED;
-      EventPair* ev = next_events(ix);
-      if (ev) (void)hipEventRecord(ev->a, st);
-      const hipError_t le = launch_sweep_listed(ix->metric, mode_m, lp, a, st);
-      if (le != hipSuccess) return fail(VDB_ERR_HIP, std::string("listed sweep launch: ") + hipGetErrorString(le));
-      if (ev) (void)hipEventRecord(ev->b, st);
-      MergeArgs m{};
-      m.part_keys = a.part_keys;
-      m.ext_ids = ix->ext_ids.as<uint64_t>();
-      m.out_ids = d_ids + (size_t)q0 * k;
-      m.out_scores = d_scores + (size_t)q0 * k;
-      m.out_n = d_n + q0;
-      m.n_lists = (uint32_t)lp.blocks;
-      m.k = k;
-      launch_merge(hib, m, lp.nq_pass, st);
-      q0 += lp.nq_pass;
+      const int32_t rc = timed_launch(ix, VDB_KERNEL_SWEEP_LISTED, st, "listed sweep launch", [&] { return launch_sweep_listed(ix->metric, mode_m, lp, a, st); });
+      if (rc != VDB_OK) return rc;
+      merge_pass(ix, higher_is_better_host(ix->metric), a.part_keys, nullptr, (uint32_t)lp.blocks, c, st);
+      q0 += c.nq;
     }
     VDB_HIP(hipGetLastError());
     return VDB_OK;
   }
-  return brute_masked_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  return brute_masked_dev(ix, s, st);
 }
 // mask substitution for ix->flt: mask = filter AND alive, n_rows bytes written per call into this context's scratch (nothing is
 // cached between calls or shared between contexts); rows past the filter's row count (inserted since) get 0
 // (mode: VDB_SEARCH_BRUTE, or one of the SQ8 / Binary / half modes — the mode's own dispatch runs under the mask)
-static int32_t brute_mode_dev(vdb_hip_index* ix, int32_t mode, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                              float* d_scores, uint32_t* d_n, hipStream_t st);
-static int32_t brute_masked_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                                float* d_scores, uint32_t* d_n, hipStream_t st, int32_t mode) {
+static int32_t brute_masked_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st, int32_t mode) {
   const RowFilter* f = ix->flt;
   const size_t mask_cap = (size_t)ix->capacity + kRowSlack;  // (what the row arrays hold: a tile kernel may look past n_rows)
   if (ix->s_flt_mask.cap < mask_cap) {
@@ -1022,8 +913,7 @@ static int32_t brute_masked_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_
   // batches: a filtered call reads it and leaves it as it was (its own verdicts are not posted: select_stage.hip)
   const uint32_t seen = ix->sel_seq_seen, h16 = ix->sel16_hold, hw = ix->wide_hold, hl2 = ix->l2_hold, hsq = ix->sq8_hold;
   ix->alive_override = ix->s_flt_mask.as<uint8_t>();
-  const int32_t rc = mode == VDB_SEARCH_BRUTE ? brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st)
-                                              : brute_mode_dev(ix, mode, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  const int32_t rc = mode == VDB_SEARCH_BRUTE ? brute_dev(ix, s, st) : brute_mode_dev(ix, mode, s, st);
   ix->alive_override = nullptr;
   ix->sel_seq_seen = seen;
   ix->sel16_hold = h16;
@@ -1040,9 +930,9 @@ static_assert(kFmModeBf16 == VDB_SEARCH_BRUTE_BF16 && kFmModeSq8 == VDB_SEARCH_B
 // that are alive now.  What the plain call in that mode refuses is refused first, in its words.  Two routes: the listed kernels (SQ8;
 // Euclidean over a half image) read only the filter's rows; mask substitution runs the mode's own dispatch, every tier of it, under the
 // call's row mask.  Same bits either way where the mode declares its summation order.
-static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k,
-                                       uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
+static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const QuerySlice& s, hipStream_t st) {
   const RowFilter* f = ix->flt;
+  const uint32_t nq = s.nq, k = s.k;
   const bool half = mode == VDB_SEARCH_BRUTE_BF16 || mode == VDB_SEARCH_BRUTE_F16, f16 = mode == VDB_SEARCH_BRUTE_F16;
   const bool metric3 = ix->metric == VDB_COSINE || ix->metric == VDB_EUCLIDEAN || ix->metric == VDB_DOT;
   if (mode == VDB_SEARCH_BRUTE_SQ8) {
@@ -1056,18 +946,15 @@ static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const fl
     if (!metric3) return fail(VDB_ERR_UNSUPPORTED, "half-precision sweep: Cosine, DotProduct and Euclidean only");
   }
   if (nq == 0) return VDB_OK;
-  if (f->count == 0 || k == 0) {  // the empty filter: no row can answer
-    VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
-    return VDB_OK;
-  }
+  if (f->count == 0 || k == 0) return zero_results(s, st);  // the empty filter: no row can answer
   bool listed_ok = false;
   if (filter_mode_has_listed(mode, ix->metric)) listed_ok = mode_listed_plan(half, ix->dim, k, f->count, nq, ix->n_cus).blocks > 0;
   if (filter_mode_route(opt_value(ix, VDB_OPT_FILTER_ROUTE), mode, ix->metric, f->count, ix->n_rows, nq, listed_ok) == kFilterRouteListed) {
-    if (half) return brute_half_l2_listed_dev(ix, f16, f->list.as<uint32_t>(), (uint32_t)f->count, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+    if (half) return brute_half_l2_listed_dev(ix, f16, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
     ix->last_kernels |= VDB_KERNEL_SQ8;
-    return brute_sq8_listed_dev(ix, f->list.as<uint32_t>(), (uint32_t)f->count, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+    return brute_sq8_listed_dev(ix, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
   }
-  return brute_masked_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st, mode);
+  return brute_masked_dev(ix, s, st, mode);
 }
 
 static uint32_t balanced_ef(uint32_t k) { return std::max<uint32_t>(128, k * 4); }  // params.rs:313
@@ -1075,11 +962,10 @@ static uint32_t balanced_ef(uint32_t k) { return std::max<uint32_t>(128, k * 4);
 // the exact sweeps over the SQ8 codes, the sign bits and the half images (VDB_SEARCH_BRUTE_SQ8 / _BINARY / _BF16 / _F16).  A filtered call
 // (vdb_hip_index_search_batch_filtered_mode) picks its route first; on the mask-substitution route it comes back here with the call's row
 // mask in place of the soft-delete flags
-static int32_t brute_mode_dev(vdb_hip_index* ix, int32_t mode, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                              float* d_scores, uint32_t* d_n, hipStream_t st) {
-  if (ix->flt && !ix->alive_override) return brute_filtered_mode_dev(ix, mode, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
-  if (mode == VDB_SEARCH_BRUTE_BF16) return brute_bf16_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
-  if (mode == VDB_SEARCH_BRUTE_F16) return brute_bf16_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st, /*f16=*/true);
+static int32_t brute_mode_dev(vdb_hip_index* ix, int32_t mode, const QuerySlice& s, hipStream_t st) {
+  if (ix->flt && !ix->alive_override) return brute_filtered_mode_dev(ix, mode, s, st);
+  if (mode == VDB_SEARCH_BRUTE_BF16) return brute_bf16_dev(ix, s, st);
+  if (mode == VDB_SEARCH_BRUTE_F16) return brute_bf16_dev(ix, s, st, /*f16=*/true);
   if (mode == VDB_SEARCH_BRUTE_SQ8) {
     // large Cosine / DotProduct batches: bf16 selection over the dequantised rows + the reference chain for the candidates +
     // proof (level 3); everything else, and what a handle's data defeats, on the exact SQ8 sweep
@@ -1087,28 +973,23 @@ static int32_t brute_mode_dev(vdb_hip_index* ix, int32_t mode, const float* d_q,
     uint32_t q0 = 0;
     // (a filtered call keeps the selection stage — level 3 and WIDE — only while enough rows are allowed for its seed sample, as brute_dev)
     const bool sel_ok = !ix->flt || filter_keeps_selection(ix->flt->count, ix->n_rows);
+    const uint32_t nq = s.nq, k = s.k;
     while (sel_ok && q0 < nq && k > 0 && ix->n_rows > 0) {
-      if (select_level_wide(ix, nq - q0, k, /*sq8=*/true)) {  // 10 < k <= 128: the WIDE selection over the dequantised image (sweep_wide.hip)
-        const uint32_t nqw = select_chunk(nq - q0, kSelectMinQueriesSq8);
-        const int32_t rcw = brute_wide_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nqw, k, d_ids + (size_t)q0 * k, d_scores + (size_t)q0 * k, d_n + q0, st, true);
-        if (rcw != VDB_OK) return rcw;
-        q0 += nqw;
-        continue;
-      }
-      if (select_level_sq8(ix, nq - q0, k) != 3) break;
-      const uint32_t nqg = select_chunk(nq - q0, kSelectMinQueriesSq8);
-      const int32_t rcs = brute_split_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nqg, k, d_ids + (size_t)q0 * k,
-                                          d_scores + (size_t)q0 * k, d_n + q0, st, 3);
+      // 10 < k <= 128 (and, selector level 3, every k): the WIDE selection over the dequantised image (sweep_wide.hip), asked first
+      const bool wide = select_level_wide(ix, nq - q0, k, /*sq8=*/true) != 0;
+      if (!wide && select_level_sq8(ix, nq - q0, k) != 3) break;
+      const QuerySlice c = s.sub(q0, select_chunk(nq - q0, kSelectMinQueriesSq8));
+      const int32_t rcs = wide ? brute_wide_dev(ix, c.d_q, c.q_stride, c.nq, k, c.d_ids, c.d_scores, c.d_n, st, true)
+                               : brute_split_dev(ix, c.d_q, c.q_stride, c.nq, k, c.d_ids, c.d_scores, c.d_n, st, 3);
       if (rcs != VDB_OK) return rcs;
-      q0 += nqg;
+      q0 += c.nq;
     }
     if (q0 == nq) return VDB_OK;
     ix->last_kernels |= VDB_KERNEL_SQ8;
-    return brute_sq8_dev(ix, d_q + (size_t)q0 * q_stride, q_stride, nq - q0, k, d_ids + (size_t)q0 * k, d_scores + (size_t)q0 * k,
-                         d_n + q0, st);
+    return brute_sq8_dev(ix, s.sub(q0, nq - q0), st);
   }
   ix->last_kernels |= VDB_KERNEL_BITS;
-  return brute_binary_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  return brute_binary_dev(ix, s, st);
 }
 // dispatch of search_with_quality (search.rs:59-94) for device-resident queries
 int32_t search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint32_t ef,
@@ -1125,11 +1006,12 @@ int32_t search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint3
     if (nq) VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
     return VDB_OK;
   }
-  if (mode == VDB_SEARCH_BRUTE) return brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  const QuerySlice s{d_q, q_stride, nq, k, d_ids, d_scores, d_n};
+  if (mode == VDB_SEARCH_BRUTE) return brute_dev(ix, s, st);
   if (mode == VDB_SEARCH_BRUTE_BF16 || mode == VDB_SEARCH_BRUTE_F16 || mode == VDB_SEARCH_BRUTE_SQ8 || mode == VDB_SEARCH_BRUTE_BINARY)
-    return brute_mode_dev(ix, mode, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+    return brute_mode_dev(ix, mode, s, st);
   if (mode == VDB_SEARCH_AUTO && ix->live <= 100 && ix->n_rows > 0)  // search.rs:75-77
-    return brute_dev(ix, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+    return brute_dev(ix, s, st);
   if (mode == VDB_SEARCH_HNSW_INT8) {
     if (used_hnsw) *used_hnsw = true;
     ix->last_kernels |= VDB_KERNEL_HNSW_INT8;
@@ -1558,13 +1440,14 @@ int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const
       diag[5]++;
     }
     uint32_t r0 = base;
+    const QuerySlice block{dq, ix->row_stride, 0, k, d_ids, d_scores, d_n};  // the staged queries / result rows of the call; a group takes [r0, r0 + nq_g)
     for (const FxGroup& g : groups) {
       if (g.route == kFilterRouteListed) continue;
       const uint32_t nq_g = (uint32_t)g.queries.size();
-      const float* q_g = dq + (size_t)r0 * ix->row_stride;
+      const QuerySlice s_g = block.sub(r0, nq_g);
       int32_t rg;
       if (g.filter == n_filters) {
-        rg = brute_dev(ix, q_g, ix->row_stride, nq_g, k, d_ids + (size_t)r0 * k, d_scores + (size_t)r0 * k, d_n + r0, st);
+        rg = brute_dev(ix, s_g, st);
       } else if (filters[g.filter]->count == 0) {  // the empty filter: no row can answer — out_n = 0 behind the merge's padding
         rg = VDB_OK;
         VDB_HIP(hipMemsetAsync(d_n + r0, 0, (size_t)nq_g * 4, st));
@@ -1572,7 +1455,7 @@ int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const
         VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_scores + (size_t)r0 * k), 0x7FC00000, (size_t)nq_g * k, st));
       } else {
         ix->flt = filters[g.filter];
-        rg = brute_masked_dev(ix, q_g, ix->row_stride, nq_g, k, d_ids + (size_t)r0 * k, d_scores + (size_t)r0 * k, d_n + r0, st);
+        rg = brute_masked_dev(ix, s_g, st);
         ix->flt = nullptr;
       }
       if (rg != VDB_OK) return rg;

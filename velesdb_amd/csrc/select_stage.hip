@@ -15,12 +15,11 @@
 #include "vdb_filter_route.hpp"
 #include "vdb_probe_env.hpp"
 #include "vdb_select_stage.hpp"
+#include "vdb_sweep_pass.hpp"
 #include "vdb_wide.hpp"
 
 namespace vdb {
 
-static inline uint32_t opt_max_tile(const vdb_hip_index* ix) { return (uint32_t)opt_value(ix, VDB_OPT_MAX_QUERY_TILE); }
-static inline int opt_engine(const vdb_hip_index* ix) { return (int)opt_value(ix, VDB_OPT_SWEEP_ENGINE); }
 static inline int opt_selector(const vdb_hip_index* ix) { return (int)opt_value(ix, VDB_OPT_SELECTOR_LEVEL); }
 // VELESDB_BF16_SEED=0: level 2 keeps the exact f32 seed sweep (A / B probes)
 static const bool g_bf16_seed = [] {
@@ -41,40 +40,30 @@ static bool gemm_bf16_glds_enabled() {
   return on;
 }
 
-
 // Euclidean over a half copy (half_precision::euclidean_distance, half_precision.rs:257-287): the streaming difference-chain sweep of
 // sweep_half_l2.hip for every batch size — query tiles of 16 (4 / 1 where LDS or the batch is smaller), the corpus re-read per tile
-static int32_t brute_half_l2_dev(vdb_hip_index* ix, const uint16_t* rows16, bool f16, const float* d_q, uint64_t q_stride, uint32_t nq,
-                                 uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
+static int32_t brute_half_l2_dev(vdb_hip_index* ix, const uint16_t* rows16, bool f16, const QuerySlice& s, hipStream_t st) {
   const uint8_t* alive = search_alive(ix);
+  const uint32_t k = s.k;
   ix->last_kernels |= VDB_KERNEL_SWEEP_HALF_L2;
-  for (uint32_t q0 = 0; q0 < nq;) {
-    const uint32_t rem = nq - q0;
+  for (uint32_t q0 = 0; q0 < s.nq;) {
+    const uint32_t rem = s.nq - q0;
     int B = rem > 4 ? 16 : (rem > 1 ? 4 : 1);
     while (B > 1 && sweep_half_l2_lds_bytes(B, k, ix->dim) > 160 * 1024) B /= 4;
     const size_t lds = sweep_half_l2_lds_bytes(B, k, ix->dim);
     if (lds > 160 * 1024) return fail(VDB_ERR_UNSUPPORTED, "half-precision Euclidean sweep: dim / k too large for the LDS query tile");
-    const uint32_t tile = std::min<uint32_t>((uint32_t)B, rem);
+    const QuerySlice c = s.sub(q0, std::min<uint32_t>((uint32_t)B, rem));
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 3));  // (three 4-wave blocks per CU: the kernel runs at 3 waves per SIMD)
     const uint32_t ngroups = (uint32_t)((ix->n_rows + (64 / B) - 1) / (64 / B));
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)ngroups + 3) / 4, (int64_t)ix->n_cus * per_cu));
     if (ix->s_part_keys.reserve((size_t)B * blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
-    EventPair* ev = next_events(ix);
-    if (ev) (void)hipEventRecord(ev->a, st);
-    const hipError_t e = launch_sweep_half_l2(f16, B, rows16, ix->bf16_stride, alive, d_q + (size_t)q0 * q_stride, q_stride,
-                                              ix->s_part_keys.as<uint64_t>(), (uint32_t)ix->n_rows, ix->dim, tile, k, blocks, st);
-    if (ev) (void)hipEventRecord(ev->b, st);
-    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("half-precision Euclidean sweep launch: ") + hipGetErrorString(e));
-    MergeArgs m{};
-    m.part_keys = ix->s_part_keys.as<uint64_t>();
-    m.ext_ids = ix->ext_ids.as<uint64_t>();
-    m.out_ids = d_ids + (size_t)q0 * k;
-    m.out_scores = d_scores + (size_t)q0 * k;
-    m.out_n = d_n + q0;
-    m.n_lists = (uint32_t)blocks;
-    m.k = k;
-    launch_merge(false, m, tile, st);
-    q0 += tile;
+    uint64_t* parts = ix->s_part_keys.as<uint64_t>();
+    const int32_t rc = timed_launch(ix, 0, st, "half-precision Euclidean sweep launch", [&] {
+      return launch_sweep_half_l2(f16, B, rows16, ix->bf16_stride, alive, c.d_q, c.q_stride, parts, (uint32_t)ix->n_rows, ix->dim, c.nq, k, blocks, st);
+    });
+    if (rc != VDB_OK) return rc;
+    merge_pass(ix, false, parts, nullptr, (uint32_t)blocks, c, st);
+    q0 += c.nq;
   }
   VDB_HIP(hipGetLastError());
   return VDB_OK;
@@ -83,41 +72,162 @@ static int32_t brute_half_l2_dev(vdb_hip_index* ix, const uint16_t* rows16, bool
 // The listed route of a filtered Euclidean call over a half image (vdb_hip_index_search_batch_filtered_mode):
 // sweep_topk_half_l2_listed over the filter's ascending row list, pass by pass (mode_listed_plan, vdb_filter_route.hpp), merge_topk behind
 // every pass.  The caller has checked the image, the metric, k > 0 and count > 0.
-int32_t brute_half_l2_listed_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const float* d_q, uint64_t q_stride,
-                                 uint32_t nq, uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
+int32_t brute_half_l2_listed_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st) {
   const uint16_t* rows16 = f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>();
+  const uint32_t k = s.k;
   ix->last_kernels |= VDB_KERNEL_SWEEP_HALF_L2 | VDB_KERNEL_SWEEP_LISTED;
-  for (uint32_t q0 = 0; q0 < nq;) {
-    const ModeListedPlan lp = mode_listed_plan(true, ix->dim, k, count, nq - q0, ix->n_cus);
+  for (uint32_t q0 = 0; q0 < s.nq;) {
+    const ModeListedPlan lp = mode_listed_plan(true, ix->dim, k, count, s.nq - q0, ix->n_cus);
     if (lp.blocks == 0) return fail(VDB_ERR_UNSUPPORTED, "half-precision Euclidean sweep: dim / k too large for the LDS query tile");
     if (ix->s_part_keys.reserve((size_t)lp.B * lp.blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
-    EventPair* ev = next_events(ix);
-    if (ev) (void)hipEventRecord(ev->a, st);
-    const hipError_t e = launch_sweep_half_l2_listed(f16, lp.B, rows16, ix->bf16_stride, ix->any_dead ? ix->alive.as<uint8_t>() : nullptr, list, count,
-                                                     lp.per_block, d_q + (size_t)q0 * q_stride, q_stride, ix->s_part_keys.as<uint64_t>(),
-                                                     (uint32_t)ix->n_rows, ix->dim, lp.nq_pass, k, lp.blocks, st);
-    if (ev) (void)hipEventRecord(ev->b, st);
-    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("listed half-precision Euclidean sweep launch: ") + hipGetErrorString(e));
-    MergeArgs m{};
-    m.part_keys = ix->s_part_keys.as<uint64_t>();
-    m.ext_ids = ix->ext_ids.as<uint64_t>();
-    m.out_ids = d_ids + (size_t)q0 * k;
-    m.out_scores = d_scores + (size_t)q0 * k;
-    m.out_n = d_n + q0;
-    m.n_lists = (uint32_t)lp.blocks;
-    m.k = k;
-    launch_merge(false, m, lp.nq_pass, st);
-    q0 += lp.nq_pass;
+    const QuerySlice c = s.sub(q0, lp.nq_pass);
+    uint64_t* parts = ix->s_part_keys.as<uint64_t>();
+    const int32_t rc = timed_launch(ix, 0, st, "listed half-precision Euclidean sweep launch", [&] {
+      return launch_sweep_half_l2_listed(f16, lp.B, rows16, ix->bf16_stride, ix->any_dead ? ix->alive.as<uint8_t>() : nullptr, list, count, lp.per_block,
+                                         c.d_q, c.q_stride, parts, (uint32_t)ix->n_rows, ix->dim, c.nq, k, lp.blocks, st);
+    });
+    if (rc != VDB_OK) return rc;
+    merge_pass(ix, false, parts, nullptr, (uint32_t)lp.blocks, c, st);
+    q0 += c.nq;
   }
   VDB_HIP(hipGetLastError());
   return VDB_OK;
 }
 
+// ---- Cosine / DotProduct over a half copy: the three tiers of brute_bf16_dev's ladder, each asked for the front of what is left ----
+struct HalfImage {
+  const uint16_t* rows16;
+  const float* norms16;  // norms of the ROUNDED rows
+  bool f16;              // the IEEE f16 copy and the f16 instances of the kernels, else bf16
+};
+
+// large batches over a large corpus: the 256 x 256 LDS-DMA kernel (sweep_gemm_bf16.hip).  Its thresholds are seeded: the 128 x 128
+// kernel first sweeps the first kGemmBf16SeedRows rows, the k-th best key found there (+ 1) is every block's starting bound — without
+// it the first row tile of every block floods the 12-key candidate buffers.
+static Took half_tier_glds(vdb_hip_index* ix, const HalfImage& h, const QuerySlice& rest, hipStream_t st) {
+  const uint32_t k = rest.k;
+  if (opt_max_tile(ix) < 128 || rest.nq < kGemmBigMinQueries || k > kGemmBf16MaxK || ix->dim % 64 != 0 || ix->dim < 128 ||
+      ix->n_rows < kGemmBf16MinRows || ix->n_rows >= 0xFFFFFF00ull || !gemm_bf16_glds_enabled())
+    return Took();
+  // the chunk this kernel takes: up to 1 024 queries that fill their 256-query tiles to >= 7/8; when the last tile would
+  // be emptier than that, the whole tiles in front of it (the rest is the next chunk: the 128 x 128 / streaming kernels)
+  uint32_t nqg = std::min<uint32_t>(rest.nq, kGemmMaxQueries);
+  if ((uint64_t)nqg * 8 < (uint64_t)((nqg + 255) / 256) * 256 * 7) nqg = nqg / 256 * 256;
+  if (nqg < kGemmBigMinQueries) return Took();
+  const QuerySlice c = rest.sub(0, nqg);
+  const uint8_t* alive = search_alive(ix);
+  // Launch schedule: rows [0, R0) by the 128 x 128 kernel (seed), then the LDS-DMA kernel over [R0, R1) and [R1, n).
+  // Every launch starts from the k-th best key over ALL rows swept before it: the number of candidates a wave has
+  // to look at per row tile falls as k / rows seen (5 per wave tile behind 16 K rows, 0.1 behind 640 K).  All
+  // launches write their partial lists into one [nq][lists][k] array that the final merge scans once.
+  const uint32_t n = (uint32_t)ix->n_rows;
+  const uint32_t R0 = kGemmBf16SeedRows;
+  // first launch: ~max(2^18, n / 16) rows, then launches of <= 2 M rows (gemm_schedule, vdb_kernels.hpp)
+  GemmSchedule sch;
+  {
+    const uint32_t G2 = (uint32_t)std::max(8, ix->n_cus / (int)((nqg + 255) / 256) / 8 * 8);
+    const uint32_t head[3] = {(uint32_t)((std::max<uint64_t>(1u << 18, n / 16) + (uint64_t)G2 * 256 - 1) / ((uint64_t)G2 * 256)), 0u, 0u};
+    gemm_schedule(nqg, R0, n, ix->n_cus, head, 1u << 21, &sch);
+  }
+  const uint32_t lists = 1 + sch.lists;
+  GemmPlan sp;  // seeding sweep over the first rows
+  sweep_gemm_plan(nqg, R0, ix->n_cus, k, &sp, /*allow_big=*/false);
+  const size_t off_ids = ((size_t)nqg * sp.G * k * 8 + 15) & ~(size_t)15, off_sc = off_ids + (size_t)nqg * k * 8,
+               off_n = off_sc + (size_t)nqg * k * 4, off_tau = (off_n + (size_t)nqg * 4 + 15) & ~(size_t)15,
+               off_qn = off_tau + (size_t)nqg * 8;
+  if (ix->s_part_keys.reserve((size_t)nqg * lists * k * 8, false, st) != hipSuccess ||
+      ix->s_seed.reserve(off_qn + (size_t)nqg * 4, false, st) != hipSuccess ||
+      ix->s_misc.reserve(((size_t)nqg + 256) * ix->bf16_stride * 2, false, st) != hipSuccess)
+    return fail(VDB_ERR_OOM, "bf16 GEMM scratch");
+  unsigned char* sd = ix->s_seed.as<unsigned char>();
+  uint64_t* parts = ix->s_part_keys.as<uint64_t>();
+  uint64_t* tau0 = reinterpret_cast<uint64_t*>(sd + off_tau);
+  const uint16_t* q16 = ix->s_misc.as<uint16_t>();
+  launch_round_queries_bf16(c.d_q, c.q_stride, ix->s_misc.as<uint16_t>(), ix->bf16_stride, nqg, ix->dim, st, h.f16);
+  float* qn_half = reinterpret_cast<float*>(sd + off_qn);  // norms of the rounded queries, once per batch
+  launch_query_norms_bf16(q16, ix->bf16_stride, qn_half, nqg, ix->dim, st, h.f16);
+  // the 256 x 256 kernel stages whole 256-query tiles: zero rows behind the batch
+  VDB_HIP(hipMemsetAsync(ix->s_misc.as<uint16_t>() + (size_t)nqg * ix->bf16_stride, 0, (size_t)256 * ix->bf16_stride * 2, st));
+  VDB_HIP(hipMemsetAsync(parts, 0xFF, (size_t)nqg * lists * k * 8, st));  // every slot: kKeyInvalid
+  // the bounds between the launches: the top-k so far (internal rows) merged into the seed scratch
+  const QuerySlice sofar{nullptr, 0, nqg, k, reinterpret_cast<uint64_t*>(sd + off_ids), reinterpret_cast<float*>(sd + off_sc),
+                         reinterpret_cast<uint32_t*>(sd + off_n)};
+  // (one timed region over the seed launch and the schedule, two error texts: the event pair stays written out here)
+  ix->last_kernels |= VDB_KERNEL_GEMM_BF16_GLDS | VDB_KERNEL_GEMM_BF16;  // (the seed prefix: the 128 x 128 kernel)
+  EventPair* evg = next_events(ix);
+  if (evg) (void)hipEventRecord(evg->a, st);
+  hipError_t e3 = launch_sweep_gemm_bf16(ix->metric, sp, h.rows16, ix->bf16_stride, h.norms16, alive, q16, ix->bf16_stride,
+                                         reinterpret_cast<uint64_t*>(sd), R0, ix->dim, nqg, k, st, h.f16);
+  if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 seed sweep launch: ") + hipGetErrorString(e3));
+  merge_pass(true, reinterpret_cast<const uint64_t*>(sd), nullptr, sp.G, sofar, st, /*ext_ids=*/nullptr);
+  launch_seed_tau(sofar.d_ids, sofar.d_scores, sofar.d_n, tau0, parts, lists, nqg, k, st);  // list 0 = the seed's top-k
+  e3 = run_gemm_schedule(
+      sch, ix->metric, h.rows16, ix->bf16_stride, h.norms16, alive, q16, ix->bf16_stride, tau0, parts, lists,
+      /*list_first=*/1, ix->dim, nqg, k, st, /*split=*/false, nullptr, nullptr, qn_half, [](int) {},
+      [&](int, uint32_t, bool last) {
+        if (last) return;  // bound for the next launch: k-th best key over everything swept so far
+        merge_pass(true, parts, nullptr, lists, sofar, st, /*ext_ids=*/nullptr);
+        launch_seed_tau(sofar.d_ids, sofar.d_scores, sofar.d_n, tau0, nullptr, 0, nqg, k, st);
+      },
+      h.f16);
+  if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 gemm sweep launch: ") + hipGetErrorString(e3));
+  if (evg) (void)hipEventRecord(evg->b, st);
+  merge_pass(ix, true, parts, nullptr, lists, c, st);
+  return Took::queries(nqg);
+}
+
+// large batches: the GEMM-structured kernel over the half rows (sweep_gemm.hip, BF16 variant): the corpus is read
+// once per <= 128 queries instead of once per 96, both operands through LDS, lock-free top-k epilogue
+static Took half_tier_gemm(vdb_hip_index* ix, const HalfImage& h, const QuerySlice& rest, hipStream_t st) {
+  const uint32_t k = rest.k;
+  if (opt_max_tile(ix) < 128 || rest.nq < kGemmMinQueries || k > kGemmMaxK || ix->dim % 64 != 0) return Took();
+  const QuerySlice c = rest.sub(0, std::min<uint32_t>(rest.nq, kGemmMaxQueries));
+  GemmPlan gp;
+  sweep_gemm_plan(c.nq, (uint32_t)ix->n_rows, ix->n_cus, k, &gp, /*allow_big=*/true);
+  if (gp.lds > 160 * 1024) return Took();
+  if (ix->s_part_keys.reserve((size_t)c.nq * gp.G * k * 8, false, st) != hipSuccess ||
+      ix->s_misc.reserve((size_t)c.nq * ix->bf16_stride * 2, false, st) != hipSuccess)
+    return fail(VDB_ERR_OOM, "bf16 GEMM scratch");
+  launch_round_queries_bf16(c.d_q, c.q_stride, ix->s_misc.as<uint16_t>(), ix->bf16_stride, c.nq, ix->dim, st, h.f16);
+  uint64_t* parts = ix->s_part_keys.as<uint64_t>();
+  const int32_t rc = timed_launch(ix, VDB_KERNEL_GEMM_BF16, st, "bf16 gemm sweep launch", [&] {
+    return launch_sweep_gemm_bf16(ix->metric, gp, h.rows16, ix->bf16_stride, h.norms16, search_alive(ix), ix->s_misc.as<uint16_t>(), ix->bf16_stride, parts,
+                                  (uint32_t)ix->n_rows, ix->dim, c.nq, k, st, h.f16);
+  });
+  if (rc != VDB_OK) return rc;
+  merge_pass(ix, true, parts, nullptr, gp.G, c, st);
+  return Took::queries(c.nq);
+}
+
+// every other shape: the streaming matrix-core kernel, 1 / 2 / 4 / 6 16-query tiles per corpus pass (f32 queries, rounded in the kernel)
+static Took half_tier_mfma(vdb_hip_index* ix, const HalfImage& h, const QuerySlice& rest, hipStream_t st) {
+  const uint32_t k = rest.k, rem = rest.nq;
+  int nqt = rem > 64 ? 6 : (rem > 32 ? 4 : (rem > 16 ? 2 : 1));
+  while (nqt > 1 && sweep_bf16_lds_bytes(nqt, k, ix->dim) > 160 * 1024) nqt = nqt == 6 ? 4 : nqt / 2;
+  if (sweep_bf16_lds_bytes(nqt, k, ix->dim) > 160 * 1024)
+    return fail(VDB_ERR_UNSUPPORTED, "bf16 sweep: dim / k too large for the LDS query tile");
+  const uint32_t Bq = (uint32_t)nqt * 16;
+  const QuerySlice c = rest.sub(0, std::min<uint32_t>(Bq, rem));
+  const int waves = nqt >= 4 ? kBf16WavesBig : kBf16WavesSmall;
+  const size_t lds = sweep_bf16_lds_bytes(nqt, k, ix->dim);
+  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, (size_t)(16 / waves)));
+  const uint32_t ntiles = (uint32_t)((ix->n_rows + 15) / 16);
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)ntiles + waves - 1) / waves, (int64_t)ix->n_cus * per_cu));
+  if (ix->s_part_keys.reserve((size_t)Bq * blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+  uint64_t* parts = ix->s_part_keys.as<uint64_t>();
+  const int32_t rc = timed_launch(ix, VDB_KERNEL_SWEEP_MFMA_BF16, st, "bf16 sweep launch", [&] {
+    return launch_sweep_bf16(ix->metric, nqt, h.rows16, ix->bf16_stride, h.norms16, search_alive(ix), c.d_q, c.q_stride, parts, (uint32_t)ix->n_rows,
+                             ix->dim, c.nq, k, blocks, st, h.f16);
+  });
+  if (rc != VDB_OK) return rc;
+  merge_pass(ix, true, parts, nullptr, (uint32_t)blocks, c, st);
+  return Took::queries(c.nq);
+}
+
 // exact sweep over a half-precision copy of the rows: half_precision::dot_product / cosine_similarity / euclidean_distance semantics
-// (half_precision.rs:199-287) for nq device-resident f32 queries (rounded to the precision on the device); f16: the IEEE f16 copy and
-// the f16 instances of the same kernels (VDB_SEARCH_BRUTE_F16), else the bf16 copy
-int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k,
-                              uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st, bool f16) {
+// (half_precision.rs:199-287) for the slice's device-resident f32 queries (rounded to the precision on the device); f16: the IEEE f16
+// copy and the f16 instances of the same kernels (VDB_SEARCH_BRUTE_F16), else the bf16 copy
+int32_t brute_bf16_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st, bool f16) {
   if (f16) {
     if (!ix->f16_enabled) return fail(VDB_ERR_STATE, "f16 sweep: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
   } else if (!ix->bf16_enabled) {
@@ -125,176 +235,23 @@ int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, u
   }
   if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
     return fail(VDB_ERR_UNSUPPORTED, "half-precision sweep: Cosine, DotProduct and Euclidean only");
-  if (nq == 0) return VDB_OK;
-  if (k == 0 || ix->n_rows == 0) {
-    VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
-    return VDB_OK;
-  }
-  const uint16_t* rows16 = f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>();
-  const float* norms16 = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
-  if (ix->metric == VDB_EUCLIDEAN) return brute_half_l2_dev(ix, rows16, f16, d_q, q_stride, nq, k, d_ids, d_scores, d_n, st);
+  if (s.nq == 0) return VDB_OK;
+  if (s.k == 0 || ix->n_rows == 0) return zero_results(s, st);
+  const HalfImage h{f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>(), f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>(), f16};
+  if (ix->metric == VDB_EUCLIDEAN) return brute_half_l2_dev(ix, h.rows16, f16, s, st);
   if (f16) ix->last_kernels |= VDB_KERNEL_F16;
-  const uint8_t* alive = search_alive(ix);
-  for (uint32_t q0 = 0; q0 < nq;) {
-    const uint32_t rem = nq - q0;
-    // large batches over a large corpus: the 256 x 256 LDS-DMA kernel (sweep_gemm_bf16.hip).  Its thresholds are seeded:
-    // the 128 x 128 kernel first sweeps the first kGemmBf16SeedRows rows, the k-th best key found there (+ 1) is every
-    // block's starting bound — without it the first row tile of every block floods the 12-key candidate buffers.
-    if (opt_max_tile(ix) >= 128 && rem >= kGemmBigMinQueries && k <= kGemmBf16MaxK && ix->dim % 64 == 0 && ix->dim >= 128 &&
-        ix->n_rows >= kGemmBf16MinRows && ix->n_rows < 0xFFFFFF00ull && gemm_bf16_glds_enabled()) {
-      // the chunk this kernel takes: up to 1 024 queries that fill their 256-query tiles to >= 7/8; when the last tile would
-      // be emptier than that, the whole tiles in front of it (the rest is the next chunk: the 128 x 128 / streaming kernels)
-      uint32_t nqg = std::min<uint32_t>(rem, kGemmMaxQueries);
-      if ((uint64_t)nqg * 8 < (uint64_t)((nqg + 255) / 256) * 256 * 7) nqg = nqg / 256 * 256;
-      if (nqg >= kGemmBigMinQueries) {
-        // Launch schedule: rows [0, R0) by the 128 x 128 kernel (seed), then the LDS-DMA kernel over [R0, R1) and [R1, n).
-        // Every launch starts from the k-th best key over ALL rows swept before it: the number of candidates a wave has
-        // to look at per row tile falls as k / rows seen (5 per wave tile behind 16 K rows, 0.1 behind 640 K).  All
-        // launches write their partial lists into one [nq][lists][k] array that the final merge scans once.
-        const uint32_t n = (uint32_t)ix->n_rows;
-        const uint32_t R0 = kGemmBf16SeedRows;
-        // first launch: ~max(2^18, n / 16) rows, then launches of <= 2 M rows (gemm_schedule, vdb_kernels.hpp)
-        GemmSchedule sch;
-        {
-          const uint32_t G2 = (uint32_t)std::max(8, ix->n_cus / (int)((nqg + 255) / 256) / 8 * 8);
-          const uint32_t head[3] = {(uint32_t)((std::max<uint64_t>(1u << 18, n / 16) + (uint64_t)G2 * 256 - 1) / ((uint64_t)G2 * 256)), 0u, 0u};
-          gemm_schedule(nqg, R0, n, ix->n_cus, head, 1u << 21, &sch);
-        }
-        const uint32_t lists = 1 + sch.lists;
-        GemmPlan sp;  // seeding sweep over the first rows
-        sweep_gemm_plan(nqg, R0, ix->n_cus, k, &sp, /*allow_big=*/false);
-        const size_t off_ids = ((size_t)nqg * sp.G * k * 8 + 15) & ~(size_t)15, off_sc = off_ids + (size_t)nqg * k * 8,
-                     off_n = off_sc + (size_t)nqg * k * 4, off_tau = (off_n + (size_t)nqg * 4 + 15) & ~(size_t)15,
-                     off_qn = off_tau + (size_t)nqg * 8;
-        hipError_t e3;
-        if ((e3 = ix->s_part_keys.reserve((size_t)nqg * lists * k * 8, false, st)) != hipSuccess ||
-            (e3 = ix->s_seed.reserve(off_qn + (size_t)nqg * 4, false, st)) != hipSuccess ||
-            (e3 = ix->s_misc.reserve(((size_t)nqg + 256) * ix->bf16_stride * 2, false, st)) != hipSuccess)
-          return fail(VDB_ERR_OOM, "bf16 GEMM scratch");
-        unsigned char* sd = ix->s_seed.as<unsigned char>();
-        uint64_t* parts = ix->s_part_keys.as<uint64_t>();
-        uint64_t* tau0 = reinterpret_cast<uint64_t*>(sd + off_tau);
-        const uint16_t* q16 = ix->s_misc.as<uint16_t>();
-        launch_round_queries_bf16(d_q + (size_t)q0 * q_stride, q_stride, ix->s_misc.as<uint16_t>(), ix->bf16_stride, nqg,
-                                  ix->dim, st, f16);
-        float* qn_half = reinterpret_cast<float*>(sd + off_qn);  // norms of the rounded queries, once per batch
-        launch_query_norms_bf16(q16, ix->bf16_stride, qn_half, nqg, ix->dim, st, f16);
-        // the 256 x 256 kernel stages whole 256-query tiles: zero rows behind the batch
-        VDB_HIP(hipMemsetAsync(ix->s_misc.as<uint16_t>() + (size_t)nqg * ix->bf16_stride, 0, (size_t)256 * ix->bf16_stride * 2, st));
-        VDB_HIP(hipMemsetAsync(parts, 0xFF, (size_t)nqg * lists * k * 8, st));  // every slot: kKeyInvalid
-        ix->last_kernels |= VDB_KERNEL_GEMM_BF16_GLDS | VDB_KERNEL_GEMM_BF16;  // (the seed prefix: the 128 x 128 kernel)
-        EventPair* evg = next_events(ix);
-        if (evg) (void)hipEventRecord(evg->a, st);
-        e3 = launch_sweep_gemm_bf16(ix->metric, sp, rows16, ix->bf16_stride, norms16,
-                                    alive, q16, ix->bf16_stride, reinterpret_cast<uint64_t*>(sd), R0, ix->dim, nqg, k, st, f16);
-        if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 seed sweep launch: ") + hipGetErrorString(e3));
-        MergeArgs ms{};
-        ms.part_keys = reinterpret_cast<const uint64_t*>(sd);
-        ms.ext_ids = nullptr;  // internal rows
-        ms.out_ids = reinterpret_cast<uint64_t*>(sd + off_ids);
-        ms.out_scores = reinterpret_cast<float*>(sd + off_sc);
-        ms.out_n = reinterpret_cast<uint32_t*>(sd + off_n);
-        ms.n_lists = sp.G;
-        ms.k = k;
-        launch_merge(true, ms, nqg, st);
-        launch_seed_tau(ms.out_ids, ms.out_scores, ms.out_n, tau0, parts, lists, nqg, k, st);  // list 0 = the seed's top-k
-        e3 = run_gemm_schedule(
-            sch, ix->metric, rows16, ix->bf16_stride, norms16, alive, q16, ix->bf16_stride, tau0, parts, lists,
-            /*list_first=*/1, ix->dim, nqg, k, st, /*split=*/false, nullptr, nullptr, qn_half, [](int) {},
-            [&](int, uint32_t, bool last) {
-              if (last) return;  // bound for the next launch: k-th best key over everything swept so far
-              ms.part_keys = parts;
-              ms.n_lists = lists;
-              launch_merge(true, ms, nqg, st);
-              launch_seed_tau(ms.out_ids, ms.out_scores, ms.out_n, tau0, nullptr, 0, nqg, k, st);
-            },
-            f16);
-        if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 gemm sweep launch: ") + hipGetErrorString(e3));
-        if (evg) (void)hipEventRecord(evg->b, st);
-        MergeArgs mg{};
-        mg.part_keys = parts;
-        mg.ext_ids = ix->ext_ids.as<uint64_t>();
-        mg.out_ids = d_ids + (size_t)q0 * k;
-        mg.out_scores = d_scores + (size_t)q0 * k;
-        mg.out_n = d_n + q0;
-        mg.n_lists = lists;
-        mg.k = k;
-        launch_merge(true, mg, nqg, st);
-        q0 += nqg;
-        continue;
-      }
-    }
-    // large batches: the GEMM-structured kernel over the bf16 rows (sweep_gemm.hip, BF16 variant): the corpus is read
-    // once per <= 128 queries instead of once per 96, both operands through LDS, lock-free top-k epilogue
-    if (opt_max_tile(ix) >= 128 && rem >= kGemmMinQueries && k <= kGemmMaxK && ix->dim % 64 == 0) {
-      const uint32_t nqg = std::min<uint32_t>(rem, kGemmMaxQueries);
-      GemmPlan gp;
-      sweep_gemm_plan(nqg, (uint32_t)ix->n_rows, ix->n_cus, k, &gp, /*allow_big=*/true);
-      if (gp.lds <= 160 * 1024) {
-        hipError_t e3;
-        if ((e3 = ix->s_part_keys.reserve((size_t)nqg * gp.G * k * 8, false, st)) != hipSuccess ||
-            (e3 = ix->s_misc.reserve((size_t)nqg * ix->bf16_stride * 2, false, st)) != hipSuccess)
-          return fail(VDB_ERR_OOM, "bf16 GEMM scratch");
-        launch_round_queries_bf16(d_q + (size_t)q0 * q_stride, q_stride, ix->s_misc.as<uint16_t>(), ix->bf16_stride, nqg,
-                                  ix->dim, st, f16);
-        ix->last_kernels |= VDB_KERNEL_GEMM_BF16;
-        EventPair* evg = next_events(ix);
-        if (evg) (void)hipEventRecord(evg->a, st);
-        e3 = launch_sweep_gemm_bf16(ix->metric, gp, rows16, ix->bf16_stride, norms16,
-                                    alive, ix->s_misc.as<uint16_t>(), ix->bf16_stride, ix->s_part_keys.as<uint64_t>(),
-                                    (uint32_t)ix->n_rows, ix->dim, nqg, k, st, f16);
-        if (evg) (void)hipEventRecord(evg->b, st);
-        if (e3 != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 gemm sweep launch: ") + hipGetErrorString(e3));
-        MergeArgs mg{};
-        mg.part_keys = ix->s_part_keys.as<uint64_t>();
-        mg.ext_ids = ix->ext_ids.as<uint64_t>();
-        mg.out_ids = d_ids + (size_t)q0 * k;
-        mg.out_scores = d_scores + (size_t)q0 * k;
-        mg.out_n = d_n + q0;
-        mg.n_lists = gp.G;
-        mg.k = k;
-        launch_merge(true, mg, nqg, st);
-        q0 += nqg;
-        continue;
-      }
-    }
-    int nqt = rem > 64 ? 6 : (rem > 32 ? 4 : (rem > 16 ? 2 : 1));
-    while (nqt > 1 && sweep_bf16_lds_bytes(nqt, k, ix->dim) > 160 * 1024) nqt = nqt == 6 ? 4 : nqt / 2;
-    if (sweep_bf16_lds_bytes(nqt, k, ix->dim) > 160 * 1024)
-      return fail(VDB_ERR_UNSUPPORTED, "bf16 sweep: dim / k too large for the LDS query tile");
-    const uint32_t Bq = (uint32_t)nqt * 16;
-    const uint32_t tile = std::min<uint32_t>(Bq, rem);
-    const int waves = nqt >= 4 ? kBf16WavesBig : kBf16WavesSmall;
-    const size_t lds = sweep_bf16_lds_bytes(nqt, k, ix->dim);
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, (size_t)(16 / waves)));
-    const uint32_t ntiles = (uint32_t)((ix->n_rows + 15) / 16);
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)ntiles + waves - 1) / waves,
-                                                                 (int64_t)ix->n_cus * per_cu));
-    hipError_t e;
-    if ((e = ix->s_part_keys.reserve((size_t)Bq * blocks * k * 8, false, st)) != hipSuccess)
-      return fail(VDB_ERR_OOM, "top-k scratch");
-    EventPair* ev = next_events(ix);
-    if (ev) (void)hipEventRecord(ev->a, st);
-    ix->last_kernels |= VDB_KERNEL_SWEEP_MFMA_BF16;
-    e = launch_sweep_bf16(ix->metric, nqt, rows16, ix->bf16_stride, norms16,
-                          alive, d_q + (size_t)q0 * q_stride, q_stride, ix->s_part_keys.as<uint64_t>(),
-                          (uint32_t)ix->n_rows, ix->dim, tile, k, blocks, st, f16);
-    if (ev) (void)hipEventRecord(ev->b, st);
-    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("bf16 sweep launch: ") + hipGetErrorString(e));
-    MergeArgs m{};
-    m.part_keys = ix->s_part_keys.as<uint64_t>();
-    m.ext_ids = ix->ext_ids.as<uint64_t>();
-    m.out_ids = d_ids + (size_t)q0 * k;
-    m.out_scores = d_scores + (size_t)q0 * k;
-    m.out_n = d_n + q0;
-    m.n_lists = (uint32_t)blocks;
-    m.k = k;
-    launch_merge(true, m, tile, st);
-    q0 += tile;
+  for (uint32_t q0 = 0; q0 < s.nq;) {
+    const QuerySlice rest = s.sub(q0, s.nq - q0);
+    Took t = half_tier_glds(ix, h, rest, st);
+    if (t.open()) t = half_tier_gemm(ix, h, rest, st);
+    if (t.open()) t = half_tier_mfma(ix, h, rest, st);
+    if (t.rc != VDB_OK) return t.rc;
+    q0 += t.n;
   }
   VDB_HIP(hipGetLastError());
   return VDB_OK;
 }
+
 
 // ---- exact Cosine / DotProduct batches: split-bf16 selection + exact re-scoring + proof (sweep_split.hip) ----------------
 // first use: build the split image of every row (and the canonical norms a DotProduct index did not need so far)

@@ -26,6 +26,7 @@
 #include "vdb_filter_route.hpp"
 #include "vdb_index.hpp"
 #include "vdb_kernels.hpp"
+#include "vdb_sweep_pass.hpp"
 
 namespace vdb {
 
@@ -513,60 +514,51 @@ int32_t sq8_fallback_flagged(vdb_hip_index* ix, const float* d_q, uint64_t q_str
   return VDB_OK;
 }
 
-int32_t brute_sq8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                      float* d_scores, uint32_t* d_n, hipStream_t st) {
+// the SQ8 codes of the handle and the slice's queries; the caller sets alive and part_keys (nq and k: the slice's)
+static Sq8Args sq8_args(const vdb_hip_index* ix, const QuerySlice& c) {
+  Sq8Args a{};
+  a.codes = ix->sq8_codes.as<uint8_t>();
+  a.vmin = ix->sq8_min.as<float>();
+  a.vmax = ix->sq8_max.as<float>();
+  a.nsq = ix->sq8_nsq.as<float>();
+  a.queries = c.d_q;
+  a.code_stride = ix->sq8_stride;
+  a.q_stride = c.q_stride;
+  a.n_rows = (uint32_t)ix->n_rows;
+  a.dim = ix->dim;
+  a.nq = c.nq;
+  a.k = c.k;
+  return a;
+}
+
+int32_t brute_sq8_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st) {
   if (ix->storage_mode != VDB_STORAGE_SQ8) return fail(VDB_ERR_STATE, "SQ8 search: set the storage mode to SQ8 first");
   if (ix->metric != VDB_COSINE && ix->metric != VDB_EUCLIDEAN && ix->metric != VDB_DOT)
     return fail(VDB_ERR_UNSUPPORTED, "SQ8 search: Cosine, Euclidean and DotProduct only");
-  if (nq == 0) return VDB_OK;
-  if (k == 0 || ix->n_rows == 0) {
-    VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
-    return VDB_OK;
-  }
-  const uint8_t* alive = search_alive(ix);
-  for (uint32_t q0 = 0; q0 < nq;) {
-    int B = nq - q0 >= 8 ? 8 : (nq - q0 >= 4 ? 4 : 1);
+  if (s.nq == 0) return VDB_OK;
+  if (s.k == 0 || ix->n_rows == 0) return zero_results(s, st);
+  const uint32_t k = s.k;
+  for (uint32_t q0 = 0; q0 < s.nq;) {
+    int B = s.nq - q0 >= 8 ? 8 : (s.nq - q0 >= 4 ? 4 : 1);
     if (B == 8 && sq8_lds_bytes(8, k, ix->dim) > 160 * 1024) B = 4;
     if (B == 4 && sq8_lds_bytes(4, k, ix->dim) > 160 * 1024) B = 1;
     const size_t lds = sq8_lds_bytes(B, k, ix->dim);
     if (lds > 160 * 1024) return fail(VDB_ERR_UNSUPPORTED, "SQ8 search: dim / k too large for the LDS query tile");
-    const uint32_t tile = std::min<uint32_t>((uint32_t)B, nq - q0);
+    const QuerySlice c = s.sub(q0, std::min<uint32_t>((uint32_t)B, s.nq - q0));
     const uint32_t ngroups = (uint32_t)((ix->n_rows + 63) / 64);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, 4));
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)ngroups + 3) / 4, (int64_t)ix->n_cus * per_cu));
-    hipError_t e;
-    if ((e = ix->s_part_keys.reserve((size_t)B * blocks * k * 8, false, st)) != hipSuccess)
-      return fail(VDB_ERR_OOM, "top-k scratch");
-    Sq8Args a{};
-    a.codes = ix->sq8_codes.as<uint8_t>();
-    a.vmin = ix->sq8_min.as<float>();
-    a.vmax = ix->sq8_max.as<float>();
-    a.nsq = ix->sq8_nsq.as<float>();
-    a.alive = alive;
-    a.queries = d_q + (size_t)q0 * q_stride;
+    if (ix->s_part_keys.reserve((size_t)B * blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+    Sq8Args a = sq8_args(ix, c);
+    a.alive = search_alive(ix);
     a.part_keys = ix->s_part_keys.as<uint64_t>();
-    a.code_stride = ix->sq8_stride;
-    a.q_stride = q_stride;
-    a.n_rows = (uint32_t)ix->n_rows;
-    a.dim = ix->dim;
-    a.nq = tile;
-    a.k = k;
-    EventPair* ev = next_events(ix);
-    if (ev) (void)hipEventRecord(ev->a, st);
-    e = B == 8 ? launch_sq8_m<8>(ix->metric, a, blocks, lds, st)
-               : (B == 4 ? launch_sq8_m<4>(ix->metric, a, blocks, lds, st) : launch_sq8_m<1>(ix->metric, a, blocks, lds, st));
-    if (ev) (void)hipEventRecord(ev->b, st);
-    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("SQ8 sweep launch: ") + hipGetErrorString(e));
-    MergeArgs m{};
-    m.part_keys = a.part_keys;
-    m.ext_ids = ix->ext_ids.as<uint64_t>();
-    m.out_ids = d_ids + (size_t)q0 * k;
-    m.out_scores = d_scores + (size_t)q0 * k;
-    m.out_n = d_n + q0;
-    m.n_lists = (uint32_t)blocks;
-    m.k = k;
-    launch_merge(ix->metric != VDB_EUCLIDEAN, m, tile, st);
-    q0 += tile;
+    const int32_t rc = timed_launch(ix, 0, st, "SQ8 sweep launch", [&] {  // (VDB_KERNEL_SQ8: the caller's)
+      return B == 8 ? launch_sq8_m<8>(ix->metric, a, blocks, lds, st)
+                    : (B == 4 ? launch_sq8_m<4>(ix->metric, a, blocks, lds, st) : launch_sq8_m<1>(ix->metric, a, blocks, lds, st));
+    });
+    if (rc != VDB_OK) return rc;
+    merge_pass(ix, ix->metric != VDB_EUCLIDEAN, a.part_keys, nullptr, (uint32_t)blocks, c, st);
+    q0 += c.nq;
   }
   VDB_HIP(hipGetLastError());
   return VDB_OK;
@@ -575,54 +567,33 @@ int32_t brute_sq8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, ui
 // The listed route of a filtered SQ8 call (vdb_hip_index_search_batch_filtered_mode): sweep_topk_sq8_listed over the
 // filter's ascending row list, pass by pass (mode_listed_plan, vdb_filter_route.hpp), merge_topk behind every pass.  The caller has
 // checked the storage mode, the metric, k > 0 and count > 0, and that the plan of the first pass fits.
-int32_t brute_sq8_listed_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const float* d_q, uint64_t q_stride, uint32_t nq,
-                             uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st) {
-  for (uint32_t q0 = 0; q0 < nq;) {
-    const ModeListedPlan lp = mode_listed_plan(false, ix->dim, k, count, nq - q0, ix->n_cus);
+int32_t brute_sq8_listed_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st) {
+  const uint32_t k = s.k;
+  for (uint32_t q0 = 0; q0 < s.nq;) {
+    const ModeListedPlan lp = mode_listed_plan(false, ix->dim, k, count, s.nq - q0, ix->n_cus);
     if (lp.blocks == 0) return fail(VDB_ERR_UNSUPPORTED, "SQ8 search: dim / k too large for the LDS query tile");
     if (ix->s_part_keys.reserve((size_t)lp.B * lp.blocks * k * 8, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
+    const QuerySlice c = s.sub(q0, lp.nq_pass);
     Sq8ListedArgs la{};
-    la.a.codes = ix->sq8_codes.as<uint8_t>();
-    la.a.vmin = ix->sq8_min.as<float>();
-    la.a.vmax = ix->sq8_max.as<float>();
-    la.a.nsq = ix->sq8_nsq.as<float>();
+    la.a = sq8_args(ix, c);
     la.a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;  // rows removed since the filter was made
-    la.a.queries = d_q + (size_t)q0 * q_stride;
     la.a.part_keys = ix->s_part_keys.as<uint64_t>();
-    la.a.code_stride = ix->sq8_stride;
-    la.a.q_stride = q_stride;
-    la.a.n_rows = (uint32_t)ix->n_rows;
-    la.a.dim = ix->dim;
-    la.a.nq = lp.nq_pass;
-    la.a.k = k;
     la.list = list;
     la.count = count;
     la.per_block = lp.per_block;
-    ix->last_kernels |= VDB_KERNEL_SWEEP_LISTED;
-    EventPair* ev = next_events(ix);
-    if (ev) (void)hipEventRecord(ev->a, st);
-    const hipError_t e = lp.B == 8 ? launch_sq8_listed_m<8>(ix->metric, la, lp.blocks, (size_t)lp.lds, st)
-                                   : (lp.B == 4 ? launch_sq8_listed_m<4>(ix->metric, la, lp.blocks, (size_t)lp.lds, st)
-                                                : launch_sq8_listed_m<1>(ix->metric, la, lp.blocks, (size_t)lp.lds, st));
-    if (ev) (void)hipEventRecord(ev->b, st);
-    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("listed SQ8 sweep launch: ") + hipGetErrorString(e));
-    MergeArgs m{};
-    m.part_keys = la.a.part_keys;
-    m.ext_ids = ix->ext_ids.as<uint64_t>();
-    m.out_ids = d_ids + (size_t)q0 * k;
-    m.out_scores = d_scores + (size_t)q0 * k;
-    m.out_n = d_n + q0;
-    m.n_lists = (uint32_t)lp.blocks;
-    m.k = k;
-    launch_merge(ix->metric != VDB_EUCLIDEAN, m, lp.nq_pass, st);
-    q0 += lp.nq_pass;
+    const int32_t rc = timed_launch(ix, VDB_KERNEL_SWEEP_LISTED, st, "listed SQ8 sweep launch", [&] {
+      return lp.B == 8 ? launch_sq8_listed_m<8>(ix->metric, la, lp.blocks, (size_t)lp.lds, st)
+                       : (lp.B == 4 ? launch_sq8_listed_m<4>(ix->metric, la, lp.blocks, (size_t)lp.lds, st)
+                                    : launch_sq8_listed_m<1>(ix->metric, la, lp.blocks, (size_t)lp.lds, st));
+    });
+    if (rc != VDB_OK) return rc;
+    merge_pass(ix, ix->metric != VDB_EUCLIDEAN, la.a.part_keys, nullptr, (uint32_t)lp.blocks, c, st);
+    q0 += c.nq;
   }
   VDB_HIP(hipGetLastError());
   return VDB_OK;
 }
 
-// BinaryQuantizedVector::hamming_distance between the sign bits of the queries and of every row: the packed-bit
-// sweep of sweep.hip over the sign-bit array (scores = distance as f32, smallest first)
 // the four-bit image of the sign-bit codes (bits_gemm.hip: batches of >= 32 queries run on the matrix cores), in the storage mode's
 // image buffers (vdb_index.hpp); built at first use, extended lazily behind inserts — inside a search: see index.hip
 // build_image_on_primary for why a build is complete before the image is handed on
@@ -646,103 +617,24 @@ static int32_t ensure_sign_image(vdb_hip_index* cx, hipStream_t st) {
   return VDB_OK;
 }
 
-int32_t brute_binary_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                         float* d_scores, uint32_t* d_n, hipStream_t st) {
-  if (ix->storage_mode != VDB_STORAGE_BINARY) return fail(VDB_ERR_STATE, "Binary search: set the storage mode to Binary first");
-  if (nq == 0) return VDB_OK;
-  if (k == 0 || ix->n_rows == 0) {
-    VDB_HIP(hipMemsetAsync(d_n, 0, (size_t)nq * 4, st));
-    return VDB_OK;
-  }
-  if ((size_t)4 * k * 8 + (size_t)ix->words * 4 + 32 > 60 * 1024)
-    return fail(VDB_ERR_UNSUPPORTED, "k too large for the fused top-k path");
-  hipError_t e;
-  // one or two queries: ONE launch — the blocks take the query's sign bits themselves, the one that finishes last merges (sweep.hip)
-  if (opt_bits_fused(ix) && sweep_bits_fused_supported(ix->words, nq, k)) {
-    const int fblocks = sweep_bits_fused_blocks(ix->n_rows, ix->n_cus);
-    if (ix->s_tickets.cap == 0) {
-      if ((e = ix->s_tickets.reserve(16, false, st)) != hipSuccess) return fail(VDB_ERR_OOM, "ticket scratch");
-      VDB_HIP(hipMemsetAsync(ix->s_tickets.p, 0, 16, st));
-    }
-    if ((e = ix->s_part_keys.reserve((size_t)nq * fblocks * k * 8, false, st)) != hipSuccess) return fail(VDB_ERR_OOM, "top-k scratch");
-    BitsFusedArgs fa{};
-    fa.bits = ix->sign_bits.as<uint32_t>();
-    fa.q = d_q;
-    fa.q_stride = q_stride;
-    fa.alive = search_alive(ix);
-    fa.part_keys = ix->s_part_keys.as<uint64_t>();
-    fa.tickets = ix->s_tickets.as<uint32_t>();
-    fa.n_rows = (uint32_t)ix->n_rows;
-    fa.words = ix->words;
-    fa.dim = ix->dim;
-    fa.k = k;
-    fa.sign_rule = 1u;
-    fa.m.ext_ids = ix->ext_ids.as<uint64_t>();
-    fa.m.out_ids = d_ids;
-    fa.m.out_scores = d_scores;
-    fa.m.out_n = d_n;
-    EventPair* evf = next_events(ix);
-    if (evf) (void)hipEventRecord(evf->a, st);
-    if ((e = launch_sweep_bits_fused(VDB_HAMMING, fa, fblocks, nq, st)) != hipSuccess)
-      return fail(VDB_ERR_HIP, std::string("one-launch sign-bit search: ") + hipGetErrorString(e));
-    if (evf) (void)hipEventRecord(evf->b, st);
-    return VDB_OK;
-  }
-  e = ix->s_qbits.reserve((size_t)nq * ix->words * 4, false, st);
-  if (e != hipSuccess) return fail(VDB_ERR_OOM, "qbits scratch");
-  hipLaunchKernelGGL(sign_bits_rows, dim3((unsigned)std::min<uint32_t>((nq + 3) / 4, 4096)), dim3(256), 0, st, d_q, q_stride,
-                     ix->s_qbits.as<uint32_t>(), ix->words, 0u, nq, ix->dim);
-  // large batches: Hamming between sign-bit codes as a four-bit GEMM distance on the matrix cores (bits_gemm.hip), exact; the rest of
-  // the batch and every other shape on the vector ALUs — the same keys either way
-  uint32_t qdone = 0;
-  while (opt_value(ix, VDB_OPT_SWEEP_ENGINE) == 1 && opt_value(ix, VDB_OPT_MAX_QUERY_TILE) >= 128) {
-    const uint32_t nqg = bits_gemm_chunk(ix, nq - qdone, k);
-    if (!nqg) break;
-    int32_t rg = ensure_sign_image(ix, st);
-    if (rg == VDB_OK)
-      rg = brute_bits_gemm_dev(ix, VDB_HAMMING, ix->sq8_img.as<uint8_t>(), ix->sq8_nrm.as<float>(), ix->s_qbits.as<uint32_t>() + (size_t)qdone * ix->words, nqg,
-                               k, d_ids + (size_t)qdone * k, d_scores + (size_t)qdone * k, d_n + qdone, st);
-    if (rg != VDB_OK) return rg;
-    qdone += nqg;
-  }
-  if (qdone == nq) return VDB_OK;
-  d_ids += (size_t)qdone * k;
-  d_scores += (size_t)qdone * k;
-  d_n += qdone;
-  const uint32_t* qbits_rest = ix->s_qbits.as<uint32_t>() + (size_t)qdone * ix->words;
-  nq -= qdone;
-  const BitsPlan bp = plan_bits_sweep(ix->n_rows, ix->n_cus, ix->words, nq, k);  // batches: 8 / 32 queries per corpus pass
-  const int blocks = bp.blocks;
-  if ((e = ix->s_part_keys.reserve((size_t)nq * blocks * k * 8, false, st)) != hipSuccess ||
-      (e = ix->s_part_cnt.reserve((size_t)nq * blocks * 4, false, st)) != hipSuccess)
-    return fail(VDB_ERR_OOM, "top-k scratch");
-  BitsArgs ba{};
-  ba.bits = ix->sign_bits.as<uint32_t>();
-  ba.qbits = qbits_rest;
-  ba.alive = search_alive(ix);
-  ba.part_keys = ix->s_part_keys.as<uint64_t>();
-  ba.part_cnt = ix->s_part_cnt.as<uint32_t>();
-  ba.n_rows = (uint32_t)ix->n_rows;
-  ba.words = ix->words;
-  ba.k = k;
-  EventPair* ev = next_events(ix);
-  if (ev) (void)hipEventRecord(ev->a, st);
-  if ((e = launch_bits_plan(VDB_HAMMING, bp, ba, nq, st)) != hipSuccess)
-    return fail(VDB_ERR_HIP, std::string("sign-bit sweep launch: ") + hipGetErrorString(e));
-  if (ev) (void)hipEventRecord(ev->b, st);
-  MergeArgs m{};
-  m.part_keys = ba.part_keys;
-  m.part_cnt = ba.part_cnt;
-  m.ext_ids = ix->ext_ids.as<uint64_t>();
-  m.out_ids = d_ids;
-  m.out_scores = d_scores;
-  m.out_n = d_n;
-  m.n_lists = (uint32_t)blocks;
-  m.k = k;
-  launch_merge(false, m, nq, st);
-  VDB_HIP(hipGetLastError());
-  return VDB_OK;
+// the queries' sign bits, by the kernel that encodes rows
+static void pack_queries_as_signs(const vdb_hip_index* ix, const QuerySlice& s, uint32_t* qbits, hipStream_t st) {
+  hipLaunchKernelGGL(sign_bits_rows, dim3((unsigned)std::min<uint32_t>((s.nq + 3) / 4, 4096)), dim3(256), 0, st, s.d_q, s.q_stride, qbits, ix->words, 0u,
+                     s.nq, ix->dim);
 }
+
+// BinaryQuantizedVector::hamming_distance between the sign bits of the queries and of every row: the packed-bit path of index.hip
+// (brute_bits_dev: one-launch kernel, four-bit GEMM on the matrix cores, vector-ALU plan) over the sign-bit array — scores = distance
+// as f32, smallest first
+int32_t brute_binary_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st) {
+  if (ix->storage_mode != VDB_STORAGE_BINARY) return fail(VDB_ERR_STATE, "Binary search: set the storage mode to Binary first");
+  if (s.nq == 0) return VDB_OK;
+  if (s.k == 0 || ix->n_rows == 0) return zero_results(s, st);
+  const BitsSource src{ix->sign_bits.as<uint32_t>(), pack_queries_as_signs, VDB_HAMMING, ensure_sign_image, &vdb_hip_index::sq8_img, &vdb_hip_index::sq8_nrm,
+                       /*sign_rule=*/1u, /*higher_is_better=*/false, "one-launch sign-bit search", "sign-bit sweep launch"};
+  return brute_bits_dev(ix, src, s, st);
+}
+
 
 }  // namespace vdb
 

@@ -332,10 +332,9 @@ int32_t search_filtered_to_device(vdb_hip_index* ix, const RowFilter* f, const f
 // ... in one of the modes VDB_SEARCH_BRUTE_SQ8 / _BINARY / _BF16 / _F16 (vdb_hip_index_search_batch_filtered_mode)
 int32_t search_filtered_mode_to_device(vdb_hip_index* ix, const RowFilter* f, int32_t mode, const float* queries, uint32_t nq, uint32_t k);
 // the listed passes of that call (storage_modes.hip / select_stage.hip): `list` = the filter's ascending rows, count > 0, k > 0
-int32_t brute_sq8_listed_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const float* d_q, uint64_t q_stride, uint32_t nq,
-                             uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st);
-int32_t brute_half_l2_listed_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const float* d_q, uint64_t q_stride,
-                                 uint32_t nq, uint32_t k, uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st);
+struct QuerySlice;  // vdb_sweep_pass.hpp: the queries a pass answers and where their answers go
+int32_t brute_sq8_listed_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
+int32_t brute_half_l2_listed_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
 // the filter belongs to this handle (generation) and to its present row numbering (row_epoch): anything else is an error
 int32_t filter_check(vdb_hip_index* ix, const RowFilter* f);
 // one optional filter per query on the exact sweep (index.hip): filters[n_filters] handles (checked inside, all of them
@@ -401,6 +400,8 @@ int32_t search_staged(vdb_hip_index* ix, uint32_t nq, uint32_t k, uint32_t ef, i
                       const uint32_t* d_extra_eps = nullptr);
 // effective option values (index.hip)
 int64_t opt_value(const vdb_hip_index* ix, int32_t option);
+static inline uint32_t opt_max_tile(const vdb_hip_index* ix) { return (uint32_t)opt_value(ix, VDB_OPT_MAX_QUERY_TILE); }
+static inline int opt_engine(const vdb_hip_index* ix) { return (int)opt_value(ix, VDB_OPT_SWEEP_ENGINE); }
 bool mode_higher_is_better(int metric, int32_t mode);
 // shard_group.hip
 int32_t group_create(vdb_hip_index* parent, const int32_t* devices, int32_t n_devices, int32_t shard_mode,
@@ -460,8 +461,7 @@ constexpr uint32_t kVlogCap = 16384;
 constexpr int kTraversalSlotsPerCu = 8;  // visited bitmaps / id logs are sized for this many queries in flight per CU
 // storage_modes.hip
 int32_t storage_mode_append(vdb_hip_index* ix, uint64_t first, uint64_t n);
-int32_t brute_sq8_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                      float* d_scores, uint32_t* d_n, hipStream_t st);
+int32_t brute_sq8_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st);
 int32_t ensure_sq8_select(vdb_hip_index* ix, hipStream_t st);
 struct SelectFinishArgs;  // vdb_kernels.hpp
 int32_t sq8_fallback_flagged(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nqg, uint32_t k, const uint32_t* qmap,
@@ -472,8 +472,7 @@ int32_t brute_split_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, 
 int select_level_sq8(vdb_hip_index* ix, uint32_t nq_left, uint32_t k);
 // bits_gemm.hip
 uint32_t bits_gemm_chunk(const vdb_hip_index* ix, uint32_t nq_left, uint32_t k);
-int32_t brute_bits_gemm_dev(vdb_hip_index* ix, int metric, const uint8_t* img, const float* cnt, const uint32_t* qbits, uint32_t nqg, uint32_t k,
-                            uint64_t* d_ids, float* d_scores, uint32_t* d_n, hipStream_t st);
-int32_t brute_binary_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids,
-                         float* d_scores, uint32_t* d_n, hipStream_t st);
+// (s.d_q is not read: the chunk's queries arrive packed in qbits [s.nq][words])
+int32_t brute_bits_gemm_dev(vdb_hip_index* ix, int metric, const uint8_t* img, const float* cnt, const uint32_t* qbits, const QuerySlice& s, hipStream_t st);
+int32_t brute_binary_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st);
 }  // namespace vdb

@@ -12,8 +12,7 @@ int blocks_for(const vdb_hip_index* ix, int B, uint32_t ngroups);      // grid o
 
 // select_stage.hip
 // exact sweep over the bf16 copy of the rows (VDB_SEARCH_BRUTE_BF16) or — f16 — over the IEEE f16 copy (VDB_SEARCH_BRUTE_F16)
-int32_t brute_bf16_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint32_t nq, uint32_t k, uint64_t* d_ids, float* d_scores,
-                       uint32_t* d_n, hipStream_t st, bool f16 = false);
+int32_t brute_bf16_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st, bool f16 = false);
 // which selection level serves the next chunk of an exact batch (0: none) and how many queries it takes
 int select_level(vdb_hip_index* ix, uint32_t nq_left, uint32_t k);
 int select_level_l2(vdb_hip_index* ix, uint32_t nq_left, uint32_t k);
