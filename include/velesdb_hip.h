@@ -373,7 +373,46 @@ int32_t vdb_hip_index_search_batch_filtered_mode(vdb_hip_index* idx, const void*
 int32_t vdb_hip_index_search_batch_filters(vdb_hip_index* idx, void** filters, uint32_t n_filters,
                                            const uint32_t* filter_of_query, const float* queries_rowmajor, uint32_t nq,
                                            uint32_t k, int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
-/* diagnostic: the plan of THIS THREAD's last vdb_hip_index_search_batch_filters call on the handle (the rule of
+/* One filter PER QUERY over the SQ8 codes, the sign bits or a half image of the rows: the reference's search_batch_with_filters works
+ * whatever the collection's storage mode.  mode is one of VDB_SEARCH_BRUTE_SQ8, VDB_SEARCH_BRUTE_BINARY,
+ * VDB_SEARCH_BRUTE_BF16, VDB_SEARCH_BRUTE_F16.  The table's conventions are vdb_hip_index_search_batch_filters': the filters are
+ * distinct handles of this index; filter_of_query[i] == n_filters means query i has no filter; n_filters == 0 with filters == NULL is
+ * legal; every filter is checked before anything runs; the outputs are untouched on error; host pointers only; the call never goes
+ * through the combining front.
+ * THE CONTRACT:
+ *  - SQ8, Binary, Euclidean over a half image: query i gets, bit for bit, what vdb_hip_index_search_batch_filtered_mode returns for
+ *    that query ALONE with its filter, the same mode and the same k — ids, ranks, score bits, out_n and padding.  A query without a
+ *    filter gets what vdb_hip_index_search_batch(mode) returns for it alone.  (These modes' summation orders are declared.)
+ *  - Cosine / DotProduct over a half image: the bits depend on the matrix-core tier, which depends on the batch size.  Query i gets
+ *    bit for bit what the one-filter mode call returns for its GROUP — the queries that name the same filter, in call order; the
+ *    group runs as exactly that job.  That result is within the mode's existing tolerance, tie-aware, of the query alone, and bit for
+ *    bit on data whose partial sums are exact.  The unfiltered queries are held to the plain mode call over them, in call order, the
+ *    same way.
+ *  - Independence: an answer never depends on the query's companions outside its group, on its position in the batch, or on
+ *    VDB_OPT_FILTER_ROUTE — the half Cosine / DotProduct tier being the one exception, as stated above.
+ *  - Empty filters: a query of an empty filter gets out_n = 0 behind the merge's padding, as vdb_hip_index_search_batch_filters
+ *    defines it, while the others are answered.
+ * Queries are grouped by filter, call order kept inside a group, and every group takes the route the one-filter mode call's rule gives
+ * it with ITS matched count and ITS number of queries (VDB_OPT_FILTER_ROUTE applies per group; auto sends an SQ8 group to the listed
+ * kernel only with at most three queries; Binary and Cosine / DotProduct over a half image have no listed kernel).  The groups on the
+ * listed route share launches — sweep_topk_sq8_listed_groups / sweep_topk_half_l2_listed_groups, at most three (one per pass width:
+ * 8 / 4 / 1 for SQ8, 16 / 4 / 1 for half Euclidean) and ONE merge, whatever n_filters and nq are —; the groups on mask substitution run
+ * one after another through the mode's own dispatch, the unfiltered queries together as one job of the plain mode call.  A call whose
+ * queries all name ONE filter runs vdb_hip_index_search_batch_filtered_mode itself: the same launches, the same
+ * vdb_hip_index_last_kernels.
+ * vdb_hip_index_last_kernels: the mode's usual bits, plus VDB_KERNEL_SWEEP_LISTED_GROUPS when a grouped launch ran;
+ * vdb_hip_index_last_filters_exact_plan reports this call's plan too.
+ * The call leaves the handle's adaptive selection state (the hold counters of the selection stages, the verdict sequence) as it found
+ * it and posts no selection verdicts, for its unfiltered job too.
+ * Errors: the table's are vdb_hip_index_search_batch_filters' (a NULL table entry or a filter of another handle, a filter_of_query
+ * value > n_filters: VDB_ERR_INVALID_ARG; a stale filter: VDB_ERR_STATE); the mode's and the state's are
+ * vdb_hip_index_search_batch_filtered_mode's: a mode whose storage mode or image is not enabled VDB_ERR_STATE (checked before an empty
+ * filter's out_n = 0); VDB_SEARCH_BRUTE (it has vdb_hip_index_search_batch_filters), every other mode, multi-device handles and
+ * process-group members VDB_ERR_UNSUPPORTED. */
+int32_t vdb_hip_index_search_batch_filters_mode(vdb_hip_index* idx, void** filters, uint32_t n_filters,
+                                                const uint32_t* filter_of_query, int32_t mode, const float* queries_rowmajor,
+                                                uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
+/* diagnostic: the plan of THIS THREAD's last vdb_hip_index_search_batch_filters or vdb_hip_index_search_batch_filters_mode call on the handle (the rule of
  * vdb_hip_index_last_kernels).  out holds six values: out[0] distinct filter groups, out[1] groups on the listed route, out[2] groups on mask
  * substitution, out[3] unfiltered queries, out[4] grouped sweep launches, out[5] merge launches behind them (a call that ran the
  * one-filter path itself has none of either: out[4] = out[5] = 0). */
@@ -796,7 +835,8 @@ enum vdb_kernel_bit {
  * the walk; next to VDB_KERNEL_HNSW_FILTERED | VDB_KERNEL_HNSW_HALF) */
 #define VDB_KERNEL_HALF_RESCORE 1048576
 /* ... and one more: sweep_topk_listed_groups / sweep_topk_listed_groups_m ran (vdb_hip_index_search_batch_filters, the grouped
- * launches of its groups on the listed route) */
+ * launches of its groups on the listed route), or sweep_topk_sq8_listed_groups / sweep_topk_half_l2_listed_groups
+ * (vdb_hip_index_search_batch_filters_mode, the same over the SQ8 codes / Euclidean over a half image) */
 #define VDB_KERNEL_SWEEP_LISTED_GROUPS 2097152
 /* ... and one more: hybrid_fuse_kernel ran (vdb_hip_index_hybrid_search sets it next to the walk's bits) */
 #define VDB_KERNEL_HYBRID_FUSE 4194304

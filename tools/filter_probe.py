@@ -49,6 +49,14 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
   min / max of the blocks of each; once under the auto route rule and once with mask substitution forced.  The answers are held
   to agree bit for bit first.  Asserted: at F = 1 the new call's median lies inside the loop's own min-max spread (it is the same
   code path); everything else is recorded.  Defaults of this leg: --rows 100000, --densities 0.001,0.01,0.1.
+  --exact-per-query F[,F...] --storage sq8|binary|f16|bf16: the same leg over that image of the rows
+  (vdb_hip_index_search_batch_filters_mode) beside a loop of vdb_hip_index_search_batch_filtered_mode calls, one per
+  filter — the only thing the library had before it —, once per forced route (listed, mask) and under the auto rule.  The answers
+  are held to agree first: bit for bit where the mode declares its summation order (SQ8, Binary, Euclidean over a half image; and
+  everywhere here, the loop's call over a filter's queries being exactly the group's job).  The F = 1 rows are the same code path
+  on both sides and are gated as above.  One run per image is recorded: profiles/filter_probe_filters_modes_sq8_100k.json and
+  profiles/filter_probe_filters_modes_f16_100k.json (in both the gate failed: the loop's own min - max is 0.1 - 0.4 % of its
+  median, 10 of 27 F = 1 medians lie outside it by at most 0.2 %, in both directions).
 
   --exact --storage sq8|binary|f16|bf16: the exact leg over that image of the rows (vdb_hip_index_search_batch_filtered_mode, DESIGN
   4.1o): per metric, batch size and selectivity the forced listed route, the forced mask route, the auto rule and — what an
@@ -99,8 +107,8 @@ p.add_argument("--out", default="")
 a = p.parse_args()
 if a.exact and (a.graph or a.exact_per_query):
     p.error("--exact names the exact leg: not with --graph / --exact-per-query")
-if a.storage and (not a.exact or a.graph or a.exact_per_query):
-    p.error("--storage goes with --exact (the exact leg over that image of the rows)")
+if a.storage and (a.graph or not (a.exact or a.exact_per_query)):
+    p.error("--storage goes with --exact or --exact-per-query (the exact legs over that image of the rows)")
 dev = torch.device("cuda", 0)
 st = torch.cuda.current_stream().cuda_stream
 METRICS = {"cosine": va.DistanceMetric.Cosine, "euclidean": va.DistanceMetric.Euclidean, "dot": va.DistanceMetric.DotProduct}
@@ -364,6 +372,11 @@ def exact_per_query_leg():
     for mname in a.metrics.split(","):
         ix = build(METRICS[mname])
         ix.set_option(va.OPT_COMBINE_MAX_BATCH, 0)
+        mode = {"": va.MODE_BRUTE, "sq8": va.MODE_BRUTE_SQ8, "binary": va.MODE_BRUTE_BINARY, "f16": va.MODE_BRUTE_F16, "bf16": va.MODE_BRUTE_BF16}[a.storage]
+        if a.storage in ("sq8", "binary"):
+            ix.set_storage_mode(va.StorageMode.SQ8 if a.storage == "sq8" else va.StorageMode.Binary)
+        elif a.storage:
+            ix.enable_half_precision(va.VectorPrecision.F16 if a.storage == "f16" else va.VectorPrecision.BF16)
         rng = np.random.default_rng(7)
         Q = rng.standard_normal((nq, a.dim)).astype(np.float32)
         for F in [int(x) for x in a.exact_per_query.split(",")]:
@@ -383,21 +396,31 @@ def exact_per_query_leg():
                 o_ids, o_sc, o_cnt = np.empty((nq, a.k), np.uint64), np.empty((nq, a.k), np.float32), np.zeros(nq, np.uint32)
                 outs = [(np.empty((len(p), a.k), np.uint64), np.empty((len(p), a.k), np.float32), np.zeros(len(p), np.uint32)) for p in parts]
 
-                new_args = (ix._h, handles, F, vp(fq), vp(Q), nq, a.k, va.MODE_BRUTE, vp(o_ids), vp(o_sc), vp(o_cnt))
-                loop_args = [(ix._h, flts[j]._h, vp(Qs[j]), len(parts[j]), a.k, va.MODE_BRUTE, vp(outs[j][0]), vp(outs[j][1]), vp(outs[j][2]))
-                             for j in range(F)]
+                if a.storage:  # (the two mode calls take the mode in front of the queries)
+                    new_fn, loop_fn = L.vdb_hip_index_search_batch_filters_mode, L.vdb_hip_index_search_batch_filtered_mode
+                    new_args = (ix._h, handles, F, vp(fq), mode, vp(Q), nq, a.k, vp(o_ids), vp(o_sc), vp(o_cnt))
+                    loop_args = [(ix._h, flts[j]._h, mode, vp(Qs[j]), len(parts[j]), a.k, vp(outs[j][0]), vp(outs[j][1]), vp(outs[j][2]))
+                                 for j in range(F)]
+                else:
+                    new_fn, loop_fn = L.vdb_hip_index_search_batch_filters, L.vdb_hip_index_search_batch_filtered
+                    new_args = (ix._h, handles, F, vp(fq), vp(Q), nq, a.k, va.MODE_BRUTE, vp(o_ids), vp(o_sc), vp(o_cnt))
+                    loop_args = [(ix._h, flts[j]._h, vp(Qs[j]), len(parts[j]), a.k, va.MODE_BRUTE, vp(outs[j][0]), vp(outs[j][1]), vp(outs[j][2]))
+                                 for j in range(F)]
 
                 def one_call():
-                    va._ffi.check(L.vdb_hip_index_search_batch_filters(*new_args))
+                    va._ffi.check(new_fn(*new_args))
                     return o_ids, o_sc, o_cnt
 
                 def loop():
                     for args in loop_args:
-                        va._ffi.check(L.vdb_hip_index_search_batch_filtered(*args))
+                        va._ffi.check(loop_fn(*args))
                     return outs
-                for rname, route in (("auto", va.FILTER_ROUTE_AUTO), ("mask", va.FILTER_ROUTE_MASK)):
+                routes = (("auto", va.FILTER_ROUTE_AUTO), ("mask", va.FILTER_ROUTE_MASK))
+                if a.storage:
+                    routes = (("listed", va.FILTER_ROUTE_LISTED),) + routes
+                for rname, route in routes:
                     ix.set_option(va.OPT_FILTER_ROUTE, route)
-                    row = dict(leg="exact_per_query", metric=mname, arith=ix.sweep_arith_mode(a.k), rows=a.rows, dim=a.dim, k=a.k, nq=nq, filters=F,
+                    row = dict(leg="exact_per_query", storage=a.storage or "f32", metric=mname, arith=ix.sweep_arith_mode(a.k), rows=a.rows, dim=a.dim, k=a.k, nq=nq, filters=F,
                                density=dens, count=count, route=rname)
                     ids, sc, cnt = one_call()
                     row["plan"] = list(ix.last_filters_exact_plan())
@@ -478,7 +501,7 @@ def storage_leg():
 
 table = []
 f1_outside = []
-if a.storage:
+if a.storage and not a.exact_per_query:
     table = storage_leg()
     a.metrics = ""
 elif a.exact_per_query:

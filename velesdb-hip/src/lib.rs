@@ -1050,6 +1050,23 @@ impl HipHnswIndex {
     /// selective filters share a constant number of launches.
     #[must_use]
     pub fn search_batch_brute_force_with_filters(&self, queries: &[&[f32]], k: usize, filters: &[Option<&HipFilter>]) -> Vec<Vec<(u64, f32)>> {
+        self.batch_with_filters_exact(queries, k, filters, sys::VDB_SEARCH_BRUTE)
+    }
+
+    /// The same over the SQ8 codes, the sign bits or a half image of the rows (`vdb_hip_index_search_batch_filters_mode`): `mode` is
+    /// one of `sys::VDB_SEARCH_BRUTE_SQ8`, `_BINARY`, `_BF16`, `_F16`.  SQ8, Binary and Euclidean over a half image: query `i` gets
+    /// bit for bit what [`Self::search_batch_filtered_mode`] returns for it alone with its filter (without one: what the plain
+    /// search of that mode returns for it alone).  Cosine / DotProduct over a half image: bit for bit what the one-filter call
+    /// returns for the query's group — the queries that name the same filter, in call order.
+    #[must_use]
+    pub fn search_batch_with_filters_mode(&self, queries: &[&[f32]], k: usize, filters: &[Option<&HipFilter>], mode: i32) -> Vec<Vec<(u64, f32)>> {
+        assert!(mode != sys::VDB_SEARCH_BRUTE, "search_batch_with_filters_mode: VDB_SEARCH_BRUTE has search_batch_brute_force_with_filters");
+        self.batch_with_filters_exact(queries, k, filters, mode)
+    }
+
+    // one optional filter per query on an exact sweep: VDB_SEARCH_BRUTE through vdb_hip_index_search_batch_filters, the SQ8 / Binary /
+    // half modes through vdb_hip_index_search_batch_filters_mode (the same table, the same outputs)
+    fn batch_with_filters_exact(&self, queries: &[&[f32]], k: usize, filters: &[Option<&HipFilter>], mode: i32) -> Vec<Vec<(u64, f32)>> {
         assert!(
             queries.len() == filters.len(),
             "Queries count ({}) does not match filters count ({})",
@@ -1092,19 +1109,35 @@ impl HipHnswIndex {
         // SAFETY: buffer sizes are n_filters / nq / nq*dim / nq*k / nq as the ABI requires; every handle of the table is live
         // (borrowed from `filters`); the library does not write through the table.
         check(unsafe {
-            sys::vdb_hip_index_search_batch_filters(
-                self.h,
-                table_p,
-                none,
-                fq.as_ptr(),
-                flat.as_ptr(),
-                nq as u32,
-                k as u32,
-                sys::VDB_SEARCH_BRUTE,
-                ids.as_mut_ptr(),
-                scores.as_mut_ptr(),
-                counts.as_mut_ptr(),
-            )
+            if mode == sys::VDB_SEARCH_BRUTE {
+                sys::vdb_hip_index_search_batch_filters(
+                    self.h,
+                    table_p,
+                    none,
+                    fq.as_ptr(),
+                    flat.as_ptr(),
+                    nq as u32,
+                    k as u32,
+                    mode,
+                    ids.as_mut_ptr(),
+                    scores.as_mut_ptr(),
+                    counts.as_mut_ptr(),
+                )
+            } else {
+                sys::vdb_hip_index_search_batch_filters_mode(
+                    self.h,
+                    table_p,
+                    none,
+                    fq.as_ptr(),
+                    mode,
+                    flat.as_ptr(),
+                    nq as u32,
+                    k as u32,
+                    ids.as_mut_ptr(),
+                    scores.as_mut_ptr(),
+                    counts.as_mut_ptr(),
+                )
+            }
         });
         (0..nq)
             .map(|i| {
@@ -1114,7 +1147,7 @@ impl HipHnswIndex {
             .collect()
     }
 
-    /// The plan of this thread's last [`Self::search_batch_brute_force_with_filters`] call
+    /// The plan of this thread's last [`Self::search_batch_brute_force_with_filters`] or [`Self::search_batch_with_filters_mode`] call
     /// (`vdb_hip_index_last_filters_exact_plan`): `[filter groups, groups on the listed route, groups on mask substitution,
     /// unfiltered queries, grouped sweep launches, merge launches behind them]`.
     #[must_use]

@@ -154,6 +154,7 @@ extern "C" {
     pub fn vdb_hip_index_search_batch_filtered_mode(idx: *mut VdbHipIndex, f: *const c_void, mode: i32, queries_rowmajor: *const f32, nq: u32, k: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filtered(idx: *mut VdbHipIndex, f: *const c_void, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, mode: i32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
     pub fn vdb_hip_index_search_batch_filters(idx: *mut VdbHipIndex, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, mode: i32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
+    pub fn vdb_hip_index_search_batch_filters_mode(idx: *mut VdbHipIndex, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, mode: i32, queries_rowmajor: *const f32, nq: u32, k: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_index_last_filters_exact_plan(idx: *mut VdbHipIndex, out: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filters(idx: *mut VdbHipIndex, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, mode: i32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;
     pub fn vdb_hip_index_search_graph_filters_half(idx: *mut VdbHipIndex, mode: i32, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, ef: u32, route: i32, max_list: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32, out_route: *mut u32) -> i32;

@@ -94,6 +94,7 @@ SIGNATURES = {
     "vdb_hip_index_search_batch_filtered_mode": (_i32, [_vp, _vp, _i32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filtered": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_index_search_batch_filters": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _i32, _vp, _vp, _vp]),
+    "vdb_hip_index_search_batch_filters_mode": (_i32, [_vp, _vp, _u32, _vp, _i32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "vdb_hip_index_last_filters_exact_plan": (_i32, [_vp, _pu32]),
     "vdb_hip_index_search_graph_filters": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_index_search_graph_filters_half": (_i32, [_vp, _i32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),

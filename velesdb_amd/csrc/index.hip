@@ -930,10 +930,9 @@ static_assert(kFmModeBf16 == VDB_SEARCH_BRUTE_BF16 && kFmModeSq8 == VDB_SEARCH_B
 // that are alive now.  What the plain call in that mode refuses is refused first, in its words.  Two routes: the listed kernels (SQ8;
 // Euclidean over a half image) read only the filter's rows; mask substitution runs the mode's own dispatch, every tier of it, under the
 // call's row mask.  Same bits either way where the mode declares its summation order.
-static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const QuerySlice& s, hipStream_t st) {
-  const RowFilter* f = ix->flt;
-  const uint32_t nq = s.nq, k = s.k;
-  const bool half = mode == VDB_SEARCH_BRUTE_BF16 || mode == VDB_SEARCH_BRUTE_F16, f16 = mode == VDB_SEARCH_BRUTE_F16;
+// (the refusals, shared with the call that takes one filter per query, DESIGN 4.1q: there they come before anything runs)
+static int32_t filtered_mode_check(const vdb_hip_index* ix, int32_t mode) {
+  const bool f16 = mode == VDB_SEARCH_BRUTE_F16;
   const bool metric3 = ix->metric == VDB_COSINE || ix->metric == VDB_EUCLIDEAN || ix->metric == VDB_DOT;
   if (mode == VDB_SEARCH_BRUTE_SQ8) {
     if (ix->storage_mode != VDB_STORAGE_SQ8) return fail(VDB_ERR_STATE, "SQ8 search: set the storage mode to SQ8 first");
@@ -945,6 +944,14 @@ static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const Qu
     if (!f16 && !ix->bf16_enabled) return fail(VDB_ERR_STATE, "bf16 sweep: call vdb_hip_index_enable_bf16 first");
     if (!metric3) return fail(VDB_ERR_UNSUPPORTED, "half-precision sweep: Cosine, DotProduct and Euclidean only");
   }
+  return VDB_OK;
+}
+static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const QuerySlice& s, hipStream_t st) {
+  const RowFilter* f = ix->flt;
+  const uint32_t nq = s.nq, k = s.k;
+  const bool half = mode == VDB_SEARCH_BRUTE_BF16 || mode == VDB_SEARCH_BRUTE_F16, f16 = mode == VDB_SEARCH_BRUTE_F16;
+  const int32_t rcm = filtered_mode_check(ix, mode);
+  if (rcm != VDB_OK) return rcm;
   if (nq == 0) return VDB_OK;
   if (f->count == 0 || k == 0) return zero_results(s, st);  // the empty filter: no row can answer
   bool listed_ok = false;
@@ -1281,9 +1288,24 @@ int32_t search_filtered_mode_to_device(vdb_hip_index* ix, const RowFilter* f, in
 // lands in the result block (h_out, `*rows_total` rows; row_of empty = row i).  One upload, one copy back, one synchronisation.
 int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                        const float* queries, uint32_t nq, uint32_t k, std::vector<uint32_t>* row_of, uint32_t* rows_total) {
+  return search_filters_mode_to_device(ix, filters, n_filters, fq, VDB_SEARCH_BRUTE, queries, nq, k, row_of, rows_total);
+}
+// The same over the SQ8 codes, the sign bits or a half image (vdb_hip_index_search_batch_filters_mode): `mode` is
+// VDB_SEARCH_BRUTE (the call above) or one of VDB_SEARCH_BRUTE_SQ8 / _BINARY / _BF16 / _F16 — then the groups take the routes of
+// filter_mode_route, the listed ones share the grouped launches of sweep_topk_sq8_listed_groups / sweep_topk_half_l2_listed_groups
+// (mode_groups_plan), the others run through brute_masked_dev / brute_mode_dev with the mode.  What the one-filter call in that mode
+// refuses is refused first, in its words.
+int32_t search_filters_mode_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq, int32_t mode,
+                                      const float* queries, uint32_t nq, uint32_t k, std::vector<uint32_t>* row_of, uint32_t* rows_total) {
+  const bool f32 = mode == VDB_SEARCH_BRUTE;
+  const bool half = mode == VDB_SEARCH_BRUTE_BF16 || mode == VDB_SEARCH_BRUTE_F16;
   for (uint32_t j = 0; j < n_filters; j++) {
     const int32_t rcf = filter_check(ix, filters[j]);
     if (rcf != VDB_OK) return rcf;
+  }
+  if (!f32) {
+    const int32_t rcm = filtered_mode_check(ix, mode);
+    if (rcm != VDB_OK) return rcm;
   }
   row_of->clear();  // (empty = row i holds query i: the one-job calls below)
   *rows_total = nq;
@@ -1292,16 +1314,16 @@ int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const
   bool one = true;
   for (uint32_t i = 1; i < nq; i++) one &= fq[i] == fq[0];
   if (one && fq[0] < n_filters) {  // every query on the same filter: the one-filter call itself
-    const int32_t rc = search_filtered_to_device(ix, filters[fq[0]], queries, nq, k);
+    const int32_t rc = search_filtered_mode_to_device(ix, filters[fq[0]], mode, queries, nq, k);
     diag[0] = 1;
     diag[1] = (ix->last_kernels & VDB_KERNEL_SWEEP_LISTED) ? 1u : 0u;
     diag[2] = 1u - diag[1];
     return rc;
   }
-  const uint32_t seen = ix->sel_seq_seen, h16 = ix->sel16_hold, hw = ix->wide_hold, hl2 = ix->l2_hold;
+  const uint32_t seen = ix->sel_seq_seen, h16 = ix->sel16_hold, hw = ix->wide_hold, hl2 = ix->l2_hold, hsq = ix->sq8_hold;
   struct Quiet {  // the call posts no verdicts and leaves the adaptive selection state as it found it, whatever path ends it
     vdb_hip_index* ix;
-    uint32_t seen, h16, hw, hl2;
+    uint32_t seen, h16, hw, hl2, hsq;
     ~Quiet() {
       ix->quiet_verdicts = false;
       ix->flt = nullptr;
@@ -1309,15 +1331,16 @@ int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const
       ix->sel16_hold = h16;
       ix->wide_hold = hw;
       ix->l2_hold = hl2;
+      ix->sq8_hold = hsq;
     }
-  } quiet{ix, seen, h16, hw, hl2};
+  } quiet{ix, seen, h16, hw, hl2, hsq};
   ix->quiet_verdicts = true;
   if (k == 0 || ix->n_rows == 0) {  // nothing can answer: the plain call's empty result
     diag[3] = nq;
-    return search_to_device(ix, queries, nq, k, 0, VDB_SEARCH_BRUTE, 0, nullptr);
+    return search_to_device(ix, queries, nq, k, 0, mode, 0, nullptr);
   }
-  const bool mode_m = sweep_mode_m(ix, k);
-  const bool listed_metric = !is_bits_metric(ix->metric);
+  const bool mode_m = f32 && sweep_mode_m(ix, k);
+  const bool listed_metric = f32 && !is_bits_metric(ix->metric);
   auto plan_of = [&](uint32_t nq_left) {
     ListedPlan lp;
     if (listed_metric) sweep_listed_plan(mode_m, ix->dim, k, 1, nq_left, ix->n_cus, &lp);
@@ -1330,7 +1353,9 @@ int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const
   auto count_of = [&](uint32_t f) { return (uint64_t)filters[f]->count; };
   auto list_of = [&](uint32_t f) { return (const uint32_t*)filters[f]->list.as<uint32_t>(); };
   auto occ_of = [&](int B, uint32_t nq_max) { return (uint32_t)listed_occupancy(mode_m, B, mode_m ? plan_of(nq_max).lds : 0); };
-  const std::vector<FxGroup> groups = filters_exact_groups(fq, nq, n_filters, opt_value(ix, VDB_OPT_FILTER_ROUTE), ix->n_rows, count_of, pass_of);
+  const int64_t opt_route = opt_value(ix, VDB_OPT_FILTER_ROUTE);
+  const std::vector<FxGroup> groups = f32 ? filters_exact_groups(fq, nq, n_filters, opt_route, ix->n_rows, count_of, pass_of)
+                                          : filters_mode_groups(fq, nq, n_filters, opt_route, mode, ix->metric, ix->n_rows, ix->dim, k, ix->n_cus, count_of);
   // rows of the call
   uint32_t n_listed = 0, extra = 0;
   for (const FxGroup& g : groups) {
@@ -1352,8 +1377,9 @@ int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const
   if (n_listed) {
     // the partial lists are [nq][lists_per_query][k] keys: the chunks of a pass are held to what 256 MB of them allow
     const uint64_t per_list = (uint64_t)nq * k * 8;
-    listed_groups_plan(groups, mode_m, ix->n_cus, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, ((uint64_t)256 << 20) / per_list)), list_of,
-                       count_of, pass_of, occ_of, &plan);
+    const uint32_t max_lists = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, ((uint64_t)256 << 20) / per_list));
+    if (f32) listed_groups_plan(groups, mode_m, ix->n_cus, max_lists, list_of, count_of, pass_of, occ_of, &plan);
+    else mode_groups_plan(groups, half, ix->dim, k, ix->n_cus, max_lists, list_of, count_of, &plan);
   }
   const size_t q_bytes = (size_t)rows * ix->row_stride * 4, items_bytes = plan.items.size() * sizeof(ListedGroupItem), gate_bytes = n_listed ? (size_t)nq * 4 : 0;
   hipStream_t st = ix->stream;
@@ -1416,14 +1442,24 @@ int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const
       a.q_stride = ix->row_stride;
       a.dim = ix->dim;
       a.k = k;
-      ix->last_kernels |= VDB_KERNEL_SWEEP_LISTED_GROUPS;
+      const uint16_t* rows16 = mode == VDB_SEARCH_BRUTE_F16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>();
+      const QuerySlice staged{dq, ix->row_stride, nq, k, d_ids, d_scores, d_n};  // (the grouped kernels address a query by its position)
+      if (!f32) ix->last_kernels |= half ? VDB_KERNEL_SWEEP_HALF_L2 : VDB_KERNEL_SQ8;  // (the mode's usual bit, as the one-filter call)
       for (uint32_t li = 0; li < plan.n_launches; li++) {
         const ListedGroupsLaunch& l = plan.launches[li];
-        EventPair* ev = next_events(ix);
-        if (ev) (void)hipEventRecord(ev->a, st);
-        const hipError_t le = launch_sweep_listed_groups(ix->metric, mode_m, l.B, a, d_items + l.begin, l.count, l.nq_max, L, st);
-        if (le != hipSuccess) return fail(VDB_ERR_HIP, std::string("grouped listed sweep launch: ") + hipGetErrorString(le));
-        if (ev) (void)hipEventRecord(ev->b, st);
+        int32_t rl;
+        if (f32) {
+          rl = timed_launch(ix, VDB_KERNEL_SWEEP_LISTED_GROUPS, st, "grouped listed sweep launch",
+                            [&] { return launch_sweep_listed_groups(ix->metric, mode_m, l.B, a, d_items + l.begin, l.count, l.nq_max, L, st); });
+        } else if (half) {
+          rl = timed_launch(ix, VDB_KERNEL_SWEEP_LISTED_GROUPS, st, "grouped listed half-precision Euclidean sweep launch", [&] {
+            return launch_sweep_half_l2_listed_groups(mode == VDB_SEARCH_BRUTE_F16, l.B, rows16, ix->bf16_stride, a.alive, dq, ix->row_stride, a.part_keys,
+                                                      ix->dim, k, d_items + l.begin, l.count, L, st);
+          });
+        } else {
+          rl = sq8_listed_groups_launch(ix, l.B, staged, a.part_keys, d_items + l.begin, l.count, L, st);
+        }
+        if (rl != VDB_OK) return rl;
         diag[4]++;
       }
       MergeArgs m{};
@@ -1447,7 +1483,7 @@ int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const
       const QuerySlice s_g = block.sub(r0, nq_g);
       int32_t rg;
       if (g.filter == n_filters) {
-        rg = brute_dev(ix, s_g, st);
+        rg = f32 ? brute_dev(ix, s_g, st) : brute_mode_dev(ix, mode, s_g, st);
       } else if (filters[g.filter]->count == 0) {  // the empty filter: no row can answer — out_n = 0 behind the merge's padding
         rg = VDB_OK;
         VDB_HIP(hipMemsetAsync(d_n + r0, 0, (size_t)nq_g * 4, st));
@@ -1455,7 +1491,7 @@ int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const
         VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_scores + (size_t)r0 * k), 0x7FC00000, (size_t)nq_g * k, st));
       } else {
         ix->flt = filters[g.filter];
-        rg = brute_masked_dev(ix, s_g, st);
+        rg = brute_masked_dev(ix, s_g, st, mode);
         ix->flt = nullptr;
       }
       if (rg != VDB_OK) return rg;

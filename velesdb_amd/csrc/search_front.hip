@@ -105,15 +105,17 @@ static int32_t search_filtered_mode_direct(vdb_hip_index* handle, const RowFilte
       [&](vdb_hip_index* ix) { deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n); });
 }
 
-// vdb_hip_index_search_batch_filters: the same with one optional filter per query; query i's answer sits in row
-// row_of[i] of the context's result block
+// vdb_hip_index_search_batch_filters (mode = VDB_SEARCH_BRUTE) and vdb_hip_index_search_batch_filters_mode (one of the
+// SQ8 / Binary / half modes): the same with one optional filter per query; query i's answer sits in row row_of[i] of the
+// context's result block
 static int32_t search_filters_exact_direct(vdb_hip_index* handle, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
-                                           const float* queries, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+                                           int32_t mode, const float* queries, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores,
+                                           uint32_t* out_n) {
   std::vector<uint32_t> row_of;  // (stays empty when the call is one job whose rows are the call's: one copy out, as the calls above)
   uint32_t rows = 0;
   return run_search(
-      handle, nq, k, 0, VDB_SEARCH_BRUTE, 0,
-      [&](vdb_hip_index* ix) { return search_filters_exact_to_device(ix, filters, n_filters, fq, queries, nq, k, &row_of, &rows); },
+      handle, nq, k, 0, mode, 0,
+      [&](vdb_hip_index* ix) { return search_filters_mode_to_device(ix, filters, n_filters, fq, mode, queries, nq, k, &row_of, &rows); },
       [&](vdb_hip_index* ix) {
         if (row_of.empty()) return deliver_slice(ix, 0, nq, nq, k, out_ids, out_scores, out_n);
         for (uint32_t i = 0; i < nq; i++)
@@ -468,12 +470,37 @@ int32_t vdb_hip_index_search_batch_filters(vdb_hip_index* ix, void** filters, ui
       return fail(VDB_ERR_INVALID_ARG, "filtered search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
                                            " of a table of " + std::to_string(n_filters));
   if (nq == 0) return VDB_OK;
-  return search_filters_exact_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq, k, out_ids,
-                                     out_scores, out_n);
+  return search_filters_exact_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, VDB_SEARCH_BRUTE, queries,
+                                     nq, k, out_ids, out_scores, out_n);
   });
 }
 
-// diagnostic: the plan of this thread's last vdb_hip_index_search_batch_filters call — {filter groups, groups on the listed route,
+// search_batch_with_filters on a collection whose rows live as SQ8 codes, sign bits or a half image: one optional filter per query in one
+// of those modes (include/velesdb_hip.h).  The table's errors are the call's above, the mode's those of
+// vdb_hip_index_search_batch_filtered_mode.
+int32_t vdb_hip_index_search_batch_filters_mode(vdb_hip_index* ix, void** filters, uint32_t n_filters, const uint32_t* filter_of_query, int32_t mode,
+                                                const float* queries, uint32_t nq, uint32_t k, uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || (n_filters && !filters) || (nq && (!queries || !out_n || !filter_of_query)) || (nq && k && (!out_ids || !out_scores)))
+    return fail(VDB_ERR_INVALID_ARG, "null argument");
+  VDB_NO_GROUP(ix, "filtered search");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, "filtered search: not available on a member of a process group");
+  if (mode != VDB_SEARCH_BRUTE_SQ8 && mode != VDB_SEARCH_BRUTE_BINARY && mode != VDB_SEARCH_BRUTE_BF16 && mode != VDB_SEARCH_BRUTE_F16)
+    return fail(VDB_ERR_UNSUPPORTED, "filtered search by mode: VDB_SEARCH_BRUTE_SQ8 / _BINARY / _BF16 / _F16 only (VDB_SEARCH_BRUTE has "
+                                     "vdb_hip_index_search_batch_filters, the graph modes vdb_hip_index_search_graph_filters)");
+  for (uint32_t j = 0; j < n_filters; j++)
+    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, "filtered search: filter " + std::to_string(j) + " of the table is null");
+  for (uint32_t i = 0; i < nq; i++)
+    if (filter_of_query[i] > n_filters)
+      return fail(VDB_ERR_INVALID_ARG, "filtered search: query " + std::to_string(i) + " names filter " + std::to_string(filter_of_query[i]) +
+                                           " of a table of " + std::to_string(n_filters));
+  if (nq == 0) return VDB_OK;
+  return search_filters_exact_direct(ix, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, mode, queries, nq, k,
+                                     out_ids, out_scores, out_n);
+  });
+}
+
+// diagnostic: the plan of this thread's last vdb_hip_index_search_batch_filters / _filters_mode call — {filter groups, groups on the listed route,
 // groups on mask substitution, unfiltered queries, grouped sweep launches, merge launches behind them}
 int32_t vdb_hip_index_last_filters_exact_plan(vdb_hip_index* ix, uint32_t* out) {
   return vdb::guarded([&]() -> int32_t {

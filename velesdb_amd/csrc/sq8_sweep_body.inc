@@ -1,6 +1,9 @@
-// sq8_sweep_body.inc — the body of sweep_topk_sq8<METRIC, B> and sweep_topk_sq8_listed<METRIC, B> (storage_modes.hip, which explains
-// why it is shared as text).  In scope where it is included: METRIC, B, `constexpr bool LISTED`, `a` (Sq8Args), and — read only when
-// LISTED — `list`, `count`, `per_block`.
+// sq8_sweep_body.inc — the body of sweep_topk_sq8<METRIC, B>, sweep_topk_sq8_listed<METRIC, B> and sweep_topk_sq8_listed_groups<METRIC, B>
+// (storage_modes.hip, which explains why it is shared as text).  In scope where it is included: METRIC, B, `constexpr bool LISTED`,
+// `constexpr bool GROUPED`, `a` (Sq8Args), and — read only when LISTED — `list`, `count`, `per_block`, and — read only when GROUPED
+// (which implies LISTED: `list` / `count` are the item's chunk, swept whole from unit 0; DESIGN 4.1q) — `it` (the block's
+// ListedGroupItem), `nq_item` and `lists_per_q`.  (The item's `units` is not read: a unit is a 64-row group here, so it is
+// ceil(count / 64), computed below anyway.)
   constexpr bool HIB = METRIC != kEuclidean;  // cosine / dot similarity: larger is better; squared L2: smaller
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -18,7 +21,7 @@
   float* qsum = reinterpret_cast<float*>(tail + (size_t)B * k * 8 + B * 8);
   float* qnsq = reinterpret_cast<float*>(tail + (size_t)B * k * 8 + B * 12);
 
-  uint32_t nq_here = a.nq, slot0 = 0;
+  uint32_t nq_here = GROUPED ? nq_item : a.nq, slot0 = 0;
   if (!LISTED && a.qmap) {
     const uint32_t listed = *a.qcount;
     slot0 = blockIdx.y * (uint32_t)B;
@@ -27,7 +30,8 @@
   }
   for (uint32_t i = tid; i < dpad * B; i += 256) {
     const uint32_t d = i / B, b = i % B;
-    const uint32_t qrow = (!LISTED && a.qmap && b < nq_here) ? a.qmap[slot0 + b] : b;
+    uint32_t qrow = (!LISTED && a.qmap && b < nq_here) ? a.qmap[slot0 + b] : b;
+    if constexpr (GROUPED) qrow = b < nq_here ? it->q[b] : 0u;  // (the pass's queries: positions in the call)
     qs[i] = (d < dim && b < nq_here) ? a.queries[(size_t)qrow * a.q_stride + d] : 0.0f;
   }
   if (tid < B) {
@@ -49,8 +53,9 @@
 
   const uint32_t n_here = LISTED ? count : a.n_rows;  // rows of the sweep: positions of the list, or rows of the index
   const uint32_t ngroups = (n_here + 63) / 64;
-  const uint32_t g_end = LISTED ? min(ngroups, (blockIdx.x + 1) * per_block) : ngroups;  // listed: the block's chunk of the list
-  for (uint32_t g = LISTED ? blockIdx.x * per_block + (uint32_t)wib : blockIdx.x * 4 + wib; g < g_end; g += LISTED ? 4u : gridDim.x * 4) {
+  const uint32_t g_end = GROUPED ? ngroups : (LISTED ? min(ngroups, (blockIdx.x + 1) * per_block) : ngroups);  // listed: the block's chunk of the list
+  for (uint32_t g = GROUPED ? (uint32_t)wib : (LISTED ? blockIdx.x * per_block + (uint32_t)wib : blockIdx.x * 4 + wib); g < g_end;
+       g += LISTED ? 4u : gridDim.x * 4) {
     const uint32_t pos = g * 64 + lane;
     const bool valid = pos < n_here;
     const uint32_t posc = valid ? pos : n_here - 1;
@@ -295,5 +300,7 @@
   for (uint32_t b = wib; b < nq_here && b < (uint32_t)B; b += 4) {
     const uint32_t c = cnts[b];
     uint64_t* out = a.part_keys + ((size_t)(slot0 + b) * gridDim.x + blockIdx.x) * k;
+    // (grouped: list it->slot of the lists_per_q the query at position it->q[b] owns; both read here, not kept across the sweep)
+    if constexpr (GROUPED) out = a.part_keys + ((size_t)it->q[b] * lists_per_q + (uint32_t)__builtin_amdgcn_readfirstlane((int)it->slot)) * k;
     for (uint32_t e = lane; e < k; e += 64) out[e] = e < c ? lists[(size_t)b * k + e] : kKeyInvalid;
   }

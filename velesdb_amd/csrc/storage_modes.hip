@@ -242,8 +242,11 @@ __device__ __forceinline__ void sq8_word_pair(float (&acc)[B], const uint32_t (&
 template <int METRIC, int B>
 __global__ __launch_bounds__(256) void sweep_topk_sq8(Sq8Args a) {
   constexpr bool LISTED = false;
+  constexpr bool GROUPED = false;
   const uint32_t* const list = nullptr;
   const uint32_t count = 0u, per_block = 0u;
+  const ListedGroupItem* const it = nullptr;
+  const uint32_t nq_item = 0u, lists_per_q = 0u;
 #include "sq8_sweep_body.inc"
 }
 // the sweep over a filter's ascending row list; a.n_rows / qmap / qcount are not read
@@ -256,9 +259,33 @@ struct Sq8ListedArgs {
 template <int METRIC, int B>
 __global__ __launch_bounds__(256) void sweep_topk_sq8_listed(Sq8ListedArgs la) {
   constexpr bool LISTED = true;
+  constexpr bool GROUPED = false;
   const Sq8Args& a = la.a;
   const uint32_t* const list = la.list;
   const uint32_t count = la.count, per_block = la.per_block;
+  const ListedGroupItem* const it = nullptr;
+  const uint32_t nq_item = 0u, lists_per_q = 0u;
+#include "sq8_sweep_body.inc"
+}
+// One filter per query over the codes (vdb_hip_index_search_batch_filters_mode): block b does work item b — one chunk of
+// one pass of one filter's list (mode_groups_plan, vdb_filter_route.hpp), as sweep_topk_listed_groups does over the f32 rows.  The item
+// is read with uniform loads: the chunk is a list of its own (pointer rebuilt as a GLOBAL one, so the list is read with global_load,
+// not flat_load) swept whole from unit 0, query b of the pass is row it->q[b] of a.queries and of the partial-list area
+// [call's queries][lists_per_q][k], and the block's lists go to slot it->slot.  a.nq / n_rows / qmap / qcount are not read.
+// (Dot, B = 8: the twin sits at 128 VGPRs, four waves per SIMD — what mode_groups_plan sizes the launch by; with the item's scalars
+// next to the sweep's the instance came out one register above it.  The compiler is told the occupancy there; 1 = no request.)
+constexpr int sq8_groups_min_waves(int metric, int b) { return metric == kDot && b == 8 ? 4 : 1; }
+template <int METRIC, int B>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sq8_groups_min_waves(METRIC, B)))) void sweep_topk_sq8_listed_groups(Sq8Args a, const ListedGroupItem* __restrict__ items, uint32_t lists_per_q) {
+  constexpr bool LISTED = true;
+  constexpr bool GROUPED = true;
+  const ListedGroupItem* const it = items + blockIdx.x;
+  typedef const __attribute__((address_space(1))) uint32_t* glb_u32_p;
+  const uint64_t lp = reinterpret_cast<uint64_t>(it->list);
+  const uint32_t* const list = (const uint32_t*)(glb_u32_p)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lp >> 32)) << 32) |
+                                                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lp));
+  const uint32_t count = (uint32_t)__builtin_amdgcn_readfirstlane((int)it->count), per_block = 0u;
+  const uint32_t nq_item = (uint32_t)__builtin_amdgcn_readfirstlane((int)it->nq);
 #include "sq8_sweep_body.inc"
 }
 
@@ -301,6 +328,27 @@ static hipError_t launch_sq8_listed_m(int metric, const Sq8ListedArgs& la, int b
   if (metric == kCosine) return launch_sq8_listed_t<kCosine, B>(la, blocks, lds, st);
   if (metric == kEuclidean) return launch_sq8_listed_t<kEuclidean, B>(la, blocks, lds, st);
   return launch_sq8_listed_t<kDot, B>(la, blocks, lds, st);
+}
+
+template <int METRIC, int B>
+static hipError_t launch_sq8_listed_groups_t(const Sq8Args& a, const ListedGroupItem* items, uint32_t n_items, uint32_t lists_per_q, size_t lds,
+                                             hipStream_t st) {
+  static bool done = false;
+  if (lds > 64 * 1024 && !done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_sq8_listed_groups<METRIC, B>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    done = true;
+  }
+  hipLaunchKernelGGL((sweep_topk_sq8_listed_groups<METRIC, B>), dim3(n_items), dim3(256), lds, st, a, items, lists_per_q);
+  return hipGetLastError();
+}
+template <int B>
+static hipError_t launch_sq8_listed_groups_m(int metric, const Sq8Args& a, const ListedGroupItem* items, uint32_t n_items, uint32_t lists_per_q,
+                                             size_t lds, hipStream_t st) {
+  if (metric == kCosine) return launch_sq8_listed_groups_t<kCosine, B>(a, items, n_items, lists_per_q, lds, st);
+  if (metric == kEuclidean) return launch_sq8_listed_groups_t<kEuclidean, B>(a, items, n_items, lists_per_q, lds, st);
+  return launch_sq8_listed_groups_t<kDot, B>(a, items, n_items, lists_per_q, lds, st);
 }
 
 // ---- selection stage over the SQ8 storage mode (select_stage.hip brute_split_dev, level 3) -------------------------------------
@@ -592,6 +640,24 @@ int32_t brute_sq8_listed_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t c
   }
   VDB_HIP(hipGetLastError());
   return VDB_OK;
+}
+
+// One grouped launch of a call with one filter per query (vdb_hip_index_search_batch_filters_mode): block b does items[b]
+// (device memory; mode_groups_plan).  s: the staged queries of the call — a query is addressed by its position in it; part_keys:
+// [call's queries][lists_per_q][k], pre-filled with invalid keys.  The caller has checked the storage mode, the metric and k > 0.
+int32_t sq8_listed_groups_launch(vdb_hip_index* ix, int B, const QuerySlice& s, uint64_t* part_keys, const ListedGroupItem* items, uint32_t n_items,
+                                 uint32_t lists_per_q, hipStream_t st) {
+  if ((B != 8 && B != 4 && B != 1) || n_items == 0 || lists_per_q == 0) return fail(VDB_ERR_INVALID_ARG, "grouped listed SQ8 sweep: bad launch");
+  const size_t lds = sq8_lds_bytes(B, s.k, ix->dim);
+  if (lds > 160 * 1024) return fail(VDB_ERR_UNSUPPORTED, "SQ8 search: dim / k too large for the LDS query tile");
+  Sq8Args a = sq8_args(ix, s);
+  a.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;  // rows removed since the filters were made
+  a.part_keys = part_keys;
+  return timed_launch(ix, VDB_KERNEL_SWEEP_LISTED_GROUPS, st, "grouped listed SQ8 sweep launch", [&] {
+    return B == 8 ? launch_sq8_listed_groups_m<8>(ix->metric, a, items, n_items, lists_per_q, lds, st)
+                  : (B == 4 ? launch_sq8_listed_groups_m<4>(ix->metric, a, items, n_items, lists_per_q, lds, st)
+                            : launch_sq8_listed_groups_m<1>(ix->metric, a, items, n_items, lists_per_q, lds, st));
+  });
 }
 
 // the four-bit image of the sign-bit codes (bits_gemm.hip: batches of >= 32 queries run on the matrix cores), in the storage mode's

@@ -63,8 +63,13 @@ __device__ __forceinline__ void unpack2(uint32_t w, float& lo, float& hi) {
 // the filter's ascending row list stands where row p stood — the row pointer comes through the list, positions past `count` re-read the
 // list's last row and are masked, the key carries the real row — and block b takes the groups [b * per_block, (b + 1) * per_block) of
 // the list.  The declared summation order above is per (row, query): the same bits wherever the row sits.
-template <bool F16, int B, bool LISTED>
-__device__ __forceinline__ void half_l2_sweep_body(const HalfL2Args& a, const uint32_t* __restrict__ list, uint32_t count, uint32_t per_block) {
+// GROUPED (one filter per query; implies LISTED): the block does ONE work item — `list` / `count` are the item's chunk of
+// its filter's list, handed over as a list of its own and swept whole from unit 0 (`per_block` = its units), a.nq the item's pass;
+// query b of the pass is row it->q[b] of a.queries and of the partial-list area [call's queries][lists_per_q][k], and the block's
+// lists go to slot it->slot.  What is only needed at the end (slot, the positions) is read there.
+template <bool F16, int B, bool LISTED, bool GROUPED = false>
+__device__ __forceinline__ void half_l2_sweep_body(const HalfL2Args& a, const uint32_t* __restrict__ list, uint32_t count, uint32_t per_block,
+                                                   const ListedGroupItem* __restrict__ it = nullptr, uint32_t lists_per_q = 0u) {
   constexpr int RPG = 64 / B;                // rows per group: 64 (row, query) pairs per lane
   constexpr int RB = RPG < 4 ? RPG : (B == 1 ? 8 : 4);  // rows in flight together
   constexpr bool HIB = false;                // a distance: smaller is better
@@ -87,14 +92,14 @@ __device__ __forceinline__ void half_l2_sweep_body(const HalfL2Args& a, const ui
   }
   for (uint32_t i = threadIdx.x; i < (uint32_t)B * qlen; i += 256) {
     const uint32_t b = i / qlen, e = i % qlen;
-    qs[i] = (b < a.nq && e < a.dim) ? half_round<F16>(a.queries[(size_t)b * a.q_stride + e]) : 0.0f;
+    qs[i] = (b < a.nq && e < a.dim) ? half_round<F16>(a.queries[(GROUPED ? (size_t)it->q[b] : (size_t)b) * a.q_stride + e]) : 0.0f;
   }
   __syncthreads();
 
   const uint32_t n_here = LISTED ? count : a.n_rows;  // rows of the sweep: positions of the list, or rows of the index
   const uint32_t ngroups = (n_here + RPG - 1) / RPG;
-  const uint32_t g_end = LISTED ? min(ngroups, (blockIdx.x + 1) * per_block) : ngroups;  // listed: the block's chunk of the list
-  for (uint32_t g = LISTED ? blockIdx.x * per_block + (uint32_t)wib : wave; g < g_end; g += LISTED ? 4u : nwaves) {
+  const uint32_t g_end = GROUPED ? per_block : (LISTED ? min(ngroups, (blockIdx.x + 1) * per_block) : ngroups);  // listed: the block's chunk of the list
+  for (uint32_t g = GROUPED ? (uint32_t)wib : (LISTED ? blockIdx.x * per_block + (uint32_t)wib : wave); g < g_end; g += LISTED ? 4u : nwaves) {
     float acc[64];
 #pragma unroll
     for (int i = 0; i < 64; i++) acc[i] = 0.0f;
@@ -156,7 +161,8 @@ __device__ __forceinline__ void half_l2_sweep_body(const HalfL2Args& a, const ui
   __syncthreads();
   for (int b = wib; b < (int)a.nq && b < B; b += 4) {
     const uint32_t c = cnts[b];
-    uint64_t* out = a.part_keys + ((size_t)b * gridDim.x + blockIdx.x) * k;
+    uint64_t* out = a.part_keys + (GROUPED ? (size_t)it->q[b] * lists_per_q + (uint32_t)__builtin_amdgcn_readfirstlane((int)it->slot)
+                                           : (size_t)b * gridDim.x + blockIdx.x) * k;
     for (uint32_t e = lane; e < k; e += 64) out[e] = e < c ? lists[(size_t)b * k + e] : kKeyInvalid;
   }
 }
@@ -174,6 +180,22 @@ struct HalfL2ListedArgs {
 template <bool F16, int B>
 __global__ __launch_bounds__(256, 3) void sweep_topk_half_l2_listed(HalfL2ListedArgs la) {
   half_l2_sweep_body<F16, B, true>(la.a, la.list, la.count, la.per_block);
+}
+
+// One filter per query over a half image (vdb_hip_index_search_batch_filters_mode): block b does work item b — one chunk
+// of one pass of one filter's list (mode_groups_plan, vdb_filter_route.hpp), as sweep_topk_listed_groups does over the f32 rows.  The
+// item is read with uniform loads; the list pointer is rebuilt as a GLOBAL one, so the list is read with global_load, not flat_load.
+template <bool F16, int B>
+__global__ __launch_bounds__(256, 3) void sweep_topk_half_l2_listed_groups(HalfL2Args a, const ListedGroupItem* __restrict__ items,
+                                                                           uint32_t lists_per_q) {
+  const ListedGroupItem* __restrict__ it = items + blockIdx.x;
+  typedef const __attribute__((address_space(1))) uint32_t* glb_u32_p;
+  const uint64_t lp = reinterpret_cast<uint64_t>(it->list);
+  const uint32_t* list = (const uint32_t*)(glb_u32_p)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(lp >> 32)) << 32) |
+                                                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)lp));
+  a.nq = (uint32_t)__builtin_amdgcn_readfirstlane((int)it->nq);
+  half_l2_sweep_body<F16, B, true, true>(a, list, (uint32_t)__builtin_amdgcn_readfirstlane((int)it->count),
+                                         (uint32_t)__builtin_amdgcn_readfirstlane((int)it->units), it, lists_per_q);
 }
 
 size_t sweep_half_l2_lds_bytes(int B, uint32_t k, uint32_t dim) { return (size_t)fm_half_l2_lds_bytes(B, k, dim); }
@@ -240,6 +262,41 @@ hipError_t launch_sweep_half_l2_listed(bool f16, int B, const uint16_t* rows, ui
   HalfL2ListedArgs la{{rows, alive, queries, part_keys, row_stride, q_stride, n_rows, dim, nq, k}, list, count, per_block};
   const size_t lds = sweep_half_l2_lds_bytes(B, k, dim);
   return f16 ? launch_half_l2_listed_b<true>(B, la, blocks, lds, st) : launch_half_l2_listed_b<false>(B, la, blocks, lds, st);
+}
+
+template <bool F16, int B>
+static hipError_t launch_half_l2_listed_groups_t(const HalfL2Args& a, const ListedGroupItem* items, uint32_t n_items, uint32_t lists_per_q,
+                                                 size_t lds, hipStream_t st) {
+  static bool done = false;
+  if (lds > 64 * 1024 && !done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_half_l2_listed_groups<F16, B>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    done = true;
+  }
+  hipLaunchKernelGGL((sweep_topk_half_l2_listed_groups<F16, B>), dim3(n_items), dim3(256), lds, st, a, items, lists_per_q);
+  return hipGetLastError();
+}
+template <bool F16>
+static hipError_t launch_half_l2_listed_groups_b(int B, const HalfL2Args& a, const ListedGroupItem* items, uint32_t n_items, uint32_t lists_per_q,
+                                                 size_t lds, hipStream_t st) {
+  switch (B) {
+    case 16: return launch_half_l2_listed_groups_t<F16, 16>(a, items, n_items, lists_per_q, lds, st);
+    case 4: return launch_half_l2_listed_groups_t<F16, 4>(a, items, n_items, lists_per_q, lds, st);
+    case 1: return launch_half_l2_listed_groups_t<F16, 1>(a, items, n_items, lists_per_q, lds, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+// one grouped launch of a call with one filter per query: block b does items[b] (device memory; mode_groups_plan); a
+// query is addressed by its position in `queries`; part_keys: [call's queries][lists_per_q][k], pre-filled with invalid keys
+hipError_t launch_sweep_half_l2_listed_groups(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,
+                                              uint64_t q_stride, uint64_t* part_keys, uint32_t dim, uint32_t k, const ListedGroupItem* items,
+                                              uint32_t n_items, uint32_t lists_per_q, hipStream_t st) {
+  if (row_stride % 8 != 0 || row_stride < dim || !items || n_items == 0 || lists_per_q == 0) return hipErrorInvalidValue;
+  HalfL2Args a{rows, alive, queries, part_keys, row_stride, q_stride, 0u, dim, 0u, k};  // (n_rows is not read; nq comes from the item)
+  const size_t lds = sweep_half_l2_lds_bytes(B, k, dim);
+  return f16 ? launch_half_l2_listed_groups_b<true>(B, a, items, n_items, lists_per_q, lds, st)
+             : launch_half_l2_listed_groups_b<false>(B, a, items, n_items, lists_per_q, lds, st);
 }
 
 }  // namespace vdb

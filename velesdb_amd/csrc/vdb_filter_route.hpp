@@ -3,10 +3,11 @@
 // query share a launch (vdb_hip_index_search_graph_filters) — the one-filter call is planned here too: it is a call
 // of the second kind with every query on the same filter — and how an EXACT call with one filter per query groups its queries and
 // cuts its listed groups into the work items of the grouped launches (vdb_hip_index_search_batch_filters), and the route
-// and the listed passes of a filtered exact call over the SQ8 / Binary / half images (vdb_hip_index_search_batch_filtered_mode).
+// and the listed passes of a filtered exact call over the SQ8 / Binary / half images (vdb_hip_index_search_batch_filtered_mode),
+// and the groups and grouped launches of such a call with one filter per query (vdb_hip_index_search_batch_filters_mode).
 // Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_mode_route_model.cpp,
-// tests/filter_graph_route_model.cpp, tests/filters_plan_model.cpp and tests/listed_groups_plan_model.cpp compile it alone and walk
-// its boundaries.
+// tests/filter_graph_route_model.cpp, tests/filters_plan_model.cpp, tests/listed_groups_plan_model.cpp and
+// tests/mode_groups_plan_model.cpp compile it alone and walk its boundaries.
 #pragma once
 #include <stdint.h>
 
@@ -294,10 +295,12 @@ struct ListedGroupsPlan {
   uint32_t n_launches = 0;
   uint32_t lists_per_query = 0;
 };
-// list_of(f) -> const uint32_t*; count_of(f) -> rows; pass_of(nq_left) -> FxPass; occ_of(B, nq_max) -> resident blocks per CU
-template <class ListOf, class CountOf, class PassOf, class OccOf>
-static inline void listed_groups_plan(const std::vector<FxGroup>& groups, bool mode_m, int n_cus, uint32_t max_lists, ListOf&& list_of,
-                                      CountOf&& count_of, PassOf&& pass_of, OccOf&& occ_of, ListedGroupsPlan* out) {
+// list_of(f) -> const uint32_t*; count_of(f) -> rows; pass_of(f, nq_left) -> FxPass; occ_of(B, nq_max) -> resident blocks per CU;
+// classes[n_classes]: the pass widths that launch, widest first (mode M: the one class 0); rpu_of(B) -> rows of a unit
+template <class ListOf, class CountOf, class PassOf, class OccOf, class RpuOf>
+static inline void listed_groups_plan_core(const std::vector<FxGroup>& groups, bool mode_m, const int* classes, int n_classes, int n_cus,
+                                           uint32_t max_lists, ListOf&& list_of, CountOf&& count_of, PassOf&& pass_of, OccOf&& occ_of,
+                                           RpuOf&& rpu_of, ListedGroupsPlan* out) {
   struct Pass {
     uint32_t group, q0, nq, units;
     int B;
@@ -308,18 +311,17 @@ static inline void listed_groups_plan(const std::vector<FxGroup>& groups, bool m
     if (g.route != kFilterRouteListed) continue;
     const uint64_t count = count_of(g.filter);
     for (uint32_t q0 = 0, nq_g = (uint32_t)g.queries.size(); q0 < nq_g;) {
-      const FxPass p = pass_of(nq_g - q0);
-      if (p.nq_pass == 0) break;  // (cannot happen for a group filters_exact_groups put on this route)
-      const uint32_t rpu = mode_m ? 64u : 64u / (uint32_t)p.B;
+      const FxPass p = pass_of(g.filter, nq_g - q0);
+      if (p.nq_pass == 0) break;  // (cannot happen for a group its grouping put on this route)
+      const uint32_t rpu = rpu_of(mode_m ? 0 : p.B);
       passes.push_back(Pass{gi, q0, p.nq_pass, (uint32_t)((count + rpu - 1) / rpu), mode_m ? 0 : p.B});
       q0 += p.nq_pass;
     }
   }
   *out = ListedGroupsPlan{};
   if (max_lists == 0) max_lists = 1;
-  static const int kClasses[3] = {8, 4, 1};
-  for (int ci = 0; ci < (mode_m ? 1 : 3); ci++) {
-    const int B = mode_m ? 0 : kClasses[ci];
+  for (int ci = 0; ci < n_classes; ci++) {
+    const int B = classes[ci];
     uint64_t units = 0;
     uint32_t n_pass = 0, nq_max = 0, units_max = 0;
     for (const Pass& p : passes) {
@@ -339,7 +341,7 @@ static inline void listed_groups_plan(const std::vector<FxGroup>& groups, bool m
     for (const Pass& p : passes) {
       if (p.B != B) continue;
       const FxGroup& g = groups[p.group];
-      const uint32_t rpu = mode_m ? 64u : 64u / (uint32_t)B;
+      const uint32_t rpu = rpu_of(B);
       uint32_t slot = 0;
       for (uint32_t u = 0; u < p.units; u += per_block, slot++) {
         ListedGroupItem it{};
@@ -357,6 +359,58 @@ static inline void listed_groups_plan(const std::vector<FxGroup>& groups, bool m
     l.count = (uint32_t)out->items.size() - l.begin;
     out->launches[out->n_launches++] = l;
   }
+}
+// the f32 rows: mode C in the classes 8 / 4 / 1 with 64 / B rows a unit, mode M in one class with 64-row tiles;
+// pass_of(nq_left) -> FxPass
+template <class ListOf, class CountOf, class PassOf, class OccOf>
+static inline void listed_groups_plan(const std::vector<FxGroup>& groups, bool mode_m, int n_cus, uint32_t max_lists, ListOf&& list_of,
+                                      CountOf&& count_of, PassOf&& pass_of, OccOf&& occ_of, ListedGroupsPlan* out) {
+  static const int kClassesC[3] = {8, 4, 1}, kClassesM[1] = {0};
+  listed_groups_plan_core(
+      groups, mode_m, mode_m ? kClassesM : kClassesC, mode_m ? 1 : 3, n_cus, max_lists, list_of, count_of,
+      [&](uint32_t, uint32_t nq_left) { return pass_of(nq_left); }, occ_of, [&](int B) { return mode_m ? 64u : 64u / (uint32_t)B; }, out);
+}
+
+// ---- one filter per query over the SQ8 / Binary / half images (vdb_hip_index_search_batch_filters_mode) ----
+// The grouping of 4.1n with the route rule of 4.1o: every group takes the route filter_mode_route gives it with ITS count and ITS
+// number of queries — `listed_available` as the one-filter call computes it: the mode and metric have a listed kernel and the plan
+// of the group's first pass fits the LDS.  (Auto therefore sends an SQ8 group to the listed kernel only with at most
+// kFmSq8ListedMaxQueries queries; Binary and Cosine / DotProduct over a half image have no listed kernel at all.)
+template <class CountOf>
+static inline std::vector<FxGroup> filters_mode_groups(const uint32_t* fq, uint32_t nq, uint32_t n_filters, int64_t opt, int mode, int metric,
+                                                       uint64_t n_rows, uint32_t dim, uint32_t k, int n_cus, CountOf&& count_of) {
+  const bool half = mode == kFmModeBf16 || mode == kFmModeF16;
+  // (filters_exact_groups asks pass_of only whether the group's first pass fits: answered per group below instead)
+  std::vector<FxGroup> g = filters_exact_groups(fq, nq, n_filters, 2, n_rows, count_of, [](uint32_t) { return FxPass{0, 0}; });
+  for (FxGroup& x : g) {
+    if (x.filter == n_filters) continue;
+    const uint32_t nq_g = (uint32_t)x.queries.size();
+    const uint64_t count = count_of(x.filter);
+    const bool listed_ok = filter_mode_has_listed(mode, metric) && mode_listed_plan(half, dim, k, count, nq_g, n_cus).blocks > 0;
+    x.route = filter_mode_route(opt, mode, metric, count, n_rows, nq_g, listed_ok);
+  }
+  return g;
+}
+// The grouped launches of the groups on the listed route: every group is cut into the passes mode_listed_plan runs for it alone
+// (SQ8: 8 / 4 / 1 queries over units of 64 rows; half Euclidean: 16 / 4 / 1 over units of 64 / B rows), every pass into chunks of
+// per_block units, per_block by the rule above with mode_listed_plan's room (n_cus x resident blocks at the class's LDS footprint),
+// so a table of one pass is mode_listed_plan's plan.  The item is 4.1n's record unchanged.
+template <class ListOf, class CountOf>
+static inline void mode_groups_plan(const std::vector<FxGroup>& groups, bool half, uint32_t dim, uint32_t k, int n_cus, uint32_t max_lists,
+                                    ListOf&& list_of, CountOf&& count_of, ListedGroupsPlan* out) {
+  static const int kClassesSq8[3] = {8, 4, 1}, kClassesHalf[3] = {16, 4, 1};
+  listed_groups_plan_core(
+      groups, false, half ? kClassesHalf : kClassesSq8, 3, n_cus, max_lists, list_of, count_of,
+      [&](uint32_t f, uint32_t nq_left) {
+        const ModeListedPlan p = mode_listed_plan(half, dim, k, count_of(f), nq_left, n_cus);
+        return FxPass{p.B, p.blocks > 0 ? p.nq_pass : 0u};
+      },
+      [&](int B, uint32_t) {
+        const uint64_t lds = half ? fm_half_l2_lds_bytes(B, k, dim) : fm_sq8_lds_bytes(B, k, dim);
+        const uint64_t per_cu = kFmLdsBudget / (lds ? lds : 1), cap = half ? 3 : 4;
+        return (uint32_t)(per_cu > cap ? cap : per_cu);
+      },
+      [&](int B) { return half ? 64u / (uint32_t)B : 64u; }, out);
 }
 
 }  // namespace vdb

@@ -342,6 +342,13 @@ int32_t filter_check(vdb_hip_index* ix, const RowFilter* f);
 // *rows_total rows, query i's answer in row (*row_of)[i]
 int32_t search_filters_exact_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq,
                                        const float* queries, uint32_t nq, uint32_t k, std::vector<uint32_t>* row_of, uint32_t* rows_total);
+// ... and over the SQ8 codes, the sign bits or a half image: mode is one of VDB_SEARCH_BRUTE_SQ8 / _BINARY / _BF16 / _F16
+int32_t search_filters_mode_to_device(vdb_hip_index* ix, const RowFilter* const* filters, uint32_t n_filters, const uint32_t* fq, int32_t mode,
+                                      const float* queries, uint32_t nq, uint32_t k, std::vector<uint32_t>* row_of, uint32_t* rows_total);
+// one grouped launch of that call over the codes (storage_modes.hip): block b does items[b]; s = the call's staged queries
+struct ListedGroupItem;
+int32_t sq8_listed_groups_launch(vdb_hip_index* ix, int B, const QuerySlice& s, uint64_t* part_keys, const ListedGroupItem* items, uint32_t n_items,
+                                 uint32_t lists_per_q, hipStream_t st);
 void last_fx_plan_of_this_thread(vdb_hip_index* ix, uint32_t out[6]);
 // filtered graph search (hnsw_filtered.hip): same locking; the result block ends in ix->h_out, routes[nq] (host, nullable) says per
 // query 1 = walk, 2 = exact pass, 0 = nothing was launched

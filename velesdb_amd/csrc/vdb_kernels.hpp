@@ -268,6 +268,12 @@ hipError_t launch_sweep_half_l2(bool f16, int B, const uint16_t* rows, uint64_t 
 hipError_t launch_sweep_half_l2_listed(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const uint32_t* list,
                                        uint32_t count, uint32_t per_block, const float* queries, uint64_t q_stride, uint64_t* part_keys,
                                        uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks, hipStream_t st);
+// ... and one grouped launch of such a call with one filter per query (sweep_topk_half_l2_listed_groups): block b does
+// items[b] (device memory; mode_groups_plan, vdb_filter_route.hpp); part_keys: [call's queries][lists_per_q][k]
+struct ListedGroupItem;
+hipError_t launch_sweep_half_l2_listed_groups(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,
+                                              uint64_t q_stride, uint64_t* part_keys, uint32_t dim, uint32_t k, const ListedGroupItem* items,
+                                              uint32_t n_items, uint32_t lists_per_q, hipStream_t st);
 void launch_merge(bool higher_is_better, const MergeArgs& m, uint32_t nq, hipStream_t st);
 // sweep_listed.hip — filtered exact search: the sweep over a LIST of rows, and the row mask of the other route
 struct ListedArgs {
@@ -295,7 +301,6 @@ int listed_occupancy(bool mode_m, int B, size_t lds);
 // one filter per query (vdb_hip_index_search_batch_filters): block b of the launch does items[b] (device memory; the
 // table is planned by listed_groups_plan, vdb_filter_route.hpp).  `a` carries what every item shares — list, count and nq travel in
 // the items; part_keys is [call's queries][lists_per_q][k]; B: the launch's class (mode C), nq_max: its largest pass (mode M LDS)
-struct ListedGroupItem;
 hipError_t launch_sweep_listed_groups(int metric, bool mode_m, int B, const ListedArgs& a, const ListedGroupItem* items, uint32_t n_items,
                                       uint32_t nq_max, uint32_t lists_per_q, hipStream_t st);
 // mask[r] = bit r of `bitmap` (r < f_rows) && (alive ? alive[r] : 1), r < n_rows

@@ -740,9 +740,39 @@ class HnswIndex:
                                                        MODE_BRUTE, _ptr(ids), _ptr(sc), _ptr(cnt)))
         return ids, sc, cnt
 
+    def search_batch_with_filters_mode(self, queries, k: int, filters, mode: int):
+        """search_batch_brute_force_with_filters over the SQ8 codes, the sign bits or a half image of the rows
+        (vdb_hip_index_search_batch_filters_mode): mode is MODE_BRUTE_SQ8, MODE_BRUTE_BINARY, MODE_BRUTE_F16 or MODE_BRUTE_BF16.
+        filters: a sequence of Optional[Filter], one per query; None = no filter.  SQ8, Binary and Euclidean over a half image: query
+        i gets bit for bit what the one-filter call of that mode returns for it alone (without a filter: the plain call of that
+        mode).  Cosine / DotProduct over a half image: bit for bit what the one-filter call returns for the query's group — the
+        queries that name the same filter, in call order.  numpy outputs."""
+        if int(k) < 0:
+            raise ValueError("filtered search: k must not be negative")
+        qs, nq, table, handles, fq, ids, sc, cnt, _ = self._filters_call_buffers(queries, int(k), filters)
+        check(lib().vdb_hip_index_search_batch_filters_mode(self._h, handles if table else None, len(table), _ptr(fq), int(mode), _ptr(qs),
+                                                            nq, int(k), _ptr(ids), _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
+
+    def search_batch_with_filters_sq8(self, queries, k: int, filters):
+        """search_batch_filtered_sq8 with one optional filter PER QUERY in one call (storage mode SQ8)."""
+        return self.search_batch_with_filters_mode(queries, k, filters, MODE_BRUTE_SQ8)
+
+    def search_batch_with_filters_binary(self, queries, k: int, filters):
+        """search_batch_filtered_binary with one optional filter PER QUERY in one call (storage mode Binary)."""
+        return self.search_batch_with_filters_mode(queries, k, filters, MODE_BRUTE_BINARY)
+
+    def search_batch_brute_force_with_filters_half(self, queries, k: int, filters, precision):
+        """search_batch_filtered_half with one optional filter PER QUERY in one call (enable_half_precision(precision) first).
+        (search_batch_with_filters_half is the GRAPH walk over the half image; this is the exact sweep over it.)"""
+        precision = VectorPrecision(int(precision))
+        if precision == VectorPrecision.F32:
+            raise ValueError("half-precision search: F16 or BF16")
+        return self.search_batch_with_filters_mode(queries, k, filters, MODE_BRUTE_F16 if precision == VectorPrecision.F16 else MODE_BRUTE_BF16)
+
     def last_filters_exact_plan(self):
-        """the plan of this thread's last search_batch_brute_force_with_filters call: (filter groups, groups on the listed route,
-        groups on mask substitution, unfiltered queries, grouped sweep launches, merge launches behind them)"""
+        """the plan of this thread's last search_batch_brute_force_with_filters / search_batch_with_filters_mode call: (filter groups,
+        groups on the listed route, groups on mask substitution, unfiltered queries, grouped sweep launches, merge launches behind them)"""
         out = (C.c_uint32 * 6)()
         check(lib().vdb_hip_index_last_filters_exact_plan(self._h, out))
         return tuple(int(v) for v in out)
