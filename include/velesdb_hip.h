@@ -652,6 +652,55 @@ int32_t vdb_hip_index_hybrid_search(vdb_hip_index* idx, const void* filter, cons
                                     const uint64_t* text_ids, const uint32_t* text_n, uint32_t text_stride,
                                     const float* vector_weights, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
 
+/* ---- the two fused searches over every form of the walk, with one optional filter PER QUERY ----
+ * rows: what the walk's distances are taken over — the f32 rows, the f16 / bf16 image (vdb_hip_index_enable_half_precision first),
+ * the u8 codes with the f32 re-score (vdb_hip_index_train_quantizer first), or a half image with the f32 re-score.
+ * oversampling_ratio is read for VDB_WALK_ROWS_INT8 (0 = the handle's option) and the two _RESCORE forms (0 = 4) only; there a value
+ * above 64 is VDB_ERR_INVALID_ARG.  ef is 0 (SearchQuality::Balanced) throughout, as in the two calls above.
+ * The filter table is vdb_hip_index_search_graph_filters': filters[n_filters] handles, filter_of_query[i] in 0..n_filters, the value
+ * n_filters = no filter; n_filters = 0 with filters = NULL is legal. */
+enum vdb_walk_rows { VDB_WALK_ROWS_F32 = 0, VDB_WALK_ROWS_F16 = 1, VDB_WALK_ROWS_BF16 = 2, VDB_WALK_ROWS_INT8 = 3,
+                     VDB_WALK_ROWS_F16_RESCORE = 4, VDB_WALK_ROWS_BF16_RESCORE = 5 };
+/* vdb_hip_index_hybrid_search for nq user queries, each with its own filter or none.  THE CONTRACT: query i gets, bit for bit, the
+ * rule of vdb_hip_hybrid_fuse applied to its text ids and to
+ *   no filter: the list the plain call of the rows form returns for it alone at k' = 2k — vdb_hip_index_search_batch with mode
+ *     VDB_SEARCH_HNSW / _HNSW_F16 / _HNSW_BF16 / _HNSW_INT8 (with a ratio of the call's own: vdb_hip_index_search_with_config at
+ *     ef_search 0, that ratio, int8 traversal, min_index_size 0), for the _RESCORE forms
+ *     vdb_hip_index_search_graph_filters_half_rescore with n_filters = 0.  Unknown or removed text ids take their rank and their
+ *     place in the cut and are dropped behind it, as in vdb_hip_index_hybrid_search;
+ *   a filter: the list the call with one filter per query of the rows form returns for it alone at k' = max(4k, k + 10), route 0,
+ *     max_list 0 — vdb_hip_index_search_graph_filters / _half / _int8 / _half_rescore — and text hits that are unknown, removed or
+ *     outside ITS filter are compacted away before ranks exist.  A query with an empty filter gets out_n = 0.
+ * A query's answer never depends on its companions or on its position.  With VDB_WALK_ROWS_F32 and no query filtered the call is
+ * vdb_hip_index_hybrid_search(filter = NULL) byte for byte, with every query on the same filter vdb_hip_index_hybrid_search(filter).
+ * Everything below is decided before anything runs, and the outputs stay untouched: rows outside 0..5, a ratio above 64, a NULL
+ * table entry, a filter of another handle, a table value above n_filters, a NaN weight, text_n[i] > text_stride, a null pointer:
+ * VDB_ERR_INVALID_ARG; the image of the rows form not enabled, the quantiser not trained, no graph, a stale filter: VDB_ERR_STATE; a
+ * Hamming / Jaccard handle with rows other than VDB_WALK_ROWS_F32, a multi-device handle, a member of a process group, a query whose
+ * OWN k' plus text_n[i] exceeds 8192 (the message names the query): VDB_ERR_UNSUPPORTED.
+ * One lease, two phases: the unfiltered queries are walked at 2k and fused into their output rows, then the filtered ones at
+ * max(4k, k + 10) (hybrid_fuse_filters_kernel reads every query's own filter); a phase without queries launches nothing; one copy
+ * back and one synchronisation behind the last fusion.  vdb_hip_index_last_kernels: the bits of both walks and
+ * VDB_KERNEL_HYBRID_FUSE; vdb_hip_index_last_search_stats: the sum over both walks. */
+int32_t vdb_hip_index_hybrid_search_filters(vdb_hip_index* idx, int32_t rows, uint32_t oversampling_ratio, void** filters,
+                                            uint32_t n_filters, const uint32_t* filter_of_query, const float* queries_rowmajor,
+                                            uint32_t nq, uint32_t k, const uint64_t* text_ids, const uint32_t* text_n,
+                                            uint32_t text_stride, const float* vector_weights, uint64_t* out_ids, float* out_scores,
+                                            uint32_t* out_n);
+/* vdb_hip_index_multi_query_search for n_groups user queries, each GROUP with its own filter or none (filter_of_group [n_groups]).
+ * The same contract per group, both kinds at k' = overfetch(top_k): an unfiltered group's lists are the plain call's of the rows form
+ * (removed rows never enter a walk's list), a filtered group's the lists of the call with one filter per query, every vector of the
+ * group on the group's filter.  The rule, its tie order, the group-size limits and the outputs are vdb_hip_index_multi_query_search's;
+ * with VDB_WALK_ROWS_F32 and no filter or one shared filter the call is that call byte for byte.  Errors as above (a group of V
+ * vectors with V * overfetch(top_k) > 8192: VDB_ERR_UNSUPPORTED, the message names the group).  fuse_lists_kernel is unchanged: a
+ * phase's groups are fused into consecutive rows of one block and handed out on the host.
+ * vdb_hip_index_last_kernels: the bits of both walks and VDB_KERNEL_FUSE. */
+int32_t vdb_hip_index_multi_query_search_filters(vdb_hip_index* idx, int32_t rows, uint32_t oversampling_ratio, void** filters,
+                                                 uint32_t n_filters, const uint32_t* filter_of_group, const float* queries_rowmajor,
+                                                 const uint32_t* group_sizes, uint32_t n_groups, uint32_t top_k, int32_t strategy,
+                                                 uint32_t rrf_k, const float* weights, uint64_t* out_ids, float* out_scores,
+                                                 uint32_t* out_n);
+
 /* ---- DistanceEngine::batch_distance / GpuAccelerator::batch_{cosine_similarity,
  * euclidean_distance,dot_product} (native/distance.rs:21-24; gpu_backend.rs:157,355,397) ----
  * n rows of dim floats against one query; out has n floats, same order as the rows. */

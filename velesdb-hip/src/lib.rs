@@ -1602,6 +1602,181 @@ impl HipHnswIndex {
         Ok((0..n as usize).map(|j| (ids[j], scores[j])).collect())
     }
 
+    // the table of distinct filter handles of a call with one optional filter per unit, and every unit's index into it
+    // (`table.len()` = no filter)
+    fn filter_table(filters: &[Option<&HipFilter>]) -> (Vec<*mut c_void>, Vec<u32>) {
+        let mut table: Vec<*mut c_void> = Vec::new();
+        let slots: Vec<Option<usize>> = filters
+            .iter()
+            .map(|f| {
+                f.map(|f| {
+                    table.iter().position(|t| *t == f.h).unwrap_or_else(|| {
+                        table.push(f.h);
+                        table.len() - 1
+                    })
+                })
+            })
+            .collect();
+        let none = table.len() as u32;
+        let of = slots.iter().map(|s| s.map_or(none, |at| at as u32)).collect();
+        (table, of)
+    }
+
+    /// [`Self::hybrid_search`] / [`Self::hybrid_search_with_filter`] for many user queries in one call, each with its own filter or
+    /// none, over any form of the walk (`vdb_hip_index_hybrid_search_filters`).  `rows` is one of `sys::VDB_WALK_ROWS_*`;
+    /// `oversampling_ratio` is read for the int8 and the re-scoring forms (0 = their default).  `text_hits[i]` = what the text index
+    /// returned for query `i` at `2 * k` (with a filter: `max(4 * k, k + 10)`), best first; `vector_weights[i]` as `vector_weight`
+    /// there.  Query `i` gets what it gets alone.
+    ///
+    /// # Errors
+    /// A count mismatch, a query of another dimension, a NaN weight.
+    ///
+    /// # Panics
+    /// On a status the library reports for the call itself (no graph, the image of `rows` not enabled, a stale filter, `k` past
+    /// what one block fuses).
+    #[allow(clippy::too_many_arguments)]
+    pub fn hybrid_search_batch_filters(
+        &self,
+        queries: &[&[f32]],
+        text_hits: &[&[u64]],
+        k: usize,
+        vector_weights: &[Option<f32>],
+        filters: &[Option<&HipFilter>],
+        rows: i32,
+        oversampling_ratio: u32,
+    ) -> Result<Vec<Vec<(u64, f32)>>, String> {
+        let nq = queries.len();
+        if text_hits.len() != nq || vector_weights.len() != nq || filters.len() != nq {
+            return Err(format!("Queries count ({nq}) does not match the text lists, weights or filters count"));
+        }
+        for q in queries {
+            if q.len() != self.dimension {
+                return Err(format!("Vector dimension mismatch: expected {}, got {}", self.dimension, q.len()));
+            }
+        }
+        let weights: Vec<f32> = vector_weights.iter().map(|w| w.unwrap_or(0.5)).collect();
+        if weights.iter().any(|w| w.is_nan()) {
+            return Err("vector_weight is NaN".into());
+        }
+        if nq == 0 {
+            return Ok(Vec::new());
+        }
+        let (mut table, fq) = Self::filter_table(filters);
+        let mut flat = Vec::with_capacity(nq * self.dimension);
+        for q in queries {
+            flat.extend_from_slice(q);
+        }
+        let stride = text_hits.iter().map(|t| t.len()).max().unwrap_or(0);
+        let mut text = vec![0u64; nq * stride];
+        for (i, t) in text_hits.iter().enumerate() {
+            text[i * stride..i * stride + t.len()].copy_from_slice(t);
+        }
+        // (a list past u32 keeps a count past every limit: the library refuses it, it never wraps to a short one)
+        let text_n: Vec<u32> = text_hits.iter().map(|t| u32::try_from(t.len()).unwrap_or(u32::MAX)).collect();
+        let kk = k.max(1);
+        let mut ids = vec![0u64; nq * kk];
+        let mut scores = vec![0f32; nq * kk];
+        let mut counts = vec![0u32; nq];
+        let table_p = if table.is_empty() { std::ptr::null_mut() } else { table.as_mut_ptr() };
+        // SAFETY: buffer sizes are n_filters / nq / nq*dim / nq*stride / nq / nq*max(k, 1) as the ABI requires; every handle of the
+        // table is live (borrowed from `filters`); the library does not write through the table.
+        check(unsafe {
+            sys::vdb_hip_index_hybrid_search_filters(
+                self.h,
+                rows,
+                oversampling_ratio,
+                table_p,
+                table.len() as u32,
+                fq.as_ptr(),
+                flat.as_ptr(),
+                nq as u32,
+                u32::try_from(k).unwrap_or(u32::MAX),
+                if stride == 0 { ptr::null() } else { text.as_ptr() },
+                text_n.as_ptr(),
+                u32::try_from(stride).unwrap_or(u32::MAX),
+                weights.as_ptr(),
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                counts.as_mut_ptr(),
+            )
+        });
+        Ok((0..nq).map(|i| (0..counts[i] as usize).map(|j| (ids[i * k + j], scores[i * k + j])).collect()).collect())
+    }
+
+    /// [`Self::multi_query_search_ids`] for many user queries in one call, each group of reformulations with its own filter or none,
+    /// over any form of the walk (`vdb_hip_index_multi_query_search_filters`).  `rows` and `oversampling_ratio` as in
+    /// [`Self::hybrid_search_batch_filters`].  Group `g` gets what it gets alone.
+    ///
+    /// # Errors
+    /// A count mismatch, an empty group, a group of more than ten vectors, a vector of another dimension.
+    ///
+    /// # Panics
+    /// On a status the library reports for the call itself.
+    pub fn multi_query_search_batch_filters(
+        &self,
+        groups: &[&[&[f32]]],
+        top_k: usize,
+        fusion: &FusionStrategy,
+        filters: &[Option<&HipFilter>],
+        rows: i32,
+        oversampling_ratio: u32,
+    ) -> Result<Vec<Vec<(u64, f32)>>, String> {
+        const MAX_VECTORS: usize = 10;
+        let ng = groups.len();
+        if filters.len() != ng {
+            return Err(format!("Groups count ({ng}) does not match filters count ({})", filters.len()));
+        }
+        let mut flat = Vec::new();
+        for g in groups {
+            if g.is_empty() {
+                return Err("multi_query_search requires at least one vector".into());
+            }
+            if g.len() > MAX_VECTORS {
+                return Err(format!("multi_query_search supports at most {MAX_VECTORS} vectors, got {}", g.len()));
+            }
+            for v in *g {
+                if v.len() != self.dimension {
+                    return Err(format!("Vector dimension mismatch: expected {}, got {}", self.dimension, v.len()));
+                }
+                flat.extend_from_slice(v);
+            }
+        }
+        if ng == 0 {
+            return Ok(Vec::new());
+        }
+        let sizes: Vec<u32> = groups.iter().map(|g| g.len() as u32).collect();
+        let (mut table, fg) = Self::filter_table(filters);
+        let kk = top_k.max(1);
+        let mut ids = vec![0u64; ng * kk];
+        let mut scores = vec![0f32; ng * kk];
+        let mut counts = vec![0u32; ng];
+        let (code, rrf_k, w) = fusion.abi();
+        let table_p = if table.is_empty() { std::ptr::null_mut() } else { table.as_mut_ptr() };
+        // SAFETY: the groups' vectors in order, sizes.len() = filters.len() = ng; outputs hold ng * max(top_k, 1) records and ng
+        // counts; the weights array outlives the call; every handle of the table is live (borrowed from `filters`).
+        check(unsafe {
+            sys::vdb_hip_index_multi_query_search_filters(
+                self.h,
+                rows,
+                oversampling_ratio,
+                table_p,
+                table.len() as u32,
+                fg.as_ptr(),
+                flat.as_ptr(),
+                sizes.as_ptr(),
+                ng as u32,
+                top_k as u32,
+                code,
+                rrf_k,
+                w.as_ptr(),
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                counts.as_mut_ptr(),
+            )
+        });
+        Ok((0..ng).map(|g| (0..counts[g] as usize).map(|j| (ids[g * top_k + j], scores[g * top_k + j])).collect()).collect())
+    }
+
     /// Boxed as the trait object `Collection` holds: what a downstream crate's `hip` feature registers with the index factory
     /// hook of velesdb-core (see Cargo.toml: the dependency points from this crate to the core, never back).
     #[must_use]

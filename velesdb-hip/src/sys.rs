@@ -104,6 +104,14 @@ pub const VDB_KERNEL_SWEEP_LISTED_GROUPS: i32 = 2097152;
 // #define VDB_KERNEL_HYBRID_FUSE (likewise)
 pub const VDB_KERNEL_HYBRID_FUSE: i32 = 4194304;
 
+// enum vdb_walk_rows (the rows the walks of the `_filters` forms of the fused searches take their distances over)
+pub const VDB_WALK_ROWS_F32: i32 = 0;
+pub const VDB_WALK_ROWS_F16: i32 = 1;
+pub const VDB_WALK_ROWS_BF16: i32 = 2;
+pub const VDB_WALK_ROWS_INT8: i32 = 3;
+pub const VDB_WALK_ROWS_F16_RESCORE: i32 = 4;
+pub const VDB_WALK_ROWS_BF16_RESCORE: i32 = 5;
+
 // enum vdb_fusion_strategy (FusionStrategy, fusion/strategy.rs:46-79)
 pub const VDB_FUSION_AVERAGE: i32 = 0;
 pub const VDB_FUSION_MAXIMUM: i32 = 1;
@@ -164,6 +172,8 @@ extern "C" {
     pub fn vdb_hip_index_multi_query_search(idx: *mut VdbHipIndex, filter: *const c_void, queries_rowmajor: *const f32, group_sizes: *const u32, n_groups: u32, top_k: u32, strategy: i32, rrf_k: u32, weights: *const f32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_hybrid_fuse(device: i32, vec_ids: *const u64, vec_n: *const u32, vec_stride: u32, text_ids: *const u64, text_n: *const u32, text_stride: u32, vector_weights: *const f32, nq: u32, k: u32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_index_hybrid_search(idx: *mut VdbHipIndex, filter: *const c_void, queries_rowmajor: *const f32, nq: u32, k: u32, text_ids: *const u64, text_n: *const u32, text_stride: u32, vector_weights: *const f32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
+    pub fn vdb_hip_index_hybrid_search_filters(idx: *mut VdbHipIndex, rows: i32, oversampling_ratio: u32, filters: *mut *mut c_void, n_filters: u32, filter_of_query: *const u32, queries_rowmajor: *const f32, nq: u32, k: u32, text_ids: *const u64, text_n: *const u32, text_stride: u32, vector_weights: *const f32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
+    pub fn vdb_hip_index_multi_query_search_filters(idx: *mut VdbHipIndex, rows: i32, oversampling_ratio: u32, filters: *mut *mut c_void, n_filters: u32, filter_of_group: *const u32, queries_rowmajor: *const f32, group_sizes: *const u32, n_groups: u32, top_k: u32, strategy: i32, rrf_k: u32, weights: *const f32, out_ids: *mut u64, out_scores: *mut f32, out_n: *mut u32) -> i32;
     pub fn vdb_hip_batch_distance(device: i32, metric: i32, kind: i32, query: *const f32, vecs_rowmajor: *const f32, n: u64, dim: u32, out: *mut f32) -> i32;
     pub fn vdb_hip_batch_distance_dev(metric: i32, kind: i32, d_query: *const f32, d_vecs_rowmajor: *const f32, n: u64, dim: u32, d_out: *mut f32, stream: *mut c_void) -> i32;
     pub fn vdb_hip_batch_norm(device: i32, vecs_rowmajor: *const f32, n: u64, dim: u32, out: *mut f32) -> i32;

@@ -19,6 +19,8 @@ from .index import KERNEL_SWEEP_LISTED_GROUPS  # noqa: F401
 from .index import (FILTER_ROUTE_AUTO, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK, KERNEL_SWEEP_LISTED, OPT_FILTER_ROUTE, Filter)  # noqa: F401
 from .index import FUSE_MAX_RECORDS, FusionError, FusionStrategy, KERNEL_FUSE, MAX_FUSED_VECTORS, fuse_arrays, fuse_groups  # noqa: F401
 from .index import HYBRID_MAX_RECORDS, KERNEL_HYBRID_FUSE, hybrid_fuse_arrays  # noqa: F401
+from .index import (WALK_ROWS_BF16, WALK_ROWS_BF16_RESCORE, WALK_ROWS_F16, WALK_ROWS_F16_RESCORE, WALK_ROWS_F32,  # noqa: F401
+                    WALK_ROWS_INT8)
 from .params import DistanceMetric, DualPrecisionConfig, HnswParams, SearchQuality, StorageMode  # noqa: F401
 
 __all__ = ["HnswIndex", "Filter", "FusionStrategy", "FusionError", "hybrid_fuse_arrays", "NativeHnswIndex", "HipDistance", "GpuAccelerator", "DistanceMetric", "HnswParams", "SearchQuality", "StorageMode", "DualPrecisionConfig", "VectorPrecision",

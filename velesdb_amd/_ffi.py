@@ -39,6 +39,8 @@ VDB_KERNEL_HALF_RESCORE = 1048576
 VDB_KERNEL_SWEEP_LISTED_GROUPS = 2097152
 # ... and of the hybrid search (vdb_hip_index_hybrid_search / vdb_hip_hybrid_fuse)
 VDB_KERNEL_HYBRID_FUSE = 4194304
+# enum vdb_walk_rows: the rows form of the walks behind vdb_hip_index_hybrid_search_filters / vdb_hip_index_multi_query_search_filters
+VDB_WALK_ROWS_F32, VDB_WALK_ROWS_F16, VDB_WALK_ROWS_BF16, VDB_WALK_ROWS_INT8, VDB_WALK_ROWS_F16_RESCORE, VDB_WALK_ROWS_BF16_RESCORE = 0, 1, 2, 3, 4, 5
 VDB_FUSION_AVERAGE, VDB_FUSION_MAXIMUM, VDB_FUSION_RRF, VDB_FUSION_WEIGHTED = 0, 1, 2, 3
 
 # every function include/velesdb_hip.h declares: name -> (restype, argtypes)
@@ -104,6 +106,8 @@ SIGNATURES = {
     "vdb_hip_index_multi_query_search": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_hybrid_fuse": (_i32, [_i32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     "vdb_hip_index_hybrid_search": (_i32, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "vdb_hip_index_hybrid_search_filters": (_i32, [_vp, _i32, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "vdb_hip_index_multi_query_search_filters": (_i32, [_vp, _i32, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
     "vdb_hip_batch_distance": (_i32, [_i32, _i32, _i32, _vp, _vp, _u64, _u32, _vp]),
     "vdb_hip_batch_distance_dev": (_i32, [_i32, _i32, _vp, _vp, _u64, _u32, _vp, _vp]),
     "vdb_hip_index_load_reference_files": (_i32, [_vp, C.c_char_p, C.c_char_p]),

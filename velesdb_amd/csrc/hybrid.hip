@@ -1,6 +1,7 @@
 // hybrid.hip — Collection::hybrid_search / hybrid_search_with_filter (collection/search/text.rs:113-299) on the device:
-// hybrid_fuse_kernel, its launcher and the stand-alone entry point vdb_hip_hybrid_fuse.  The rule itself is vdb_hybrid.hpp (shared
-// with the host model of the CPU tier); DESIGN 4.1p.
+// hybrid_fuse_kernel, its form with one optional filter per query hybrid_fuse_filters_kernel (one body, hybrid_fuse_block),
+// their launchers and the stand-alone entry point vdb_hip_hybrid_fuse.  The rule itself is vdb_hybrid.hpp (shared with the host model
+// of the CPU tier); DESIGN 4.1p.
 //
 // One block per user query.  The query's records sit in LDS as 16-byte (list << 13 | position, live, id) entries, as in fusion.hip:
 //   1. filtered form only: every thread looks at eight consecutive text hits, a block-wide scan of the kept counts gives every kept
@@ -40,23 +41,28 @@ __device__ __forceinline__ uint32_t hybrid_scan(uint32_t* __restrict__ scan, uin
   return scan[tid] - v;
 }
 
-__global__ void __launch_bounds__(1024) hybrid_fuse_kernel(const HybridArgs a) {
+// The body of both kernels below, for one block = one user query.  g: the query's vector list and HybridQuery in the launch's
+// arrays; q: its row in the call's text and output arrays (hybrid_fuse_kernel: q = g).  filtered, filter_bits and filter_rows are
+// uniform over the block: the launch's (hybrid_fuse_kernel) or the query's own (hybrid_fuse_filters_kernel).  The bitmap pointer is
+// typed as a global address, so that the per-hit read is a global load whichever kernel the pointer came from.
+typedef const __attribute__((address_space(1))) uint32_t* hybrid_glb_u32_p;
+__device__ __forceinline__ void hybrid_fuse_block(const HybridArgs& a, const uint32_t g, const uint32_t q, const bool filtered,
+                                                  const hybrid_glb_u32_p filter_bits, const uint32_t filter_rows) {
   extern __shared__ Rec hybrid_recs[];  // [a.lds_records] entries, then [blockDim.x] u32
   Rec* recs = hybrid_recs;
   uint32_t* scan = reinterpret_cast<uint32_t*>(hybrid_recs + a.lds_records);
-  const uint32_t tid = threadIdx.x, nt = blockDim.x, g = blockIdx.x;
+  const uint32_t tid = threadIdx.x, nt = blockDim.x;
   const HybridQuery Q = a.queries[g];
   const uint32_t nv = Q.nv, ntx = Q.nt;
-  const size_t ob = (size_t)g * (a.k ? a.k : 1u);
+  const size_t ob = (size_t)q * (a.k ? a.k : 1u);
   const float nan = fusion::u2f(0x7FC00000u);
-  const bool filtered = a.filtered != 0;
   // (nv + ntx > lds_records cannot happen: the host sized the launch by the largest query; then also ntx <= nt * kHybridItems)
   bool nothing = a.k == 0 || nv + ntx == 0 || nv + ntx > a.lds_records;
   uint32_t n = nv + ntx;
 
   if (!nothing) {
     // the text hits of this thread: [tid * 8, tid * 8 + 8)
-    const size_t tb = (size_t)g * a.text_stride;
+    const size_t tb = (size_t)q * a.text_stride;
     uint32_t keep = 0, live = 0, cnt = 0;
 #pragma unroll
     for (uint32_t e = 0; e < kHybridItems; e++) {
@@ -66,7 +72,7 @@ __global__ void __launch_bounds__(1024) hybrid_fuse_kernel(const HybridArgs a) {
       if (a.text_rows) {
         const uint32_t row = a.text_rows[tb + i];  // ~0u: the handle does not know the id
         const bool lv = row < a.n_rows && (!a.alive || a.alive[row] != 0);
-        const bool al = lv && filtered && row < a.filter_rows && ((a.filter_bits[row >> 5] >> (row & 31u)) & 1u);
+        const bool al = lv && filtered && row < filter_rows && ((filter_bits[row >> 5] >> (row & 31u)) & 1u);
         flags = (lv ? hybrid::kTextLive : 0u) | (al ? hybrid::kTextAllowed : 0u);
       }
       if (hybrid::text_ranked(flags, filtered)) {
@@ -96,7 +102,7 @@ __global__ void __launch_bounds__(1024) hybrid_fuse_kernel(const HybridArgs a) {
       a.out_ids[ob + e] = ~0ull;
       a.out_scores[ob + e] = nan;
     }
-    if (tid == 0) a.out_n[g] = 0;
+    if (tid == 0) a.out_n[q] = 0;
     return;
   }
   const uint32_t P = lds_pow2(n);  // <= lds_records (a power of two >= the largest nv + ntx)
@@ -174,7 +180,27 @@ __global__ void __launch_bounds__(1024) hybrid_fuse_kernel(const HybridArgs a) {
     a.out_ids[ob + e] = ~0ull;
     a.out_scores[ob + e] = nan;
   }
-  if (tid == 0) a.out_n[g] = written;
+  if (tid == 0) a.out_n[q] = written;
+}
+
+__global__ void __launch_bounds__(1024) hybrid_fuse_kernel(const HybridArgs a) {
+  hybrid_fuse_block(a, blockIdx.x, blockIdx.x, a.filtered != 0, (hybrid_glb_u32_p)a.filter_bits, a.filter_rows);
+}
+
+// One optional filter PER QUERY (vdb_hip_index_hybrid_search_filters): block b serves slot b of the launch — vector list
+// and HybridQuery b, the text hits and the output row of call position slots[b].query, the filter descs[slots[b].filter] (entry
+// n_filters: none, the unfiltered form).  The slot and the descriptor are the same for every thread of the block; the descriptor's
+// bitmap pointer comes out of memory, so it is made wave-uniform and a global address by hand (as hnsw_filtered.hip's uniform_ptr).
+__global__ void __launch_bounds__(1024) hybrid_fuse_filters_kernel(const HybridFiltersArgs fa) {
+  const HybridSlot s = fa.slots[blockIdx.x];
+  const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.filter);
+  const bool filtered = f < fa.n_filters;
+  const HybridFilterDesc d = fa.descs[filtered ? f : fa.n_filters];
+  const uint64_t bp = (uint64_t)d.bits;
+  const hybrid_glb_u32_p bits = (hybrid_glb_u32_p)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bp >> 32)) << 32) |
+                                                   (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bp));
+  hybrid_fuse_block(fa.h, blockIdx.x, (uint32_t)__builtin_amdgcn_readfirstlane((int)s.query), filtered, bits,
+                    (uint32_t)__builtin_amdgcn_readfirstlane((int)d.rows));
 }
 
 // The per-query table of a call from the list lengths and weights (host): the ONE validation of both entry points.  weights null =
@@ -207,23 +233,33 @@ int32_t hybrid_plan(const uint32_t* vec_n, uint64_t vec_stride, const uint32_t* 
   return VDB_OK;
 }
 
-// one launch for nq queries; a.lds_records is set here (max_records = the largest query's nv + nt, <= VDB_HYBRID_MAX_RECORDS: hybrid_plan)
-int32_t hybrid_launch(HybridArgs a, uint32_t nq, uint32_t max_records, hipStream_t st) {
+// one launch for nq queries; the LDS array of the launch is sized here (max_records = the largest query's nv + nt,
+// <= VDB_HYBRID_MAX_RECORDS: hybrid_plan) and handed to the kernel in args_of(a).lds_records
+template <class Args, class Kernel, class ArgsOf>
+static int32_t hybrid_launch_of(Kernel kernel, const char* name, Args a, ArgsOf&& args_of, uint32_t nq, uint32_t max_records, hipStream_t st) {
   if (nq == 0) return VDB_OK;
   uint32_t P = 1;
   while (P < max_records) P <<= 1;
-  a.lds_records = P;
+  args_of(a).lds_records = P;
   const uint32_t nt = std::min<uint32_t>(1024, std::max<uint32_t>(64, P / kHybridItems));  // nt * kHybridItems >= P
   const size_t lds = (size_t)P * sizeof(Rec) + (size_t)nt * 4;
   static_assert((size_t)VDB_HYBRID_MAX_RECORDS * sizeof(Rec) + 1024 * 4 <= 160 * 1024, "the largest query must fit the CU's LDS");
   static_assert(VDB_HYBRID_MAX_RECORDS <= 1024 * kHybridItems && VDB_HYBRID_MAX_RECORDS <= (1u << fusion::kPosBits), "eight records per thread; 13 position bits");
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(hybrid_fuse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("hybrid_fuse_kernel LDS attribute: ") + hipGetErrorString(e));
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string(name) + " LDS attribute: " + hipGetErrorString(e));
   }
-  hipLaunchKernelGGL(hybrid_fuse_kernel, dim3(nq), dim3(nt), lds, st, a);
+  hipLaunchKernelGGL(kernel, dim3(nq), dim3(nt), lds, st, a);
   VDB_HIP(hipGetLastError());
   return VDB_OK;
+}
+int32_t hybrid_launch(HybridArgs a, uint32_t nq, uint32_t max_records, hipStream_t st) {
+  return hybrid_launch_of(hybrid_fuse_kernel, "hybrid_fuse_kernel", a, [](HybridArgs& x) -> HybridArgs& { return x; }, nq, max_records, st);
+}
+// the per-query form: nq = the slots of the launch (fa.slots, fa.h.vec_ids and fa.h.queries hold one entry per slot)
+int32_t hybrid_filters_launch(HybridFiltersArgs fa, uint32_t nq, uint32_t max_records, hipStream_t st) {
+  return hybrid_launch_of(hybrid_fuse_filters_kernel, "hybrid_fuse_filters_kernel", fa, [](HybridFiltersArgs& x) -> HybridArgs& { return x.h; }, nq,
+                          max_records, st);
 }
 
 namespace {

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "vdb_combiner.hpp"
+#include "vdb_filter_route.hpp"
 #include "vdb_fusion.hpp"
 #include "vdb_hybrid.hpp"
 #include "vdb_index.hpp"
@@ -305,6 +306,344 @@ static int32_t hybrid_direct(vdb_hip_index* handle, const RowFilter* f, const fl
           std::memcpy(out_scores, h + o_os, (size_t)nq * k * 4);
         }
         std::memcpy(out_n, h + o_on, (size_t)nq * 4);
+      });
+}
+
+// ---- the fused searches with one optional filter per query over any rows form ----
+// What the two calls below share.  A call runs in two phases on one lease (fused_phases_plan, vdb_filter_route.hpp): the walk of the
+// unfiltered units through the plain call of the rows form and their fusion launch, then the walk of the filtered units through the
+// call with one filter per query and theirs.  Either walk ends with the context's result block on the host and a synchronisation;
+// a fusion launch is only enqueued behind it.  So the fusion of phase 1 may still be reading the result block when phase 2 reserves
+// it: fused_reserve_out sizes the block for the larger phase in front of both, after which no reserve of the call moves it.
+// the plain walk of a rows form (FiltersRows 4 / 5 have no mode of their own: the filters walk with an empty table)
+static_assert((int)VDB_WALK_ROWS_F32 == (int)kFiltersF32 && (int)VDB_WALK_ROWS_F16 == (int)kFiltersF16 && (int)VDB_WALK_ROWS_BF16 == (int)kFiltersBF16 &&
+                  (int)VDB_WALK_ROWS_INT8 == (int)kFiltersInt8 && (int)VDB_WALK_ROWS_F16_RESCORE == (int)kFiltersF16Rescore &&
+                  (int)VDB_WALK_ROWS_BF16_RESCORE == (int)kFiltersBF16Rescore,
+              "enum vdb_walk_rows is FiltersRows");
+static int32_t fused_plain_mode(int rows) {
+  return rows == kFiltersF16 ? VDB_SEARCH_HNSW_F16 : rows == kFiltersBF16 ? VDB_SEARCH_HNSW_BF16 : rows == kFiltersInt8 ? VDB_SEARCH_HNSW_INT8 : VDB_SEARCH_HNSW;
+}
+// every status the walks would decide on the handle's state, decided in front of both (the lock is held): the image or the quantiser
+// of the rows form, every filter of the table (foreign: INVALID_ARG, stale: STATE), the graph
+static int32_t fused_check_state(vdb_hip_index* ix, int rows, const RowFilter* const* filters, uint32_t n_filters, const char* what) {
+  const bool f16 = rows == kFiltersF16 || rows == kFiltersF16Rescore, bf16 = rows == kFiltersBF16 || rows == kFiltersBF16Rescore;
+  if (f16 && !ix->f16_enabled) return fail(VDB_ERR_STATE, std::string(what) + " over the f16 image: call vdb_hip_index_enable_half_precision(VDB_PRECISION_F16) first");
+  if (bf16 && !ix->bf16_enabled) return fail(VDB_ERR_STATE, std::string(what) + " over the bf16 image: call vdb_hip_index_enable_half_precision(VDB_PRECISION_BF16) first");
+  if (rows == kFiltersInt8 && !ix->quantizer_trained) return fail(VDB_ERR_STATE, std::string(what) + " over the int8 codes: call vdb_hip_index_train_quantizer first");
+  for (uint32_t j = 0; j < n_filters; j++) {
+    const int32_t rc = filter_check(ix, filters[j]);
+    if (rc != VDB_OK) return rc;
+  }
+  if (!ix->graph_valid) return fail(VDB_ERR_STATE, std::string(what) + ": HNSW graph not built for all rows");
+  return VDB_OK;
+}
+static size_t out_block_bytes(uint64_t lists, uint64_t list_len) {
+  const size_t kk = (size_t)std::max<uint64_t>(list_len, 1);
+  return (size_t)lists * kk * 12 + (size_t)lists * 4;  // reserve_out's layout
+}
+static int32_t fused_reserve_out(vdb_hip_index* ix, const FusedPhasesPlan& plan) {
+  size_t bytes = 0;
+  for (const FusedPhase& P : plan.phase)
+    if (!P.units.empty()) bytes = std::max(bytes, out_block_bytes(P.lists, P.list_len));
+  if (ix->s_out.reserve(bytes, false, ix->stream) != hipSuccess) return fail(VDB_ERR_OOM, "search scratch");
+  return VDB_OK;
+}
+// the walk of one phase: n vectors (caller memory, gathered) at list length kf; the lists end in ix->s_out_ids at stride max(kf, 1),
+// their lengths in ix->h_out.  fq_sub: the phase's table indices, one per vector (kPhaseFiltered only)
+static int32_t fused_walk(vdb_hip_index* ix, int phase, int rows, uint32_t ratio, const RowFilter* const* filters, uint32_t n_filters,
+                          const uint32_t* fq_sub, const float* q, uint32_t n, uint32_t kf) {
+  if (phase == kPhaseUnfiltered && rows <= kFiltersInt8)  // (the int8 walk takes the call's ratio as its rerank_k; 0 = the handle's option)
+    return search_to_device(ix, q, n, kf, 0, fused_plain_mode(rows), rows == kFiltersInt8 ? ratio : 0, nullptr);
+  uint32_t r = ratio;
+  if (rows == kFiltersInt8 && r == 0) r = (uint32_t)opt_value(ix, VDB_OPT_INT8_OVERSAMPLING);
+  if (rows >= kFiltersF16Rescore && r == 0) r = 4u;  // DualPrecisionConfig::default, as vdb_hip_index_search_graph_filters_half_rescore
+  std::vector<uint32_t> routes(n, 0u);
+  if (phase == kPhaseFiltered) return search_graph_filters_to_device(ix, filters, n_filters, fq_sub, q, n, kf, 0, 0, 0, routes.data(), rows, r);
+  const std::vector<uint32_t> none(n, 0u);  // (a table of no filters: value 0 = n_filters = no filter)
+  return search_graph_filters_to_device(ix, nullptr, 0, none.data(), q, n, kf, 0, 0, 0, routes.data(), rows, r);
+}
+// the vectors of a phase's units in one array; `keep` owns the copy when the phase is not the whole call
+template <class FirstOf>
+static const float* fused_gather(const float* queries, uint32_t dim, const FusedPhase& P, uint64_t lists_total, FirstOf&& first_of,
+                                 std::vector<float>* keep) {
+  if (P.lists == lists_total) return queries;
+  keep->resize((size_t)P.lists * dim);
+  size_t at = 0;
+  for (uint32_t u : P.units) {
+    const uint64_t first = first_of(u), n = first_of(u + 1) - first;
+    std::memcpy(keep->data() + at * dim, queries + (size_t)first * dim, (size_t)n * dim * 4);
+    at += (size_t)n;
+  }
+  return keep->data();
+}
+// What a finished walk leaves on its context — the kernel bits and the counters of vdb_hip_index_last_search_stats — is reset by the
+// next walk; a call of two phases reports the OR and the sum.  take(): behind the first walk (the plain walks keep their counters on
+// the device until somebody asks: fetched here, the stream is idle behind the walk's own synchronisation); give(): behind the second
+struct WalkCarry {
+  bool any = false;
+  uint32_t kernels = 0;
+  uint64_t n_dist = 0, n_expand = 0, pf_hits = 0;
+  static int32_t settle(vdb_hip_index* ix) {
+    if (!ix->stats_pending) return VDB_OK;
+    unsigned long long h[3] = {0, 0, 0};
+    VDB_HIP(hipMemcpyAsync(h, ix->s_stats.p, 24, hipMemcpyDeviceToHost, ix->stream));
+    VDB_HIP(hipStreamSynchronize(ix->stream));
+    ix->last_n_dist = h[0];
+    ix->last_n_expand = h[1];
+    ix->last_pf_hits = h[2];
+    ix->stats_pending = false;
+    return VDB_OK;
+  }
+  int32_t take(vdb_hip_index* ix) {
+    const int32_t rc = settle(ix);
+    if (rc != VDB_OK) return rc;
+    any = true;
+    kernels = ix->last_kernels;
+    n_dist = ix->last_n_dist;
+    n_expand = ix->last_n_expand;
+    pf_hits = ix->last_pf_hits;
+    return VDB_OK;
+  }
+  int32_t give(vdb_hip_index* ix) const {
+    if (!any) return VDB_OK;
+    const int32_t rc = settle(ix);
+    if (rc != VDB_OK) return rc;
+    ix->last_kernels |= kernels;
+    ix->last_n_dist += n_dist;
+    ix->last_n_expand += n_expand;
+    ix->last_pf_hits += pf_hits;
+    return VDB_OK;
+  }
+};
+
+// vdb_hip_index_hybrid_search_filters: hybrid_direct with one optional filter per query over any rows form.  ONE lease,
+// one block in s_fuse / h_fuse: [HybridQuery of the filtered slots | HybridQuery of the unfiltered slots | slots, unfiltered first |
+// filter descriptors | text ids | text rows | out ids | out scores | out n].  The phase that runs first uploads everything in front
+// of the outputs but the other phase's HybridQuery entries, which go up behind that phase's walk (they hold the walk's counts) — the
+// layout makes either upload one contiguous copy.  hybrid_fuse_filters_kernel writes every query's records into its own row of the
+// one output block; one copy back and one synchronisation behind the last fusion.
+static int32_t hybrid_filters_direct(vdb_hip_index* handle, int rows, uint32_t ratio, const RowFilter* const* filters, uint32_t n_filters,
+                                     const uint32_t* fq, const float* queries, uint32_t nq, uint32_t k, const FusedPhasesPlan& plan,
+                                     const uint64_t* text_ids, const uint32_t* text_n, uint32_t text_stride, const std::vector<HybridQuery>& table,
+                                     uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  const size_t kk = std::max<uint32_t>(k, 1);
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t tcells = (size_t)nq * text_stride;
+  const uint32_t n_un = (uint32_t)plan.phase[kPhaseUnfiltered].units.size(), n_fl = (uint32_t)plan.phase[kPhaseFiltered].units.size();
+  const size_t o_hq_un = (size_t)n_fl * sizeof(HybridQuery), o_sl = (size_t)nq * sizeof(HybridQuery), o_de = o_sl + up16((size_t)nq * sizeof(HybridSlot)),
+               o_tx = o_de + ((size_t)n_filters + 1) * sizeof(HybridFilterDesc), o_tr = o_tx + up16(tcells * 8), o_oi = o_tr + up16(tcells * 4),
+               o_os = o_oi + up16((size_t)nq * kk * 8), o_on = o_os + up16((size_t)nq * kk * 4), total = o_on + up16((size_t)nq * 4);
+  return run_search(
+      handle, nq, k, 0, VDB_SEARCH_HNSW, 0,
+      [&](vdb_hip_index* ix) -> int32_t {
+        int32_t rc = fused_check_state(ix, rows, filters, n_filters, "hybrid_search_filters");
+        if (rc != VDB_OK) return rc;
+        hipStream_t st = ix->stream;
+        if (ix->s_fuse.reserve(total, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "hybrid fusion scratch");
+        if (ix->h_fuse.reserve(total) != hipSuccess) return fail(VDB_ERR_OOM, "pinned hybrid fusion staging");
+        if ((rc = fused_reserve_out(ix, plan)) != VDB_OK) return rc;
+        unsigned char* h = ix->h_fuse.as<unsigned char>();
+        unsigned char* d = ix->s_fuse.as<unsigned char>();
+        // text ids -> rows, as hybrid_direct maps them: beside the first walk when there are many
+        auto map_rows = [&, h]() {
+          uint32_t* h_rows = reinterpret_cast<uint32_t*>(h + o_tr);
+          const vdb_hip_index* own = primary_of(ix);
+          for (uint32_t i = 0; i < nq; i++)
+            for (uint32_t j = 0; j < text_stride; j++) {
+              uint32_t row = 0xFFFFFFFFu;
+              if (j < text_n[i]) {
+                auto it = own->id_to_idx.find(text_ids[(size_t)i * text_stride + j]);
+                if (it != own->id_to_idx.end() && it->second < ix->n_rows) row = (uint32_t)it->second;
+              }
+              h_rows[(size_t)i * text_stride + j] = row;
+            }
+        };
+        struct Joined {
+          std::thread t;
+          ~Joined() {
+            if (t.joinable()) t.join();
+          }
+        } mapper;
+        if (tcells >= kHybridMapThreadCells) mapper.t = std::thread(map_rows); else map_rows();
+        // what does not wait for a walk: the slots (unfiltered first), the descriptors, the text ids
+        HybridSlot* h_slots = reinterpret_cast<HybridSlot*>(h + o_sl);
+        uint32_t at = 0;
+        for (int ph = 0; ph < 2; ph++)
+          for (uint32_t i : plan.phase[ph].units) h_slots[at++] = HybridSlot{i, fq[i]};
+        HybridFilterDesc* h_desc = reinterpret_cast<HybridFilterDesc*>(h + o_de);
+        for (uint32_t j = 0; j < n_filters; j++)
+          h_desc[j] = HybridFilterDesc{filters[j]->bitmap.as<uint32_t>(), (uint32_t)filters[j]->n_rows, 0};  // (n_rows <= ix->n_rows: filter_check)
+        h_desc[n_filters] = HybridFilterDesc{nullptr, 0, 0};
+        if (tcells) std::memcpy(h + o_tx, text_ids, tcells * 8);
+        HybridFiltersArgs fa{};
+        fa.h.text_ids = reinterpret_cast<const uint64_t*>(d + o_tx);
+        fa.h.text_rows = reinterpret_cast<const uint32_t*>(d + o_tr);
+        fa.h.text_stride = text_stride;
+        fa.h.alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+        fa.h.n_rows = (uint32_t)ix->n_rows;
+        fa.h.k = k;
+        fa.h.out_ids = reinterpret_cast<uint64_t*>(d + o_oi);
+        fa.h.out_scores = reinterpret_cast<float*>(d + o_os);
+        fa.h.out_n = reinterpret_cast<uint32_t*>(d + o_on);
+        fa.descs = reinterpret_cast<const HybridFilterDesc*>(d + o_de);
+        fa.n_filters = n_filters;
+        WalkCarry carry;
+        bool shared_up = false;  // the slots, descriptors and text hits are on the device
+        std::vector<float> qbuf;
+        std::vector<uint32_t> fq_sub;
+        for (int ph = 0; ph < 2; ph++) {
+          const FusedPhase& P = plan.phase[ph];
+          const uint32_t n = (uint32_t)P.units.size(), kf = (uint32_t)P.list_len;  // (kf <= 8192: the plan's limit)
+          if (n == 0) continue;
+          const float* q = fused_gather(queries, ix->dim, P, nq, [](uint32_t u) { return (uint64_t)u; }, &qbuf);
+          if (ph == kPhaseFiltered) {
+            fq_sub.resize(n);
+            for (uint32_t b = 0; b < n; b++) fq_sub[b] = fq[P.units[b]];
+          }
+          rc = fused_walk(ix, ph, rows, ratio, filters, n_filters, fq_sub.data(), q, n, kf);
+          if (mapper.t.joinable()) mapper.t.join();
+          if (rc != VDB_OK) {
+            (void)hipStreamSynchronize(st);  // (the first phase's fusion may be in flight over this context's scratch)
+            return rc;
+          }
+          const bool more = ph == kPhaseUnfiltered && n_fl != 0;
+          if (more && (rc = carry.take(ix)) != VDB_OK) return rc;
+          if (!more && (rc = carry.give(ix)) != VDB_OK) return rc;
+          const uint32_t* h_n = reinterpret_cast<const uint32_t*>(ix->h_out.as<unsigned char>() + ((unsigned char*)ix->s_out_n.p - (unsigned char*)ix->s_out.p));
+          const size_t o_hq = ph == kPhaseUnfiltered ? o_hq_un : 0;
+          HybridQuery* h_q = reinterpret_cast<HybridQuery*>(h + o_hq);
+          uint32_t most = 0;
+          for (uint32_t b = 0; b < n; b++) {
+            h_q[b] = table[P.units[b]];
+            h_q[b].nv = std::min<uint32_t>(h_n[b], kf);  // (a walk returns at most k' records)
+            most = std::max(most, h_q[b].nv + h_q[b].nt);
+          }
+          // this phase's HybridQuery entries, and with the first upload of the call everything behind them
+          const size_t up_end = shared_up ? o_hq + (size_t)n * sizeof(HybridQuery) : o_oi;
+          VDB_HIP(hipMemcpyAsync(d + o_hq, h + o_hq, up_end - o_hq, hipMemcpyHostToDevice, st));
+          shared_up = true;
+          fa.h.vec_ids = ix->s_out_ids.as<uint64_t>();
+          fa.h.vec_stride = std::max<uint32_t>(kf, 1);
+          fa.h.queries = reinterpret_cast<const HybridQuery*>(d + o_hq);
+          fa.slots = reinterpret_cast<const HybridSlot*>(d + o_sl) + (ph == kPhaseFiltered ? n_un : 0);
+          rc = hybrid_filters_launch(fa, n, most, st);
+          if (rc != VDB_OK) return rc;
+        }
+        ix->last_kernels |= VDB_KERNEL_HYBRID_FUSE;
+        VDB_HIP(hipMemcpyAsync(h + o_oi, d + o_oi, total - o_oi, hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipStreamSynchronize(st));
+        return VDB_OK;
+      },
+      [&](vdb_hip_index* ix) {
+        const unsigned char* h = ix->h_fuse.as<unsigned char>();
+        if (k) {
+          std::memcpy(out_ids, h + o_oi, (size_t)nq * k * 8);
+          std::memcpy(out_scores, h + o_os, (size_t)nq * k * 4);
+        }
+        std::memcpy(out_n, h + o_on, (size_t)nq * 4);
+      });
+}
+
+// vdb_hip_index_multi_query_search_filters: multi_query_direct with one optional filter per GROUP over any rows form.
+// The same two phases, both at the over-fetched k; fuse_lists_kernel is unchanged — a phase's groups are fused into consecutive rows
+// of the one output block (the unfiltered groups first) and the host hands every group its row.  One block in s_fuse / h_fuse:
+// [lists and groups of the unfiltered phase | lists and groups of the filtered phase | out ids | out scores | out n]; a phase's tables
+// go up behind its walk (they hold the walk's counts), one copy each.
+static int32_t multi_query_filters_direct(vdb_hip_index* handle, int rows, uint32_t ratio, const RowFilter* const* filters, uint32_t n_filters,
+                                          const uint32_t* fg, const float* queries, const uint32_t* group_sizes, uint32_t n_groups, uint32_t nq,
+                                          uint32_t top_k, const FusedPhasesPlan& plan, int32_t strategy, uint32_t rrf_k, const float* w,
+                                          uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  const size_t kk = std::max<uint32_t>(top_k, 1);
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const FusedPhase& UN = plan.phase[kPhaseUnfiltered];
+  const uint32_t n_un = (uint32_t)UN.units.size();
+  const size_t tab_un = (size_t)UN.lists * sizeof(FuseList) + (size_t)n_un * sizeof(FuseGroup);
+  const size_t o_oi = (size_t)nq * sizeof(FuseList) + (size_t)n_groups * sizeof(FuseGroup), o_os = o_oi + up16((size_t)n_groups * kk * 8),
+               o_on = o_os + up16((size_t)n_groups * kk * 4), total = o_on + up16((size_t)n_groups * 4);
+  std::vector<uint64_t> first(n_groups + 1u, 0);  // the first vector of every group
+  for (uint32_t g = 0; g < n_groups; g++) first[g + 1] = first[g] + group_sizes[g];
+  std::vector<uint32_t> row_of(n_groups, 0u);     // where a group's answer sits in the output block
+  return run_search(
+      handle, nq, top_k, 0, VDB_SEARCH_HNSW, 0,
+      [&](vdb_hip_index* ix) -> int32_t {
+        int32_t rc = fused_check_state(ix, rows, filters, n_filters, "multi_query_search_filters");
+        if (rc != VDB_OK) return rc;
+        hipStream_t st = ix->stream;
+        if (ix->s_fuse.reserve(total, false, st) != hipSuccess) return fail(VDB_ERR_OOM, "fusion scratch");
+        if (ix->h_fuse.reserve(total) != hipSuccess) return fail(VDB_ERR_OOM, "pinned fusion staging");
+        if ((rc = fused_reserve_out(ix, plan)) != VDB_OK) return rc;
+        unsigned char* h = ix->h_fuse.as<unsigned char>();
+        unsigned char* d = ix->s_fuse.as<unsigned char>();
+        FuseArgs a{};
+        a.strategy = strategy;
+        a.rrf_k = rrf_k;
+        a.w_avg = w[0];
+        a.w_max = w[1];
+        a.w_hit = w[2];
+        a.top_k = top_k;
+        WalkCarry carry;
+        std::vector<float> qbuf;
+        std::vector<uint32_t> fq_sub, sizes;
+        std::vector<FuseList> lists;
+        std::vector<FuseGroup> groups;
+        for (int ph = 0; ph < 2; ph++) {
+          const FusedPhase& P = plan.phase[ph];
+          const uint32_t n = (uint32_t)P.units.size(), nv = (uint32_t)P.lists, kf = (uint32_t)P.list_len;
+          if (n == 0) continue;
+          const uint32_t row0 = ph == kPhaseFiltered ? n_un : 0;
+          const float* q = fused_gather(queries, ix->dim, P, nq, [&](uint32_t g) { return first[g]; }, &qbuf);
+          sizes.resize(n);
+          fq_sub.clear();
+          for (uint32_t b = 0; b < n; b++) {
+            const uint32_t g = P.units[b];
+            sizes[b] = group_sizes[g];
+            row_of[g] = row0 + b;
+            if (ph == kPhaseFiltered) fq_sub.insert(fq_sub.end(), group_sizes[g], fg[g]);  // every vector of a group on the group's filter
+          }
+          rc = fused_walk(ix, ph, rows, ratio, filters, n_filters, fq_sub.data(), q, nv, kf);
+          if (rc != VDB_OK) {
+            (void)hipStreamSynchronize(st);  // (the first phase's fusion may be in flight over this context's scratch)
+            return rc;
+          }
+          const bool more = ph == kPhaseUnfiltered && !plan.phase[kPhaseFiltered].units.empty();
+          if (more && (rc = carry.take(ix)) != VDB_OK) return rc;
+          if (!more && (rc = carry.give(ix)) != VDB_OK) return rc;
+          const uint32_t* h_n = reinterpret_cast<const uint32_t*>(ix->h_out.as<unsigned char>() + ((unsigned char*)ix->s_out_n.p - (unsigned char*)ix->s_out.p));
+          uint32_t most = 0;
+          rc = fuse_plan(h_n, nv, std::max<uint32_t>(kf, 1), sizes.data(), n, &lists, &groups, &most);
+          if (rc != VDB_OK) return rc;
+          const size_t o_li = ph == kPhaseFiltered ? tab_un : 0, o_gr = o_li + (size_t)nv * sizeof(FuseList), o_end = o_gr + (size_t)n * sizeof(FuseGroup);
+          std::memcpy(h + o_li, lists.data(), o_gr - o_li);
+          std::memcpy(h + o_gr, groups.data(), o_end - o_gr);
+          VDB_HIP(hipMemcpyAsync(d + o_li, h + o_li, o_end - o_li, hipMemcpyHostToDevice, st));
+          a.ids = ix->s_out_ids.as<uint64_t>();
+          a.scores = ix->s_out_scores.as<float>();
+          a.list_stride = std::max<uint32_t>(kf, 1);
+          a.lists = reinterpret_cast<const FuseList*>(d + o_li);
+          a.groups = reinterpret_cast<const FuseGroup*>(d + o_gr);
+          a.out_ids = reinterpret_cast<uint64_t*>(d + o_oi) + (size_t)row0 * kk;
+          a.out_scores = reinterpret_cast<float*>(d + o_os) + (size_t)row0 * kk;
+          a.out_n = reinterpret_cast<uint32_t*>(d + o_on) + row0;
+          rc = fuse_launch(a, n, most, st);
+          if (rc != VDB_OK) return rc;
+        }
+        ix->last_kernels |= VDB_KERNEL_FUSE;
+        VDB_HIP(hipMemcpyAsync(h + o_oi, d + o_oi, total - o_oi, hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipStreamSynchronize(st));
+        return VDB_OK;
+      },
+      [&](vdb_hip_index* ix) {
+        const unsigned char* h = ix->h_fuse.as<unsigned char>();
+        const uint64_t* h_ids = reinterpret_cast<const uint64_t*>(h + o_oi);
+        const float* h_sc = reinterpret_cast<const float*>(h + o_os);
+        const uint32_t* h_cnt = reinterpret_cast<const uint32_t*>(h + o_on);
+        for (uint32_t g = 0; g < n_groups; g++) {
+          if (top_k) {
+            std::memcpy(out_ids + (size_t)g * top_k, h_ids + (size_t)row_of[g] * kk, (size_t)top_k * 8);
+            std::memcpy(out_scores + (size_t)g * top_k, h_sc + (size_t)row_of[g] * kk, (size_t)top_k * 4);
+          }
+          out_n[g] = h_cnt[row_of[g]];
+        }
       });
 }
 
@@ -690,6 +1029,96 @@ int32_t vdb_hip_index_hybrid_search(vdb_hip_index* ix, const void* filter, const
   if (rcp != VDB_OK || nq == 0) return rcp;
   return hybrid_direct(ix, static_cast<const RowFilter*>(filter), queries, nq, k, (uint32_t)kf, text_ids, text_n, text_stride, table, out_ids, out_scores,
                        out_n);
+  });
+}
+
+// The argument checks the two calls below share, in the order of include/velesdb_hip.h: the rows form, the ratio (read for the forms
+// that have one), the multi-device handle and the process group, the table; then — behind each call's own argument checks — the metric.
+static int32_t fused_filters_check_args(vdb_hip_index* ix, const char* what, int32_t rows, uint32_t ratio, void** filters, uint32_t n_filters,
+                                        const uint32_t* filter_of, uint32_t n_units) {
+  const std::string w(what);
+  if (rows < kFiltersF32 || rows > kFiltersBF16Rescore) return fail(VDB_ERR_INVALID_ARG, w + ": rows is one of enum vdb_walk_rows (0..5)");
+  if (rows >= kFiltersInt8 && ratio > 64) return fail(VDB_ERR_INVALID_ARG, w + ": oversampling_ratio 0 (the rows form's default) or 1..64");
+  if (ix->group) return fail(VDB_ERR_UNSUPPORTED, w + ": not available on a multi-device handle");
+  if (ix->pcomm) return fail(VDB_ERR_UNSUPPORTED, w + ": not available on a member of a process group");
+  for (uint32_t j = 0; j < n_filters; j++)
+    if (!filters[j]) return fail(VDB_ERR_INVALID_ARG, w + ": filter " + std::to_string(j) + " of the table is null");
+  for (uint32_t i = 0; i < n_units; i++)
+    if (filter_of[i] > n_filters)
+      return fail(VDB_ERR_INVALID_ARG, w + ": entry " + std::to_string(i) + " names filter " + std::to_string(filter_of[i]) + " of a table of " + std::to_string(n_filters));
+  return VDB_OK;
+}
+static int32_t fused_filters_check_metric(const vdb_hip_index* ix, const char* what, int32_t rows) {
+  if (rows != kFiltersF32 && ix->metric != VDB_COSINE && ix->metric != VDB_DOT && ix->metric != VDB_EUCLIDEAN)
+    return fail(VDB_ERR_UNSUPPORTED, std::string(what) + ": the half and int8 rows forms serve Cosine, DotProduct and Euclidean only");
+  return VDB_OK;
+}
+
+// vdb_hip_index_hybrid_search with one optional filter per query over any rows form of the walk (include/velesdb_hip.h)
+int32_t vdb_hip_index_hybrid_search_filters(vdb_hip_index* ix, int32_t rows, uint32_t oversampling_ratio, void** filters, uint32_t n_filters,
+                                            const uint32_t* filter_of_query, const float* queries, uint32_t nq, uint32_t k, const uint64_t* text_ids,
+                                            const uint32_t* text_n, uint32_t text_stride, const float* vector_weights, uint64_t* out_ids,
+                                            float* out_scores, uint32_t* out_n) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || !fg_table_ok(filters, n_filters, filter_of_query, nq) || (nq && (!queries || !text_n || !out_n)) || (nq && k && (!out_ids || !out_scores)) ||
+      (nq && text_stride && !text_ids))
+    return fail(VDB_ERR_INVALID_ARG, "null argument");
+  int32_t rc = fused_filters_check_args(ix, "hybrid_search_filters", rows, oversampling_ratio, filters, n_filters, filter_of_query, nq);
+  if (rc != VDB_OK) return rc;
+  // the weights and the text lists: hybrid_plan's checks and statuses (the vector lists are planned below, phase by phase)
+  std::vector<HybridQuery> table;
+  uint32_t most = 0;
+  rc = hybrid_plan(nullptr, 0, text_n, text_stride, vector_weights, nq, &table, &most);
+  if (rc != VDB_OK) return rc;
+  if ((rc = fused_filters_check_metric(ix, "hybrid_search_filters", rows)) != VDB_OK) return rc;
+  const FusedPhasesPlan plan = fused_phases_plan(
+      filter_of_query, nq, n_filters, hybrid_list_len(k, false), hybrid_list_len(k, true), VDB_HYBRID_MAX_RECORDS, [](uint32_t) { return 1u; },
+      [&](uint32_t i) { return text_n[i]; });
+  if (plan.over >= 0)
+    return fail(VDB_ERR_UNSUPPORTED, "hybrid_search_filters: query " + std::to_string(plan.over) + " would fuse a vector list of up to " +
+                                         std::to_string(plan.phase[plan.over_phase].list_len) + " ids (" +
+                                         (plan.over_phase == kPhaseFiltered ? "filtered" : "unfiltered") + ") and " + std::to_string(text_n[plan.over]) +
+                                         " text hits, more than the " + std::to_string(VDB_HYBRID_MAX_RECORDS) + " records one block's LDS takes");
+  if (nq == 0) return VDB_OK;
+  return hybrid_filters_direct(ix, rows, oversampling_ratio, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_query, queries, nq,
+                               k, plan, text_ids, text_n, text_stride, table, out_ids, out_scores, out_n);
+  });
+}
+
+// vdb_hip_index_multi_query_search with one optional filter per group over any rows form of the walk
+int32_t vdb_hip_index_multi_query_search_filters(vdb_hip_index* ix, int32_t rows, uint32_t oversampling_ratio, void** filters, uint32_t n_filters,
+                                                 const uint32_t* filter_of_group, const float* queries, const uint32_t* group_sizes,
+                                                 uint32_t n_groups, uint32_t top_k, int32_t strategy, uint32_t rrf_k, const float* weights,
+                                                 uint64_t* out_ids, float* out_scores, uint32_t* out_n) {
+  return vdb::guarded([&]() -> int32_t {
+  if (!ix || !fg_table_ok(filters, n_filters, filter_of_group, n_groups) || (n_groups && (!queries || !group_sizes || !out_n)) ||
+      (n_groups && top_k && (!out_ids || !out_scores)))
+    return fail(VDB_ERR_INVALID_ARG, "null argument");
+  int32_t rc = fused_filters_check_args(ix, "multi_query_search_filters", rows, oversampling_ratio, filters, n_filters, filter_of_group, n_groups);
+  if (rc != VDB_OK) return rc;
+  float w[3];
+  if ((rc = fuse_check_strategy(strategy, weights, w)) != VDB_OK) return rc;
+  const uint64_t kf = fusion::overfetch(top_k);
+  uint64_t nq = 0;
+  for (uint32_t g = 0; g < n_groups; g++) {
+    if (group_sizes[g] == 0)
+      return fail(VDB_ERR_INVALID_ARG, "multi_query_search_filters requires at least one vector (group " + std::to_string(g) + ")");
+    if (group_sizes[g] > VDB_MAX_FUSED_VECTORS)
+      return fail(VDB_ERR_INVALID_ARG, "multi_query_search_filters supports at most " + std::to_string(VDB_MAX_FUSED_VECTORS) + " vectors, got " +
+                                           std::to_string(group_sizes[g]) + " (group " + std::to_string(g) + ")");
+    nq += group_sizes[g];
+  }
+  if (nq > 0xFFFFFFFFull) return fail(VDB_ERR_INVALID_ARG, "multi_query_search_filters: more than 2^32 - 1 vectors in one call");
+  if ((rc = fused_filters_check_metric(ix, "multi_query_search_filters", rows)) != VDB_OK) return rc;
+  const FusedPhasesPlan plan = fused_phases_plan(
+      filter_of_group, n_groups, n_filters, kf, kf, VDB_FUSE_MAX_RECORDS, [&](uint32_t g) { return group_sizes[g]; }, [](uint32_t) { return 0u; });
+  if (plan.over >= 0)
+    return fail(VDB_ERR_UNSUPPORTED, "multi_query_search_filters: group " + std::to_string(plan.over) + " would fuse " + std::to_string(group_sizes[plan.over]) +
+                                         " lists of " + std::to_string(kf) + " records, more than the " + std::to_string(VDB_FUSE_MAX_RECORDS) +
+                                         " one block's LDS takes");
+  if (n_groups == 0) return VDB_OK;
+  return multi_query_filters_direct(ix, rows, oversampling_ratio, reinterpret_cast<const RowFilter* const*>(filters), n_filters, filter_of_group, queries,
+                                    group_sizes, n_groups, (uint32_t)nq, top_k, plan, strategy, rrf_k, w, out_ids, out_scores, out_n);
   });
 }
 

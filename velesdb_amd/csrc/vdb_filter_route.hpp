@@ -4,10 +4,12 @@
 // of the second kind with every query on the same filter — and how an EXACT call with one filter per query groups its queries and
 // cuts its listed groups into the work items of the grouped launches (vdb_hip_index_search_batch_filters), and the route
 // and the listed passes of a filtered exact call over the SQ8 / Binary / half images (vdb_hip_index_search_batch_filtered_mode),
-// and the groups and grouped launches of such a call with one filter per query (vdb_hip_index_search_batch_filters_mode).
+// and the groups and grouped launches of such a call with one filter per query (vdb_hip_index_search_batch_filters_mode),
+// and the two phases of a fused search with one filter per query (vdb_hip_index_hybrid_search_filters /
+// vdb_hip_index_multi_query_search_filters).
 // Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_mode_route_model.cpp,
-// tests/filter_graph_route_model.cpp, tests/filters_plan_model.cpp, tests/listed_groups_plan_model.cpp and
-// tests/mode_groups_plan_model.cpp compile it alone and walk its boundaries.
+// tests/filter_graph_route_model.cpp, tests/filters_plan_model.cpp, tests/listed_groups_plan_model.cpp,
+// tests/mode_groups_plan_model.cpp and tests/hybrid_filters_plan_model.cpp compile it alone and walk its boundaries.
 #pragma once
 #include <stdint.h>
 
@@ -411,6 +413,56 @@ static inline void mode_groups_plan(const std::vector<FxGroup>& groups, bool hal
         return (uint32_t)(per_cu > cap ? cap : per_cu);
       },
       [&](int B) { return half ? 64u / (uint32_t)B : 64u; }, out);
+}
+
+// ---- one filter per query in the fused searches (vdb_hip_index_hybrid_search_filters, vdb_hip_index_multi_query_search_filters;
+// DESIGN 4.1r) ----
+// The two kinds of a call ask their walks for lists of different lengths (hybrid: 2k without a filter, max(4k, k + 10) with one), so a
+// call runs in two PHASES on one lease: the unfiltered units through the plain walk, then the filtered ones through the walk with one
+// filter per query; each phase is one walk call and one fusion launch over that walk's result block.  A unit is a user query (hybrid)
+// or a group of reformulations (multi-query); it fuses lists_of(u) vector lists of its phase's length plus extra_of(u) further records
+// (its text hits), and that sum is held to `limit` (what one block's LDS takes) unit by unit, with the unit's OWN list length: a
+// query that is legal without a filter may be past the limit with one.
+constexpr int kPhaseUnfiltered = 0, kPhaseFiltered = 1;
+// text.rs:137 (k * 2) and 244 (k.saturating_mul(4).max(k + 10)); 64-bit, so that a product past u32 is seen by the limit
+static inline uint64_t hybrid_list_len(uint32_t k, bool filtered) {
+  const uint64_t a = (uint64_t)k * 4, b = (uint64_t)k + 10;
+  return filtered ? (a > b ? a : b) : (uint64_t)k * 2;
+}
+struct FusedPhase {
+  uint64_t list_len = 0;         // k' of the phase's walk
+  std::vector<uint32_t> units;   // positions in the call, ascending
+  uint64_t lists = 0;            // vectors the phase's walk searches (the sum of lists_of over its units)
+  uint64_t most = 0;             // records of its largest unit: sizes the fusion launch
+};
+struct FusedPhasesPlan {
+  FusedPhase phase[2];           // [kPhaseUnfiltered], [kPhaseFiltered]; a phase without units launches nothing
+  int64_t over = -1;             // the first unit past `limit` (nothing may run then), -1: none ...
+  uint64_t over_records = 0;     // ... and what it would fuse
+  int over_phase = 0;
+};
+// fq[u] in 0..n_filters, n_filters = no filter (null with n_units = 0 only); len_unfiltered / len_filtered: the phases' k'
+template <class ListsOf, class ExtraOf>
+static inline FusedPhasesPlan fused_phases_plan(const uint32_t* fq, uint32_t n_units, uint32_t n_filters, uint64_t len_unfiltered,
+                                                uint64_t len_filtered, uint64_t limit, ListsOf&& lists_of, ExtraOf&& extra_of) {
+  FusedPhasesPlan p;
+  p.phase[kPhaseUnfiltered].list_len = len_unfiltered;
+  p.phase[kPhaseFiltered].list_len = len_filtered;
+  for (uint32_t u = 0; u < n_units; u++) {
+    const int ph = fq[u] < n_filters ? kPhaseFiltered : kPhaseUnfiltered;
+    FusedPhase& P = p.phase[ph];
+    const uint64_t lists = lists_of(u);
+    const uint64_t records = lists * P.list_len + (uint64_t)extra_of(u);  // (lists <= 2^32, list_len < 2^35: inside 64 bits)
+    if (records > limit && p.over < 0) {
+      p.over = u;
+      p.over_records = records;
+      p.over_phase = ph;
+    }
+    P.units.push_back(u);
+    P.lists += lists;
+    if (records > P.most) P.most = records;
+  }
+  return p;
 }
 
 }  // namespace vdb

@@ -519,5 +519,23 @@ struct HybridArgs {
 int32_t hybrid_plan(const uint32_t* vec_n, uint64_t vec_stride, const uint32_t* text_n, uint32_t text_stride, const float* weights, uint32_t nq,
                     std::vector<HybridQuery>* queries, uint32_t* max_records);
 int32_t hybrid_launch(HybridArgs a, uint32_t nq, uint32_t max_records, hipStream_t st);
+// the form with one optional filter per query (hybrid_fuse_filters_kernel; vdb_hip_index_hybrid_search_filters)
+struct HybridFilterDesc {      // device layout, 16 bytes
+  const uint32_t* bits;        // the filter's bitmap (read only for rows < rows); entry n_filters of a table: null
+  uint32_t rows;               // rows the bitmap covers
+  uint32_t pad;
+};
+struct HybridSlot {            // one block of a launch
+  uint32_t query;              // the query's position in the call: its row in text_ids / text_rows and in the outputs
+  uint32_t filter;             // its entry of the descriptor table; n_filters = no filter (the unfiltered form)
+};
+struct HybridFiltersArgs {
+  HybridArgs h;                    // vec_ids / queries: one entry per SLOT of the launch; text_* / out_*: the call's arrays, addressed
+                                   // by HybridSlot::query; filtered / filter_bits / filter_rows: unused
+  const HybridFilterDesc* descs;   // [n_filters + 1]
+  const HybridSlot* slots;         // [blocks of the launch]
+  uint32_t n_filters;
+};
+int32_t hybrid_filters_launch(HybridFiltersArgs fa, uint32_t nq, uint32_t max_records, hipStream_t st);
 
 }  // namespace vdb

@@ -54,6 +54,9 @@ FUSE_MAX_RECORDS = 8192     # records of one group the fusion kernel takes (VDB_
 # hybrid search (HnswIndex.hybrid_search / hybrid_fuse_arrays): the kernel's bit, |V| + |T| of one query (VDB_HYBRID_MAX_RECORDS)
 KERNEL_HYBRID_FUSE = _ffi.VDB_KERNEL_HYBRID_FUSE
 HYBRID_MAX_RECORDS = 8192
+# the rows the walks of hybrid_search_batch_filters / multi_query_search_batch_filters take their distances over (enum vdb_walk_rows)
+WALK_ROWS_F32, WALK_ROWS_F16, WALK_ROWS_BF16, WALK_ROWS_INT8 = _ffi.VDB_WALK_ROWS_F32, _ffi.VDB_WALK_ROWS_F16, _ffi.VDB_WALK_ROWS_BF16, _ffi.VDB_WALK_ROWS_INT8
+WALK_ROWS_F16_RESCORE, WALK_ROWS_BF16_RESCORE = _ffi.VDB_WALK_ROWS_F16_RESCORE, _ffi.VDB_WALK_ROWS_BF16_RESCORE
 _PAD_ID = 0xFFFFFFFFFFFFFFFF  # what the library pads result ids with (the score beside it: NaN 0x7FC00000)
 SHARD_REPLICA, SHARD_RANGE = 0, 1
 COMM_ID_BYTES = 128
@@ -915,6 +918,80 @@ class HnswIndex:
         the text ranks: `text_hits` = the ids text_index.search(text, max(4k, k + 10)) returned."""
         ids, sc, cnt = self.hybrid_search_batch(_f32(query).reshape(1, -1), [text_hits], k, vector_weight, flt)
         return self._tuples(ids[0], sc[0], cnt[0])
+
+    @staticmethod
+    def _filter_table(filters, n: int, what: str):
+        """the table of distinct filters (by object identity) of a call with one optional filter per unit, and every unit's index
+        into it (len(table) = no filter)"""
+        filters = list(filters)
+        if len(filters) != n:
+            raise ValueError(f"{what} count ({n}) does not match filters count ({len(filters)})")
+        table, slot_of = [], {}
+        for f in filters:
+            if f is not None and id(f) not in slot_of:
+                slot_of[id(f)] = len(table)
+                table.append(f)
+        of = np.array([len(table) if f is None else slot_of[id(f)] for f in filters], dtype=np.uint32)
+        handles = (C.c_void_p * max(len(table), 1))(*[f._h for f in table])
+        return table, handles, of
+
+    def hybrid_search_batch_filters(self, queries, text_hits, k: int, vector_weight=None, filters=None, rows: int = WALK_ROWS_F32,
+                                    oversampling: int = 0):
+        """hybrid_search_batch with one optional filter PER QUERY over any form of the walk (vdb_hip_index_hybrid_search_filters).
+        filters: a sequence of Optional[Filter], one per query (None: no query is filtered).  rows: WALK_ROWS_F32, _F16 / _BF16
+        (enable_half_precision first), _INT8 (train_quantizer first) or _F16_RESCORE / _BF16_RESCORE; oversampling is read for the
+        last three (0 = the handle's option for _INT8, 4 for the re-score forms).  An unfiltered query is walked at 2k by the plain
+        call of that rows form, a filtered one at max(4k, k + 10) by the call with one filter per query, and its text hits outside
+        ITS filter are dropped before ranks exist; `text_hits[i]` is what the text index returned at that length.  Query i gets bit
+        for bit what it gets alone.  Returns (ids, fused scores, counts) as hybrid_search_batch."""
+        qs = _f32(queries)
+        if qs.ndim == 1:
+            qs = qs.reshape(1, -1)
+        self._validate(qs)
+        nq, kk = qs.shape[0], max(k, 1)
+        table, handles, fq = self._filter_table([None] * nq if filters is None else filters, nq, "Queries")
+        tids, tn, ts = _id_lists(text_hits, nq)
+        w = _hybrid_weights(vector_weight, nq)
+        ids = np.full((nq, kk), _PAD_ID, dtype=np.uint64)          # (k = 0: the library writes counts only)
+        sc = np.full((nq, kk), np.nan, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        check(lib().vdb_hip_index_hybrid_search_filters(self._h, int(rows), int(oversampling), handles if table else None, len(table),
+                                                        _ptr(fq) if nq else None, _ptr(qs) if nq else None, nq, k,
+                                                        _ptr(tids) if ts else None, _ptr(tn) if nq else None, ts,
+                                                        _ptr(w) if w is not None and nq else None, _ptr(ids), _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
+
+    def multi_query_search_batch_filters(self, groups, top_k: int, fusion: FusionStrategy, filters=None, rows: int = WALK_ROWS_F32,
+                                         oversampling: int = 0):
+        """multi_query_search_batch with one optional filter PER GROUP over any form of the walk
+        (vdb_hip_index_multi_query_search_filters).  filters: a sequence of Optional[Filter], one per group; rows / oversampling as
+        in hybrid_search_batch_filters.  Every vector is searched at the over-fetched k — an unfiltered group's by the plain call of
+        the rows form, a filtered group's by the call with one filter per query, all of them on the group's filter.  Group g gets bit
+        for bit what it gets alone.  Returns (ids, scores, counts) as multi_query_search_batch."""
+        mats = []
+        for g in groups:
+            vs = [_f32(v).reshape(-1) for v in g]
+            if not vs:
+                raise ValueError("multi_query_search requires at least one vector")
+            if len(vs) > MAX_FUSED_VECTORS:
+                raise ValueError(f"multi_query_search supports at most {MAX_FUSED_VECTORS} vectors, got {len(vs)}")
+            for v in vs:
+                if v.shape[0] != self._dimension:
+                    raise ValueError(f"Vector dimension mismatch: expected {self._dimension}, got {v.shape[0]}")
+            mats.append(np.stack(vs))
+        sizes = np.array([m.shape[0] for m in mats], dtype=np.uint32)
+        qs = np.ascontiguousarray(np.concatenate(mats)) if mats else np.zeros((0, self._dimension), np.float32)
+        ng, kk = len(mats), max(top_k, 1)
+        table, handles, fg = self._filter_table([None] * ng if filters is None else filters, ng, "Groups")
+        ids = np.full((ng, kk), _PAD_ID, dtype=np.uint64)          # (top_k = 0: the library writes counts only)
+        sc = np.full((ng, kk), np.nan, dtype=np.float32)
+        cnt = np.zeros(ng, dtype=np.uint32)
+        w, wp = fusion._weights_ptr()
+        check(lib().vdb_hip_index_multi_query_search_filters(self._h, int(rows), int(oversampling), handles if table else None, len(table),
+                                                             _ptr(fg) if ng else None, _ptr(qs) if ng else None,
+                                                             _ptr(sizes) if ng else None, ng, top_k, fusion.code, fusion.rrf_k, wp,
+                                                             _ptr(ids), _ptr(sc), _ptr(cnt)))
+        return ids, sc, cnt
 
     def search_brute_force_filtered(self, query, k: int, flt: Filter) -> List[Tuple[int, float]]:
         """search_brute_force among the filter's rows only (one query)."""
