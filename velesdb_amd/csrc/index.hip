@@ -911,15 +911,11 @@ static int32_t brute_masked_dev(vdb_hip_index* ix, const QuerySlice& s, hipStrea
   VDB_HIP(hipGetLastError());
   // the handle's adaptive selection state (park-after-failure counters, the verdict sequence it has seen) is for its unfiltered
   // batches: a filtered call reads it and leaves it as it was (its own verdicts are not posted: select_stage.hip)
-  const uint32_t seen = ix->sel_seq_seen, h16 = ix->sel16_hold, hw = ix->wide_hold, hl2 = ix->l2_hold, hsq = ix->sq8_hold;
+  const vdb::SelectHolds holds = ix->holds;
   ix->alive_override = ix->s_flt_mask.as<uint8_t>();
   const int32_t rc = mode == VDB_SEARCH_BRUTE ? brute_dev(ix, s, st) : brute_mode_dev(ix, mode, s, st);
   ix->alive_override = nullptr;
-  ix->sel_seq_seen = seen;
-  ix->sel16_hold = h16;
-  ix->wide_hold = hw;
-  ix->l2_hold = hl2;
-  ix->sq8_hold = hsq;
+  ix->holds = holds;
   return rc;
 }
 
@@ -1005,6 +1001,7 @@ int32_t search_dev(vdb_hip_index* ix, const float* d_q, uint64_t q_stride, uint3
   if (used_hnsw) *used_hnsw = false;
   ix->ev_used = 0;
   ix->sel_ev_used = 0;
+  ix->holds.call++;  // (the selectors' holds count search calls: vdb_select_hold.hpp)
   // diagnostics describe THIS call: brute_split_dev / the sweep paths overwrite them when they run
   ix->last_select_level = 0;
   ix->split_flags_n = 0;
@@ -1320,20 +1317,15 @@ int32_t search_filters_mode_to_device(vdb_hip_index* ix, const RowFilter* const*
     diag[2] = 1u - diag[1];
     return rc;
   }
-  const uint32_t seen = ix->sel_seq_seen, h16 = ix->sel16_hold, hw = ix->wide_hold, hl2 = ix->l2_hold, hsq = ix->sq8_hold;
   struct Quiet {  // the call posts no verdicts and leaves the adaptive selection state as it found it, whatever path ends it
     vdb_hip_index* ix;
-    uint32_t seen, h16, hw, hl2, hsq;
+    vdb::SelectHolds holds;
     ~Quiet() {
       ix->quiet_verdicts = false;
       ix->flt = nullptr;
-      ix->sel_seq_seen = seen;
-      ix->sel16_hold = h16;
-      ix->wide_hold = hw;
-      ix->l2_hold = hl2;
-      ix->sq8_hold = hsq;
+      ix->holds = holds;
     }
-  } quiet{ix, seen, h16, hw, hl2, hsq};
+  } quiet{ix, ix->holds};
   ix->quiet_verdicts = true;
   if (k == 0 || ix->n_rows == 0) {  // nothing can answer: the plain call's empty result
     diag[3] = nq;

@@ -404,14 +404,7 @@ int select_level(vdb_hip_index* ix, uint32_t nq_left, uint32_t k) {
   if (!select_chunk(nq_left)) return 0;
   if (want < 2 || ix->dim % 64 != 0 || ix->dim < 128) return 1;
   // what did the finished level-2 batches of this handle look like?  (pinned host memory, written by the re-scoring launch, sweep_split.hip selection_batch_tail)
-  if (ix->sel_stats && ix->sel_stats[2] != ix->sel_seq_seen) {
-    ix->sel_seq_seen = ix->sel_stats[2];
-    if (ix->sel_stats[3] == 2u && (uint64_t)ix->sel_stats[0] * 16 > ix->sel_stats[1]) ix->sel16_hold = 64;  // > 1/16 unproven
-  }
-  if (ix->sel16_hold) {
-    ix->sel16_hold--;
-    return 1;
-  }
+  if (ix->holds.sel16.ask(ix->sel_stats, ix->holds.call)) return 1;  // (> 1/16 of a level-2 batch unproven: level 1 for 64 batches, vdb_select_hold.hpp)
   return 2;
 }
 
@@ -483,14 +476,7 @@ int select_level_l2(vdb_hip_index* ix, uint32_t nq_left, uint32_t k) {
   if (k == 0 || k > kGemmBf16MaxK || ix->n_rows < kGemmBf16MinRows || ix->n_rows >= 0xFFFFFF00ull) return 0;
   if (!l2_gather_fits(ix->dim, k)) return 0;
   if (!select_chunk(nq_left)) return 0;
-  if (ix->sel_stats && ix->sel_stats[2] != ix->sel_seq_seen) {
-    ix->sel_seq_seen = ix->sel_stats[2];
-    if (ix->sel_stats[3] == 5u && (uint64_t)ix->sel_stats[0] * 16 > ix->sel_stats[1]) ix->l2_hold = 64;
-  }
-  if (ix->l2_hold) {
-    ix->l2_hold--;
-    return 0;
-  }
+  if (ix->holds.l2.ask(ix->sel_stats, ix->holds.call)) return 0;
   return 2;
 }
 
@@ -501,14 +487,7 @@ int select_level_sq8(vdb_hip_index* ix, uint32_t nq_left, uint32_t k) {
   if (ix->dim % 64 != 0 || ix->dim < 128 || ix->row_stride != ix->dim) return 0;
   if (k == 0 || k > kGemmBf16MaxK || ix->n_rows < kGemmBf16MinRows || ix->n_rows >= 0xFFFFFF00ull) return 0;
   if (!select_chunk(nq_left, kSelectMinQueriesSq8)) return 0;
-  if (ix->sel_stats && ix->sel_stats[2] != ix->sel_seq_seen) {
-    ix->sel_seq_seen = ix->sel_stats[2];
-    if (ix->sel_stats[3] == 3u && (uint64_t)ix->sel_stats[0] * 16 > ix->sel_stats[1]) ix->sq8_hold = 64;
-  }
-  if (ix->sq8_hold) {
-    ix->sq8_hold--;
-    return 0;
-  }
+  if (ix->holds.sq8.ask(ix->sel_stats, ix->holds.call)) return 0;
   return 3;
 }
 
@@ -944,14 +923,7 @@ int select_level_wide(vdb_hip_index* ix, uint32_t nq_left, uint32_t k, bool sq8)
   if (!sq8 && ix->metric != VDB_EUCLIDEAN && sweep_mfma_lds_bytes(1, k, ix->dim) > 160 * 1024) return 0;
   if (!sq8 && ix->metric == VDB_EUCLIDEAN && !l2_gather_fits(ix->dim, k)) return 0;
   if (!select_chunk(nq_left, sq8 ? kSelectMinQueriesSq8 : 0)) return 0;
-  if (ix->sel_stats && ix->sel_stats[2] != ix->sel_seq_seen) {
-    ix->sel_seq_seen = ix->sel_stats[2];
-    if (ix->sel_stats[3] == 4u && (uint64_t)ix->sel_stats[0] * 16 > ix->sel_stats[1]) ix->wide_hold = 64;  // > 1/16 unproven
-  }
-  if (ix->wide_hold) {
-    ix->wide_hold--;
-    return 0;
-  }
+  if (ix->holds.wide.ask(ix->sel_stats, ix->holds.call)) return 0;
   return 4;
 }
 

@@ -21,6 +21,7 @@
 
 #include "../../include/velesdb_hip.h"
 #include "vdb_host_sync.hpp"
+#include "vdb_select_hold.hpp"
 
 namespace vdb {
 
@@ -193,8 +194,10 @@ struct vdb_hip_index {
   // level 2 (plain bf16 selection) adaptivity: the verdict counts of finished batches arrive in pinned host memory
   // ({unproven, queries, sequence, level}); too many unproven queries park the handle at level 1 for a while
   volatile uint32_t* sel_stats = nullptr;
-  uint32_t sel_seq = 0, sel_seq_seen = 0, sel16_hold = 0;
-  uint32_t wide_hold = 0;   // batches with 10 < k answered by the exact kernels after a batch the WIDE selection could not prove (sweep_wide.hip)
+  uint32_t sel_seq = 0;
+  // park-after-failure state of the four selectors (vdb_select_hold.hpp): WIDE -> the levels below it / the exact kernels, level 2 ->
+  // level 1, Euclidean level 2 -> the f32 matrix-core path, SQ8 level 3 -> the exact SQ8 sweep.  Each keeps its own seen-sequence.
+  vdb::SelectHolds holds;
   int last_select_level = 0;
   uint32_t last_kernels = 0;  // vdb_kernel_bit set of the last search call (vdb_hip_index_last_kernels)
   // Euclidean batches through the selection stage: augmented bf16 image [capacity][dim + 64], augmented f32 seed prefix
@@ -204,7 +207,6 @@ struct vdb_hip_index {
   // the selection then runs as a DotProduct of unit vectors (no row norm in the kernel's bound): sweep_split.hip seln_rows_kernel
   vdb::DevBuf cosn_img, cosn_rho;
   uint64_t cosn_rows = 0;   // rows converted so far
-  uint32_t l2_hold = 0;     // batches to answer on the f32 matrix-core path after a batch the selection could not prove
   uint64_t split_rows = 0;   // rows converted so far
   size_t split_flags_off = 0;     // where the last split batch left its per-query verdicts in s_seed
   uint32_t split_flags_n = 0;
@@ -221,7 +223,6 @@ struct vdb_hip_index {
   // rows' bit counts as floats; built at the first large batch, kept current by inserts from then on
   vdb::DevBuf bits_img, bits_cnt;
   uint64_t bits_img_rows = 0;
-  uint32_t sq8_hold = 0;   // batches to answer with the exact SQ8 sweep after a batch the selection could not prove
   // graph
   std::vector<vdb::GraphLayer> layers;
   bool graph_valid = true;   // false once rows exist that are not linked into the graph

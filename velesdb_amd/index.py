@@ -1237,6 +1237,14 @@ class HipDistance:
                                            c.shape[0], q.size, _ptr(out)))
         return out
 
+    def batch_distance_dev(self, d_query: int, d_rows: int, n: int, dim: int, d_out: int, stream: int = 0,
+                           kind: int = KIND_ENGINE) -> None:
+        """The same over device-resident buffers (vdb_hip_batch_distance_dev): `d_query` dim floats, `d_rows` n x dim floats row-major,
+        `d_out` n floats — device addresses aligned to 4 bytes or better — enqueued on `stream`; nothing synchronises.  Runs on the
+        device the buffers live on (the caller's current device), not on `self.device`."""
+        check(lib().vdb_hip_batch_distance_dev(int(self._metric), kind, C.c_void_p(d_query), C.c_void_p(d_rows), n, dim,
+                                               C.c_void_p(d_out), C.c_void_p(stream)))
+
     def distance(self, a, b) -> float:
         return float(self.batch_distance(a, _f32(b).reshape(1, -1))[0])
 
