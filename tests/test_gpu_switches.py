@@ -29,6 +29,7 @@ against the oracle) must hold.
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
@@ -80,11 +81,37 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("env,target", CASES, ids=[",".join(f"{k}={v}" for k, v in e.items()) + ":" + t[0].split("/")[-1] for e, t in CASES])
-def test_parity_holds_under_the_switch(gpu_required, env, target):
+IDS = [",".join(f"{k}={v}" for k, v in e.items()) + ":" + t[0].split("/")[-1] for e, t in CASES]
+# Children at a time.  One after the other the 23 children were the longest file of the GPU suite by far (a child of SPLIT alone runs
+# 52 s, that of SPLIT_ALL 110 s), most of it start-up, data generation and single-threaded host work during which the GPU idles; they
+# share nothing but the device and the CPUs.  Four at a time: the whole file in 6.6 min, no case waiting longer than 130 s.
+CHILDREN_AT_A_TIME = 4
+
+
+def _run_child(env, target):
     child_env = dict(os.environ, VDB_TEST_PROBE_LIB="1", **env)   # (tests/conftest.py binds the child to libvelesdb_hip_probe.so)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", *target], cwd=ROOT, env=child_env,
-                       capture_output=True, text=True, timeout=900)
+    return subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", *target], cwd=ROOT, env=child_env,
+                          capture_output=True, text=True, timeout=900)
+
+
+@pytest.fixture(scope="module")
+def children(request):
+    """The child runs of the cases this session selected, started in the order of CASES, CHILDREN_AT_A_TIME at once: id -> future of the
+    finished process.  Every case still has its own child, its own time limit and its own assertions."""
+    if va.device_count() == 0:   # (gpu_required skips every case)
+        yield {}
+        return
+    selected = {i.callspec.id for i in request.session.items if getattr(i, "module", None) is request.module and hasattr(i, "callspec")}
+    pool = ThreadPoolExecutor(max_workers=CHILDREN_AT_A_TIME)
+    try:
+        yield {cid: pool.submit(_run_child, env, target) for cid, (env, target) in zip(IDS, CASES) if cid in selected}
+    finally:
+        pool.shutdown(wait=True, cancel_futures=True)   # (a session that stops early leaves no child behind)
+
+
+@pytest.mark.parametrize("env,target", CASES, ids=IDS)
+def test_parity_holds_under_the_switch(gpu_required, children, request, env, target):
+    r = children[request.node.callspec.id].result()
     tail = (r.stdout or "")[-1500:] + (r.stderr or "")[-500:]
     assert r.returncode == 0, f"parity broke under {env}:\n{tail}"
     assert " passed" in r.stdout and " failed" not in r.stdout, tail
