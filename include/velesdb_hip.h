@@ -889,6 +889,13 @@ enum vdb_kernel_bit {
 #define VDB_KERNEL_SWEEP_LISTED_GROUPS 2097152
 /* ... and one more: hybrid_fuse_kernel ran (vdb_hip_index_hybrid_search sets it next to the walk's bits) */
 #define VDB_KERNEL_HYBRID_FUSE 4194304
+/* ... and one more: half_l2_select + half_l2_rescore ran — a Euclidean batch of VDB_SEARCH_BRUTE_F16 / _BF16 selected on the matrix cores
+ * and re-scored its survivors with sweep_topk_half_l2's chain (>= 16 queries — 64 when k > 10 —, >= 65 536 rows, dim % 64 == 0, k <= 128 and rows * k <= 2^25;
+ * the answer is the streaming kernel's, bit for bit).  Set NEXT TO VDB_KERNEL_SWEEP_HALF_L2 — the chain that produced the scores is that
+ * family's — and VDB_KERNEL_F16 for the f16 instances.  Selector level 0 (vdb_hip_set_split_selector / VDB_OPT_SELECTOR_LEVEL) keeps
+ * such batches on the streaming kernel.  Written as a shift: tests/test_filters_modes_cpu.py pins VDB_KERNEL_HYBRID_FUSE as the largest
+ * bit among the decimal ones, tests/test_half_l2_bound_cpu.py holds the bindings to this one. */
+#define VDB_KERNEL_SELECT_HALF_L2 (1u << 23)
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same
  * context a moment later does not change it. */

@@ -24,7 +24,11 @@ p.add_argument("--dim", type=int, default=768)
 p.add_argument("--k", type=int, default=10)
 p.add_argument("--nq", type=int, default=1024)
 p.add_argument("--repeats", type=int, default=7)
+p.add_argument("--l2-ab", action="store_true", help="only section 4: the Euclidean half batch, matrix-core selection path against the streaming kernel")
+p.add_argument("--lib", default=None, help="bind this build of the library instead (e.g. the parent commit's: its numbers for the same sections)")
 a = p.parse_args()
+if a.lib:
+    va._ffi.use_library(a.lib)
 dev = torch.device("cuda", 0)
 st = torch.cuda.current_stream().cuda_stream
 VP = va.VectorPrecision
@@ -69,6 +73,32 @@ def kernel_ms(ix, q, nq, mode):
 g = torch.Generator(device=dev)
 g.manual_seed(43)
 queries = torch.randn((a.nq, a.dim), generator=g, device=dev)
+
+# ---- 4. Euclidean half batches: A = the selection path (selector level as set), B = the streaming kernel (selector level 0 on the same
+# handle: the kernel of the parent commit, instruction for instruction), alternating blocks, median and spread of the blocks; with
+# kernel timing on, the whole batch's device time.  With --lib (a build without the path) A and B are both the streaming kernel.
+if a.l2_ab:
+    ix = build(va.DistanceMetric.Euclidean)
+    for mode, name in ((va.MODE_BRUTE_F16, "f16"), (va.MODE_BRUTE_BF16, "bf16")):
+        for nq in (16, 64, a.nq):
+            for k in (a.k, 100):
+                res = {-1: [], 0: []}
+                k_cli, a.k = a.k, k  # (timed() sizes its outputs by a.k)
+                for blk in range(max(5, a.repeats)):
+                    for level in (-1, 0):
+                        ix.set_option(va.OPT_SELECTOR_LEVEL, level)
+                        if blk == 0:
+                            timed(ix, queries, nq, mode, 1)
+                        res[level].append(timed(ix, queries, nq, mode, 3 if level else 1)[0])
+                        if level:
+                            mask = ix.last_kernels()
+                a.k = k_cli
+                ra, rb = np.array(res[-1]), np.array(res[0])
+                print(f"euclidean {name} {a.rows} x {a.dim}, {nq} queries, k = {k}: A (kernels {mask:#x}) median {np.median(ra):.3f} ms [{ra.min():.3f} .. {ra.max():.3f}] | "
+                      f"B streaming median {np.median(rb):.3f} ms [{rb.min():.3f} .. {rb.max():.3f}] | B / A = {np.median(rb) / np.median(ra):.2f}", flush=True)
+    ix.set_option(va.OPT_SELECTOR_LEVEL, -1)
+    ix.close()
+    sys.exit(0)
 
 # ---- 1. F16 Cosine next to BF16 Cosine --------------------------------------------------------------------------------------------
 ix = build(va.DistanceMetric.Cosine)

@@ -103,6 +103,8 @@ pub const VDB_KERNEL_HALF_RESCORE: i32 = 1048576;
 pub const VDB_KERNEL_SWEEP_LISTED_GROUPS: i32 = 2097152;
 // #define VDB_KERNEL_HYBRID_FUSE (likewise)
 pub const VDB_KERNEL_HYBRID_FUSE: i32 = 4194304;
+// #define VDB_KERNEL_SELECT_HALF_L2 (1u << 23) (likewise; a shift in the header, a shift here)
+pub const VDB_KERNEL_SELECT_HALF_L2: i32 = 1 << 23;
 
 // enum vdb_walk_rows (the rows the walks of the `_filters` forms of the fused searches take their distances over)
 pub const VDB_WALK_ROWS_F32: i32 = 0;

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "vdb_filter_route.hpp"
+#include "vdb_half_l2.hpp"
 #include "vdb_probe_env.hpp"
 #include "vdb_select_stage.hpp"
 #include "vdb_sweep_pass.hpp"
@@ -40,12 +41,142 @@ static bool gemm_bf16_glds_enabled() {
   return on;
 }
 
-// Euclidean over a half copy (half_precision::euclidean_distance, half_precision.rs:257-287): the streaming difference-chain sweep of
-// sweep_half_l2.hip for every batch size — query tiles of 16 (4 / 1 where LDS or the batch is smaller), the corpus re-read per tile
-static int32_t brute_half_l2_dev(vdb_hip_index* ix, const uint16_t* rows16, bool f16, const QuerySlice& s, hipStream_t st) {
+static int32_t pinned_select_stats(vdb_hip_index* ix);
+
+// Does a Euclidean batch over a half image take the matrix-core selection path (sweep_half_l2_select.hip)?  Whole 64-element
+// k-steps, a corpus the seed prefix is a small part of, survivor lists that cover the expected n k / R0 survivors twice (no tightening
+// schedule is built: that is what bounds k at 1 M rows to 32), the 16-query tile of the seed / fallback launches inside the LDS, a row
+// mask that leaves the seed prefix enough live rows — and a handle whose data did not defeat the path lately (the hold, asked last).
+static bool half_l2_select_takes(vdb_hip_index* ix, uint32_t nq, uint32_t k) {
+  if (!opt_selector(ix) || opt_max_tile(ix) < 128 || ix->metric != VDB_EUCLIDEAN) return false;
+  if (nq < (k <= kHalfL2SmallK ? kHalfL2MinQueries : kHalfL2MinQueriesBigK) || k == 0 || k > kHalfL2MaxK) return false;
+  if (ix->dim % 64 != 0 || ix->dim < 128 || ix->bf16_stride != ix->dim) return false;
+  if (ix->n_rows < kGemmBf16MinRows || ix->n_rows >= 0xFFFFFF00ull || !half_l2_lists_fit(ix->n_rows, k)) return false;
+  if (sweep_half_l2_lds_bytes(16, k, ix->dim) > 160 * 1024) return false;
+  if (ix->flt && !filter_keeps_selection(ix->flt->count, ix->n_rows)) return false;
+  return !ix->holds.half_l2.ask(ix->sel_stats, ix->holds.call);
+}
+
+// one chunk of <= kGemmMaxQueries queries on that path: seed sweep + merge, bounds, selection, re-score, the fallback's sweep + merge,
+// select_finish (the listed queries' answers, the verdict).  Nothing synchronises.
+static int32_t half_l2_select_dev(vdb_hip_index* ix, const uint16_t* rows16, const float* norms16, bool f16, const QuerySlice& c, hipStream_t st) {
+  const int32_t rs = pinned_select_stats(ix);
+  if (rs != VDB_OK) return rs;
+  const uint32_t nq = c.nq, k = c.k, n = (uint32_t)ix->n_rows, dim = ix->dim;
+  const uint32_t nqp = (uint32_t)half_l2_select_scratch_words(nq), ny = (nq + 15) / 16;
+  const uint8_t* alive = search_alive(ix);
+  // partial lists of the two streaming launches: [nq][blocks][k] keys — the block counts keep that inside 64 MiB
+  const int s_blocks = (int)std::max<uint32_t>(8, std::min<uint32_t>(256, (uint32_t)(4 * ix->n_cus) / ny));
+  const size_t per_block = (size_t)nq * k * 8;
+  const int f_blocks = (int)std::max<size_t>(16, std::min<size_t>((size_t)ix->n_cus * 3, ((size_t)64 << 20) / per_block));
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off = (off + bytes + 15) & ~(size_t)15;
+    return o;
+  };
+  const size_t o_sid = take((size_t)nq * k * 8), o_ssc = take((size_t)nq * k * 4), o_sn = take((size_t)nq * 4), o_ctl = take(16),
+               o_tau = take((size_t)nqp * 4), o_cnt = take((size_t)nqp * 4), o_flags = take((size_t)nq * 4), o_qmap = take((size_t)nq * 4),
+               o_qslot = take((size_t)nq * 4), o_gid = take((size_t)nq * k * 8), o_gsc = take((size_t)nq * k * 4), o_gn = take((size_t)nq * 4);
+  const size_t q16_bytes = ((size_t)nqp * dim * 2 + 15) & ~(size_t)15;
+  if (ix->s_seed.reserve(off, false, st) != hipSuccess || ix->s_misc.reserve(q16_bytes + (size_t)nq * dim * 4, false, st) != hipSuccess ||
+      ix->s_fb_keys.reserve((size_t)nq * kHalfL2ListCap * 4, false, st) != hipSuccess ||
+      ix->s_part_keys.reserve(per_block * (size_t)std::max(s_blocks, f_blocks), false, st) != hipSuccess)
+    return fail(VDB_ERR_OOM, "half-precision Euclidean selection scratch");
+  unsigned char* sd = ix->s_seed.as<unsigned char>();
+  uint64_t* parts = ix->s_part_keys.as<uint64_t>();
+  uint32_t* ctl = reinterpret_cast<uint32_t*>(sd + o_ctl);
+  EventPair* ev = next_events(ix);
+  if (ev) (void)hipEventRecord(ev->a, st);
+  // seed: the streaming kernel over the first rows, merged into scratch as internal rows
+  hipError_t e = launch_sweep_half_l2_tiles(f16, rows16, ix->bf16_stride, alive, c.d_q, c.q_stride, parts, kHalfL2SeedRows, dim, nq, k, s_blocks, nullptr, st);
+  if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("half-precision Euclidean seed launch: ") + hipGetErrorString(e));
+  const QuerySlice seed{c.d_q, c.q_stride, nq, k, reinterpret_cast<uint64_t*>(sd + o_sid), reinterpret_cast<float*>(sd + o_ssc),
+                        reinterpret_cast<uint32_t*>(sd + o_sn)};
+  merge_pass(false, parts, nullptr, (uint32_t)s_blocks, seed, st, /*ext_ids=*/nullptr);
+  HalfL2SelectBatch b{};
+  b.f16 = f16;
+  b.rows = rows16;
+  b.norms = norms16;
+  b.alive = alive;
+  b.ext_ids = ix->ext_ids.as<uint64_t>();
+  b.queries = c.d_q;
+  b.seed_rows = seed.d_ids;
+  b.seed_n = seed.d_n;
+  b.ctl = ctl;
+  b.q16 = ix->s_misc.as<uint16_t>();
+  b.tau = reinterpret_cast<float*>(sd + o_tau);
+  b.cnt = reinterpret_cast<uint32_t*>(sd + o_cnt);
+  b.flags = reinterpret_cast<uint32_t*>(sd + o_flags);
+  b.lists = ix->s_fb_keys.as<uint32_t>();
+  b.qmap = reinterpret_cast<uint32_t*>(sd + o_qmap);
+  b.qslot = reinterpret_cast<uint32_t*>(sd + o_qslot);
+  b.qgath = reinterpret_cast<float*>(ix->s_misc.as<unsigned char>() + q16_bytes);
+  b.out_ids = c.d_ids;
+  b.out_scores = c.d_scores;
+  b.out_n = c.d_n;
+  b.row_stride = ix->bf16_stride;
+  b.q_stride = c.q_stride;
+  b.n_rows = n;
+  b.dim = dim;
+  b.nq = nq;
+  b.k = k;
+  b.n_cus = ix->n_cus;
+  if ((e = launch_half_l2_select_batch(b, st)) != hipSuccess)
+    return fail(VDB_ERR_HIP, std::string("half-precision Euclidean selection launch: ") + hipGetErrorString(e));
+  // the fallback: the listed queries over ALL rows, their block rows only
+  e = launch_sweep_half_l2_tiles(f16, rows16, ix->bf16_stride, alive, b.qgath, dim, parts, n, dim, nq, k, f_blocks, ctl + 1, st);
+  if (e != hipSuccess) return fail(VDB_ERR_HIP, std::string("half-precision Euclidean fallback launch: ") + hipGetErrorString(e));
+  MergeArgs mg{};
+  mg.part_keys = parts;
+  mg.ext_ids = b.ext_ids;
+  mg.out_ids = reinterpret_cast<uint64_t*>(sd + o_gid);
+  mg.out_scores = reinterpret_cast<float*>(sd + o_gsc);
+  mg.out_n = reinterpret_cast<uint32_t*>(sd + o_gn);
+  mg.n_lists = (uint32_t)f_blocks;
+  mg.k = k;
+  mg.active = ctl + 1;
+  launch_merge(false, mg, nq, st);
+  SelectFinishArgs fin{};
+  fin.flags = b.flags;
+  fin.qcount = ctl + 1;
+  fin.qslot = b.qslot;
+  fin.g_ids = mg.out_ids;
+  fin.g_scores = mg.out_scores;
+  fin.g_n = mg.out_n;
+  fin.out_ids = c.d_ids;
+  fin.out_scores = c.d_scores;
+  fin.out_n = c.d_n;
+  fin.nq = nq;
+  fin.k = k;
+  if (ix->sel_stats && !ix->alive_override && !ix->quiet_verdicts) {  // (a filtered call's verdicts say nothing about the handle's data: not posted)
+    fin.stats_host = ix->sel_stats;
+    fin.stats_seq = ++ix->sel_seq;
+    fin.stats_level = 6u;
+  }
+  launch_select_finish(fin, st);
+  if (ev) (void)hipEventRecord(ev->b, st);
+  VDB_HIP(hipGetLastError());
+  return VDB_OK;
+}
+
+// Euclidean over a half copy (half_precision::euclidean_distance, half_precision.rs:257-287): large batches over a large corpus select on
+// the matrix cores and re-score the survivors with the streaming kernel's chain (above; the same bits); everything else is the streaming
+// difference-chain sweep of sweep_half_l2.hip — query tiles of 16 (4 / 1 where LDS or the batch is smaller), the corpus re-read per tile
+static int32_t brute_half_l2_dev(vdb_hip_index* ix, const uint16_t* rows16, const float* norms16, bool f16, const QuerySlice& s, hipStream_t st) {
   const uint8_t* alive = search_alive(ix);
   const uint32_t k = s.k;
   ix->last_kernels |= VDB_KERNEL_SWEEP_HALF_L2;
+  if (half_l2_select_takes(ix, s.nq, k)) {
+    ix->last_kernels |= VDB_KERNEL_SELECT_HALF_L2 | (f16 ? VDB_KERNEL_F16 : 0u);
+    for (uint32_t q0 = 0; q0 < s.nq;) {
+      const QuerySlice c = s.sub(q0, std::min<uint32_t>(s.nq - q0, kGemmMaxQueries));
+      const int32_t rc = half_l2_select_dev(ix, rows16, norms16, f16, c, st);
+      if (rc != VDB_OK) return rc;
+      q0 += c.nq;
+    }
+    return VDB_OK;
+  }
   for (uint32_t q0 = 0; q0 < s.nq;) {
     const uint32_t rem = s.nq - q0;
     int B = rem > 4 ? 16 : (rem > 1 ? 4 : 1);
@@ -238,7 +369,7 @@ int32_t brute_bf16_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st, b
   if (s.nq == 0) return VDB_OK;
   if (s.k == 0 || ix->n_rows == 0) return zero_results(s, st);
   const HalfImage h{f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>(), f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>(), f16};
-  if (ix->metric == VDB_EUCLIDEAN) return brute_half_l2_dev(ix, h.rows16, f16, s, st);
+  if (ix->metric == VDB_EUCLIDEAN) return brute_half_l2_dev(ix, h.rows16, h.norms16, f16, s, st);
   if (f16) ix->last_kernels |= VDB_KERNEL_F16;
   for (uint32_t q0 = 0; q0 < s.nq;) {
     const QuerySlice rest = s.sub(q0, s.nq - q0);

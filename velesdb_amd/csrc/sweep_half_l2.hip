@@ -26,6 +26,7 @@
 
 #include "vdb_device.hpp"
 #include "vdb_filter_route.hpp"
+#include "vdb_half_l2.hpp"
 #include "vdb_kernels.hpp"
 
 namespace vdb {
@@ -39,25 +40,7 @@ struct HalfL2Args {
   uint32_t n_rows, dim, nq, k;
 };
 
-template <bool F16>
-__device__ __forceinline__ float half_round(float x) {  // the value a half copy holds, back in f32
-  if (F16) return (float)(_Float16)x;  // v_cvt_f16_f32 (round to nearest even, overflow to inf, subnormals kept) and back
-  uint32_t u = __float_as_uint(x);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return __uint_as_float(((u >> 16) | 0x0040u) << 16);  // NaN stays NaN (quiet)
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return __uint_as_float(u & 0xFFFF0000u);
-}
-// the two half values of one dword, lower address first
-template <bool F16>
-__device__ __forceinline__ void unpack2(uint32_t w, float& lo, float& hi) {
-  if (F16) {
-    lo = (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu));
-    hi = (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
-  } else {
-    lo = __uint_as_float(w << 16);
-    hi = __uint_as_float(w & 0xFFFF0000u);
-  }
-}
+// (half_round, unpack2 / unpack8 and the chunk of the declared chain, half_l2_chunk: vdb_half_l2.hpp — shared with the selection path)
 
 // The body is shared by the sweep over all rows and the LISTED one (filtered search over a half image): there position p of
 // the filter's ascending row list stands where row p stood — the row pointer comes through the list, positions past `count` re-read the
@@ -129,10 +112,7 @@ __device__ __forceinline__ void half_l2_sweep_body(const HalfL2Args& a, const ui
 #pragma unroll
           for (int b = 0; b < B; b++) {
             const float* qp = qs + (size_t)b * qlen + (size_t)c * 8;
-            float s = acc[(r0 + rr) * B + b];
-            s = chain4<kOpL2>(s, ld4(qp), x0);
-            s = chain4<kOpL2>(s, ld4(qp + 4), x1);
-            acc[(r0 + rr) * B + b] = s;
+            acc[(r0 + rr) * B + b] = half_l2_chunk(acc[(r0 + rr) * B + b], qp, x0, x1);
             if (B > 1 && (b & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // (keeps the query reads of a step from being hoisted together)
           }
         }
@@ -169,6 +149,19 @@ __device__ __forceinline__ void half_l2_sweep_body(const HalfL2Args& a, const ui
 template <bool F16, int B>
 __global__ __launch_bounds__(256, 3) void sweep_topk_half_l2(HalfL2Args a) {
   half_l2_sweep_body<F16, B, false>(a, nullptr, 0u, 0u);
+}
+// Many 16-query tiles in ONE launch (the seed and the fallback of the selection path, sweep_half_l2_select.hip): block row
+// blockIdx.y sweeps a.n_rows rows for queries [16 y, 16 y + 16) of a.queries, lists at part_keys[query][gridDim.x][k].  qcount (nullable):
+// a device word — only the first *qcount queries exist (the fallback's gathered queries; the other block rows leave at once).
+template <bool F16>
+__global__ __launch_bounds__(256, 3) void sweep_topk_half_l2_tiles(HalfL2Args a, const uint32_t* __restrict__ qcount) {
+  const uint32_t nq_all = qcount ? min((uint32_t)__builtin_amdgcn_readfirstlane((int)*qcount), a.nq) : a.nq;
+  const uint32_t q0 = blockIdx.y * 16u;
+  if (q0 >= nq_all) return;  // (block-uniform, before the first barrier)
+  a.nq = min(16u, nq_all - q0);
+  a.queries += (size_t)q0 * a.q_stride;
+  a.part_keys += (size_t)q0 * gridDim.x * a.k;
+  half_l2_sweep_body<F16, 16, false>(a, nullptr, 0u, 0u);
 }
 // the sweep over a filter's ascending row list; a.n_rows is not read
 struct HalfL2ListedArgs {
@@ -229,6 +222,28 @@ hipError_t launch_sweep_half_l2(bool f16, int B, const uint16_t* rows, uint64_t 
   HalfL2Args a{rows, alive, queries, part_keys, row_stride, q_stride, n_rows, dim, nq, k};
   const size_t lds = sweep_half_l2_lds_bytes(B, k, dim);
   return f16 ? launch_half_l2_b<true>(B, a, blocks, lds, st) : launch_half_l2_b<false>(B, a, blocks, lds, st);
+}
+
+template <bool F16>
+static hipError_t launch_half_l2_tiles_t(const HalfL2Args& a, const uint32_t* qcount, int blocks, size_t lds, hipStream_t st) {
+  static bool done = false;
+  if (lds > 64 * 1024 && !done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_topk_half_l2_tiles<F16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024);
+    if (e != hipSuccess) return e;
+    done = true;
+  }
+  hipLaunchKernelGGL((sweep_topk_half_l2_tiles<F16>), dim3(blocks, (a.nq + 15) / 16), dim3(256), lds, st, a, qcount);
+  return hipGetLastError();
+}
+// nq queries (any number) in tiles of 16, one launch; part_keys: [nq][blocks][k]; qcount: see the kernel
+hipError_t launch_sweep_half_l2_tiles(bool f16, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,
+                                      uint64_t q_stride, uint64_t* part_keys, uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks,
+                                      const uint32_t* qcount, hipStream_t st) {
+  const size_t lds = sweep_half_l2_lds_bytes(16, k, dim);
+  if (row_stride % 8 != 0 || row_stride < dim || nq == 0 || n_rows == 0 || lds > 160 * 1024) return hipErrorInvalidValue;
+  HalfL2Args a{rows, alive, queries, part_keys, row_stride, q_stride, n_rows, dim, nq, k};
+  return f16 ? launch_half_l2_tiles_t<true>(a, qcount, blocks, lds, st) : launch_half_l2_tiles_t<false>(a, qcount, blocks, lds, st);
 }
 
 template <bool F16, int B>

@@ -274,6 +274,41 @@ struct ListedGroupItem;
 hipError_t launch_sweep_half_l2_listed_groups(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,
                                               uint64_t q_stride, uint64_t* part_keys, uint32_t dim, uint32_t k, const ListedGroupItem* items,
                                               uint32_t n_items, uint32_t lists_per_q, hipStream_t st);
+// ... nq queries (any number) in tiles of 16 in ONE launch (sweep_topk_half_l2_tiles): part_keys [nq][blocks][k]; qcount (nullable): a
+// device word, only the first *qcount queries exist.  The 16-query LDS tile must fit 160 KiB (sweep_half_l2_lds_bytes(16, k, dim))
+hipError_t launch_sweep_half_l2_tiles(bool f16, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,
+                                      uint64_t q_stride, uint64_t* part_keys, uint32_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int blocks,
+                                      const uint32_t* qcount, hipStream_t st);
+// The matrix-core selection path of those batches (sweep_half_l2_select.hip), behind the seed sweep and its merge:
+// bounds + query image, selection, re-score.  Queries that need the fallback are left listed (ctl[1] = their number, qmap / qslot,
+// their f32 rows gathered in qgath in list order, flags[q] = 1); every other query's answer is in out_*.
+struct HalfL2SelectBatch {
+  bool f16;
+  const uint16_t* rows;       // the half image [n_rows (+ kRowSlack)][row_stride], row_stride == dim, dim % 64 == 0
+  const float* norms;         // norms of the rounded rows
+  const uint8_t* alive;       // nullable
+  const uint64_t* ext_ids;
+  const float* queries;       // [nq][q_stride] f32
+  const uint64_t* seed_rows;  // [nq][k] internal rows of the seed's merged answer
+  const uint32_t* seed_n;     // [nq]
+  uint32_t* ctl;              // [2] control words: ctl[1] = the fallback's count (cleared here)
+  uint16_t* q16;              // [nq padded to 128][row_stride]
+  float* tau;                 // [padded]
+  uint32_t* cnt;              // [padded]
+  uint32_t* flags;            // [nq]
+  uint32_t* lists;            // [nq][kHalfL2ListCap]
+  uint32_t* qmap;             // [nq]
+  uint32_t* qslot;            // [nq]
+  float* qgath;               // [nq][row_stride]
+  uint64_t* out_ids;
+  float* out_scores;
+  uint32_t* out_n;
+  uint64_t row_stride, q_stride;
+  uint32_t n_rows, dim, nq, k;
+  int n_cus;
+};
+size_t half_l2_select_scratch_words(uint32_t nq);  // nq padded to whole 128-query tiles
+hipError_t launch_half_l2_select_batch(const HalfL2SelectBatch& b, hipStream_t st);
 void launch_merge(bool higher_is_better, const MergeArgs& m, uint32_t nq, hipStream_t st);
 // sweep_listed.hip — filtered exact search: the sweep over a LIST of rows, and the row mask of the other route
 struct ListedArgs {

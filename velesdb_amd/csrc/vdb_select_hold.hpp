@@ -45,6 +45,7 @@ struct SelectHold {
 // the four selectors of one search context; a filtered call copies the set and puts it back (its verdicts are not the handle's)
 struct SelectHolds {
   SelectHold wide{4u}, sel16{2u}, l2{5u}, sq8{3u};
+  SelectHold half_l2{6u};  // Euclidean batches over a half image (select_stage.hip half_l2_select_dev) -> the streaming sweep
   uint64_t call = 0;  // search calls of the context so far (search_dev counts)
 };
 

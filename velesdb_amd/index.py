@@ -53,6 +53,8 @@ MAX_FUSED_VECTORS = 10      # MAX_VECTORS of multi_query_search (collection/sear
 FUSE_MAX_RECORDS = 8192     # records of one group the fusion kernel takes (VDB_FUSE_MAX_RECORDS)
 # hybrid search (HnswIndex.hybrid_search / hybrid_fuse_arrays): the kernel's bit, |V| + |T| of one query (VDB_HYBRID_MAX_RECORDS)
 KERNEL_HYBRID_FUSE = _ffi.VDB_KERNEL_HYBRID_FUSE
+# Euclidean batches over a half image on the matrix cores (next to KERNEL_SWEEP_HALF_L2; selector level 0 keeps the streaming kernel)
+KERNEL_SELECT_HALF_L2 = _ffi.VDB_KERNEL_SELECT_HALF_L2
 HYBRID_MAX_RECORDS = 8192
 # the rows the walks of hybrid_search_batch_filters / multi_query_search_batch_filters take their distances over (enum vdb_walk_rows)
 WALK_ROWS_F32, WALK_ROWS_F16, WALK_ROWS_BF16, WALK_ROWS_INT8 = _ffi.VDB_WALK_ROWS_F32, _ffi.VDB_WALK_ROWS_F16, _ffi.VDB_WALK_ROWS_BF16, _ffi.VDB_WALK_ROWS_INT8
