@@ -343,7 +343,13 @@ int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* idx, const void* f, c
  * half image).  Same bits on both where the bits are declared.  Auto (checked against one measurement): Euclidean over a
  * half image takes the listed kernel iff matched <= 3/4 rows; SQ8 only for calls of at most three queries, with the same cut.  With
  * fewer than 1/16 of the rows allowed the SQ8 selection stage is skipped, as the f32 one.
- * vdb_hip_index_last_kernels: the mode's usual bits, plus VDB_KERNEL_SWEEP_LISTED when a listed kernel ran.
+ * VDB_OPT_FILTER_ROUTE = 3 gives Cosine / DotProduct over a half image a third route, the GATHERED matrix-core tier:
+ * sweep_topk_half_gathered multiplies the filter's rows, gathered by index, with the whole batch (chunks of <= 1 024 queries, any dim,
+ * k while the lists of 16 queries fit the LDS) and reads nothing else of the corpus.  A pair's score bits depend on the row, the query
+ * and dim only; the contract above holds as for the other tiers (tolerance, bit for bit on exact data).  Where that tier has no plan,
+ * and in every other mode and metric, 3 behaves as auto; auto itself never takes the tier.
+ * vdb_hip_index_last_kernels: the mode's usual bits, plus VDB_KERNEL_SWEEP_LISTED when a listed kernel ran; the gathered tier sets
+ * VDB_KERNEL_SWEEP_LISTED | VDB_KERNEL_GEMM_HALF_GATHERED (| VDB_KERNEL_F16).
  * Errors: null arguments and a filter of another handle VDB_ERR_INVALID_ARG; a stale filter VDB_ERR_STATE; a mode whose storage mode or
  * image is not enabled VDB_ERR_STATE, as the plain call; any other mode (VDB_SEARCH_BRUTE has the call above), multi-device handles and
  * process-group members VDB_ERR_UNSUPPORTED.  The outputs are untouched on error.  The call never goes through the combining front,
@@ -400,6 +406,8 @@ int32_t vdb_hip_index_search_batch_filters(vdb_hip_index* idx, void** filters, u
  * one after another through the mode's own dispatch, the unfiltered queries together as one job of the plain mode call.  A call whose
  * queries all name ONE filter runs vdb_hip_index_search_batch_filtered_mode itself: the same launches, the same
  * vdb_hip_index_last_kernels.
+ * Under VDB_OPT_FILTER_ROUTE = 3 a Cosine / DotProduct group over a half image runs the gathered matrix-core tier, one group at a time
+ * (the one-filter call's launches; VDB_KERNEL_GEMM_HALF_GATHERED): there a query's bits do not depend on its group either.
  * vdb_hip_index_last_kernels: the mode's usual bits, plus VDB_KERNEL_SWEEP_LISTED_GROUPS when a grouped launch ran;
  * vdb_hip_index_last_filters_exact_plan reports this call's plan too.
  * The call leaves the handle's adaptive selection state (the hold counters of the selection stages, the verdict sequence) as it found
@@ -772,7 +780,9 @@ enum vdb_option {
   VDB_OPT_COMBINE_WINDOW_US = 6,
   VDB_OPT_COMBINE_INFLIGHT = 7,
   /* route of vdb_hip_index_search_batch_filtered: <= 0 = auto (the rule stated there), 1 = the listed sweep wherever the metric has
-   * it, 2 = mask substitution.  Like every option it never changes a result. */
+   * it, 2 = mask substitution, 3 = the gathered matrix-core tier of vdb_hip_index_search_batch_filtered_mode wherever its plan exists
+   * (Cosine / DotProduct over a half image) and auto everywhere else — every other mode and metric, the f32 call, the graph calls.
+   * Like every option it never changes a result where the bits are declared. */
   VDB_OPT_FILTER_ROUTE = 8,
   VDB_OPT_COUNT_ = 9
 };
@@ -896,6 +906,10 @@ enum vdb_kernel_bit {
  * such batches on the streaming kernel.  Written as a shift: tests/test_filters_modes_cpu.py pins VDB_KERNEL_HYBRID_FUSE as the largest
  * bit among the decimal ones, tests/test_half_l2_bound_cpu.py holds the bindings to this one. */
 #define VDB_KERNEL_SELECT_HALF_L2 (1u << 23)
+/* ... and one more, a shift as well: sweep_topk_half_gathered ran — the gathered matrix-core tier of a filtered Cosine / DotProduct call
+ * over a half image (vdb_hip_index_search_batch_filtered_mode / _filters_mode under VDB_OPT_FILTER_ROUTE = 3).  Set NEXT TO
+ * VDB_KERNEL_SWEEP_LISTED — only the filter's rows were read — and VDB_KERNEL_F16 for the f16 instances. */
+#define VDB_KERNEL_GEMM_HALF_GATHERED (1u << 24)
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same
  * context a moment later does not change it. */

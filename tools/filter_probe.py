@@ -480,19 +480,30 @@ def storage_leg():
                         else:  # (a probe that times wrong answers measures nothing)
                             assert np.array_equal(ref[0], got[0]), (mname, nq, sel, name)
                             assert not declared or np.array_equal(ref[1].view(np.uint32), got[1].view(np.uint32)), (mname, nq, sel, name)
+                    # the gathered matrix-core tier (route 3): Cosine / DotProduct over a half image only
+                    gathered = a.storage in ("f16", "bf16") and mname in ("cosine", "dot")
+                    if gathered:
+                        ix.set_option(va.OPT_FILTER_ROUTE, va.FILTER_ROUTE_GATHERED)
+                        got = filtered(Q, a.k, flt)
+                        row["gathered_kernel_ran"] = bool(ix.last_kernels() & va.KERNEL_GEMM_HALF_GATHERED)
+                        row["gathered_ids_equal_mask"] = bool(np.array_equal(ref[0], got[0]))
 
                     def call(route):
                         def fn():
                             ix.set_option(va.OPT_FILTER_ROUTE, route)
                             filtered(Q, a.k, flt)
                         return fn
-                    res = measure_many([lambda: plain(Q, a.k), call(va.FILTER_ROUTE_LISTED), call(va.FILTER_ROUTE_MASK), call(va.FILTER_ROUTE_AUTO)])
-                    for name, (ms, sp) in zip(("unfiltered", "listed", "mask", "auto"), res):
+                    res = measure_many([lambda: plain(Q, a.k), call(va.FILTER_ROUTE_LISTED), call(va.FILTER_ROUTE_MASK), call(va.FILTER_ROUTE_AUTO)] +
+                                       ([call(va.FILTER_ROUTE_GATHERED)] if gathered else []))
+                    for name, (ms, sp) in zip(("unfiltered", "listed", "mask", "auto", "gathered"), res):
                         row[name + "_ms"], row[name + "_spread"] = ms, sp
                     best = min(("listed", "mask"), key=lambda r: row[r + "_ms"])
                     row["better"] = best
                     row["auto_over_better"] = row["auto_ms"] / row[best + "_ms"]
                     row["listed_over_unfiltered"] = row["listed_ms"] / row["unfiltered_ms"]
+                    if gathered:
+                        row["gathered_over_mask"] = row["gathered_ms"] / row["mask_ms"]
+                        row["gathered_over_unfiltered"] = row["gathered_ms"] / row["unfiltered_ms"]
                     rows_out.append(row)
                     print(json.dumps(row), flush=True)
         ix.close()

@@ -17,7 +17,8 @@ from .index import KERNEL_SELECT_HALF_L2  # noqa: F401
 from .index import KERNEL_HNSW_HALF, MODE_HNSW_BF16, MODE_HNSW_F16  # noqa: F401
 from .index import KERNEL_FILTER_RANK, KERNEL_HALF_RESCORE, KERNEL_HNSW_FILTERED, ROUTE_AUTO, ROUTE_EXACT, ROUTE_WALK  # noqa: F401
 from .index import KERNEL_SWEEP_LISTED_GROUPS  # noqa: F401
-from .index import (FILTER_ROUTE_AUTO, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK, KERNEL_SWEEP_LISTED, OPT_FILTER_ROUTE, Filter)  # noqa: F401
+from .index import (FILTER_ROUTE_AUTO, FILTER_ROUTE_GATHERED, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK, KERNEL_GEMM_HALF_GATHERED,  # noqa: F401
+                    KERNEL_SWEEP_LISTED, OPT_FILTER_ROUTE, Filter, half_gather_plan)
 from .index import FUSE_MAX_RECORDS, FusionError, FusionStrategy, KERNEL_FUSE, MAX_FUSED_VECTORS, fuse_arrays, fuse_groups  # noqa: F401
 from .index import HYBRID_MAX_RECORDS, KERNEL_HYBRID_FUSE, hybrid_fuse_arrays  # noqa: F401
 from .index import (WALK_ROWS_BF16, WALK_ROWS_BF16_RESCORE, WALK_ROWS_F16, WALK_ROWS_F16_RESCORE, WALK_ROWS_F32,  # noqa: F401

@@ -868,7 +868,7 @@ static int32_t brute_filtered_dev(vdb_hip_index* ix, const QuerySlice& s, hipStr
   const bool mode_m = sweep_mode_m(ix, k);
   ListedPlan lp;
   if (!is_bits_metric(ix->metric)) sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, s.nq, ix->n_cus, &lp);
-  if (filter_route(opt_value(ix, VDB_OPT_FILTER_ROUTE), lp.blocks > 0, f->count, ix->n_rows, s.nq) == kFilterRouteListed) {
+  if (filter_route(filter_route_opt(opt_value(ix, VDB_OPT_FILTER_ROUTE)), lp.blocks > 0, f->count, ix->n_rows, s.nq) == kFilterRouteListed) {
     for (uint32_t q0 = 0; q0 < s.nq;) {
       sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, s.nq - q0, ix->n_cus, &lp);
       const QuerySlice c = s.sub(q0, lp.nq_pass);
@@ -942,6 +942,13 @@ static int32_t filtered_mode_check(const vdb_hip_index* ix, int32_t mode) {
   }
   return VDB_OK;
 }
+// VDB_OPT_FILTER_ROUTE = 3: Cosine / DotProduct over a half image takes the gathered matrix-core tier wherever its plan
+// exists; every other mode, metric and shape sees the value as auto (filter_route_opt)
+static bool half_gathered_takes(const vdb_hip_index* ix, int32_t mode, int64_t opt_route, uint64_t count, uint32_t nq, uint32_t k) {
+  if (opt_route != kFilterRouteOptGathered || (mode != VDB_SEARCH_BRUTE_BF16 && mode != VDB_SEARCH_BRUTE_F16)) return false;
+  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT) return false;
+  return half_gather_plan(ix->dim, k, count, nq, ix->n_cus).blocks > 0;
+}
 static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const QuerySlice& s, hipStream_t st) {
   const RowFilter* f = ix->flt;
   const uint32_t nq = s.nq, k = s.k;
@@ -950,9 +957,11 @@ static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const Qu
   if (rcm != VDB_OK) return rcm;
   if (nq == 0) return VDB_OK;
   if (f->count == 0 || k == 0) return zero_results(s, st);  // the empty filter: no row can answer
+  const int64_t opt_route = opt_value(ix, VDB_OPT_FILTER_ROUTE);
+  if (half_gathered_takes(ix, mode, opt_route, f->count, nq, k)) return brute_half_gathered_dev(ix, f16, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
   bool listed_ok = false;
   if (filter_mode_has_listed(mode, ix->metric)) listed_ok = mode_listed_plan(half, ix->dim, k, f->count, nq, ix->n_cus).blocks > 0;
-  if (filter_mode_route(opt_value(ix, VDB_OPT_FILTER_ROUTE), mode, ix->metric, f->count, ix->n_rows, nq, listed_ok) == kFilterRouteListed) {
+  if (filter_mode_route(filter_route_opt(opt_route), mode, ix->metric, f->count, ix->n_rows, nq, listed_ok) == kFilterRouteListed) {
     if (half) return brute_half_l2_listed_dev(ix, f16, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
     ix->last_kernels |= VDB_KERNEL_SQ8;
     return brute_sq8_listed_dev(ix, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
@@ -1346,8 +1355,8 @@ int32_t search_filters_mode_to_device(vdb_hip_index* ix, const RowFilter* const*
   auto list_of = [&](uint32_t f) { return (const uint32_t*)filters[f]->list.as<uint32_t>(); };
   auto occ_of = [&](int B, uint32_t nq_max) { return (uint32_t)listed_occupancy(mode_m, B, mode_m ? plan_of(nq_max).lds : 0); };
   const int64_t opt_route = opt_value(ix, VDB_OPT_FILTER_ROUTE);
-  const std::vector<FxGroup> groups = f32 ? filters_exact_groups(fq, nq, n_filters, opt_route, ix->n_rows, count_of, pass_of)
-                                          : filters_mode_groups(fq, nq, n_filters, opt_route, mode, ix->metric, ix->n_rows, ix->dim, k, ix->n_cus, count_of);
+  const std::vector<FxGroup> groups = f32 ? filters_exact_groups(fq, nq, n_filters, filter_route_opt(opt_route), ix->n_rows, count_of, pass_of)
+                                          : filters_mode_groups(fq, nq, n_filters, filter_route_opt(opt_route), mode, ix->metric, ix->n_rows, ix->dim, k, ix->n_cus, count_of);
   // rows of the call
   uint32_t n_listed = 0, extra = 0;
   for (const FxGroup& g : groups) {
@@ -1483,7 +1492,10 @@ int32_t search_filters_mode_to_device(vdb_hip_index* ix, const RowFilter* const*
         VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_scores + (size_t)r0 * k), 0x7FC00000, (size_t)nq_g * k, st));
       } else {
         ix->flt = filters[g.filter];
-        rg = brute_masked_dev(ix, s_g, st, mode);
+        if (half_gathered_takes(ix, mode, opt_route, ix->flt->count, nq_g, k))  // (one group at a time: the one-filter call's launches)
+          rg = brute_half_gathered_dev(ix, mode == VDB_SEARCH_BRUTE_F16, ix->flt->list.as<uint32_t>(), (uint32_t)ix->flt->count, s_g, st);
+        else
+          rg = brute_masked_dev(ix, s_g, st, mode);
         ix->flt = nullptr;
       }
       if (rg != VDB_OK) return rg;
@@ -1626,7 +1638,7 @@ int32_t vdb_hip_index_set_option(vdb_hip_index* ix, int32_t option, int64_t valu
           v = (int32_t)value;
           break;
         case VDB_OPT_FILTER_ROUTE:
-          if (value > 2) return fail(VDB_ERR_INVALID_ARG, "filter route: 0 (auto), 1 (listed sweep) or 2 (mask substitution)");
+          if (value > 3) return fail(VDB_ERR_INVALID_ARG, "filter route: 0 (auto), 1 (listed sweep), 2 (mask substitution) or 3 (gathered matrix-core tier)");
           v = (int32_t)value;
           break;
         default: v = value ? 1 : 0; break;

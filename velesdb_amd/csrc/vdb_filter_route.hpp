@@ -6,7 +6,8 @@
 // and the listed passes of a filtered exact call over the SQ8 / Binary / half images (vdb_hip_index_search_batch_filtered_mode),
 // and the groups and grouped launches of such a call with one filter per query (vdb_hip_index_search_batch_filters_mode),
 // and the two phases of a fused search with one filter per query (vdb_hip_index_hybrid_search_filters /
-// vdb_hip_index_multi_query_search_filters).
+// vdb_hip_index_multi_query_search_filters), and the launch plan of the gathered matrix-core tier of Cosine / DotProduct
+// over a half image (VDB_OPT_FILTER_ROUTE = 3; tests/half_gather_plan_model.cpp).
 // Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_mode_route_model.cpp,
 // tests/filter_graph_route_model.cpp, tests/filters_plan_model.cpp, tests/listed_groups_plan_model.cpp,
 // tests/mode_groups_plan_model.cpp and tests/hybrid_filters_plan_model.cpp compile it alone and walk its boundaries.
@@ -19,7 +20,7 @@ namespace vdb {
 
 enum FilterRoute : int { kFilterRouteDense = 0, kFilterRouteListed = 1 };
 
-// VDB_OPT_FILTER_ROUTE: <= 0 auto, 1 the listed sweep wherever it exists, 2 mask substitution.
+// VDB_OPT_FILTER_ROUTE: <= 0 auto, 1 the listed sweep wherever it exists, 2 mask substitution (3: filter_route_opt, below).
 // `listed_available`: the metric has a listed kernel (Cosine / DotProduct / Euclidean) and its k-lists fit the LDS.
 // Auto is a STATED GUESS, not a measurement: listed iff count <= n_rows / 4 and count * nq <= 8 * n_rows.  The exact path takes a
 // flat 0.44-0.53 ms for 16-256 queries at 1 M x 768 whatever the mask; the listed kernel reads count rows once per pass of <= 16
@@ -115,6 +116,55 @@ static inline ModeListedPlan mode_listed_plan(bool half, uint32_t dim, uint32_t 
   p.B = B;
   p.nq_pass = nq_left < (uint32_t)B ? nq_left : (uint32_t)B;
   p.lds = lds;
+  return p;
+}
+
+// ---- the gathered matrix-core tier of Cosine / DotProduct over a half image (sweep_half_gathered.hip) ----
+// VDB_OPT_FILTER_ROUTE = 3: that tier wherever its plan exists; everywhere else the value behaves as auto does, so the route
+// functions above are asked with filter_route_opt(value).
+constexpr int64_t kFilterRouteOptGathered = 3;
+static inline int64_t filter_route_opt(int64_t opt) { return opt == kFilterRouteOptGathered ? 0 : opt; }
+// One launch of sweep_topk_half_gathered: a chunk of <= 1 024 queries in query tiles of TN (128 from 64 queries up, else 16; 16 as
+// well where the k-lists of 128 queries do not fit), the list's 64-row tiles cut into `spans` contiguous runs of per_block tiles;
+// grid = spans x qtiles, no block without a tile.  LDS: two slab buffers of 64-element slices (64 rows + TN queries, 128 B a line)
+// | TN k-lists | counters and locks | three tiles' row indices and norms — nothing in it depends on dim.
+// blocks == 0: no plan (count, k or nq zero, a list past 2^32 - 1 rows, or the lists of even 16 queries do not fit 160 KiB).
+constexpr uint32_t kHgTileRows = 64, kHgMaxQueries = 1024;
+constexpr uint64_t kHgScratchCap = (uint64_t)256 << 20;  // partial keys [nq][spans][k]: the cap of the grouped calls
+static constexpr uint64_t hg_slab_bytes(int TN) { return 2ull * ((uint64_t)kHgTileRows * 128 + (uint64_t)TN * 128); }
+static constexpr uint64_t hg_lds_bytes(int TN, uint32_t k) {
+  return (hg_slab_bytes(TN) + (uint64_t)TN * k * 8 + (uint64_t)TN * 8 + 3ull * kHgTileRows * 8 + 15) & ~(uint64_t)15;
+}
+struct HalfGatherPlan {
+  int blocks = 0;  // spans x qtiles
+  int TN = 0;
+  uint32_t nq_chunk = 0, qtiles = 0, per_block = 0, spans = 0;
+  uint64_t lds = 0;
+};
+static inline HalfGatherPlan half_gather_plan(uint32_t dim, uint32_t k, uint64_t count, uint32_t nq_left, int n_cus) {
+  (void)dim;  // (K-sliced operands: no dim class, no refusal)
+  HalfGatherPlan p;
+  if (count == 0 || k == 0 || nq_left == 0 || count > 0xFFFFFFFFull) return p;
+  const uint32_t nq = nq_left < kHgMaxQueries ? nq_left : kHgMaxQueries;
+  int TN = nq >= 64 ? 128 : 16;
+  if (hg_lds_bytes(TN, k) > kFmLdsBudget) TN = 16;
+  const uint64_t lds = hg_lds_bytes(TN, k);
+  if (lds > kFmLdsBudget) return p;
+  const uint64_t qtiles = ((uint64_t)nq + TN - 1) / TN, ntiles = (count + kHgTileRows - 1) / kHgTileRows;
+  uint64_t per_cu = kFmLdsBudget / lds, cap = TN == 128 ? 2 : 4;  // (four-wave blocks at >= 2 / >= 4 waves per SIMD)
+  if (per_cu > cap) per_cu = cap;
+  uint64_t spans = (uint64_t)(n_cus > 0 ? n_cus : 1) * per_cu / qtiles;
+  const uint64_t by_scratch = kHgScratchCap / ((uint64_t)nq * k * 8);
+  if (spans > by_scratch) spans = by_scratch;
+  if (spans > ntiles) spans = ntiles;
+  if (spans < 1) spans = 1;
+  p.per_block = (uint32_t)((ntiles + spans - 1) / spans);
+  p.spans = (uint32_t)((ntiles + p.per_block - 1) / p.per_block);
+  p.qtiles = (uint32_t)qtiles;
+  p.nq_chunk = nq;
+  p.TN = TN;
+  p.lds = lds;
+  p.blocks = (int)(p.spans * p.qtiles);
   return p;
 }
 

@@ -336,6 +336,7 @@ int32_t search_filtered_mode_to_device(vdb_hip_index* ix, const RowFilter* f, in
 struct QuerySlice;  // vdb_sweep_pass.hpp: the queries a pass answers and where their answers go
 int32_t brute_sq8_listed_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
 int32_t brute_half_l2_listed_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
+int32_t brute_half_gathered_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
 // the filter belongs to this handle (generation) and to its present row numbering (row_epoch): anything else is an error
 int32_t filter_check(vdb_hip_index* ix, const RowFilter* f);
 // one optional filter per query on the exact sweep (index.hip): filters[n_filters] handles (checked inside, all of them

@@ -274,6 +274,13 @@ struct ListedGroupItem;
 hipError_t launch_sweep_half_l2_listed_groups(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,
                                               uint64_t q_stride, uint64_t* part_keys, uint32_t dim, uint32_t k, const ListedGroupItem* items,
                                               uint32_t n_items, uint32_t lists_per_q, hipStream_t st);
+// the gathered matrix-core tier of Cosine / DotProduct over a half image (sweep_half_gathered.hip): one launch over the
+// filter's ascending row list for a chunk of <= 1 024 rounded queries (queries16 / qnorms: launch_round_queries_bf16 /
+// launch_query_norms_bf16); the plan: half_gather_plan, vdb_filter_route.hpp; part_keys [nq][p.spans][k]
+struct HalfGatherPlan;
+hipError_t launch_sweep_half_gathered(int metric, bool f16, const HalfGatherPlan& p, const uint16_t* rows, uint64_t row_stride, const float* norms,
+                                      const uint8_t* alive, const uint32_t* list, uint32_t count, const uint16_t* queries16, uint64_t q_stride,
+                                      const float* qnorms, uint64_t* part_keys, uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st);
 // ... nq queries (any number) in tiles of 16 in ONE launch (sweep_topk_half_l2_tiles): part_keys [nq][blocks][k]; qcount (nullable): a
 // device word, only the first *qcount queries exist.  The 16-query LDS tile must fit 160 KiB (sweep_half_l2_lds_bytes(16, k, dim))
 hipError_t launch_sweep_half_l2_tiles(bool f16, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,

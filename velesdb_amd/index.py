@@ -38,7 +38,7 @@ KERNEL_HNSW_HALF = 1 << 15
 # filtered exact search (HnswIndex.create_filter / search_batch_brute_force_filtered): the route option (0 auto, 1 listed sweep,
 # 2 mask substitution) and the listed sweep's kernel bit
 OPT_FILTER_ROUTE = _ffi.VDB_OPT_FILTER_ROUTE
-FILTER_ROUTE_AUTO, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK = 0, 1, 2
+FILTER_ROUTE_AUTO, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK, FILTER_ROUTE_GATHERED = 0, 1, 2, 3
 KERNEL_SWEEP_LISTED = _ffi.VDB_KERNEL_SWEEP_LISTED
 # filtered graph search (HnswIndex.search_batch_filtered_graph): the route of a call / of a query, and the two kernel families
 ROUTE_AUTO, ROUTE_WALK, ROUTE_EXACT = 0, 1, 2
@@ -55,6 +55,27 @@ FUSE_MAX_RECORDS = 8192     # records of one group the fusion kernel takes (VDB_
 KERNEL_HYBRID_FUSE = _ffi.VDB_KERNEL_HYBRID_FUSE
 # Euclidean batches over a half image on the matrix cores (next to KERNEL_SWEEP_HALF_L2; selector level 0 keeps the streaming kernel)
 KERNEL_SELECT_HALF_L2 = _ffi.VDB_KERNEL_SELECT_HALF_L2
+# the gathered matrix-core tier of filtered Cosine / DotProduct calls over a half image (FILTER_ROUTE_GATHERED; next to KERNEL_SWEEP_LISTED)
+KERNEL_GEMM_HALF_GATHERED = _ffi.VDB_KERNEL_GEMM_HALF_GATHERED
+
+
+def half_gather_plan(dim, k, count, nq_left, n_cus):
+    """The launch plan of that tier: csrc/vdb_filter_route.hpp half_gather_plan restated (tests/test_half_gathered_cpu.py holds the two
+    together).  None where the tier has no plan and FILTER_ROUTE_GATHERED behaves as auto; else tn, nq_chunk, qtiles, per_block, spans, lds."""
+    if count == 0 or k == 0 or nq_left == 0 or count > 0xFFFFFFFF:
+        return None
+    budget, nq = 160 * 1024, min(nq_left, 1024)
+
+    def lds_of(tn):
+        return (2 * (64 * 128 + tn * 128) + tn * k * 8 + tn * 8 + 3 * 64 * 8 + 15) & ~15
+    tn = 128 if nq >= 64 and lds_of(128) <= budget else 16
+    if lds_of(tn) > budget:
+        return None
+    qtiles, ntiles = -(-nq // tn), -(-count // 64)
+    spans = max(1, n_cus) * min(budget // lds_of(tn), 2 if tn == 128 else 4) // qtiles
+    spans = max(1, min(spans, (256 << 20) // (nq * k * 8), ntiles))
+    per_block = -(-ntiles // spans)
+    return dict(tn=tn, nq_chunk=nq, qtiles=qtiles, per_block=per_block, spans=-(-ntiles // per_block), lds=lds_of(tn))
 HYBRID_MAX_RECORDS = 8192
 # the rows the walks of hybrid_search_batch_filters / multi_query_search_batch_filters take their distances over (enum vdb_walk_rows)
 WALK_ROWS_F32, WALK_ROWS_F16, WALK_ROWS_BF16, WALK_ROWS_INT8 = _ffi.VDB_WALK_ROWS_F32, _ffi.VDB_WALK_ROWS_F16, _ffi.VDB_WALK_ROWS_BF16, _ffi.VDB_WALK_ROWS_INT8
