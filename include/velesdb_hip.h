@@ -325,7 +325,10 @@ void vdb_hip_filter_destroy(void* f);
  * DotProduct / Euclidean; VDB_KERNEL_SWEEP_LISTED) and MASK SUBSTITUTION (the filter AND the live flags become the call's row mask
  * and every tier of the exact path serves it).  VDB_OPT_FILTER_ROUTE picks; auto = listed iff matched <= rows / 4 and
  * matched * nq <= 8 * rows (a stated guess, not a measurement: DESIGN 4.1g).  A filtered call never shares a launch with another
- * call (it does not go through the combining front) and leaves the handle's adaptive selection state as it found it. */
+ * call (it does not go through the combining front) and leaves the handle's adaptive selection state as it found it.
+ * Hamming / Jaccard have no listed sweep; VDB_OPT_FILTER_ROUTE = 3 gives them the gathered FOUR-BIT tier (DESIGN 4.1t;
+ * sweep_topk_bits_gathered over the filter's packed rows, stated at the mode call below) wherever its plan exists: the same bits,
+ * VDB_KERNEL_BITS | VDB_KERNEL_SWEEP_LISTED | VDB_KERNEL_BITS_GATHERED.  Auto never takes it; for the three float metrics 3 is auto. */
 int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* idx, const void* f, const float* queries_rowmajor, uint32_t nq,
                                             uint32_t k, int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
 /* The same over the SQ8 codes, the sign bits or a half image of the rows: the reference's search_with_filter works
@@ -350,6 +353,10 @@ int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* idx, const void* f, c
  * and in every other mode and metric, 3 behaves as auto; auto itself never takes the tier.
  * vdb_hip_index_last_kernels: the mode's usual bits, plus VDB_KERNEL_SWEEP_LISTED when a listed kernel ran; the gathered tier sets
  * VDB_KERNEL_SWEEP_LISTED | VDB_KERNEL_GEMM_HALF_GATHERED (| VDB_KERNEL_F16).
+ * Under the same value VDB_SEARCH_BRUTE_BINARY takes the gathered FOUR-BIT tier: sweep_topk_bits_gathered reads the PACKED
+ * sign bits of the filter's rows (dim / 8 bytes a row, no four-bit image of the rows is built or read), expands them to E2M1 nibbles on
+ * the way into LDS and multiplies them with the whole batch on v_mfma_scale_f32_16x16x128_f8f6f4 — the same bits as mask substitution
+ * (exact integers); VDB_KERNEL_BITS | VDB_KERNEL_SWEEP_LISTED | VDB_KERNEL_BITS_GATHERED, never VDB_KERNEL_BITS_GEMM.
  * Errors: null arguments and a filter of another handle VDB_ERR_INVALID_ARG; a stale filter VDB_ERR_STATE; a mode whose storage mode or
  * image is not enabled VDB_ERR_STATE, as the plain call; any other mode (VDB_SEARCH_BRUTE has the call above), multi-device handles and
  * process-group members VDB_ERR_UNSUPPORTED.  The outputs are untouched on error.  The call never goes through the combining front,
@@ -408,6 +415,8 @@ int32_t vdb_hip_index_search_batch_filters(vdb_hip_index* idx, void** filters, u
  * vdb_hip_index_last_kernels.
  * Under VDB_OPT_FILTER_ROUTE = 3 a Cosine / DotProduct group over a half image runs the gathered matrix-core tier, one group at a time
  * (the one-filter call's launches; VDB_KERNEL_GEMM_HALF_GATHERED): there a query's bits do not depend on its group either.
+ * Likewise a filtered group of the Binary mode — and, in vdb_hip_index_search_batch_filters, of a Hamming / Jaccard index — runs the
+ * gathered four-bit tier under that value (VDB_KERNEL_BITS_GATHERED).
  * vdb_hip_index_last_kernels: the mode's usual bits, plus VDB_KERNEL_SWEEP_LISTED_GROUPS when a grouped launch ran;
  * vdb_hip_index_last_filters_exact_plan reports this call's plan too.
  * The call leaves the handle's adaptive selection state (the hold counters of the selection stages, the verdict sequence) as it found
@@ -782,6 +791,8 @@ enum vdb_option {
   /* route of vdb_hip_index_search_batch_filtered: <= 0 = auto (the rule stated there), 1 = the listed sweep wherever the metric has
    * it, 2 = mask substitution, 3 = the gathered matrix-core tier of vdb_hip_index_search_batch_filtered_mode wherever its plan exists
    * (Cosine / DotProduct over a half image) and auto everywhere else — every other mode and metric, the f32 call, the graph calls.
+   * 3 is also the gathered FOUR-BIT tier of the Binary mode and, in vdb_hip_index_search_batch_filtered itself, of a
+   * Hamming / Jaccard index, wherever that tier's plan exists.
    * Like every option it never changes a result where the bits are declared. */
   VDB_OPT_FILTER_ROUTE = 8,
   VDB_OPT_COUNT_ = 9
@@ -910,6 +921,11 @@ enum vdb_kernel_bit {
  * over a half image (vdb_hip_index_search_batch_filtered_mode / _filters_mode under VDB_OPT_FILTER_ROUTE = 3).  Set NEXT TO
  * VDB_KERNEL_SWEEP_LISTED — only the filter's rows were read — and VDB_KERNEL_F16 for the f16 instances. */
 #define VDB_KERNEL_GEMM_HALF_GATHERED (1u << 24)
+/* ... and its four-bit counterpart, a shift as well: sweep_topk_bits_gathered ran — the gathered matrix-core tier of a filtered call over
+ * packed bits (a Hamming / Jaccard index through vdb_hip_index_search_batch_filtered / _filters, the Binary mode through
+ * vdb_hip_index_search_batch_filtered_mode / _filters_mode; VDB_OPT_FILTER_ROUTE = 3).  Set NEXT TO VDB_KERNEL_BITS and
+ * VDB_KERNEL_SWEEP_LISTED — only the filter's packed rows were read; VDB_KERNEL_BITS_GEMM is NOT set: no four-bit image of the rows. */
+#define VDB_KERNEL_BITS_GATHERED (1u << 25)
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same
  * context a moment later does not change it. */

@@ -65,6 +65,9 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
   (max - min) / median of the blocks of each; whether a listed kernel ran on the forced listed route (Binary and Cosine / DotProduct
   over a half image have none: the column then repeats the mask route); which route auto took.  The routes are held to agree first:
   bit for bit where the mode declares its summation order (SQ8, Binary, Euclidean over a half image), the same ids otherwise.
+  --exact --storage bits --metrics hamming,jaccard: the same leg over a Hamming / Jaccard index's own packed rows
+  (vdb_hip_index_search_batch_filtered).  There and with --storage binary a fifth call goes round, the gathered four-bit tier
+  (FILTER_ROUTE_GATHERED), held to mask substitution's ids and score bits first; gathered_over_mask is its ratio.
 
 Every figure is the median of --repeats blocks, each block the mean over enough calls to last ~--block-ms; the spread is
 (max - min) / median over the blocks.  Not part of the product or the test-suite."""
@@ -96,7 +99,8 @@ p.add_argument("--graph", action="store_true", help="the filtered graph search l
 p.add_argument("--graph-nq", type=int, default=1024)
 p.add_argument("--per-query", type=int, default=0, help="with --graph: F distinct filters per density in one call against F single-filter calls")
 p.add_argument("--exact", action="store_true", help="the exact leg (the default leg; names it next to --storage)")
-p.add_argument("--storage", default="", choices=["", "sq8", "binary", "f16", "bf16"], help="with --exact: the image of the rows the filtered exact call reads")
+p.add_argument("--storage", default="", choices=["", "sq8", "binary", "f16", "bf16", "bits"],
+               help="with --exact: the image of the rows the filtered exact call reads (bits: the packed rows of a --metrics hamming,jaccard index)")
 p.add_argument("--exact-per-query", default="", help="F[,F...]: distinct filters per call of the exact per-query-filters leg")
 p.add_argument("--precision", default="f32", choices=["f32", "f16", "bf16", "int8"], help="with --graph: the rows the filtered walk reads")
 p.add_argument("--ratio", type=int, default=4, help="with --precision int8, or with --rescore: the oversampling ratio")
@@ -111,7 +115,8 @@ if a.storage and (a.graph or not (a.exact or a.exact_per_query)):
     p.error("--storage goes with --exact or --exact-per-query (the exact legs over that image of the rows)")
 dev = torch.device("cuda", 0)
 st = torch.cuda.current_stream().cuda_stream
-METRICS = {"cosine": va.DistanceMetric.Cosine, "euclidean": va.DistanceMetric.Euclidean, "dot": va.DistanceMetric.DotProduct}
+METRICS = {"cosine": va.DistanceMetric.Cosine, "euclidean": va.DistanceMetric.Euclidean, "dot": va.DistanceMetric.DotProduct,
+           "hamming": va.DistanceMetric.Hamming, "jaccard": va.DistanceMetric.Jaccard}
 
 
 def build(metric):
@@ -453,11 +458,13 @@ def storage_leg():
         elif a.storage == "binary":
             ix.set_storage_mode(va.StorageMode.Binary)
             plain, filtered = ix.search_batch_binary, ix.search_batch_filtered_binary
+        elif a.storage == "bits":  # a Hamming / Jaccard index: the f32 call over its own packed rows (bit = x > 0.5)
+            plain, filtered = ix.search_batch_brute_force, ix.search_batch_brute_force_filtered
         else:
             prec = va.VectorPrecision.F16 if a.storage == "f16" else va.VectorPrecision.BF16
             ix.enable_half_precision(prec)
             plain, filtered = (lambda Q, k: ix.search_batch_brute_force_half(Q, k, prec)), (lambda Q, k, f: ix.search_batch_filtered_half(Q, k, f, prec))
-        declared = a.storage in ("sq8", "binary") or mname == "euclidean"  # the mode's summation order is declared: the routes agree bit for bit
+        declared = a.storage in ("sq8", "binary", "bits") or mname == "euclidean"  # the mode's summation order is declared: the routes agree bit for bit
         rng = np.random.default_rng(7)
         for nq in [int(x) for x in a.nq.split(",")]:
             Q = rng.standard_normal((nq, a.dim)).astype(np.float32)
@@ -480,13 +487,15 @@ def storage_leg():
                         else:  # (a probe that times wrong answers measures nothing)
                             assert np.array_equal(ref[0], got[0]), (mname, nq, sel, name)
                             assert not declared or np.array_equal(ref[1].view(np.uint32), got[1].view(np.uint32)), (mname, nq, sel, name)
-                    # the gathered matrix-core tier (route 3): Cosine / DotProduct over a half image only
-                    gathered = a.storage in ("f16", "bf16") and mname in ("cosine", "dot")
+                    # the gathered matrix-core tiers (route 3): Cosine / DotProduct over a half image, packed bits (4.1t)
+                    packed = a.storage in ("binary", "bits")
+                    gathered = packed or (a.storage in ("f16", "bf16") and mname in ("cosine", "dot"))
                     if gathered:
                         ix.set_option(va.OPT_FILTER_ROUTE, va.FILTER_ROUTE_GATHERED)
                         got = filtered(Q, a.k, flt)
-                        row["gathered_kernel_ran"] = bool(ix.last_kernels() & va.KERNEL_GEMM_HALF_GATHERED)
+                        row["gathered_kernel_ran"] = bool(ix.last_kernels() & (va.KERNEL_BITS_GATHERED if packed else va.KERNEL_GEMM_HALF_GATHERED))
                         row["gathered_ids_equal_mask"] = bool(np.array_equal(ref[0], got[0]))
+                        assert not packed or (row["gathered_ids_equal_mask"] and np.array_equal(ref[1].view(np.uint32), got[1].view(np.uint32))), (mname, nq, sel)
 
                     def call(route):
                         def fn():

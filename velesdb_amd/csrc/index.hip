@@ -555,6 +555,11 @@ static void pack_queries_as_rows(const vdb_hip_index* ix, const QuerySlice& s, u
   pa.words = ix->words;
   launch_prep_rows(pa, st);
 }
+// the packed rows of a Hamming / Jaccard index
+static BitsSource packed_rows_source(const vdb_hip_index* ix) {
+  return {ix->bits.as<uint32_t>(), pack_queries_as_rows, ix->metric, ensure_bits_image, &vdb_hip_index::bits_img, &vdb_hip_index::bits_cnt,
+          /*sign_rule=*/0u, higher_is_better_host(ix->metric), "one-launch packed-bit search", "packed-bit sweep launch"};
+}
 
 int32_t brute_bits_dev(vdb_hip_index* ix, const BitsSource& src, const QuerySlice& s, hipStream_t st) {
   const uint32_t k = s.k;
@@ -621,6 +626,40 @@ int32_t brute_bits_dev(vdb_hip_index* ix, const BitsSource& src, const QuerySlic
   const int32_t rc = timed_launch(ix, VDB_KERNEL_BITS, st, src.what_sweep, [&] { return launch_bits_plan(src.metric, bp, ba, rest.nq, st); });
   if (rc != VDB_OK) return rc;
   merge_pass(ix, src.higher_is_better, ba.part_keys, ba.part_cnt, nw, rest, st);
+  VDB_HIP(hipGetLastError());
+  return VDB_OK;
+}
+
+// The gathered four-bit tier of a filtered call over packed bits (VDB_OPT_FILTER_ROUTE = 3): sweep_topk_bits_gathered over
+// the filter's ascending row list, chunk by chunk of <= 1 024 queries (bits_gather_plan, vdb_filter_route.hpp) — the chunk's queries
+// packed the source's way and expanded once to their nibble image (s_misc) and bit counts (s_seed; Hamming: dim), one launch,
+// merge_topk.  The rows are read PACKED: no image of them is built, asked for or read.  The caller has checked k > 0, count > 0 and
+// that the plan of the whole call exists (a later chunk is never larger: its plan exists too).
+int32_t brute_bits_gathered_dev(vdb_hip_index* ix, const BitsSource& src, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st) {
+  const uint32_t k = s.k, stride = bits_image_stride(ix->dim);
+  ix->last_kernels |= VDB_KERNEL_BITS | VDB_KERNEL_SWEEP_LISTED;
+  for (uint32_t q0 = 0; q0 < s.nq;) {
+    const HalfGatherPlan gp = bits_gather_plan(k, count, s.nq - q0, ix->n_cus);
+    if (gp.blocks == 0) return fail(VDB_ERR_UNSUPPORTED, "gathered packed-bit sweep: k too large for the LDS query tile");
+    const QuerySlice c = s.sub(q0, gp.nq_chunk);
+    if (ix->s_qbits.reserve((size_t)c.nq * ix->words * 4, false, st) != hipSuccess ||
+        ix->s_part_keys.reserve((size_t)c.nq * gp.spans * k * 8, false, st) != hipSuccess ||
+        ix->s_misc.reserve((size_t)c.nq * stride, false, st) != hipSuccess || ix->s_seed.reserve((size_t)c.nq * 4, false, st) != hipSuccess)
+      return fail(VDB_ERR_OOM, "gathered packed-bit sweep scratch");
+    uint32_t* qbits = ix->s_qbits.as<uint32_t>();
+    uint8_t* qimg = ix->s_misc.as<uint8_t>();
+    float* qcnt = ix->s_seed.as<float>();
+    uint64_t* parts = ix->s_part_keys.as<uint64_t>();
+    src.pack_queries(ix, c, qbits, st);
+    launch_bits_expand(src.metric, qbits, ix->words, qimg, stride, qcnt, 0, c.nq, ix->dim, (float)ix->dim, st);
+    const int32_t rc = timed_launch(ix, VDB_KERNEL_BITS_GATHERED, st, "gathered packed-bit sweep launch", [&] {
+      return launch_sweep_bits_gathered(src.metric, gp, src.bits, ix->words, ix->any_dead ? ix->alive.as<uint8_t>() : nullptr, list, count, qimg, stride,
+                                        qcnt, parts, ix->dim, c.nq, k, st);
+    });
+    if (rc != VDB_OK) return rc;
+    merge_pass(ix, src.higher_is_better, parts, nullptr, gp.spans, c, st);
+    q0 += c.nq;
+  }
   VDB_HIP(hipGetLastError());
   return VDB_OK;
 }
@@ -820,11 +859,7 @@ static int32_t brute_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st)
   if (ix->flt && !ix->alive_override) return brute_filtered_dev(ix, s, st);
   // ... and keeps the selection stage only while enough rows are allowed for its seed sample (vdb_filter_route.hpp)
   const bool sel_ok = !ix->flt || filter_keeps_selection(ix->flt->count, ix->n_rows);
-  if (is_bits_metric(ix->metric)) {
-    const BitsSource src{ix->bits.as<uint32_t>(), pack_queries_as_rows, ix->metric, ensure_bits_image, &vdb_hip_index::bits_img, &vdb_hip_index::bits_cnt,
-                         /*sign_rule=*/0u, higher_is_better_host(ix->metric), "one-launch packed-bit search", "packed-bit sweep launch"};
-    return brute_bits_dev(ix, src, s, st);
-  }
+  if (is_bits_metric(ix->metric)) return brute_bits_dev(ix, packed_rows_source(ix), s, st);
   const bool euclid = ix->metric == VDB_EUCLIDEAN;
   uint32_t euclid_skip_until = 0;  // Euclidean chunk without proofs: [q0, this) goes through the exact tiles
   for (uint32_t q0 = 0; q0 < s.nq;) {
@@ -860,11 +895,26 @@ static bool sweep_mode_m(const vdb_hip_index* ix, uint32_t k) {
   return opt_engine(ix) == 1 && (ix->metric == VDB_COSINE || ix->metric == VDB_DOT) && sweep_mfma_lds_bytes(1, k, ix->dim) <= 160 * 1024;
 }
 
+// VDB_OPT_FILTER_ROUTE = 3 over packed bits: a Hamming / Jaccard index (mode VDB_SEARCH_BRUTE) and the Binary mode take the
+// gathered four-bit tier wherever its plan exists; everything else sees the value as auto (filter_route_opt)
+static bool bits_gathered_takes(const vdb_hip_index* ix, int32_t mode, int64_t opt_route, uint64_t count, uint32_t nq, uint32_t k) {
+  if (opt_route != kFilterRouteOptGathered) return false;
+  if (mode == VDB_SEARCH_BRUTE ? !is_bits_metric(ix->metric) : mode != VDB_SEARCH_BRUTE_BINARY) return false;
+  return bits_gather_plan(k, count, nq, ix->n_cus).blocks > 0;
+}
+// the call of that tier for the rows of ix->flt
+static int32_t bits_gathered_dev(vdb_hip_index* ix, int32_t mode, const QuerySlice& s, hipStream_t st) {
+  const RowFilter* f = ix->flt;
+  if (mode == VDB_SEARCH_BRUTE_BINARY) return brute_binary_gathered_dev(ix, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
+  return brute_bits_gathered_dev(ix, packed_rows_source(ix), f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
+}
+
 // vdb_hip_index_search_batch_filtered: exact top-k among the rows of ix->flt that are alive now.  Two routes, same bits.
 static int32_t brute_filtered_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st) {
   const RowFilter* f = ix->flt;
   const uint32_t k = s.k;
   if (f->count == 0) return zero_results(s, st);  // the empty filter: no row can answer
+  if (bits_gathered_takes(ix, VDB_SEARCH_BRUTE, opt_value(ix, VDB_OPT_FILTER_ROUTE), f->count, s.nq, k)) return bits_gathered_dev(ix, VDB_SEARCH_BRUTE, s, st);
   const bool mode_m = sweep_mode_m(ix, k);
   ListedPlan lp;
   if (!is_bits_metric(ix->metric)) sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, s.nq, ix->n_cus, &lp);
@@ -959,6 +1009,7 @@ static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const Qu
   if (f->count == 0 || k == 0) return zero_results(s, st);  // the empty filter: no row can answer
   const int64_t opt_route = opt_value(ix, VDB_OPT_FILTER_ROUTE);
   if (half_gathered_takes(ix, mode, opt_route, f->count, nq, k)) return brute_half_gathered_dev(ix, f16, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
+  if (bits_gathered_takes(ix, mode, opt_route, f->count, nq, k)) return bits_gathered_dev(ix, mode, s, st);
   bool listed_ok = false;
   if (filter_mode_has_listed(mode, ix->metric)) listed_ok = mode_listed_plan(half, ix->dim, k, f->count, nq, ix->n_cus).blocks > 0;
   if (filter_mode_route(filter_route_opt(opt_route), mode, ix->metric, f->count, ix->n_rows, nq, listed_ok) == kFilterRouteListed) {
@@ -1494,6 +1545,8 @@ int32_t search_filters_mode_to_device(vdb_hip_index* ix, const RowFilter* const*
         ix->flt = filters[g.filter];
         if (half_gathered_takes(ix, mode, opt_route, ix->flt->count, nq_g, k))  // (one group at a time: the one-filter call's launches)
           rg = brute_half_gathered_dev(ix, mode == VDB_SEARCH_BRUTE_F16, ix->flt->list.as<uint32_t>(), (uint32_t)ix->flt->count, s_g, st);
+        else if (bits_gathered_takes(ix, mode, opt_route, ix->flt->count, nq_g, k))
+          rg = bits_gathered_dev(ix, mode, s_g, st);
         else
           rg = brute_masked_dev(ix, s_g, st, mode);
         ix->flt = nullptr;

@@ -7,7 +7,8 @@
 // and the groups and grouped launches of such a call with one filter per query (vdb_hip_index_search_batch_filters_mode),
 // and the two phases of a fused search with one filter per query (vdb_hip_index_hybrid_search_filters /
 // vdb_hip_index_multi_query_search_filters), and the launch plan of the gathered matrix-core tier of Cosine / DotProduct
-// over a half image (VDB_OPT_FILTER_ROUTE = 3; tests/half_gather_plan_model.cpp).
+// over a half image (VDB_OPT_FILTER_ROUTE = 3; tests/half_gather_plan_model.cpp) and of its four-bit counterpart over
+// packed bits (tests/bits_gather_plan_model.cpp).
 // Pure host logic without a HIP header: tests/filter_route_model.cpp, tests/filter_mode_route_model.cpp,
 // tests/filter_graph_route_model.cpp, tests/filters_plan_model.cpp, tests/listed_groups_plan_model.cpp,
 // tests/mode_groups_plan_model.cpp and tests/hybrid_filters_plan_model.cpp compile it alone and walk its boundaries.
@@ -166,6 +167,13 @@ static inline HalfGatherPlan half_gather_plan(uint32_t dim, uint32_t k, uint64_t
   p.lds = lds;
   p.blocks = (int)(p.spans * p.qtiles);
   return p;
+}
+// ... and of the gathered FOUR-BIT tier of Hamming / Jaccard indexes and the Binary mode (sweep_bits_gathered.hip, DESIGN 4.1t;
+// tests/bits_gather_plan_model.cpp): the same work split, and a 128-B line holds a slice of 256 four-bit values where the half tier's
+// holds 64 elements, so the LDS layout is that one byte for byte (the third tile array holds the rows' bit counts instead of their
+// norms) — the same fields under the same rules.  A slice covers 8 packed words of a row whatever dim is.
+static inline HalfGatherPlan bits_gather_plan(uint32_t k, uint64_t count, uint32_t nq_left, int n_cus) {
+  return half_gather_plan(0, k, count, nq_left, n_cus);
 }
 
 // ---- filtered graph search (vdb_hip_index_search_graph_filtered): walk or exact pass, and the walk's first list ----

@@ -281,6 +281,12 @@ struct HalfGatherPlan;
 hipError_t launch_sweep_half_gathered(int metric, bool f16, const HalfGatherPlan& p, const uint16_t* rows, uint64_t row_stride, const float* norms,
                                       const uint8_t* alive, const uint32_t* list, uint32_t count, const uint16_t* queries16, uint64_t q_stride,
                                       const float* qnorms, uint64_t* part_keys, uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st);
+// the gathered four-bit tier over packed bit rows (sweep_bits_gathered.hip): one launch over the filter's ascending row
+// list for a chunk of <= 1 024 queries; bits [n_rows][words] packed rows (no image of them is read); qimg / qcnt: launch_bits_expand over
+// the packed queries (Hamming: fill = dim), q_stride = bits_image_stride(dim); the plan: bits_gather_plan; part_keys [nq][p.spans][k]
+hipError_t launch_sweep_bits_gathered(int metric, const HalfGatherPlan& p, const uint32_t* bits, uint32_t words, const uint8_t* alive,
+                                      const uint32_t* list, uint32_t count, const uint8_t* qimg, uint32_t q_stride, const float* qcnt,
+                                      uint64_t* part_keys, uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st);
 // ... nq queries (any number) in tiles of 16 in ONE launch (sweep_topk_half_l2_tiles): part_keys [nq][blocks][k]; qcount (nullable): a
 // device word, only the first *qcount queries exist.  The 16-query LDS tile must fit 160 KiB (sweep_half_l2_lds_bytes(16, k, dim))
 hipError_t launch_sweep_half_l2_tiles(bool f16, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,

@@ -108,5 +108,8 @@ struct BitsSource {
   const char* what_sweep;
 };
 int32_t brute_bits_dev(vdb_hip_index* ix, const BitsSource& src, const QuerySlice& s, hipStream_t st);
+// the gathered four-bit tier of a filtered call over either source (index.hip; VDB_OPT_FILTER_ROUTE = 3): reads src.bits of
+// the listed rows and nothing else of the corpus — src.ensure_image is never called
+int32_t brute_bits_gathered_dev(vdb_hip_index* ix, const BitsSource& src, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
 
 }  // namespace vdb

@@ -76,6 +76,13 @@ def half_gather_plan(dim, k, count, nq_left, n_cus):
     spans = max(1, min(spans, (256 << 20) // (nq * k * 8), ntiles))
     per_block = -(-ntiles // spans)
     return dict(tn=tn, nq_chunk=nq, qtiles=qtiles, per_block=per_block, spans=-(-ntiles // per_block), lds=lds_of(tn))
+# ... and its four-bit counterpart over packed bits (Hamming / Jaccard indexes, the Binary mode; next to KERNEL_BITS | KERNEL_SWEEP_LISTED)
+KERNEL_BITS_GATHERED = _ffi.VDB_KERNEL_BITS_GATHERED
+
+
+def bits_gather_plan(k, count, nq_left, n_cus):
+    """The launch plan of that tier (csrc/vdb_filter_route.hpp bits_gather_plan): the half tier's plan, which never depended on dim."""
+    return half_gather_plan(0, k, count, nq_left, n_cus)
 HYBRID_MAX_RECORDS = 8192
 # the rows the walks of hybrid_search_batch_filters / multi_query_search_batch_filters take their distances over (enum vdb_walk_rows)
 WALK_ROWS_F32, WALK_ROWS_F16, WALK_ROWS_BF16, WALK_ROWS_INT8 = _ffi.VDB_WALK_ROWS_F32, _ffi.VDB_WALK_ROWS_F16, _ffi.VDB_WALK_ROWS_BF16, _ffi.VDB_WALK_ROWS_INT8
