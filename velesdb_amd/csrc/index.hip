@@ -630,38 +630,87 @@ int32_t brute_bits_dev(vdb_hip_index* ix, const BitsSource& src, const QuerySlic
   return VDB_OK;
 }
 
-// The gathered four-bit tier of a filtered call over packed bits (VDB_OPT_FILTER_ROUTE = 3): sweep_topk_bits_gathered over
-// the filter's ascending row list, chunk by chunk of <= 1 024 queries (bits_gather_plan, vdb_filter_route.hpp) — the chunk's queries
-// packed the source's way and expanded once to their nibble image (s_misc) and bit counts (s_seed; Hamming: dim), one launch,
-// merge_topk.  The rows are read PACKED: no image of them is built, asked for or read.  The caller has checked k > 0, count > 0 and
-// that the plan of the whole call exists (a later chunk is never larger: its plan exists too).
-int32_t brute_bits_gathered_dev(vdb_hip_index* ix, const BitsSource& src, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st) {
-  const uint32_t k = s.k, stride = bits_image_stride(ix->dim);
-  ix->last_kernels |= VDB_KERNEL_BITS | VDB_KERNEL_SWEEP_LISTED;
+// ---- the gathered matrix-core tiers of a filtered call (VDB_OPT_FILTER_ROUTE = 3; sweep_gathered.hip) ----
+enum GatheredKind : int { kGatheredNone = 0, kGatheredHalf, kGatheredBits };
+// Which of them takes the call?  Half: Cosine / DotProduct in one of the half modes; bits: a Hamming /
+// Jaccard index (mode VDB_SEARCH_BRUTE) and the Binary mode — each wherever its plan exists.  Everything else sees the option's value
+// as auto (filter_route_opt).
+static GatheredKind gathered_takes(const vdb_hip_index* ix, int32_t mode, int64_t opt_route, uint64_t count, uint32_t nq, uint32_t k) {
+  if (opt_route != kFilterRouteOptGathered) return kGatheredNone;
+  if (mode == VDB_SEARCH_BRUTE_BF16 || mode == VDB_SEARCH_BRUTE_F16) {
+    if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT) return kGatheredNone;
+    return half_gather_plan(ix->dim, k, count, nq, ix->n_cus).blocks > 0 ? kGatheredHalf : kGatheredNone;
+  }
+  if (mode == VDB_SEARCH_BRUTE ? !is_bits_metric(ix->metric) : mode != VDB_SEARCH_BRUTE_BINARY) return kGatheredNone;
+  return bits_gather_plan(k, count, nq, ix->n_cus).blocks > 0 ? kGatheredBits : kGatheredNone;
+}
+// the chunk loop of both tiers, written once.  A kind is its refusal text, its order of keys and `chunk(gp, c, parts_bytes)`: reserve
+// the scratch, prepare the chunk's queries, launch into s_part_keys [c.nq][gp.spans][k]; VDB_OK or the error
+template <class Chunk>
+static int32_t gathered_chunks(vdb_hip_index* ix, uint32_t count, const QuerySlice& s, hipStream_t st, const char* what_k, bool higher_is_better,
+                               Chunk&& chunk) {
   for (uint32_t q0 = 0; q0 < s.nq;) {
-    const HalfGatherPlan gp = bits_gather_plan(k, count, s.nq - q0, ix->n_cus);
-    if (gp.blocks == 0) return fail(VDB_ERR_UNSUPPORTED, "gathered packed-bit sweep: k too large for the LDS query tile");
+    const HalfGatherPlan gp = half_gather_plan(ix->dim, s.k, count, s.nq - q0, ix->n_cus);  // (bits_gather_plan is this plan: dim is not read)
+    if (gp.blocks == 0) return fail(VDB_ERR_UNSUPPORTED, what_k);
     const QuerySlice c = s.sub(q0, gp.nq_chunk);
-    if (ix->s_qbits.reserve((size_t)c.nq * ix->words * 4, false, st) != hipSuccess ||
-        ix->s_part_keys.reserve((size_t)c.nq * gp.spans * k * 8, false, st) != hipSuccess ||
+    const int32_t rc = chunk(gp, c, (size_t)c.nq * gp.spans * s.k * 8);
+    if (rc != VDB_OK) return rc;
+    merge_pass(ix, higher_is_better, ix->s_part_keys.as<uint64_t>(), nullptr, gp.spans, c, st);
+    q0 += c.nq;
+  }
+  VDB_HIP(hipGetLastError());
+  return VDB_OK;
+}
+// The call of the tier that gathered_takes named: `list` = the filter's ascending rows (count > 0) against the batch, chunk by
+// chunk of <= 1 024 queries (half_gather_plan / bits_gather_plan, vdb_filter_route.hpp) — the chunk's queries prepared once, one
+// launch, merge_topk.
+//   half: the queries rounded to the image's format and their norms (s_misc);
+//   bits: the queries packed the source's way (s_qbits) and expanded once to their nibble image (s_misc) and bit counts (s_seed;
+//   Hamming: dim).  The rows are read PACKED: no image of them is built, asked for or read (src.ensure_image is never called).
+// The caller has checked the mode (the image, the storage mode, the metric), k > 0, count > 0 and that the plan of the whole call exists
+// (a later chunk is never larger: its plan exists too).
+static int32_t brute_gathered_dev(vdb_hip_index* ix, GatheredKind kind, int32_t mode, const uint32_t* list, uint32_t count, const QuerySlice& s,
+                                  hipStream_t st) {
+  const uint32_t k = s.k;
+  const uint8_t* alive = ix->any_dead ? ix->alive.as<uint8_t>() : nullptr;
+  if (kind == kGatheredHalf) {
+    const bool f16 = mode == VDB_SEARCH_BRUTE_F16;
+    const uint16_t* rows16 = f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>();
+    const float* norms16 = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
+    ix->last_kernels |= VDB_KERNEL_SWEEP_LISTED | (f16 ? VDB_KERNEL_F16 : 0u);
+    return gathered_chunks(ix, count, s, st, "gathered half-precision sweep: k too large for the LDS query tile", true,
+               [&](const HalfGatherPlan& gp, const QuerySlice& c, size_t parts_bytes) -> int32_t {
+      const size_t q_bytes = ((size_t)c.nq * ix->bf16_stride * 2 + 15) & ~(size_t)15;
+      if (ix->s_part_keys.reserve(parts_bytes, false, st) != hipSuccess || ix->s_misc.reserve(q_bytes + (size_t)c.nq * 4, false, st) != hipSuccess)
+        return fail(VDB_ERR_OOM, "gathered half-precision sweep scratch");
+      uint16_t* q16 = ix->s_misc.as<uint16_t>();
+      float* qn = reinterpret_cast<float*>(ix->s_misc.as<unsigned char>() + q_bytes);  // norms of the rounded queries
+      launch_round_queries_bf16(c.d_q, c.q_stride, q16, ix->bf16_stride, c.nq, ix->dim, st, f16);
+      launch_query_norms_bf16(q16, ix->bf16_stride, qn, c.nq, ix->dim, st, f16);
+      return timed_launch(ix, VDB_KERNEL_GEMM_HALF_GATHERED, st, "gathered half-precision sweep launch", [&] {
+        return launch_sweep_half_gathered(ix->metric, f16, gp, rows16, ix->bf16_stride, norms16, alive, list, count, q16, ix->bf16_stride, qn,
+                                          ix->s_part_keys.as<uint64_t>(), ix->dim, c.nq, k, st);
+      });
+    });
+  }
+  const BitsSource src = mode == VDB_SEARCH_BRUTE_BINARY ? sign_bits_source(ix) : packed_rows_source(ix);
+  const uint32_t stride = bits_image_stride(ix->dim);
+  ix->last_kernels |= VDB_KERNEL_BITS | VDB_KERNEL_SWEEP_LISTED;
+  return gathered_chunks(ix, count, s, st, "gathered packed-bit sweep: k too large for the LDS query tile", src.higher_is_better,
+             [&](const HalfGatherPlan& gp, const QuerySlice& c, size_t parts_bytes) -> int32_t {
+    if (ix->s_qbits.reserve((size_t)c.nq * ix->words * 4, false, st) != hipSuccess || ix->s_part_keys.reserve(parts_bytes, false, st) != hipSuccess ||
         ix->s_misc.reserve((size_t)c.nq * stride, false, st) != hipSuccess || ix->s_seed.reserve((size_t)c.nq * 4, false, st) != hipSuccess)
       return fail(VDB_ERR_OOM, "gathered packed-bit sweep scratch");
     uint32_t* qbits = ix->s_qbits.as<uint32_t>();
     uint8_t* qimg = ix->s_misc.as<uint8_t>();
     float* qcnt = ix->s_seed.as<float>();
-    uint64_t* parts = ix->s_part_keys.as<uint64_t>();
     src.pack_queries(ix, c, qbits, st);
     launch_bits_expand(src.metric, qbits, ix->words, qimg, stride, qcnt, 0, c.nq, ix->dim, (float)ix->dim, st);
-    const int32_t rc = timed_launch(ix, VDB_KERNEL_BITS_GATHERED, st, "gathered packed-bit sweep launch", [&] {
-      return launch_sweep_bits_gathered(src.metric, gp, src.bits, ix->words, ix->any_dead ? ix->alive.as<uint8_t>() : nullptr, list, count, qimg, stride,
-                                        qcnt, parts, ix->dim, c.nq, k, st);
+    return timed_launch(ix, VDB_KERNEL_BITS_GATHERED, st, "gathered packed-bit sweep launch", [&] {
+      return launch_sweep_bits_gathered(src.metric, gp, src.bits, ix->words, alive, list, count, qimg, stride, qcnt, ix->s_part_keys.as<uint64_t>(),
+                                        ix->dim, c.nq, k, st);
     });
-    if (rc != VDB_OK) return rc;
-    merge_pass(ix, src.higher_is_better, parts, nullptr, gp.spans, c, st);
-    q0 += c.nq;
-  }
-  VDB_HIP(hipGetLastError());
-  return VDB_OK;
+  });
 }
 
 // ---- f32 rows: the tiers of brute_dev's ladder.  Each is asked for the front of what is left of the batch (`rest`) ----
@@ -895,26 +944,13 @@ static bool sweep_mode_m(const vdb_hip_index* ix, uint32_t k) {
   return opt_engine(ix) == 1 && (ix->metric == VDB_COSINE || ix->metric == VDB_DOT) && sweep_mfma_lds_bytes(1, k, ix->dim) <= 160 * 1024;
 }
 
-// VDB_OPT_FILTER_ROUTE = 3 over packed bits: a Hamming / Jaccard index (mode VDB_SEARCH_BRUTE) and the Binary mode take the
-// gathered four-bit tier wherever its plan exists; everything else sees the value as auto (filter_route_opt)
-static bool bits_gathered_takes(const vdb_hip_index* ix, int32_t mode, int64_t opt_route, uint64_t count, uint32_t nq, uint32_t k) {
-  if (opt_route != kFilterRouteOptGathered) return false;
-  if (mode == VDB_SEARCH_BRUTE ? !is_bits_metric(ix->metric) : mode != VDB_SEARCH_BRUTE_BINARY) return false;
-  return bits_gather_plan(k, count, nq, ix->n_cus).blocks > 0;
-}
-// the call of that tier for the rows of ix->flt
-static int32_t bits_gathered_dev(vdb_hip_index* ix, int32_t mode, const QuerySlice& s, hipStream_t st) {
-  const RowFilter* f = ix->flt;
-  if (mode == VDB_SEARCH_BRUTE_BINARY) return brute_binary_gathered_dev(ix, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
-  return brute_bits_gathered_dev(ix, packed_rows_source(ix), f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
-}
-
 // vdb_hip_index_search_batch_filtered: exact top-k among the rows of ix->flt that are alive now.  Two routes, same bits.
 static int32_t brute_filtered_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st) {
   const RowFilter* f = ix->flt;
   const uint32_t k = s.k;
   if (f->count == 0) return zero_results(s, st);  // the empty filter: no row can answer
-  if (bits_gathered_takes(ix, VDB_SEARCH_BRUTE, opt_value(ix, VDB_OPT_FILTER_ROUTE), f->count, s.nq, k)) return bits_gathered_dev(ix, VDB_SEARCH_BRUTE, s, st);
+  if (const GatheredKind g = gathered_takes(ix, VDB_SEARCH_BRUTE, opt_value(ix, VDB_OPT_FILTER_ROUTE), f->count, s.nq, k))
+    return brute_gathered_dev(ix, g, VDB_SEARCH_BRUTE, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
   const bool mode_m = sweep_mode_m(ix, k);
   ListedPlan lp;
   if (!is_bits_metric(ix->metric)) sweep_listed_plan(mode_m, ix->dim, k, (uint32_t)f->count, s.nq, ix->n_cus, &lp);
@@ -992,13 +1028,6 @@ static int32_t filtered_mode_check(const vdb_hip_index* ix, int32_t mode) {
   }
   return VDB_OK;
 }
-// VDB_OPT_FILTER_ROUTE = 3: Cosine / DotProduct over a half image takes the gathered matrix-core tier wherever its plan
-// exists; every other mode, metric and shape sees the value as auto (filter_route_opt)
-static bool half_gathered_takes(const vdb_hip_index* ix, int32_t mode, int64_t opt_route, uint64_t count, uint32_t nq, uint32_t k) {
-  if (opt_route != kFilterRouteOptGathered || (mode != VDB_SEARCH_BRUTE_BF16 && mode != VDB_SEARCH_BRUTE_F16)) return false;
-  if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT) return false;
-  return half_gather_plan(ix->dim, k, count, nq, ix->n_cus).blocks > 0;
-}
 static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const QuerySlice& s, hipStream_t st) {
   const RowFilter* f = ix->flt;
   const uint32_t nq = s.nq, k = s.k;
@@ -1008,8 +1037,7 @@ static int32_t brute_filtered_mode_dev(vdb_hip_index* ix, int32_t mode, const Qu
   if (nq == 0) return VDB_OK;
   if (f->count == 0 || k == 0) return zero_results(s, st);  // the empty filter: no row can answer
   const int64_t opt_route = opt_value(ix, VDB_OPT_FILTER_ROUTE);
-  if (half_gathered_takes(ix, mode, opt_route, f->count, nq, k)) return brute_half_gathered_dev(ix, f16, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
-  if (bits_gathered_takes(ix, mode, opt_route, f->count, nq, k)) return bits_gathered_dev(ix, mode, s, st);
+  if (const GatheredKind g = gathered_takes(ix, mode, opt_route, f->count, nq, k)) return brute_gathered_dev(ix, g, mode, f->list.as<uint32_t>(), (uint32_t)f->count, s, st);
   bool listed_ok = false;
   if (filter_mode_has_listed(mode, ix->metric)) listed_ok = mode_listed_plan(half, ix->dim, k, f->count, nq, ix->n_cus).blocks > 0;
   if (filter_mode_route(filter_route_opt(opt_route), mode, ix->metric, f->count, ix->n_rows, nq, listed_ok) == kFilterRouteListed) {
@@ -1543,10 +1571,8 @@ int32_t search_filters_mode_to_device(vdb_hip_index* ix, const RowFilter* const*
         VDB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_scores + (size_t)r0 * k), 0x7FC00000, (size_t)nq_g * k, st));
       } else {
         ix->flt = filters[g.filter];
-        if (half_gathered_takes(ix, mode, opt_route, ix->flt->count, nq_g, k))  // (one group at a time: the one-filter call's launches)
-          rg = brute_half_gathered_dev(ix, mode == VDB_SEARCH_BRUTE_F16, ix->flt->list.as<uint32_t>(), (uint32_t)ix->flt->count, s_g, st);
-        else if (bits_gathered_takes(ix, mode, opt_route, ix->flt->count, nq_g, k))
-          rg = bits_gathered_dev(ix, mode, s_g, st);
+        if (const GatheredKind gk = gathered_takes(ix, mode, opt_route, ix->flt->count, nq_g, k))  // (one group at a time: the one-filter call's launches)
+          rg = brute_gathered_dev(ix, gk, mode, ix->flt->list.as<uint32_t>(), (uint32_t)ix->flt->count, s_g, st);
         else
           rg = brute_masked_dev(ix, s_g, st, mode);
         ix->flt = nullptr;

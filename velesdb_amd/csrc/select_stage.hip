@@ -225,40 +225,6 @@ int32_t brute_half_l2_listed_dev(vdb_hip_index* ix, bool f16, const uint32_t* li
   return VDB_OK;
 }
 
-// The gathered matrix-core tier of a filtered Cosine / DotProduct call over a half image (VDB_OPT_FILTER_ROUTE = 3):
-// sweep_topk_half_gathered over the filter's ascending row list, chunk by chunk of <= 1 024 queries (half_gather_plan,
-// vdb_filter_route.hpp) — the chunk's queries rounded once, their norms once, one launch, merge_topk.  The caller has checked the image,
-// the metric, k > 0, count > 0 and that the plan of the whole call exists (a later chunk is never larger: its plan exists too).
-int32_t brute_half_gathered_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st) {
-  const uint16_t* rows16 = f16 ? ix->rows_f16.as<uint16_t>() : ix->rows_bf16.as<uint16_t>();
-  const float* norms16 = f16 ? ix->norms_f16.as<float>() : ix->norms_bf16.as<float>();
-  const uint32_t k = s.k;
-  ix->last_kernels |= VDB_KERNEL_SWEEP_LISTED | (f16 ? VDB_KERNEL_F16 : 0u);
-  for (uint32_t q0 = 0; q0 < s.nq;) {
-    const HalfGatherPlan gp = half_gather_plan(ix->dim, k, count, s.nq - q0, ix->n_cus);
-    if (gp.blocks == 0) return fail(VDB_ERR_UNSUPPORTED, "gathered half-precision sweep: k too large for the LDS query tile");
-    const QuerySlice c = s.sub(q0, gp.nq_chunk);
-    const size_t q_bytes = ((size_t)c.nq * ix->bf16_stride * 2 + 15) & ~(size_t)15;
-    if (ix->s_part_keys.reserve((size_t)c.nq * gp.spans * k * 8, false, st) != hipSuccess ||
-        ix->s_misc.reserve(q_bytes + (size_t)c.nq * 4, false, st) != hipSuccess)
-      return fail(VDB_ERR_OOM, "gathered half-precision sweep scratch");
-    uint16_t* q16 = ix->s_misc.as<uint16_t>();
-    float* qn = reinterpret_cast<float*>(ix->s_misc.as<unsigned char>() + q_bytes);  // norms of the rounded queries
-    uint64_t* parts = ix->s_part_keys.as<uint64_t>();
-    launch_round_queries_bf16(c.d_q, c.q_stride, q16, ix->bf16_stride, c.nq, ix->dim, st, f16);
-    launch_query_norms_bf16(q16, ix->bf16_stride, qn, c.nq, ix->dim, st, f16);
-    const int32_t rc = timed_launch(ix, VDB_KERNEL_GEMM_HALF_GATHERED, st, "gathered half-precision sweep launch", [&] {
-      return launch_sweep_half_gathered(ix->metric, f16, gp, rows16, ix->bf16_stride, norms16, ix->any_dead ? ix->alive.as<uint8_t>() : nullptr, list, count,
-                                        q16, ix->bf16_stride, qn, parts, ix->dim, c.nq, k, st);
-    });
-    if (rc != VDB_OK) return rc;
-    merge_pass(ix, true, parts, nullptr, gp.spans, c, st);
-    q0 += c.nq;
-  }
-  VDB_HIP(hipGetLastError());
-  return VDB_OK;
-}
-
 // ---- Cosine / DotProduct over a half copy: the three tiers of brute_bf16_dev's ladder, each asked for the front of what is left ----
 struct HalfImage {
   const uint16_t* rows16;

@@ -692,7 +692,7 @@ static void pack_queries_as_signs(const vdb_hip_index* ix, const QuerySlice& s, 
 // BinaryQuantizedVector::hamming_distance between the sign bits of the queries and of every row: the packed-bit path of index.hip
 // (brute_bits_dev: one-launch kernel, four-bit GEMM on the matrix cores, vector-ALU plan) over the sign-bit array — scores = distance
 // as f32, smallest first
-static BitsSource sign_bits_source(const vdb_hip_index* ix) {
+BitsSource sign_bits_source(const vdb_hip_index* ix) {
   return {ix->sign_bits.as<uint32_t>(), pack_queries_as_signs, VDB_HAMMING, ensure_sign_image, &vdb_hip_index::sq8_img, &vdb_hip_index::sq8_nrm,
           /*sign_rule=*/1u, /*higher_is_better=*/false, "one-launch sign-bit search", "sign-bit sweep launch"};
 }
@@ -701,9 +701,6 @@ int32_t brute_binary_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st)
   if (s.nq == 0) return VDB_OK;
   if (s.k == 0 || ix->n_rows == 0) return zero_results(s, st);
   return brute_bits_dev(ix, sign_bits_source(ix), s, st);
-}
-int32_t brute_binary_gathered_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st) {
-  return brute_bits_gathered_dev(ix, sign_bits_source(ix), list, count, s, st);
 }
 
 

@@ -120,7 +120,7 @@ static inline ModeListedPlan mode_listed_plan(bool half, uint32_t dim, uint32_t 
   return p;
 }
 
-// ---- the gathered matrix-core tier of Cosine / DotProduct over a half image (sweep_half_gathered.hip) ----
+// ---- the gathered matrix-core tier of Cosine / DotProduct over a half image (sweep_gathered.hip) ----
 // VDB_OPT_FILTER_ROUTE = 3: that tier wherever its plan exists; everywhere else the value behaves as auto does, so the route
 // functions above are asked with filter_route_opt(value).
 constexpr int64_t kFilterRouteOptGathered = 3;
@@ -168,7 +168,7 @@ static inline HalfGatherPlan half_gather_plan(uint32_t dim, uint32_t k, uint64_t
   p.blocks = (int)(p.spans * p.qtiles);
   return p;
 }
-// ... and of the gathered FOUR-BIT tier of Hamming / Jaccard indexes and the Binary mode (sweep_bits_gathered.hip, DESIGN 4.1t;
+// ... and of the gathered FOUR-BIT tier of Hamming / Jaccard indexes and the Binary mode (sweep_gathered.hip, DESIGN 4.1t;
 // tests/bits_gather_plan_model.cpp): the same work split, and a 128-B line holds a slice of 256 four-bit values where the half tier's
 // holds 64 elements, so the LDS layout is that one byte for byte (the third tile array holds the rows' bit counts instead of their
 // norms) — the same fields under the same rules.  A slice covers 8 packed words of a row whatever dim is.

@@ -336,7 +336,6 @@ int32_t search_filtered_mode_to_device(vdb_hip_index* ix, const RowFilter* f, in
 struct QuerySlice;  // vdb_sweep_pass.hpp: the queries a pass answers and where their answers go
 int32_t brute_sq8_listed_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
 int32_t brute_half_l2_listed_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
-int32_t brute_half_gathered_dev(vdb_hip_index* ix, bool f16, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
 // the filter belongs to this handle (generation) and to its present row numbering (row_epoch): anything else is an error
 int32_t filter_check(vdb_hip_index* ix, const RowFilter* f);
 // one optional filter per query on the exact sweep (index.hip): filters[n_filters] handles (checked inside, all of them
@@ -484,7 +483,4 @@ uint32_t bits_gemm_chunk(const vdb_hip_index* ix, uint32_t nq_left, uint32_t k);
 // (s.d_q is not read: the chunk's queries arrive packed in qbits [s.nq][words])
 int32_t brute_bits_gemm_dev(vdb_hip_index* ix, int metric, const uint8_t* img, const float* cnt, const uint32_t* qbits, const QuerySlice& s, hipStream_t st);
 int32_t brute_binary_dev(vdb_hip_index* ix, const QuerySlice& s, hipStream_t st);
-// ... and its gathered four-bit tier over a filter's row list (brute_bits_gathered_dev over the sign-bit source; the caller has checked
-// the storage mode and the plan)
-int32_t brute_binary_gathered_dev(vdb_hip_index* ix, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
 }  // namespace vdb

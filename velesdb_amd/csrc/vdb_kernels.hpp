@@ -274,14 +274,14 @@ struct ListedGroupItem;
 hipError_t launch_sweep_half_l2_listed_groups(bool f16, int B, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,
                                               uint64_t q_stride, uint64_t* part_keys, uint32_t dim, uint32_t k, const ListedGroupItem* items,
                                               uint32_t n_items, uint32_t lists_per_q, hipStream_t st);
-// the gathered matrix-core tier of Cosine / DotProduct over a half image (sweep_half_gathered.hip): one launch over the
+// the gathered matrix-core tier of Cosine / DotProduct over a half image (sweep_gathered.hip): one launch over the
 // filter's ascending row list for a chunk of <= 1 024 rounded queries (queries16 / qnorms: launch_round_queries_bf16 /
 // launch_query_norms_bf16); the plan: half_gather_plan, vdb_filter_route.hpp; part_keys [nq][p.spans][k]
 struct HalfGatherPlan;
 hipError_t launch_sweep_half_gathered(int metric, bool f16, const HalfGatherPlan& p, const uint16_t* rows, uint64_t row_stride, const float* norms,
                                       const uint8_t* alive, const uint32_t* list, uint32_t count, const uint16_t* queries16, uint64_t q_stride,
                                       const float* qnorms, uint64_t* part_keys, uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st);
-// the gathered four-bit tier over packed bit rows (sweep_bits_gathered.hip): one launch over the filter's ascending row
+// the gathered four-bit tier over packed bit rows (sweep_gathered.hip): one launch over the filter's ascending row
 // list for a chunk of <= 1 024 queries; bits [n_rows][words] packed rows (no image of them is read); qimg / qcnt: launch_bits_expand over
 // the packed queries (Hamming: fill = dim), q_stride = bits_image_stride(dim); the plan: bits_gather_plan; part_keys [nq][p.spans][k]
 hipError_t launch_sweep_bits_gathered(int metric, const HalfGatherPlan& p, const uint32_t* bits, uint32_t words, const uint8_t* alive,

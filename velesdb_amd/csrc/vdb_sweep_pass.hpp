@@ -108,8 +108,8 @@ struct BitsSource {
   const char* what_sweep;
 };
 int32_t brute_bits_dev(vdb_hip_index* ix, const BitsSource& src, const QuerySlice& s, hipStream_t st);
-// the gathered four-bit tier of a filtered call over either source (index.hip; VDB_OPT_FILTER_ROUTE = 3): reads src.bits of
-// the listed rows and nothing else of the corpus — src.ensure_image is never called
-int32_t brute_bits_gathered_dev(vdb_hip_index* ix, const BitsSource& src, const uint32_t* list, uint32_t count, const QuerySlice& s, hipStream_t st);
+// the sign-bit codes of the Binary storage mode as a source (storage_modes.hip); the gathered four-bit tier of a filtered call
+// (index.hip brute_gathered_dev; VDB_OPT_FILTER_ROUTE = 3) reads it as it reads a Hamming / Jaccard index's packed rows
+BitsSource sign_bits_source(const vdb_hip_index* ix);
 
 }  // namespace vdb
