@@ -328,7 +328,12 @@ void vdb_hip_filter_destroy(void* f);
  * call (it does not go through the combining front) and leaves the handle's adaptive selection state as it found it.
  * Hamming / Jaccard have no listed sweep; VDB_OPT_FILTER_ROUTE = 3 gives them the gathered FOUR-BIT tier (DESIGN 4.1t;
  * sweep_topk_bits_gathered over the filter's packed rows, stated at the mode call below) wherever its plan exists: the same bits,
- * VDB_KERNEL_BITS | VDB_KERNEL_SWEEP_LISTED | VDB_KERNEL_BITS_GATHERED.  Auto never takes it; for the three float metrics 3 is auto. */
+ * VDB_KERNEL_BITS | VDB_KERNEL_SWEEP_LISTED | VDB_KERNEL_BITS_GATHERED.  Cosine / DotProduct over the f32 rows take the gathered
+ * F32 tier under that value wherever the handle answers this k in mode M (vdb_hip_index_sweep_arith_mode = 1: the
+ * matrix engine, a dim and k its tile holds) and the plan exists: sweep_topk_f32_gathered, a GEMM of the filter's ascending row list
+ * with the whole batch on v_mfma_f32_16x16x4_f32 in mode M's own chain order, one launch per chunk of <= 1 024 queries — the bits of
+ * the other two routes, VDB_KERNEL_SWEEP_LISTED | VDB_KERNEL_GEMM_F32_GATHERED.  Auto never takes either; for Euclidean, for engine 0
+ * and for a dim or k that puts the handle in mode C, 3 is auto. */
 int32_t vdb_hip_index_search_batch_filtered(vdb_hip_index* idx, const void* f, const float* queries_rowmajor, uint32_t nq,
                                             uint32_t k, int32_t mode, uint64_t* out_ids, float* out_scores, uint32_t* out_n);
 /* The same over the SQ8 codes, the sign bits or a half image of the rows: the reference's search_with_filter works
@@ -378,7 +383,9 @@ int32_t vdb_hip_index_search_batch_filtered_mode(vdb_hip_index* idx, const void*
  * through the exact path, and the unfiltered queries together as one such job.  A call whose queries all name ONE filter runs
  * vdb_hip_index_search_batch_filtered itself: the same launches, the same vdb_hip_index_last_kernels.
  * The call leaves the handle's adaptive selection state as it found it and posts no selection verdicts, for its unfiltered queries
- * too.  It never goes through the combining front.  All five metrics (Hamming / Jaccard: mask substitution per group).  k limits
+ * too.  It never goes through the combining front.  All five metrics (Hamming / Jaccard: mask substitution per group).  Under
+ * VDB_OPT_FILTER_ROUTE = 3 a group that the gathered f32 or four-bit tier takes runs that tier, one group at a time (the one-filter
+ * call's launches; VDB_KERNEL_GEMM_F32_GATHERED / VDB_KERNEL_BITS_GATHERED): a query's bits do not depend on its group.  k limits
  * and k errors as vdb_hip_index_search_batch_filtered.
  * Errors, checked for every filter of the table before anything runs: a NULL table entry or a filter of another handle, a
  * filter_of_query value > n_filters: VDB_ERR_INVALID_ARG; a stale filter: VDB_ERR_STATE; mode other than VDB_SEARCH_BRUTE,
@@ -926,6 +933,10 @@ enum vdb_kernel_bit {
  * vdb_hip_index_search_batch_filtered_mode / _filters_mode; VDB_OPT_FILTER_ROUTE = 3).  Set NEXT TO VDB_KERNEL_BITS and
  * VDB_KERNEL_SWEEP_LISTED — only the filter's packed rows were read; VDB_KERNEL_BITS_GEMM is NOT set: no four-bit image of the rows. */
 #define VDB_KERNEL_BITS_GATHERED (1u << 25)
+/* ... and the f32 one, a shift as well: sweep_topk_f32_gathered ran — the gathered matrix-core tier of a filtered Cosine / DotProduct call
+ * over the f32 rows of a handle in mode M (vdb_hip_index_search_batch_filtered / _filters under VDB_OPT_FILTER_ROUTE = 3).  Set NEXT TO
+ * VDB_KERNEL_SWEEP_LISTED — only the filter's rows were read. */
+#define VDB_KERNEL_GEMM_F32_GATHERED (1u << 26)
 /* which kernels served THIS THREAD's last search on the handle: taken when that search's context was released (or, for a call the
  * combining front had another thread launch, handed back with the call's result), so a search of another thread that takes the same
  * context a moment later does not change it. */

@@ -7,6 +7,8 @@ yardstick is measured through the same kind of call).  Prints and writes what DE
     ms per call on the forced listed route, on the forced mask route, under the auto rule, and of the unfiltered VDB_SEARCH_BRUTE
     call on the same handle in the same run (no unfiltered code differs from the parent: that is the yardstick);
     which forced route is faster, and how far auto is from it;
+    Cosine / DotProduct: the forced gathered f32 tier (FILTER_ROUTE_GATHERED) beside them, held to their ids and score
+    bits first; gathered_over_better is its ratio to the faster of listed and mask (profiles/filter_probe_f32_gathered_100k.json);
     one query on the listed route: count x dim x 4 B / time, as a fraction of the whole-row gather rate --gather-tbs;
   --rider: HnswIndex.search_filtered (the over-fetch rule) for one query with the number of results it actually returned
   (needs the graph: build_graph over every row first — minutes at 1 M rows, off by default).
@@ -551,19 +553,35 @@ for mname in [m for m in a.metrics.split(",") if m]:
             with ix.create_filter(allowed) as flt:
                 row = dict(metric=mname, rows=a.rows, dim=a.dim, k=a.k, nq=nq, selectivity=sel, count=count, unfiltered_ms=plain, unfiltered_spread=plain_sp)
                 ref = None
-                for name, route in (("listed", va.FILTER_ROUTE_LISTED), ("mask", va.FILTER_ROUTE_MASK), ("auto", va.FILTER_ROUTE_AUTO)):
+                # (the forced gathered f32 tier, DESIGN 4.1u: Cosine / DotProduct; everyone else sees that value as auto)
+                routes = (("listed", va.FILTER_ROUTE_LISTED), ("mask", va.FILTER_ROUTE_MASK), ("auto", va.FILTER_ROUTE_AUTO)) + \
+                    ((("gathered", va.FILTER_ROUTE_GATHERED),) if mname in ("cosine", "dot") else ())
+                for name, route in routes:
                     ix.set_option(va.OPT_FILTER_ROUTE, route)
                     got = ix.search_batch_brute_force_filtered(Q, a.k, flt)
                     if name == "auto":
                         row["auto_took"] = "listed" if ix.last_kernels() & va.KERNEL_SWEEP_LISTED else "mask"
+                    if name == "gathered":
+                        row["gathered_kernel_ran"] = bool(ix.last_kernels() & va.KERNEL_GEMM_F32_GATHERED)
                     if ref is None:
                         ref = got
                     else:  # the routes agree bit for bit (a probe that times wrong answers measures nothing)
                         assert np.array_equal(ref[0], got[0]) and np.array_equal(ref[1].view(np.uint32), got[1].view(np.uint32)), (mname, nq, sel, name)
-                    row[name + "_ms"], row[name + "_spread"] = measure(lambda: ix.search_batch_brute_force_filtered(Q, a.k, flt))
+
+                def call(route):
+                    def fn():
+                        ix.set_option(va.OPT_FILTER_ROUTE, route)
+                        ix.search_batch_brute_force_filtered(Q, a.k, flt)
+                    return fn
+                # (the routes' timing blocks alternate: they see the same clocks and the same neighbours)
+                for (name, _), (ms, sp) in zip(routes, measure_many([call(route) for _, route in routes])):
+                    row[name + "_ms"], row[name + "_spread"] = ms, sp
                 best = min(("listed", "mask"), key=lambda r: row[r + "_ms"])
                 row["better"] = best
                 row["auto_over_better"] = row["auto_ms"] / row[best + "_ms"]
+                if "gathered_ms" in row:
+                    row["gathered_over_better"] = row["gathered_ms"] / row[best + "_ms"]
+                ix.set_option(va.OPT_FILTER_ROUTE, va.FILTER_ROUTE_AUTO)
                 if nq == 1:
                     row["listed_gather_tbs"] = count * a.dim * 4 / (row["listed_ms"] * 1e-3) / 1e12
                     row["listed_gather_fraction"] = row["listed_gather_tbs"] / a.gather_tbs

@@ -109,6 +109,8 @@ pub const VDB_KERNEL_SELECT_HALF_L2: i32 = 1 << 23;
 pub const VDB_KERNEL_GEMM_HALF_GATHERED: i32 = 1 << 24;
 // #define VDB_KERNEL_BITS_GATHERED (1u << 25) (likewise)
 pub const VDB_KERNEL_BITS_GATHERED: i32 = 1 << 25;
+// #define VDB_KERNEL_GEMM_F32_GATHERED (1u << 26) (likewise)
+pub const VDB_KERNEL_GEMM_F32_GATHERED: i32 = 1 << 26;
 
 // enum vdb_walk_rows (the rows the walks of the `_filters` forms of the fused searches take their distances over)
 pub const VDB_WALK_ROWS_F32: i32 = 0;

@@ -20,6 +20,7 @@ from .index import KERNEL_SWEEP_LISTED_GROUPS  # noqa: F401
 from .index import (FILTER_ROUTE_AUTO, FILTER_ROUTE_GATHERED, FILTER_ROUTE_LISTED, FILTER_ROUTE_MASK, KERNEL_GEMM_HALF_GATHERED,  # noqa: F401
                     KERNEL_SWEEP_LISTED, OPT_FILTER_ROUTE, Filter, half_gather_plan)
 from .index import KERNEL_BITS_GATHERED, bits_gather_plan  # noqa: F401
+from .index import KERNEL_GEMM_F32_GATHERED  # noqa: F401
 from .index import FUSE_MAX_RECORDS, FusionError, FusionStrategy, KERNEL_FUSE, MAX_FUSED_VECTORS, fuse_arrays, fuse_groups  # noqa: F401
 from .index import HYBRID_MAX_RECORDS, KERNEL_HYBRID_FUSE, hybrid_fuse_arrays  # noqa: F401
 from .index import (WALK_ROWS_BF16, WALK_ROWS_BF16_RESCORE, WALK_ROWS_F16, WALK_ROWS_F16_RESCORE, WALK_ROWS_F32,  # noqa: F401

@@ -45,6 +45,8 @@ VDB_KERNEL_SELECT_HALF_L2 = 1 << 23
 VDB_KERNEL_GEMM_HALF_GATHERED = 1 << 24
 # ... and of its four-bit counterpart over packed bits: Hamming / Jaccard indexes and the Binary mode (next to VDB_KERNEL_BITS)
 VDB_KERNEL_BITS_GATHERED = 1 << 25
+# ... and of the f32 one: filtered Cosine / DotProduct calls over the f32 rows of a handle in mode M (next to VDB_KERNEL_SWEEP_LISTED)
+VDB_KERNEL_GEMM_F32_GATHERED = 1 << 26
 # enum vdb_walk_rows: the rows form of the walks behind vdb_hip_index_hybrid_search_filters / vdb_hip_index_multi_query_search_filters
 VDB_WALK_ROWS_F32, VDB_WALK_ROWS_F16, VDB_WALK_ROWS_BF16, VDB_WALK_ROWS_INT8, VDB_WALK_ROWS_F16_RESCORE, VDB_WALK_ROWS_BF16_RESCORE = 0, 1, 2, 3, 4, 5
 VDB_FUSION_AVERAGE, VDB_FUSION_MAXIMUM, VDB_FUSION_RRF, VDB_FUSION_WEIGHTED = 0, 1, 2, 3

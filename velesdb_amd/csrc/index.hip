@@ -631,16 +631,20 @@ int32_t brute_bits_dev(vdb_hip_index* ix, const BitsSource& src, const QuerySlic
 }
 
 // ---- the gathered matrix-core tiers of a filtered call (VDB_OPT_FILTER_ROUTE = 3; sweep_gathered.hip) ----
-enum GatheredKind : int { kGatheredNone = 0, kGatheredHalf, kGatheredBits };
+enum GatheredKind : int { kGatheredNone = 0, kGatheredHalf, kGatheredBits, kGatheredF32 };
+static bool sweep_mode_m(const vdb_hip_index* ix, uint32_t k);
 // Which of them takes the call?  Half: Cosine / DotProduct in one of the half modes; bits: a Hamming /
-// Jaccard index (mode VDB_SEARCH_BRUTE) and the Binary mode — each wherever its plan exists.  Everything else sees the option's value
-// as auto (filter_route_opt).
+// Jaccard index (mode VDB_SEARCH_BRUTE) and the Binary mode; f32: Cosine / DotProduct over the f32 rows (mode
+// VDB_SEARCH_BRUTE) of a handle that answers this k in mode M (sweep_mode_m: the matrix engine, a dim and k its LDS tile holds) — each
+// wherever its plan exists.  Everything else — Euclidean, engine 0, a mode-C dim or k — sees the option's value as auto (filter_route_opt).
 static GatheredKind gathered_takes(const vdb_hip_index* ix, int32_t mode, int64_t opt_route, uint64_t count, uint32_t nq, uint32_t k) {
   if (opt_route != kFilterRouteOptGathered) return kGatheredNone;
   if (mode == VDB_SEARCH_BRUTE_BF16 || mode == VDB_SEARCH_BRUTE_F16) {
     if (ix->metric != VDB_COSINE && ix->metric != VDB_DOT) return kGatheredNone;
     return half_gather_plan(ix->dim, k, count, nq, ix->n_cus).blocks > 0 ? kGatheredHalf : kGatheredNone;
   }
+  if (mode == VDB_SEARCH_BRUTE && (ix->metric == VDB_COSINE || ix->metric == VDB_DOT))
+    return sweep_mode_m(ix, k) && half_gather_plan(ix->dim, k, count, nq, ix->n_cus).blocks > 0 ? kGatheredF32 : kGatheredNone;
   if (mode == VDB_SEARCH_BRUTE ? !is_bits_metric(ix->metric) : mode != VDB_SEARCH_BRUTE_BINARY) return kGatheredNone;
   return bits_gather_plan(k, count, nq, ix->n_cus).blocks > 0 ? kGatheredBits : kGatheredNone;
 }
@@ -665,6 +669,7 @@ static int32_t gathered_chunks(vdb_hip_index* ix, uint32_t count, const QuerySli
 // chunk of <= 1 024 queries (half_gather_plan / bits_gather_plan, vdb_filter_route.hpp) — the chunk's queries prepared once, one
 // launch, merge_topk.
 //   half: the queries rounded to the image's format and their norms (s_misc);
+//   f32: the queries as the caller staged them and their mode-C norms (s_misc; Cosine);
 //   bits: the queries packed the source's way (s_qbits) and expanded once to their nibble image (s_misc) and bit counts (s_seed;
 //   Hamming: dim).  The rows are read PACKED: no image of them is built, asked for or read (src.ensure_image is never called).
 // The caller has checked the mode (the image, the storage mode, the metric), k > 0, count > 0 and that the plan of the whole call exists
@@ -690,6 +695,20 @@ static int32_t brute_gathered_dev(vdb_hip_index* ix, GatheredKind kind, int32_t 
       return timed_launch(ix, VDB_KERNEL_GEMM_HALF_GATHERED, st, "gathered half-precision sweep launch", [&] {
         return launch_sweep_half_gathered(ix->metric, f16, gp, rows16, ix->bf16_stride, norms16, alive, list, count, q16, ix->bf16_stride, qn,
                                           ix->s_part_keys.as<uint64_t>(), ix->dim, c.nq, k, st);
+      });
+    });
+  }
+  if (kind == kGatheredF32) {
+    ix->last_kernels |= VDB_KERNEL_SWEEP_LISTED;  // (only the filter's rows are read)
+    return gathered_chunks(ix, count, s, st, "gathered f32 sweep: k too large for the LDS query tile", true,
+               [&](const HalfGatherPlan& gp, const QuerySlice& c, size_t parts_bytes) -> int32_t {
+      if (ix->s_part_keys.reserve(parts_bytes, false, st) != hipSuccess || ix->s_misc.reserve((size_t)c.nq * 4, false, st) != hipSuccess)
+        return fail(VDB_ERR_OOM, "gathered f32 sweep scratch");
+      float* qn = ix->s_misc.as<float>();  // the queries' canonical (mode C) norms
+      if (ix->metric == VDB_COSINE) launch_query_norms_f32(c.d_q, c.q_stride, qn, c.nq, ix->dim, st);
+      return timed_launch(ix, VDB_KERNEL_GEMM_F32_GATHERED, st, "gathered f32 sweep launch", [&] {
+        return launch_sweep_f32_gathered(ix->metric, gp, ix->rows.as<float>(), ix->row_stride, ix->norms.as<float>(), alive, list, count, c.d_q,
+                                         c.q_stride, qn, ix->s_part_keys.as<uint64_t>(), ix->dim, c.nq, k, st);
       });
     });
   }
@@ -1434,8 +1453,13 @@ int32_t search_filters_mode_to_device(vdb_hip_index* ix, const RowFilter* const*
   auto list_of = [&](uint32_t f) { return (const uint32_t*)filters[f]->list.as<uint32_t>(); };
   auto occ_of = [&](int B, uint32_t nq_max) { return (uint32_t)listed_occupancy(mode_m, B, mode_m ? plan_of(nq_max).lds : 0); };
   const int64_t opt_route = opt_value(ix, VDB_OPT_FILTER_ROUTE);
-  const std::vector<FxGroup> groups = f32 ? filters_exact_groups(fq, nq, n_filters, filter_route_opt(opt_route), ix->n_rows, count_of, pass_of)
-                                          : filters_mode_groups(fq, nq, n_filters, filter_route_opt(opt_route), mode, ix->metric, ix->n_rows, ix->dim, k, ix->n_cus, count_of);
+  std::vector<FxGroup> groups = f32 ? filters_exact_groups(fq, nq, n_filters, filter_route_opt(opt_route), ix->n_rows, count_of, pass_of)
+                                    : filters_mode_groups(fq, nq, n_filters, filter_route_opt(opt_route), mode, ix->metric, ix->n_rows, ix->dim, k, ix->n_cus, count_of);
+  // a group the gathered f32 tier takes leaves the grouped listed launches, which auto may have given it, for the
+  // group-by-group loop below, where the tier is asked — the other kinds' groups are there already (their modes have no such launch)
+  for (FxGroup& g : groups)
+    if (g.route == kFilterRouteListed && gathered_takes(ix, mode, opt_route, count_of(g.filter), (uint32_t)g.queries.size(), k) == kGatheredF32)
+      g.route = kFilterRouteDense;
   // rows of the call
   uint32_t n_listed = 0, extra = 0;
   for (const FxGroup& g : groups) {

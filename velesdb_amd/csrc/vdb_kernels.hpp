@@ -287,6 +287,14 @@ hipError_t launch_sweep_half_gathered(int metric, bool f16, const HalfGatherPlan
 hipError_t launch_sweep_bits_gathered(int metric, const HalfGatherPlan& p, const uint32_t* bits, uint32_t words, const uint8_t* alive,
                                       const uint32_t* list, uint32_t count, const uint8_t* qimg, uint32_t q_stride, const float* qcnt,
                                       uint64_t* part_keys, uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st);
+// the gathered f32 tier of Cosine / DotProduct over the f32 rows (sweep_gathered.hip; oracle mode M, the bits of
+// sweep_topk_mfma_f32 / sweep_topk_listed_m): one launch over the filter's ascending row list for a chunk of <= 1 024 queries.  rows /
+// queries: 16-byte aligned, strides in whole float4; qnorms: launch_query_norms_f32 (the mode-C norms; Cosine); the plan:
+// half_gather_plan; part_keys [nq][p.spans][k]
+void launch_query_norms_f32(const float* queries, uint64_t q_stride, float* out, uint32_t nq, uint32_t dim, hipStream_t st);
+hipError_t launch_sweep_f32_gathered(int metric, const HalfGatherPlan& p, const float* rows, uint64_t row_stride, const float* norms,
+                                     const uint8_t* alive, const uint32_t* list, uint32_t count, const float* queries, uint64_t q_stride,
+                                     const float* qnorms, uint64_t* part_keys, uint32_t dim, uint32_t nq, uint32_t k, hipStream_t st);
 // ... nq queries (any number) in tiles of 16 in ONE launch (sweep_topk_half_l2_tiles): part_keys [nq][blocks][k]; qcount (nullable): a
 // device word, only the first *qcount queries exist.  The 16-query LDS tile must fit 160 KiB (sweep_half_l2_lds_bytes(16, k, dim))
 hipError_t launch_sweep_half_l2_tiles(bool f16, const uint16_t* rows, uint64_t row_stride, const uint8_t* alive, const float* queries,

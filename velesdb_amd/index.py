@@ -83,6 +83,9 @@ KERNEL_BITS_GATHERED = _ffi.VDB_KERNEL_BITS_GATHERED
 def bits_gather_plan(k, count, nq_left, n_cus):
     """The launch plan of that tier (csrc/vdb_filter_route.hpp bits_gather_plan): the half tier's plan, which never depended on dim."""
     return half_gather_plan(0, k, count, nq_left, n_cus)
+# ... and the f32 one: filtered Cosine / DotProduct calls over the f32 rows where the handle answers in mode M (FILTER_ROUTE_GATHERED on
+# search_batch_brute_force_filtered / _with_filters; next to KERNEL_SWEEP_LISTED; the plan is half_gather_plan's)
+KERNEL_GEMM_F32_GATHERED = _ffi.VDB_KERNEL_GEMM_F32_GATHERED
 HYBRID_MAX_RECORDS = 8192
 # the rows the walks of hybrid_search_batch_filters / multi_query_search_batch_filters take their distances over (enum vdb_walk_rows)
 WALK_ROWS_F32, WALK_ROWS_F16, WALK_ROWS_BF16, WALK_ROWS_INT8 = _ffi.VDB_WALK_ROWS_F32, _ffi.VDB_WALK_ROWS_F16, _ffi.VDB_WALK_ROWS_BF16, _ffi.VDB_WALK_ROWS_INT8
